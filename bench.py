@@ -7,10 +7,15 @@ device-resident on rank 0 after the RCCL gather of enhanced waveforms (N > 1).  
 DCCRN complex-mask, compressed input (p_in 0.5 / p_out 2.0), batch 256 per MI355X, utterances sharded across
 ranks (weak scaling: per-GPU batch fixed).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1: either launched as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...
   bench.py --gpus N` (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or from a bare shell - then it starts its own
   ranks that way.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else this file measures:
+the per-kernel profile of the timed steps and the roofline figures built on it, BASELINE's other configurations, the rest
+of the zoo and the CPU baseline (each of them can still be switched off with its --no-* option).  --dump-outputs DIR writes
+the enhanced waveforms of the last timed step to DIR/enhanced.npy (see dump_outputs).
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 """
@@ -235,6 +240,22 @@ def run_other_configs(torch, local_rank, steps, configs=None):
     return rows
 
 
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(d, rows):
+    """`--dump-outputs DIR`: what a caller of the timed path receives from its last step - the enhanced waveforms of every
+    rank's clips, in rank order, as landed on rank 0 - written to DIR/enhanced.npy (float32, [rows, samples]).  A batch larger
+    than DUMP_BUDGET_BYTES is written as a fixed sample of whole rows (numpy seed 0, ascending row order), so that two builds
+    run with the same arguments can be compared output for output."""
+    y = np.concatenate([r.detach().cpu().numpy() for r in rows]).astype(np.float32, copy=False)
+    keep = min(len(y), max(1, DUMP_BUDGET_BYTES // max(y[0].nbytes, 1)))
+    if keep < len(y):
+        y = y[np.sort(np.random.default_rng(0).choice(len(y), keep, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'enhanced.npy'), np.ascontiguousarray(y))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` from a bare shell: start one rank per GPU under torch.distributed.run (rendezvous on
     127.0.0.1, a free port) with the same arguments and hand back its exit code."""
@@ -259,6 +280,11 @@ def main():
                     help='torch.distributed backend of the waveform gather (nccl = RCCL over xGMI; gloo stages through the host)')
     ap.add_argument('--force-pg', action='store_true',
                     help='initialise the process group and run the gather collective even with one rank (RCCL smoke on a 1-GPU box)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the per-kernel profile of the timed steps and the roofline '
+                         "figures, BASELINE's other configurations, the rest of the zoo and the CPU baseline")
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='after the timed steps, write the enhanced waveforms of the last timed step to DIR/enhanced.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-profile', action='store_true')
     ap.add_argument('--no-configs', action='store_true', help="skip BASELINE's other configurations (roofline.configs)")
@@ -332,11 +358,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    profile = args.full and not args.no_profile
     for _ in range(args.warmup):
         step()
     pipe.finish()
     fence()
-    if not args.no_profile:
+    if profile:
         eng.set_profiling(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -344,8 +371,8 @@ def main():
     rows = pipe.finish()    # every gather of the timed steps has landed on rank 0
     fence()
     dt = time.perf_counter() - t0
-    prof = eng.get_profile() if not args.no_profile else None
-    stages = eng.get_stage_profile() if not args.no_profile else None
+    prof = eng.get_profile() if profile else None
+    stages = eng.get_stage_profile() if profile else None
     eng.set_profiling(False)
 
     if use_pg:
@@ -357,6 +384,8 @@ def main():
         assert bool(torch.isfinite(out).all()), "non-finite output"
         if use_pg:          # the gathered rows of the last step: rank r's rows are its own clips' enhancement
             assert len(rows) == world and all(bool(torch.isfinite(r).all()) for r in rows), "non-finite gathered rows"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rows)
         utts = world * B * args.steps
         value = utts / dt
         res = {
@@ -424,7 +453,7 @@ def main():
                  "frac": round(v['bytes'] / 1e9 / max(v['ms'] * 1e-3, 1e-12) / HBM_PEAK_GBS, 4),
                  "share_of_step": round(v['ms'] / (1e3 * dt / args.steps), 5)}
                 for k, v in stages.items() if v['launches'] > 0]
-        if world == 1 and not args.no_configs and "roofline" in res:
+        if args.full and world == 1 and not args.no_configs and "roofline" in res:
             # the headline engine's 24 GB go back first (FullSubNet's shard needs most of the HBM)
             del model, eng, pipe, out, wav
             torch.cuda.empty_cache()
@@ -440,7 +469,7 @@ def main():
             res["roofline"]["configs_note"] = ("whole decode path per config: utt/s x SURVEY 8(d) GFLOP per utterance against the "
                                               "f32 MFMA peak; unprofiled steps timed by the host clock around a device sync; two passes per config, "
                                               "their MEAN reported (utt_s, ms_per_step), both in ms_per_step_passes, the faster one in utt_s_best_pass")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(seed, p_in, p_out)
         print(json.dumps(res), flush=True)
     if use_pg:

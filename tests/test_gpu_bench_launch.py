@@ -59,3 +59,19 @@ def test_bench_rejects_more_ranks_than_gpus():
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--batch', '2', '--steps', '1',
                         '--warmup', '0', '--no-cpu-baseline'], env=e, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode != 0 and 'GPU(s) visible' in (p.stdout + p.stderr)
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run reports the headline alone (the profile, the other configurations and the CPU baseline are --full's), and
+    --dump-outputs writes the last timed step's enhanced waveforms: finite, one row per clip, equal rows for the equal clips
+    (bench.py tiles 16 synthetic clips over the batch), and the same again in a second run with the same arguments."""
+    import numpy as np
+    args = ['--gpus', '1', '--batch', '32', '--steps', '2', '--warmup', '1']
+    r = _run(args + ['--dump-outputs', str(tmp_path / 'a')])
+    assert r['steps'] == 2 and r['warmup'] == 1 and r['ms_per_step'] > 0 and r['value'] > 0
+    assert not {'roofline', 'roofline_whole_path', 'roofline_stages', 'cpu_baseline'} & set(r), sorted(r)
+    _run(args + ['--dump-outputs', str(tmp_path / 'b')])
+    a, b = np.load(tmp_path / 'a' / 'enhanced.npy'), np.load(tmp_path / 'b' / 'enhanced.npy')
+    assert a.dtype == np.float32 and a.ndim == 2 and a.shape[0] == 32 and np.isfinite(a).all()
+    assert np.abs(a[:16] - a[16:]).max() <= 1e-5 * np.abs(a).max()
+    assert np.abs(a - b).max() <= 1e-5 * np.abs(a).max()

@@ -179,3 +179,23 @@ def test_bench_roofline_inputs():
     assert (rd + wr) / 1e9 <= step_traffic < 1.75 * (rd + wr) / 1e9
     assert 0.80 * 256 * 53.4e-3 < pmc['executed_mfma_tflop_per_step'] < 0.90 * 256 * 53.4e-3
     assert bench.DCCRN_GFLOP_PER_UTT == 53.4 and bench.F32_MFMA_PEAK_TFLOPS == 157.3
+
+
+def test_bench_dump_outputs_caps_size_with_a_fixed_row_sample(tmp_path):
+    """bench.py --dump-outputs: a last step that fits the budget is written whole, in rank order; a larger one as the same
+    seeded sample of whole rows, ascending, on every call - so that two builds can be compared output for output."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    small = [torch.arange(6 * 5, dtype=torch.float32).view(6, 5), -torch.ones(2, 5)]
+    bench.dump_outputs(str(tmp_path / 's'), small)
+    y = np.load(tmp_path / 's' / 'enhanced.npy')
+    assert y.dtype == np.float32 and np.array_equal(y, torch.cat(small).numpy())
+    n = 256
+    big = [torch.arange(n, dtype=torch.float32)[:, None].expand(n, 64000).contiguous()]
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), big)
+    a, b = (np.load(tmp_path / d / 'enhanced.npy') for d in ('a', 'b'))
+    assert a.nbytes <= bench.DUMP_BUDGET_BYTES < 64e6 and a.shape[1] == 64000 and a.shape[0] > n // 2
+    rows = a[:, 0]
+    assert np.array_equal(a, b) and np.all(np.diff(rows) > 0) and np.array_equal(a, rows[:, None] * np.ones((1, 64000)))

@@ -30,7 +30,7 @@ for step in "$@"; do
     dbg)
       (export ${c//,/ }; timeout 200 python $ROOT/tools/sweep.py --models $a --batch $b --steps 5 --no-profile 2>&1 | grep utt_per_s | cut -c1-100 | sed "s/^/[$c] /") ;;
     bench)
-      (cd $ROOT && timeout 600 python bench.py --steps ${a:-10} --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; python tools/bench_digest.py $OUT/bench.json) ;;
+      (cd $ROOT && timeout 600 python bench.py --full --steps ${a:-10} --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; python tools/bench_digest.py $OUT/bench.json) ;;
     *) echo "unknown step $step" ;;
   esac
 done
