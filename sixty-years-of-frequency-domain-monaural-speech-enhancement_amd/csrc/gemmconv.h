@@ -133,6 +133,9 @@ struct GCParams {
     int flat_units;          // B * flat_upr
 };
 constexpr int GC_NRM_MAXC = 128;
+// batch rows whose InstanceNorm parameters a flattened tile with NRM holds in LDS (gc_kernel: nrmC / nrmK); gc_launch only
+// sends a normalising launch to the flattened tiles when no tile spans more rows than this
+constexpr int GC_FLAT_NRM_ROWS = 2;
 
 // Device tables of one patch geometry (owned by the plan)
 struct GCGeom {
@@ -203,5 +206,23 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream);
 // two launches that would both take the thin path (the frequency-parity classes of a transposed conv on a few frames) as one;
 // false: nothing was launched
 bool gc_launch_thin_pair(const GCParams& p0, const GCParams& p1, hipStream_t stream);
+
+// Geometry of one dispatch, for tests that must know which kernel form a launch reached (csrc/tests/gc_probe.hip).  Host-side
+// only: nothing the kernels compute depends on it.
+enum GCFamily : int { GC_FAM_TILE = 0, GC_FAM_THIN = 1, GC_FAM_THIN_PAIR = 2, GC_FAM_DIRECT = 3, GC_FAM_DIRECT_LDS = 4 };
+struct GCLaunchRec {
+    int family = GC_FAM_TILE;
+    int BM = 0, BN = 0;          // tile (GC_FAM_TILE)
+    int flat_upr = 0, upt = 0;   // flattened column tiles: units per batch row, units per tile (0: plain tiles)
+    int flat_rows = 0;           // flattened: most batch rows one tile spans
+    int qt2 = 0, nrm = 0, res = 0, trim = 0, stats = 0, ragged = 0;
+    int flat_nrm_refused = 0;    // the flattened tiles were considered and refused because a normalising tile would span
+                                 // more than GC_FLAT_NRM_ROWS rows (value: rows spanned)
+    long nblk = 0;               // workgroups
+};
+// nullptr (the default): nothing is recorded.  Otherwise every dispatch of this thread appends its record.
+void gc_set_launch_log(std::vector<GCLaunchRec>* log);
+// most batch rows that one flattened tile of `upt` units touches when B rows of `upr` units each are laid end to end
+int gc_flat_rows_spanned(int B, int upr, int upt);
 
 }  // namespace se

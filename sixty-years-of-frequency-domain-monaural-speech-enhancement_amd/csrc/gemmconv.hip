@@ -270,7 +270,8 @@ __global__ __launch_bounds__(256, RES ? 1 : (FZ || (BM >= 128 && BN >= 256)) ? (
     // NRM: per input channel {scale, shift, slope - 1, x0} of this batch row, and per K row of a staged chunk the same with
     // scale = shift = 0 where the row's frequency tap lies outside the plane (double-buffered with the chunks)
     // (FLAT: a tile's units may lie in two batch rows - both rows' channel parameters, and per buffer both rows' K-row parameters)
-    constexpr int NRMB = FLAT ? 2 : 1;
+    constexpr int NRMB = FLAT ? GC_FLAT_NRM_ROWS : 1;      // (gc_launch: no normalising flattened tile spans more rows)
+    static_assert(GC_FLAT_NRM_ROWS == 2, "the nrmC / nrmK fills below serve a tile's first row and the one after it");
     floatx4* nrmC = reinterpret_cast<floatx4*>(ep + 4 * BM);                     // [NRMB][GC_NRM_MAXC]
     floatx4* nrmK = nrmC + NRMB * GC_NRM_MAXC;                                   // [2][NRMB][KCP_MAX] + 2 (the pipeline reads one pair ahead)
     // FLAT: per unit k of the tile {batch row - b, first frame, valid, -}
@@ -1467,6 +1468,41 @@ static void gc_thin_launch_n(const GCParams& p, dim3 grid, int n, hipStream_t st
     else if (n <= 4) hipLaunchKernelGGL((gc_thin_kernel<EPI, 4>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((gc_thin_kernel<EPI, 8>), grid, dim3(256), 0, stream, p);
 }
+// gc_set_launch_log: per-thread record of the dispatches (tests only; off unless a log is set)
+static thread_local std::vector<GCLaunchRec>* g_launch_log = nullptr;
+static thread_local int g_flat_nrm_refused = 0;      // gc_launch -> the record of its dispatch
+void gc_set_launch_log(std::vector<GCLaunchRec>* log) { g_launch_log = log; }
+static void gc_log_launch(int family, const GCParams& p, long nblk, int BM = 0, int BN = 0, bool res = false) {
+    if (!g_launch_log) return;
+    GCLaunchRec r;
+    r.family = family;
+    r.BM = BM;
+    r.BN = BN;
+    r.flat_upr = p.flat_upr;
+    r.upt = p.flat_upr ? BN / 32 : 0;
+    r.flat_rows = p.flat_upr ? gc_flat_rows_spanned(p.B, p.flat_upr, BN / 32) : 0;
+    r.qt2 = p.qt2;
+    r.nrm = (p.nrm0 || p.nrm1) ? 1 : 0;
+    r.res = res ? 1 : 0;
+    r.trim = p.trim;
+    r.stats = (p.stats || p.cstats) ? 1 : 0;
+    r.ragged = p.tlen ? 1 : 0;
+    r.flat_nrm_refused = g_flat_nrm_refused;
+    r.nblk = nblk;
+    g_launch_log->push_back(r);
+}
+int gc_flat_rows_spanned(int B, int upr, int upt) {
+    // tile k covers units [k upt, (k + 1) upt); tile k + upr starts exactly upt rows further on, so the first upr tiles show
+    // every pattern (a shortened last tile spans no more rows than the full one of its pattern)
+    const long units = (long)B * upr, tiles = (units + upt - 1) / upt;
+    int most = 0;
+    for (long k = 0; k < std::min<long>(tiles, upr); ++k) {
+        const long u0 = k * upt, u1 = std::min(u0 + upt, units) - 1;
+        most = std::max(most, (int)(u1 / upr - u0 / upr + 1));
+    }
+    return most;
+}
+
 // number of workgroups of the launch on the thin path, 0: not a thin launch
 static long gc_thin_blocks(const GCParams& p) {
     static const int thin_env = getenv("SE_GC_THIN") ? atoi(getenv("SE_GC_THIN")) : 1;
@@ -1508,6 +1544,7 @@ static bool gc_thin_launch(const GCParams& p, hipStream_t stream) {
         default: return false;
     }
     SE_HIP(hipGetLastError());
+    gc_log_launch(GC_FAM_THIN, p, nblk);
     return true;
 }
 
@@ -1536,6 +1573,7 @@ bool gc_launch_thin_pair(const GCParams& p0, const GCParams& p1, hipStream_t str
         default: return false;
     }
     SE_HIP(hipGetLastError());
+    gc_log_launch(GC_FAM_THIN_PAIR, p0, n0 + n1);
     return true;
 }
 
@@ -1572,6 +1610,7 @@ static void gc_small_launch(const GCParams& p, const GCSmallGeom& sg, hipStream_
             default: SE_CHECK(false, "direct small-M path: unsupported epilogue");
         }
         SE_HIP(hipGetLastError());
+        gc_log_launch(GC_FAM_DIRECT_LDS, p, nblk8);
         return;
     }
     const long nblk = (long)((p.Tout + 255) / 256) * p.Q * p.B * p.Z;
@@ -1587,6 +1626,7 @@ static void gc_small_launch(const GCParams& p, const GCSmallGeom& sg, hipStream_
         default: SE_CHECK(false, "direct small-M path: unsupported epilogue");
     }
     SE_HIP(hipGetLastError());
+    gc_log_launch(GC_FAM_DIRECT, p, nblk);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1594,7 +1634,7 @@ static void gc_small_launch(const GCParams& p, const GCSmallGeom& sg, hipStream_
 // ------------------------------------------------------------------------------------------------
 static size_t gc_lds_bytes(const GCParams& p, int BM, size_t epi_bytes, int nbuf = 2) {
     const size_t as = (size_t)((p.KCp * (BM / 4) + 255) / 256) * 1024, bs = (size_t)((p.CI_C * p.nrows * p.Wp + 255) / 256) * 256;
-    const size_t nrb = p.flat_upr ? 2 : 1;      // FLAT: parameters of two batch rows
+    const size_t nrb = p.flat_upr ? GC_FLAT_NRM_ROWS : 1;      // FLAT: parameters of two batch rows
     const size_t nrm = ((p.nrm0 || p.nrm1) ? (size_t)(nrb * GC_NRM_MAXC + 2 * nrb * gc_kcp_max(BM) + 2) * 16 : 0) + (p.flat_upr ? 128 : 0);      // gc_kernel NRM: nrmC + nrmK; FLAT: utab
     const size_t cst = p.cstats ? (size_t)4 * 256 * 2 * 4 : 0;      // GCParams::cstats: cpart [WM][4][BN][2] <= 8 KB, behind the strips inside the staging area
     return std::max((size_t)nbuf * (as + bs) * 4, epi_bytes + cst) + (GC_TAB_KOFF + GC_MAX_KCP + 8) * 4 + (size_t)4 * BM * 4 + 64 + nrm;
@@ -1964,6 +2004,7 @@ static void gc_launch_flat_k(const GCParams& p, long nblk, size_t lds, hipStream
     }
     hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, false, false, false, NRMv, UWv>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
     SE_HIP(hipGetLastError());
+    gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN);
 }
 
 template <int BM, int BN, int WM, int WN, int EPI, bool RES = false>
@@ -1988,6 +2029,8 @@ static void gc_launch_e(const GCParams& p_in, hipStream_t stream) {
                 if constexpr (EPI == EPI_ACT && BM == 64) {
                     if (nrm) {
                         SE_CHECK(p.causal && p.Z == 1 && p.C0 + p.C1 <= GC_NRM_MAXC, "gc_launch: on-the-fly InstanceNorm needs causal taps and <= 128 input channels");
+                        SE_CHECK(gc_flat_rows_spanned(p.B, p.flat_upr, BN / 32) <= GC_FLAT_NRM_ROWS,
+                                 "gc_launch: a flattened tile with on-the-fly InstanceNorm would span more batch rows than it holds parameters for");
                         gc_launch_flat_k<BM, BN, WM, WN, EPI, true, 36>(p, nblk, lds, stream);
                         return;
                     }
@@ -2002,6 +2045,8 @@ static void gc_launch_e(const GCParams& p_in, hipStream_t stream) {
                 if constexpr (EPI == EPI_ACT && BM == 64) {
                     if (nrm) {
                         SE_CHECK(p.causal && p.Z == 1 && p.C0 + p.C1 <= GC_NRM_MAXC, "gc_launch: on-the-fly InstanceNorm needs causal taps and <= 128 input channels");
+                        SE_CHECK(gc_flat_rows_spanned(p.B, p.flat_upr, BN / 32) <= GC_FLAT_NRM_ROWS,
+                                 "gc_launch: a flattened tile with on-the-fly InstanceNorm would span more batch rows than it holds parameters for");
                         gc_launch_flat_k<BM, BN, WM, WN, EPI, true, 32>(p, nblk, lds, stream);
                         return;
                     }
@@ -2023,6 +2068,7 @@ static void gc_launch_e(const GCParams& p_in, hipStream_t stream) {
             }
             hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, false, false, true>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
             SE_HIP(hipGetLastError());
+            gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN);
             return;
         }
     }
@@ -2038,6 +2084,7 @@ static void gc_launch_e(const GCParams& p_in, hipStream_t stream) {
             }
             hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, false, false, false, true>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
             SE_HIP(hipGetLastError());
+            gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN);
             return;
         }
     }
@@ -2051,12 +2098,14 @@ static void gc_launch_e(const GCParams& p_in, hipStream_t stream) {
             }
             hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, false, true>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
             SE_HIP(hipGetLastError());
+            gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN);
             return;
         }
     }
     SE_CHECK(!p.trim, "gc_launch: no trimming variant of this kernel");
     hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, RES>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
     SE_HIP(hipGetLastError());
+    gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN, RES);
 }
 
 template <int BM, int BN, int WM, int WN, bool RES = false>
@@ -2110,6 +2159,7 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
     SE_CHECK(p.C0 == pl.p.C0 && p.C1 == pl.p.C1, "gc_launch: source channel split differs from the plan");
     SE_CHECK(!p.dst_elu || (p.epi == EPI_GLU && p.Z == 1), "gc_launch: the second (ELU) store belongs to the gated epilogue");
     if (p.epi == EPI_LSTM && p.first_step && p.C1 == 0) p.C0 = 0;       // h_{-1} = 0: no matrix work (a step that also projects its input keeps both)
+    g_flat_nrm_refused = 0;
     if (p.t_base > 0 && gc_thin_launch(p, stream)) return;       // (any first frame)
     if (p.tb_soft) p.t_base &= ~3;
     const int tb = p.t_base, Tspan = p.Tout - tb;
@@ -2216,8 +2266,14 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
             const long tiles_flat = ((long)p.B * upr + upt - 1) / upt;
             // (a unit of a later batch row adds (rows ahead) x batch stride to a 32-bit byte offset)
             const double span = ((double)(upt + upr - 1) / upr + 1.0) * sbmax;
-            if (fg.BN && gc_flat_supported(pl.BM, fg.BN, p.epi, pl.flat_uw) && tiles_flat * 100 <= tiles_plain * 94 && span < 3.0e9 &&
-                (wide || flat_qt2 || !would_qt2)) {
+            // a normalising tile holds the InstanceNorm parameters of GC_FLAT_NRM_ROWS batch rows: rows shorter than a tile
+            // (wide: upr 1, 2, 3, 5; narrow: upr 1) would put three or more rows into some tiles - those launches keep the plain tiles
+            const int nrm_rows = (p.nrm0 || p.nrm1) ? gc_flat_rows_spanned(p.B, upr, upt) : 0;
+            const bool nrm_ok = nrm_rows <= GC_FLAT_NRM_ROWS;
+            const bool flat_ok = fg.BN && gc_flat_supported(pl.BM, fg.BN, p.epi, pl.flat_uw) && tiles_flat * 100 <= tiles_plain * 94 &&
+                                 span < 3.0e9 && (wide || flat_qt2 || !would_qt2);
+            if (flat_ok && !nrm_ok) g_flat_nrm_refused = nrm_rows;
+            if (flat_ok && nrm_ok) {
                 GCParams pa = p;
                 pa.flat_upr = upr;
                 pa.flat_units = p.B * upr;
