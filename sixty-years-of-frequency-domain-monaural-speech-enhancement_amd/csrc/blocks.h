@@ -43,14 +43,10 @@ inline void norm2d_prelu(const NormAct& n, const float* x, float* y, int B, int 
     }
 }
 // conv / deconv -> InstanceNorm -> PReLU (+ res): the conv's epilogue hands the norm its statistics as per-tile partial
-// sums, so the norm pass reads the plane once instead of twice (SE_IN_STATS=0: separate statistics pass).  Falls back to
-// the two-kernel sequence for the cumulative-LayerNorm variants and for tile configurations without the epilogue.
-inline bool in_stats_enabled() {
-    static const bool on = !(getenv("SE_IN_STATS") && atoi(getenv("SE_IN_STATS")) == 0);
-    // (round 6: the epilogue cuts its partial sums at the row's own frame count - gc_kernel `tstat` - and the norm kernels divide
-    // by it, so ragged batches and the padded equal-length batches of model.h PadFrames keep the epilogue statistics and the fold)
-    return on;
-}
+// sums, so the norm pass reads the plane once instead of twice.  Falls back to the two-kernel sequence for the
+// cumulative-LayerNorm variants and for tile configurations without the epilogue.
+// (round 6: the epilogue cuts its partial sums at the row's own frame count - gc_kernel `tstat` - and the norm kernels divide
+// by it, so ragged batches and the padded equal-length batches of model.h PadFrames keep the epilogue statistics and the fold)
 inline float* in_stats_scratch(int B, int C, int F, int T, hipStream_t st) {
     return reinterpret_cast<float*>(device_scratch(2, (size_t)B * C * F * ((T + 31) / 32) * 2 * sizeof(float), st));
 }
@@ -69,7 +65,7 @@ inline void conv_norm2d_prelu(const GCPlan& pl, const NormAct& n, const Act4& s0
         launch_cln_parts(y, out, n.g, n.b, n.s, parts, B, C, Fout, T, st, res);
         return;
     }
-    if (!n.cum && in_stats_enabled() && conv_stats_supported(pl)) {
+    if (!n.cum && conv_stats_supported(pl)) {
         float* stats = in_stats_scratch(B, C, Fout, T, st);
         run_conv(pl, s0, s1, y, C, Fout, B, T, T, st, pf, stats);
         launch_instnorm_prelu_stats(y, out, n.g, n.b, n.s, stats, Fout * ((T + 31) / 32), B, C, Fout * T, st, res, T);
@@ -88,7 +84,7 @@ inline void deconv_norm2d_prelu(const DeconvPlan& pl, const NormAct& n, const Ac
         launch_cln_parts(y, out, n.g, n.b, n.s, parts, B, C, Fout, T, st, res);
         return;
     }
-    if (!n.cum && in_stats_enabled() && deconv_stats_supported(pl)) {
+    if (!n.cum && deconv_stats_supported(pl)) {
         float* stats = in_stats_scratch(B, C, Fout, T, st);
         run_deconv(pl, s0, s1, y, C, Fout, B, T, T, st, pf, stats);
         launch_instnorm_prelu_stats(y, out, n.g, n.b, n.s, stats, Fout * ((T + 31) / 32), B, C, Fout * T, st, res, T);
@@ -177,26 +173,18 @@ struct TcmScratch {
 };
 
 // x [B][256][T] -> y [B][256][T]
-// batch from which one workgroup per utterance beats the multi-launch path (SE_TCM_FUSED_MINB; 0 = never fuse)
+// batch from which one workgroup per utterance beats the multi-launch path (96)
 // (a model that runs several TCM sequences side by side lowers it for its own calls - G2Net, round 6: with three sequences in
-// flight the one-workgroup-per-utterance kernel wins from one clip on; the environment variable overrides both)
+// flight the one-workgroup-per-utterance kernel wins from one clip on)
 inline int& tcm_fused_min_override() {
     static thread_local int v = 0;
     return v;
 }
 inline int tcm_fused_min_batch() {
-    static const int env = getenv("SE_TCM_FUSED_MINB") ? atoi(getenv("SE_TCM_FUSED_MINB")) : -1;
-    if (env >= 0) return env;
     return tcm_fused_min_override() > 0 ? tcm_fused_min_override() : 96;
 }
 inline void run_tcm(const TcmBlock& k, const float* x, float* y, const TcmScratch& s, int B, int T, hipStream_t st, Profiler* pf) {
-    if (stream_ctx() && k.sfused.w_in && k.nL.cum && k.nO.cum && tcm_stream_enabled()) {
-        const TcmFusedHeads hd{k.nL.s, k.nL.g, k.nL.b, k.firL, k.nR.s, k.nR.g, k.nR.b, k.firR, k.nO.s, k.nO.g, k.nO.b};
-        launch_tcm_stream(k.sfused, hd, x, y, k.d, k.K, st);
-        return;
-    }
-    static const bool cum_fused = !(getenv("SE_TCM_FUSED_CLN") && atoi(getenv("SE_TCM_FUSED_CLN")) == 0);
-    if (k.fused.w1 && !stream_ctx() && (!k.nL.cum || cum_fused) && tcm_fused_min_batch() > 0 && B >= tcm_fused_min_batch() &&
+    if (k.fused.w1 && !stream_ctx() && B >= tcm_fused_min_batch() &&
         tcm_fused_supported(T)) {
         const TcmFusedHeads hd{k.nL.s, k.nL.g, k.nL.b, k.firL, k.nR.s, k.nR.g, k.nR.b, k.firR, k.nO.s, k.nO.g, k.nO.b};
         const bool timed = pf && pf->on;
@@ -238,7 +226,7 @@ inline const float* run_tcm_chain(const TcmBlock* blk, int n, const float* x, fl
     while (i < n) {
         int m = 1;
         auto chainable = [&](const TcmBlock& k) { return k.sfused.w_in && k.nL.cum && k.nO.cum; };
-        if (stream_ctx() && tcm_chain_enabled() && chainable(blk[i])) {
+        if (stream_ctx() && chainable(blk[i])) {
             while (m < 8 && i + m < n && chainable(blk[i + m]) && blk[i + m].sfused.ks == blk[i].sfused.ks) ++m;
             const TcmStreamW* f[8];
             TcmFusedHeads hd[8];

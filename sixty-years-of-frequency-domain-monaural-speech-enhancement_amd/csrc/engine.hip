@@ -190,10 +190,7 @@ int se_engine_create(const se_config* cfg, se_engine** out) {
                                           : (cfg->model == SE_MODEL_UFORMER || cfg->model == SE_MODEL_DPCRN || cfg->model == SE_MODEL_CTSNET ||
                                              cfg->model == SE_MODEL_TAYLORSENET);
         if (split && e->ctx.max_batch >= 64) {
-            static const int parts_env = getenv("SE_BATCH_PARTS") ? atoi(getenv("SE_BATCH_PARTS")) : 0;
-            const int parts = parts_env >= 2 && parts_env <= 1 + se_engine::MAX_TWINS
-                                  ? parts_env
-                                  : ((cfg->model == SE_MODEL_UFORMER || cfg->model == SE_MODEL_DPCRN) ? 3 : 2);
+            const int parts = (cfg->model == SE_MODEL_UFORMER || cfg->model == SE_MODEL_DPCRN) ? 3 : 2;
             e->ntwins = parts - 1;
             SE_HIP(hipEventCreateWithFlags(&e->ev_tfork, hipEventDisableTiming));
             for (int i = 0; i < e->ntwins; ++i) {

@@ -1503,20 +1503,20 @@ int gc_flat_rows_spanned(int B, int upr, int upt) {
     return most;
 }
 
+// most workgroups a launch may have on the thin path
+constexpr long GC_THIN_MAX_BLOCKS = 8192;
 // number of workgroups of the launch on the thin path, 0: not a thin launch
 static long gc_thin_blocks(const GCParams& p) {
-    static const int thin_env = getenv("SE_GC_THIN") ? atoi(getenv("SE_GC_THIN")) : 1;
     const int n = p.Tout - p.t_base;
     // (layers with <= 4 output channels have the packed matrix too: a one-frame launch of the direct kernel walks its whole K
     // in one thread per output - 20-40 us; the fused parity pair of a transposed conv only exists there)
-    if (!thin_env || (p.Ws && p.pair) || n > GC_THIN_NT || p.Z > 1 || p.stats || p.cstats || p.nrm0 || p.nrm1) return 0;
+    if ((p.Ws && p.pair) || n > GC_THIN_NT || p.Z > 1 || p.stats || p.cstats || p.nrm0 || p.nrm1) return 0;
     if (p.epi != EPI_ACT && p.epi != EPI_ADD && p.epi != EPI_MUL && p.epi != EPI_GLU && p.epi != EPI_LSTM) return 0;
     if (p.epi == EPI_LSTM && (p.M & 3)) return 0;
     const long nblk = (long)((p.M + 7) >> 3) * p.Q * p.B;
     // (a few frames per row is not yet a small launch: the LSTM input projections of a batch-1 decode are 1 "frame" wide
     // and 401 rows high with K = 1024 - matrix work)
-    static const long thin_max = getenv("SE_GC_THIN_MAX") ? atol(getenv("SE_GC_THIN_MAX")) : 8192;
-    if (nblk > thin_max) return 0;
+    if (nblk > GC_THIN_MAX_BLOCKS) return 0;
     // Both paths are latency-bound at these sizes: a thin block walks K / 32 rows with 1 + NT loads each (~0.08 us per row
     // and load, ~2 048 blocks in flight) and re-reads its 8 weight rows from L2 (32 B x K per block: 16 streams x one frame of
     // DCCRN's 256-channel layers = 4 096 blocks x 80 KB - 110 us against 80 us of the MFMA tiles); an MFMA workgroup makes K / 16
@@ -1556,9 +1556,8 @@ static void gc_thin_pair_launch_n(const GCThinPair& a, dim3 grid, int n, hipStre
     else hipLaunchKernelGGL((gc_thin_pair_kernel<EPI, 8>), grid, dim3(256), 0, stream, a);
 }
 bool gc_launch_thin_pair(const GCParams& p0, const GCParams& p1, hipStream_t stream) {
-    static const int pair_env = getenv("SE_GC_THIN_PAIR") ? atoi(getenv("SE_GC_THIN_PAIR")) : 1;
     const long n0 = gc_thin_blocks(p0), n1 = gc_thin_blocks(p1);
-    if (!pair_env || n0 <= 0 || n1 <= 0 || p0.epi != p1.epi || p0.Tout - p0.t_base != p1.Tout - p1.t_base) return false;
+    if (n0 <= 0 || n1 <= 0 || p0.epi != p1.epi || p0.Tout - p0.t_base != p1.Tout - p1.t_base) return false;
     GCThinPair a;
     a.p[0] = p0;
     a.p[1] = p1;
@@ -1586,17 +1585,15 @@ static void gc_small_lds_launch(const GCParams& p, dim3 grid, size_t shm, int CC
 template <int MM>
 static void gc_small_launch(const GCParams& p, const GCSmallGeom& sg, hipStream_t stream) {
     // LDS-tiled form when the launch still fills the chip with 8-row workgroups and the patch of at least 2 channels fits
-    static const int lds_env = getenv("SE_GC_SMALL_LDS") ? atoi(getenv("SE_GC_SMALL_LDS")) : 1;
     const int NR = (SQB - 1) * p.si + (sg.dfmax - sg.dfmin) + 1;
-    static const int small_kb = getenv("SE_GC_SMALL_KB") ? atoi(getenv("SE_GC_SMALL_KB")) : 24;       // LDS budget of the staged patch (KB): 2-channel chunks, 6-7 workgroups per CU (40 KB: DCCRN -0.4 %, CTSNet -1.7 %)
+    constexpr int small_kb = 24;       // LDS budget of the staged patch (KB): 2-channel chunks, 6-7 workgroups per CU (40 KB: DCCRN -0.4 %, CTSNet -1.7 %)
     // <= 8: s_w holds 8 channels; <= 24 patch rows per chunk: a wave carries 6 rows of the next chunk in registers (gc_small_lds_kernel)
     const int CC = std::min(std::min(8, 24 / std::max(NR, 1)), (int)((size_t)small_kb * 1024 / ((size_t)NR * SWT * sizeof(float))));
     const long nblk8 = (long)((p.Tout + 255) / 256) * ((p.Q + SQB - 1) / SQB) * p.B * p.Z;
     // (worth it from three frequency rows per output row on: with one or two the plain kernel's caches do as well - CRN /
     // DPCRN last layers measured 1-3 % slower here, DCCRN's 5-tap deconv 1 % faster with a third of the fetches)
-    if (lds_env && CC >= 2 && p.Q >= SQB && (p.si == 1 || p.si == 2) && sg.dtmax - sg.dtmin <= SWT - 256 &&
-        ((nblk8 >= 4 * 256 && (sg.dfmax - sg.dfmin >= 2 || (sg.dfmax - sg.dfmin >= 1 && MM >= 2 && p.C0 + p.C1 >= 64))) ||
-         lds_env == 2)) {        // 2: always (tests)
+    if (CC >= 2 && p.Q >= SQB && (p.si == 1 || p.si == 2) && sg.dtmax - sg.dtmin <= SWT - 256 && nblk8 >= 4 * 256 &&
+        (sg.dfmax - sg.dfmin >= 2 || (sg.dfmax - sg.dfmin >= 1 && MM >= 2 && p.C0 + p.C1 >= 64))) {
         SE_CHECK(nblk8 < (1L << 31), "grid size");
         const size_t shm = (size_t)CC * NR * SWT * sizeof(float);
         dim3 grid((unsigned)nblk8);
@@ -1721,26 +1718,23 @@ GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float
     p.dtmin = dtmin;
     p.Wp = pl.BN + (dtmax - dtmin);                         // LDS row stride of the patch (multiple of 4)
     SE_CHECK(p.nrows * p.Wp <= gc_bld_max(pl.BM) * 256, "tap span too wide for one staged patch");
-    // chunking: largest CI_C within the staging budgets (SE_GC_KCP: tuning override)
-    static const int kcp_cap = getenv("SE_GC_KCP") ? atoi(getenv("SE_GC_KCP")) : GC_MAX_KCP;
-    static const bool pw_chunks = !(getenv("SE_GC_PW4") && atoi(getenv("SE_GC_PW4")) == 0);
+    // chunking: largest CI_C within the staging budgets
     // chunk = CI_C input channels x all taps.  Among the sizes that fit the staging budgets take the one that wastes the
     // fewest K rows on padding to a multiple of 4 (rows of zeros cost full MFMAs), then the largest: measured on the DCCRN
     // bench, 20 exact rows per barrier beat 30 rows padded to 32 (taps = 10), 24 beat 30 / 32 (taps = 6)
-    static const bool wide_chunk_env = !(getenv("SE_GC_WIDE_CHUNK") && atoi(getenv("SE_GC_WIDE_CHUNK")) == 0);
     int cic = 1;
     double best = -1.0;
     for (int c = 1; c <= std::max(std::max(C0, Cin - C0), 1); ++c) {
         const int kc = c * taps.ntaps, kcp = (kc + 3) & ~3;
         // pointwise layers stage 16 B groups (4x the slots) and size the chunk by the LDS budget of 3 blocks per CU
-        const bool pw = taps.ntaps == 1 && pw_chunks;
+        const bool pw = taps.ntaps == 1;
         const int kmax = pw ? (pl.BM >= 128 ? 24 : 32) : gc_kcp_max(pl.BM);
         const int cap = gc_bld_max(pl.BM) * 256 * (pw ? 4 : 1);
-        if (kcp > std::min(kmax, kcp_cap) || c * p.nrows * p.Wp > cap) continue;
+        if (kcp > kmax || c * p.nrows * p.Wp > cap) continue;
         // 64-row layers: keep the chunk small enough for the 64 x 256 tile's patch (3 workgroups per CU) when that still
         // leaves >= 12 K rows per barrier - G2Net's 3-tap convs would stage 8 channels x 3 rows and fall back to 64 x 128
         // tiles (measured: + 4 % for the whole model at batch 256 with 4-channel chunks)
-        if (wide_chunk_env && pl.BM == 64 && pl.BN == 128 && taps.ntaps > 1 && epi != EPI_LSTM && kc > 12 &&
+        if (pl.BM == 64 && pl.BN == 128 && taps.ntaps > 1 && epi != EPI_LSTM && kc > 12 &&
             (long)c * p.nrows * (256 + (dtmax - dtmin)) > 4608)
             continue;
         const double score = (double)kc / kcp + 1e-4 * kc;       // padding efficiency first, size second
@@ -1763,19 +1757,15 @@ GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float
         p.desc4 = g.desc4;
         // narrower geometries for the last, mostly empty time tile of a row (T = 401 fills 17 of 128 columns of its 4th
         // tile): same weights and chunking, own patch tables; gc_launch sends that tile to a 32- / 64-column kernel
-        static const int tail_env = getenv("SE_GC_TAIL") ? atoi(getenv("SE_GC_TAIL")) : 1;
         // (only where the narrow kernel keeps all four waves busy: 128 rows x 32 columns; a 64-row layer would leave half
         // its waves on padding again - measured slower than the skip logic of the full-width tile)
         // (pointwise layers get the geometry for tiny launches only: as a separate tail launch it doubled the launch count
         // of FullSubNet's per-step LSTM GEMMs)
-        pl.tail_split = !(taps.ntaps == 1 && pw_chunks);
-        if (tail_env && pl.BN == 128 && pl.BM == 128) {
-            for (int i = 0; i < 1; ++i) {
-                const int bn = 32;
-                pl.tail[i].BN = bn;
-                pl.tail[i].Wp = bn + (dtmax - dtmin);
-                pl.tail[i].g = gc_build_geom(taps, rows, dtmin, p.nrows, pl.tail[i].Wp, cic, p.KC, gc_bld_max(pl.BM));
-            }
+        pl.tail_split = taps.ntaps != 1;
+        if (pl.BN == 128 && pl.BM == 128) {
+            pl.tail[0].BN = 32;
+            pl.tail[0].Wp = 32 + (dtmax - dtmin);
+            pl.tail[0].g = gc_build_geom(taps, rows, dtmin, p.nrows, pl.tail[0].Wp, cic, p.KC, gc_bld_max(pl.BM));
         }
         // 64-column geometry of the whole layer (tail[1]) for launches that would not fill the chip with 128-column
         // tiles: the batch is only known at launch time, gc_launch picks
@@ -1799,8 +1789,7 @@ GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float
         }
         // 256-column geometry of a 64-row layer (tail[2]): 1 x 4 waves of 64 x 64 do the 128 x 128 tile's matrix work per
         // staged K row (the 64 x 128 tile does half of it), for big launches whose rows fill the wide tiles (T = 501: 98 %)
-        static const int wide_env = getenv("SE_GC_WIDE") ? atoi(getenv("SE_GC_WIDE")) : 1;
-        if (wide_env && pl.BN == 128 && pl.BM == 64 && epi != EPI_LSTM && taps.ntaps > 1) {
+        if (pl.BN == 128 && pl.BM == 64 && epi != EPI_LSTM && taps.ntaps > 1) {
             pl.tail[2].BN = 256;
             pl.tail[2].Wp = 256 + (dtmax - dtmin);
             pl.tail[2].g = gc_build_geom(taps, rows, dtmin, p.nrows, pl.tail[2].Wp, cic, p.KC, gc_bld_max(pl.BM));
@@ -1812,7 +1801,7 @@ GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float
         // workgroups per CU instead of three, coarser tails; with loads and epilogue ablated both tiles run the same
         // 132 - 134 TFLOP/s, so the K loop itself gains nothing) - hence only here
         static const int wide128_env = getenv("SE_GC_WIDE128") ? atoi(getenv("SE_GC_WIDE128")) : 1;
-        if (wide128_env && pl.BN == 128 && pl.BM == 128 && taps.ntaps == 1 && pw_chunks && epi == EPI_LSTM && cic * 256 <= 6 * 1024) {
+        if (wide128_env && pl.BN == 128 && pl.BM == 128 && taps.ntaps == 1 && epi == EPI_LSTM && cic * 256 <= 6 * 1024) {
             pl.tail[2].BN = 256;
             pl.tail[2].Wp = 256;
             pl.tail[2].g = gc_build_geom(taps, rows, dtmin, p.nrows, 256, cic, p.KC, gc_bld_max(pl.BM));
@@ -1869,8 +1858,7 @@ GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float
     pl.dA = to_device(packed);
     p.A = pl.dA;
     // direct path (gc_small_kernel): plain weights [z][ci][tap][MM] for layers with <= 4 output channels
-    static const int small_env = getenv("SE_GC_SMALL") ? atoi(getenv("SE_GC_SMALL")) : 1;
-    if (small_env && M <= 4 && (epi == EPI_ACT || epi == EPI_ADD || epi == EPI_MUL || (epi == EPI_GLU && M % 2 == 0))) {
+    if (M <= 4 && (epi == EPI_ACT || epi == EPI_ADD || epi == EPI_MUL || (epi == EPI_GLU && M % 2 == 0))) {
         const int MM = M <= 1 ? 1 : (M <= 2 ? 2 : 4);
         std::vector<float> ws((size_t)Z * Cin * taps.ntaps * MM, 0.f);
         for (int z = 0; z < Z; ++z)
@@ -2128,8 +2116,7 @@ static void gc_launch_t(const GCParams& p, hipStream_t stream) {
 }
 // all chunks of a source resident in LDS at once (gc_kernel RES): launches of at most one workgroup per CU whose staging fits
 static bool gc_resident_fits(GCParams& p, int BM, int BM_div_WM) {
-    static const int res_env = getenv("SE_GC_RES") ? atoi(getenv("SE_GC_RES")) : 1;
-    if (!res_env || p.trim || p.epi == EPI_LSTM || p.epi == EPI_CMB || p.fz || p.nrm0 || p.nrm1 || p.cstats) return false;
+    if (p.trim || p.epi == EPI_LSTM || p.epi == EPI_CMB || p.fz || p.nrm0 || p.nrm1 || p.cstats) return false;
     const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;
     const int nch0 = p.C0 > 0 ? (p.C0 + p.CI_C - 1) / p.CI_C : 0, nch1 = p.C1 > 0 ? (p.C1 + p.CI_C - 1) / p.CI_C : 0;
     int nb = std::max(std::max(nch0, nch1), 1);
@@ -2174,17 +2161,15 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
     // patch offsets inside one staged chunk are 32-bit (the 64-bit part of an address is the per-block / per-chunk base)
     SE_CHECK((double)p.CI_C * (double)std::max(p.s0_c, p.s1_c) + (double)p.Fin * (double)std::max(p.s0_f, p.s1_f) + p.Tin < 1.0e9,
              "gc_launch: source plane too large for 32-bit patch byte offsets");
-    static const int pw4_env = getenv("SE_GC_PW4") ? atoi(getenv("SE_GC_PW4")) : 1;
     // 16 B staging groups: exact when no group straddles the end of a row (Tin % 4 == 0); for causal tap sets a straddling
     // group only feeds output frames >= Tin, which are never stored - then it merely has to stay inside mapped memory
     // (a tap set that looks ahead would read the straddling group's foreign frames into stored outputs: the kernel trims
     // them in LDS, GC_TRIM_TAIL)
-    static const int trim_env = getenv("SE_GC_TRIM") ? atoi(getenv("SE_GC_TRIM")) : 1;
     // the trimming variant exists for the plain epilogue (DCCRN's decoder); it pays from a few thousand workgroups on - small
     // launches are latency-bound and the extra LDS stores per chunk cost them 3 % (batch 1)
-    static const long trim_min = getenv("SE_GC_TRIM_MIN") ? atol(getenv("SE_GC_TRIM_MIN")) : 8192;
-    const bool trim_ok = trim_env && p.epi == EPI_ACT && (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles >= trim_min;
-    p.pw4 = (pw4_env && p.desc4 && (p.Tin % 4 == 0 || ((p.causal || trim_ok) && gc_overread_ok(p.src0) && gc_overread_ok(p.src1)))) ? 1 : 0;
+    constexpr long trim_min = 8192;
+    const bool trim_ok = p.epi == EPI_ACT && (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles >= trim_min;
+    p.pw4 = (p.desc4 && (p.Tin % 4 == 0 || ((p.causal || trim_ok) && gc_overread_ok(p.src0) && gc_overread_ok(p.src1)))) ? 1 : 0;
     p.trim = (p.pw4 && !p.causal && p.Tin % 4 != 0) ? 1 : 0;
     SE_CHECK(!p.stats || gc_stats_supported(pl), "gc_launch: this tile configuration has no statistics epilogue");
     SE_CHECK(!p.cstats || (gc_stats_supported(pl) && p.n_mtiles == 1 && p.Z == 1),
@@ -2208,20 +2193,19 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
     // B = 64, + 4 % at B = 256, + 16 % at B = 8; DCCRN's big grids lose 1 %), 128-row layers only below one workgroup
     // per CU (B = 8: + 15 %; B = 64: - 3 %)
     {
-        static const int alt_env = getenv("SE_GC_ALT") ? atoi(getenv("SE_GC_ALT")) : 1;
         const GCTail& alt = pl.tail[1];
         const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;
         static const int alt_n64 = getenv("SE_GC_ALT_N64") ? atoi(getenv("SE_GC_ALT_N64")) : 4096;
-        if (alt_env && alt.BN == 64 && nblk < (pl.BM == 64 ? alt_n64 : 256)) {
+        if (alt.BN == 64 && nblk < (pl.BM == 64 ? alt_n64 : 256)) {
             GCParams pa = p;
             pa.n_ttiles = (Tspan + 63) / 64;
             pa.Wp = alt.Wp;
             pa.tab = alt.g.tab;
             pa.desc = alt.g.desc;
             pa.desc4 = alt.g.desc4;
-            static const int alt32_env = getenv("SE_GC_ALT32") ? atoi(getenv("SE_GC_ALT32")) : 512;
+            constexpr long alt32_max = 512;      // 64-column workgroup count below which a 128-row layer uses 32-column tiles
             const long nblk64 = (long)p.Z * p.B * p.Q * pa.n_ttiles * p.n_mtiles;
-            if (pl.BM == 128 && pl.tail[0].BN == 32 && nblk64 < alt32_env) {       // tiny launches: 32 columns
+            if (pl.BM == 128 && pl.tail[0].BN == 32 && nblk64 < alt32_max) {       // tiny launches: 32 columns
                 pa.n_ttiles = (Tspan + 31) / 32;
                 pa.Wp = pl.tail[0].Wp;
                 pa.tab = pl.tail[0].g.tab;
@@ -2245,19 +2229,13 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
     // 13 B / 8 (or / 4) tiles - 19 % fewer workgroups for the same stored values
     {
         static const int flat_env = getenv("SE_GC_FLAT") ? atoi(getenv("SE_GC_FLAT")) : 1;
-        static const long flat_min = getenv("SE_GC_FLAT_MIN") ? atol(getenv("SE_GC_FLAT_MIN")) : 1024;
+        constexpr long flat_min = 1024;
         static const long wide_min = getenv("SE_GC_WIDE_MIN") ? atol(getenv("SE_GC_WIDE_MIN")) : 6144;
         const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;      // (128-column tiles)
         const int upr = (Tspan + 31) / 32;
         const double sbmax = 4.0 * (double)std::max(p.s0_b, p.s1_b);
-        // (A/B switch: SE_GC_FLAT_QT2=0 keeps the two-row tiles where they apply)
-        static const int flat_qt2 = getenv("SE_GC_FLAT_QT2") ? atoi(getenv("SE_GC_FLAT_QT2")) : 1;
-        static const int qt2_env_f = getenv("SE_GC_QT2") ? atoi(getenv("SE_GC_QT2")) : 1;
-        static const long qt2_min_f = getenv("SE_GC_QT2_MIN") ? atol(getenv("SE_GC_QT2_MIN")) : 4096;
-        const bool would_qt2 = qt2_env_f && pl.qt2.BN == 64 && pl.BN == 128 && p.Q >= 2 && !p.stats && !p.cstats && p.pad_lo == 0 &&
-                               !p.nrm0 && !p.nrm1 && nblk >= qt2_min_f;
-        if (flat_env && pl.BM == 64 && pl.flat_uw && tb == 0 && p.pw4 && !p.trim && !p.fz && p.Z == 1 && nblk >= flat_min && p.B > 1 &&
-            true) {
+        // (flattened tiles take precedence over the two-row tiles where both apply)
+        if (flat_env && pl.BM == 64 && pl.flat_uw && tb == 0 && p.pw4 && !p.trim && !p.fz && p.Z == 1 && nblk >= flat_min && p.B > 1) {
             // tile width as the plain path would choose it
             const bool wide = pl.BM == 64 && pl.flat[1].BN == 256 && nblk >= wide_min && gc_flat_supported(64, 256, p.epi, pl.flat_uw);
             const GCTail& fg = wide ? pl.flat[1] : pl.flat[0];
@@ -2271,7 +2249,7 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
             const int nrm_rows = (p.nrm0 || p.nrm1) ? gc_flat_rows_spanned(p.B, upr, upt) : 0;
             const bool nrm_ok = nrm_rows <= GC_FLAT_NRM_ROWS;
             const bool flat_ok = fg.BN && gc_flat_supported(pl.BM, fg.BN, p.epi, pl.flat_uw) && tiles_flat * 100 <= tiles_plain * 94 &&
-                                 span < 3.0e9 && (wide || flat_qt2 || !would_qt2);
+                                 span < 3.0e9;
             if (flat_ok && !nrm_ok) g_flat_nrm_refused = nrm_rows;
             if (flat_ok && nrm_ok) {
                 GCParams pa = p;
@@ -2311,8 +2289,8 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
     // big launches of the per-step LSTM GEMM: 128 x 256 tiles (two workgroups per CU)
     {
         const GCTail& wd = pl.tail[2];
-        static const long wide128_min = getenv("SE_GC_WIDE128_MIN") ? atol(getenv("SE_GC_WIDE128_MIN")) : 1536;
-        static const int wide128_fill = getenv("SE_GC_WIDE128_FILL") ? atoi(getenv("SE_GC_WIDE128_FILL")) : 75;
+        constexpr long wide128_min = 1536;      // 128-column workgroup count from which the 128 x 256 tile is used
+        constexpr int wide128_fill = 75;        // least fill of the wide tiles in percent
         const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;
         const int nt = (Tspan + 255) / 256;
         if (wd.BN == 256 && pl.BM == 128 && p.epi == EPI_LSTM && p.pw4 && !p.trim && !p.stats && nblk >= wide128_min &&
@@ -2329,10 +2307,9 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
     }
     // big launches of layers whose neighbouring output rows share input rows: two-row tiles (2 x 64 frames)
     {
-        static const int qt2_env = getenv("SE_GC_QT2") ? atoi(getenv("SE_GC_QT2")) : 1;
         static const long qt2_min = getenv("SE_GC_QT2_MIN") ? atol(getenv("SE_GC_QT2_MIN")) : 4096;
         const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;
-        if (qt2_env && pl.qt2.BN == 64 && pl.BN == 128 && p.Q >= 2 && !p.stats && !p.cstats && p.pad_lo == 0 && p.epi != EPI_LSTM &&
+        if (pl.qt2.BN == 64 && pl.BN == 128 && p.Q >= 2 && !p.stats && !p.cstats && p.pad_lo == 0 && p.epi != EPI_LSTM &&
             !p.nrm0 && !p.nrm1 && nblk >= qt2_min) {
             GCParams pa = p;
             pa.qt2 = 1;

@@ -1121,9 +1121,8 @@ static void launch_c8(LstmCoopArgs a, hipStream_t s) {
 template <int H>
 static bool launch_c16(LstmCoopArgs a, int n_cu, hipStream_t s) {
     static const int on = getenv("SE_COOP16") ? atoi(getenv("SE_COOP16")) : 1;
-    static const int min_s = getenv("SE_COOP16_MINS") ? atoi(getenv("SE_COOP16_MINS")) : 17;
     constexpr int US = H / 16;
-    if (!on || a.S < min_s || US * a.Z > n_cu || (long)a.S * H * 8 >= (1L << 31) || (double)a.gx_row * 4 * H * 4 >= 4.0e9 ||
+    if (!on || a.S < 17 || US * a.Z > n_cu || (long)a.S * H * 8 >= (1L << 31) || (double)a.gx_row * 4 * H * 4 >= 4.0e9 ||
         (double)a.out_row * H >= 4.0e9)
         return false;
     const int NT = (a.S + 15) / 16;
@@ -1212,11 +1211,9 @@ void launch_lstm_coop_chunk(const LstmCoopArgs& a, int n_layers, hipStream_t s) 
 template <int H>
 static bool launch_c4_n(LstmCoopArgs a, int n_cu, hipStream_t s) {
     static const int on = getenv("SE_COOP4") ? atoi(getenv("SE_COOP4")) : 1;
-    static const int min_s = getenv("SE_COOP4_MINS") ? atoi(getenv("SE_COOP4_MINS")) : 17;
-    static const int lead_env = getenv("SE_COOP4_LEAD") ? atoi(getenv("SE_COOP4_LEAD")) : 0;
     constexpr int US = H / 16;
     // (the per-lane parts of the gate / output addresses are 32-bit offsets inside one LSTM's tensors)
-    if (!on || a.S < min_s || US * a.Z > n_cu || (long)a.S * H * 8 >= (1L << 31) || (double)a.gx_row * 4 * H * 4 >= 4.0e9 ||
+    if (!on || a.S < 17 || US * a.Z > n_cu || (long)a.S * H * 8 >= (1L << 31) || (double)a.gx_row * 4 * H * 4 >= 4.0e9 ||
         (double)a.out_row * H >= 4.0e9)
         return false;
     const int NS4 = (a.S + 3) / 4;
@@ -1225,7 +1222,6 @@ static bool launch_c4_n(LstmCoopArgs a, int n_cu, hipStream_t s) {
     const int nsub_min = NS4 / a.SS;                           // the fewest sub-tiles a workgroup owns (>= 1)
     int lead = std::min(3, nsub_min);
     if (nsub_min >= 3 && nsub_min < 6) lead = 2;             // a fetch issued 3 slots ahead of a 4-slot cycle would read before h_{t-1} is out
-    if (lead_env > 0) lead = std::min(lead_env, std::min(3, nsub_min));
     if (lead <= 1) launch_c8<H, 1, 4>(a, s);
     else if (lead == 2) launch_c8<H, 2, 4>(a, s);
     else launch_c8<H, 3, 4>(a, s);
@@ -1264,15 +1260,9 @@ static void launch_ks(LstmCoopArgs a, hipStream_t s) {
 template <int H>
 static void launch_ks_n(const LstmCoopArgs& a, hipStream_t s) {
     // (the tagged exchange pays while a wave's share of h is one or two loads per lane: 4.9 -> 3.1 us per step at one sequence,
-    // 5.4 -> 4.2 at four, nothing at sixteen; SE_COOP_TAG=0: flags everywhere)
-    static const bool tag = !(getenv("SE_COOP_TAG") && atoi(getenv("SE_COOP_TAG")) == 0);
-    if (tag && a.S <= 4) {
-        if (a.S <= 1) launch_ks<H, 1, true>(a, s);
-        else launch_ks<H, 4, true>(a, s);
-        return;
-    }
-    if (a.S <= 1) launch_ks<H, 1, false>(a, s);
-    else if (a.S <= 4) launch_ks<H, 4, false>(a, s);
+    // 5.4 -> 4.2 at four, nothing at sixteen)
+    if (a.S <= 1) launch_ks<H, 1, true>(a, s);
+    else if (a.S <= 4) launch_ks<H, 4, true>(a, s);
     else launch_ks<H, 16, false>(a, s);
 }
 
@@ -1298,14 +1288,13 @@ static void launch_stack_t(LstmStackArgs a, hipStream_t s) {
                                       (unsigned)shmem, s));
 }
 bool lstm_stack_supported(int H, int L) {
-    static const bool on = !(getenv("SE_LSTM_STACK") && atoi(getenv("SE_LSTM_STACK")) == 0);
     static int n_cu = 0;
     if (!n_cu) {
         int dev = 0;
         SE_HIP(hipGetDevice(&dev));
         SE_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     }
-    return on && (H == 1024 || H == 512) && (L == 2 || L == 3) && H / 4 <= n_cu;
+    return (H == 1024 || H == 512) && (L == 2 || L == 3) && H / 4 <= n_cu;
 }
 void launch_lstm_stack(const LstmStackArgs& a, hipStream_t s) {
     SE_CHECK(lstm_stack_supported(a.H, a.L), "launch_lstm_stack: 2 or 3 layers of 512 / 1024 units on one sequence");
@@ -1321,11 +1310,10 @@ void launch_lstm_coop(const LstmCoopArgs& a, hipStream_t s) {
         SE_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     }
     SE_CHECK(a.Z * std::max(1, std::min((a.S + 15) / 16, n_cu / ((a.H / 16) * a.Z))) <= 256, "cooperative LSTM: too many slices");
-    static const bool ks_on = !(getenv("SE_COOP_KS") && atoi(getenv("SE_COOP_KS")) == 0);
     // one tile: every CU on the K-split form (H = 1024: 7.5 -> 5.1 ... 5.9 us per step for 1 ... 16 sequences; H = 512: 4.4 -> 3.8 at
     // one sequence, nothing from 8 on or with two LSTMs per launch - tools/coopbench.cpp)
-    static const int ks_z = getenv("SE_COOP_KS_Z") ? atoi(getenv("SE_COOP_KS_Z")) : 2;      // (two LSTMs per launch, GCRN: 4.4 -> 2.5 ... 3.0 us)
-    if (ks_on && a.S <= (a.H == 1024 ? 16 : 4) && (a.H == 1024 || a.Z <= ks_z) && (a.H / 4) * a.Z <= n_cu && (a.H / 4) * a.Z <= 256) {
+    constexpr int ks_z = 2;      // most LSTMs per launch on the K-split form (two, GCRN: 4.4 -> 2.5 ... 3.0 us)
+    if (a.S <= (a.H == 1024 ? 16 : 4) && (a.H == 1024 || a.Z <= ks_z) && (a.H / 4) * a.Z <= n_cu && (a.H / 4) * a.Z <= 256) {
         if (a.H == 1024) launch_ks_n<1024>(a, s);
         else if (a.H == 512) launch_ks_n<512>(a, s);
         else SE_CHECK(false, "cooperative LSTM kernel is built for H = 512 / 1024");
@@ -1333,12 +1321,10 @@ void launch_lstm_coop(const LstmCoopArgs& a, hipStream_t s) {
     }
     // 16-sequence tiles (lstm_coop16_kernel) unless a workgroup would own a single tile per step AND fewer than 16 sequences per
     // unit slice's share of the chip are left to split: there the 4-sequence sub-tiles overlap their own exchange (batch 32,
-    // H = 1024: 5.1 us per step against 7.4; batch 64: 8.1 against 7.8; SE_COOP4_FIRST = 1 / 0 forces / forbids)
-    static const int sub4_env = getenv("SE_COOP4_FIRST") ? atoi(getenv("SE_COOP4_FIRST")) : -1;
+    // H = 1024: 5.1 us per step against 7.4; batch 64: 8.1 against 7.8)
     const int us_z = (a.H / 16) * a.Z, nt16 = (a.S + 15) / 16;
-    const bool sub4 = sub4_env >= 0 ? sub4_env != 0 : (us_z <= n_cu && nt16 <= n_cu / us_z && a.S * us_z < 60 * n_cu / 4 && a.H == 1024);
-    if (sub4 && a.H == 1024 && launch_c4_n<1024>(a, n_cu, s)) return;
-    if (sub4 && a.H == 512 && launch_c4_n<512>(a, n_cu, s)) return;
+    const bool sub4 = a.H == 1024 && us_z <= n_cu && nt16 <= n_cu / us_z && a.S * us_z < 60 * n_cu / 4;
+    if (sub4 && launch_c4_n<1024>(a, n_cu, s)) return;
     if (a.H == 1024 && launch_c16<1024>(a, n_cu, s)) return;
     if (a.H == 512 && launch_c16<512>(a, n_cu, s)) return;
     if (a.H == 1024 && launch_c4_n<1024>(a, n_cu, s)) return;

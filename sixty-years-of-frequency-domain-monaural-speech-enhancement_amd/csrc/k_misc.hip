@@ -1104,9 +1104,8 @@ __global__ __launch_bounds__(256) void cln_window_reg_kernel(const float* __rest
 // frame-online chunk: launch_cln(..., res) adds the residual in its own launch (the one- / two-frame register form)
 bool cln_stream_takes_res(int C, int F) {
     const StreamCtx* cx = stream_ctx();
-    static const bool reg_on = !(getenv("SE_CLN_REG") && atoi(getenv("SE_CLN_REG")) == 0);
     static const bool res_on = !(getenv("SE_CLN_STREAM_RES") && atoi(getenv("SE_CLN_STREAM_RES")) == 0);
-    return cx && reg_on && res_on && cx->n <= 2 && (long)C * F <= 256L * 41 && C <= 256;
+    return cx && res_on && cx->n <= 2 && (long)C * F <= 256L * 41 && C <= 256;
 }
 void launch_cln(const float* x, float* y, const float* gain, const float* bias, const float* pre_slope,
                 const float* post_slope, const float* fir, int K, int B, int C, int F, int T, hipStream_t s, const float* res) {
@@ -1131,8 +1130,7 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
         cx->memo_src = nullptr;
         double* carry = static_cast<double*>(cx->slot((size_t)B * 2 * sizeof(double), s));
         const long tg0 = cx->t0 - cx->H;
-        static const bool reg_on = !(getenv("SE_CLN_REG") && atoi(getenv("SE_CLN_REG")) == 0);
-        if (reg_on && K <= 0 && !pre_slope && cx->n <= 2 && (long)R * cx->n <= 256L * 41 * cx->n && R <= 256 * 41 && C <= 256) {
+        if (K <= 0 && !pre_slope && cx->n <= 2 && (long)R * cx->n <= 256L * 41 * cx->n && R <= 256 * 41 && C <= 256) {
             // (every frame of the chunk is live: tg0 + c0 = the stream index of the first new frame >= 0)
             if (cx->n == 1)
                 hipLaunchKernelGGL((cln_window_reg_kernel<1, 41>), dim3(B), dim3(256), 0, s, x, y, gain, bias, post_slope, R, F, T,

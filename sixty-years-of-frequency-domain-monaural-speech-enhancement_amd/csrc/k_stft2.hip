@@ -1,5 +1,4 @@
-// Register-resident STFT / iSTFT-OLA for gfx950 (round 3; the round-1/2 LDS-Stockham kernels stay in k_stft.hip behind
-// SE_STFT_V1=1 for A/B runs).
+// Register-resident STFT / iSTFT-OLA for gfx950.
 //
 // Reference behaviour: see k_stft.hip (torch.stft / librosa.stft, centre = True, reflect pad, periodic Hann, one-sided;
 // torch.istft / librosa.istft with window-sum-square normalisation) - e.g. DCCRN/dccrn_decode_vb.py:37-38, :59-60.
@@ -524,11 +523,6 @@ void set_lds(Kern kernel, size_t bytes) {
 }
 
 }  // namespace
-
-bool stft2_enabled() {
-    static const bool on = !(getenv("SE_STFT_V1") && atoi(getenv("SE_STFT_V1")) != 0);
-    return on;
-}
 
 void launch_stft2(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale, float p_in,
                   float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0) {

@@ -568,9 +568,8 @@ void launch_tcm_fused(const TcmFusedW& f, const TcmFusedHeads& hd, const float* 
                    {hd.sL, hd.gL, hd.bL, hd.firL}, {hd.sR, hd.gR, hd.bR, hd.firR}, {hd.sO, hd.gO, hd.bO, nullptr},
                    dil, K, rg ? rg->tlen : nullptr, 0, tcm_dbg_env()};
     size_t lds = ((size_t)TCM_C * Tp + TCM_NW * TCM_C + 5 * TCM_C + 2 * 16 * 128) * sizeof(float);
-    static const bool strip_env = !(getenv("SE_TCM_STRIP") && atoi(getenv("SE_TCM_STRIP")) == 0);
     const size_t strip_bytes = (size_t)TCM_NW * 32 * 36 * sizeof(float);
-    if (strip_env && lds + strip_bytes <= 160 * 1024) {      // T <= 416: the strips fit next to the [64][Tp] tensor
+    if (lds + strip_bytes <= 160 * 1024) {      // T <= 416: the strips fit next to the [64][Tp] tensor
         a.strip = 1;
         lds += strip_bytes;
     }

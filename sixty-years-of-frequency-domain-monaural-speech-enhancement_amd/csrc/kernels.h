@@ -87,9 +87,8 @@ void launch_istft(const StftGeom& g, const float* spec_ri, int B, int T, int Tp,
 void launch_stream_rms(const float* wav, long pitch, int B, int n_total, int n_new, double* sumsq, float* c, float* frame_inv,
                        int ring, int t0, int t1, hipStream_t s);
 
-// round-3 kernels behind the two launchers above (k_stft2.hip): FFT points in registers, two LDS exchanges, 32-frame tiles
-// moved through LDS so that the [F][T]-major spectrogram is touched in 128 B runs; SE_STFT_V1=1 selects the old kernels
-bool stft2_enabled();
+// the kernels behind the two launchers above (k_stft2.hip): FFT points in registers, two LDS exchanges, 32-frame tiles
+// moved through LDS so that the [F][T]-major spectrogram is touched in 128 B runs
 void launch_stft2(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale, float p_in,
                   float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0);
 void launch_istft2(const StftGeom& g, const float* spec_ri, int B, int T, int Tp, const float* c_scale, float* wav_out,
@@ -237,10 +236,7 @@ struct TcmStreamW {         // device weights, transposed (output row contiguous
 TcmStreamW tcm_stream_build(const std::vector<float>& w_in, const std::vector<float>& w_left, const std::vector<float>* w_right,
                             const std::vector<float>& w_out, int ks);
 void tcm_stream_free(TcmStreamW& f);
-bool tcm_stream_enabled();      // SE_TCM_STREAM=0: the multi-launch path of round 2
-void launch_tcm_stream(const TcmStreamW& f, const TcmFusedHeads& hd, const float* x, float* y, int dil, int K, hipStream_t s);
-// up to 8 blocks that feed each other as one launch (SE_TCM_CHAIN=0: one launch per block)
-bool tcm_chain_enabled();
+// up to 8 blocks that feed each other as one launch
 void launch_tcm_chain(const TcmStreamW* const* f, const TcmFusedHeads* hd, const int* dil, const int* K, int nblk, const float* x,
                       float* y, hipStream_t s);
 

@@ -95,14 +95,12 @@ struct Profiler;
 // stats (optional): [B][dstC][Fout][ceil(T / 32)][2] partial sums of the stored output (GCParams::stats)
 // fz (optional, plans for which conv_folds_interaction() holds): the complex branch's tensor [B][2 * dstC][Fout][Tp] whose
 // interaction with this launch's output is folded into the store (GCParams::fz); fz_planes = 3: fz is the REAL plane of a
-// three-plane tensor [B][3 * dstC][Fout][Tp] = [S | R | I] (gauss.h; the sum plane is the caller's to refresh)
+// three-plane tensor [B][3 * dstC][Fout][Tp] = [S | R | I] (gauss.h; the epilogue that rewrites R and I stores S = R + I too)
 // colstats: `stats` is [B][Fout][T][2] - per (b, output row, frame) sums over all output channels (GCParams::cstats, for a
 // CumulativeLayerNorm behind the layer) - instead of the per-channel partials of an InstanceNorm
 void run_conv(const GCPlan& pl, const Act4& s0, const Act4* s1, float* dst, int dstC, int Fout, int B, int T, int Tp,
               hipStream_t st, Profiler* prof = nullptr, float* stats = nullptr, int t_base = 0, float* fz = nullptr, int fz_planes = 2,
               bool colstats = false, float* dst_elu = nullptr);      // dst_elu: GCParams::dst_elu (gated layers on the matrix path)
-// true: a folded interaction into a three-plane tensor (fz_planes = 3) also stores its sum plane S = R + I
-bool conv_fold_writes_sum();
 inline bool conv_folds_interaction(const GCPlan& pl) { return pl.p.Ws == nullptr && (pl.p.epi == EPI_ACT || pl.p.epi == EPI_ADD); }
 inline bool conv_folds_interaction(const DeconvPlan& pl) {
     if (pl.has_pair || pl.par.empty()) return false;

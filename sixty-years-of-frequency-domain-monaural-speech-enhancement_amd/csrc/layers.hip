@@ -271,9 +271,8 @@ DeconvPlan make_deconv_plan(const DenseW& d, int sf, int pf, int toff, int act, 
             g.p.pad_lo = -pf;
         }
     }
-    static const bool pair_env = !(getenv("SE_GC_PAIR") && atoi(getenv("SE_GC_PAIR")) == 0);
     const bool pair_epi = epi == EPI_ACT || (epi == EPI_GLU && d.M == 2 && slope.empty());     // one gated output channel: rows (value, gate)
-    if (pair_env && sf == 2 && d.M <= 2 && pair_epi && pf >= 0 && out.par.size() == 2 && out.par[0].p.Ws && out.par[1].p.Ws) {
+    if (sf == 2 && d.M <= 2 && pair_epi && pf >= 0 && out.par.size() == 2 && out.par[0].p.Ws && out.par[1].p.Ws) {
         TapSpec un;
         for (int c = 0; c < 2; ++c)
             for (int j = 0; j < cls_taps[c].ntaps; ++j) {
@@ -467,12 +466,7 @@ static void set_fz(GCParams& p, float* fz, int dstC, int Fout, int Tp, int plane
     p.fz_c = (long)Fout * Tp;
     p.fz_f = Tp;
     // three planes [S | R | I] (fz = the R plane): the epilogue that rewrites R and I stores S = R + I as well - no gauss_sum pass
-    static const bool fzs = !(getenv("SE_UF_FOLD_SUM") && atoi(getenv("SE_UF_FOLD_SUM")) == 0);
-    p.fz_s = (planes == 3 && fzs) ? -p.fz_im : 0;
-}
-bool conv_fold_writes_sum() {
-    static const bool fzs = !(getenv("SE_UF_FOLD_SUM") && atoi(getenv("SE_UF_FOLD_SUM")) == 0);
-    return fzs;
+    p.fz_s = planes == 3 ? -p.fz_im : 0;
 }
 
 void run_conv(const GCPlan& pl, const Act4& s0, const Act4* s1, float* dst, int dstC, int Fout, int B, int T, int Tp,

@@ -139,9 +139,8 @@ struct PadFrames {
     bool on = false;
     int T;                  // frame count (row pitch) to run with
     PadFrames(EngineCtx& ctx, int B, int L, int Lpad, int T_true, int olen, hipStream_t st, int mult = 4) : T(T_true) {
-        static const bool env = !(getenv("SE_PAD_FRAMES") && atoi(getenv("SE_PAD_FRAMES")) == 0);
         const int m = mult == 1 ? 1 : pad_frames_mult(mult);      // (mult 1: never pad - the caller's switch is off)
-        if (!env || T_true % m == 0) return;
+        if (T_true % m == 0) return;
         T = (T_true + m - 1) / m * m;
         if (ragged_ctx()) return;          // rows of different lengths already carry their sizes
         const int MB = ctx.max_batch;

@@ -462,7 +462,6 @@ class Dccrn final : public Model {
         // epilogue has no trimming variant; PadFrames gives every offline decode such rows)
         static const bool cmb_env = !(getenv("SE_GAUSS_CMB") && atoi(getenv("SE_GAUSS_CMB")) == 0);
         const bool cmb = cmb_env && T % 4 == 0 && co >= 64;
-        static const bool cmb_sum = !(getenv("SE_GAUSS_CMB_SUM") && atoi(getenv("SE_GAUSS_CMB_SUM")) == 0);      // 0: S by a gauss_sum pass
         Profiler* pf = &ctx.prof;
         const long kz = (long)B * co * Fout * T;
         const Ragged* rg = ragged_ctx();
@@ -497,7 +496,7 @@ class Dccrn final : public Model {
                 q.cmb_neg = 2;                                   // z = 0: I = f(k1 + k2); z = 1: R = f(k1 - k3)
                 const long CPo = (long)co * Fout * T, oR = dst3 ? CPo : 0L, oI = dst3 ? 2 * CPo : CPo;
                 q.dst = dst + oI; q.dst_z = oR - oI; q.d_b = (dst3 ? 3 : 2) * CPo;
-                if (dst3 && cmb_sum) {
+                if (dst3) {
                     // a three-plane output: I first, then R in a launch of its own whose epilogue reads the finished I and writes
                     // S = R + I with it - no gauss_sum pass over the tensor (2.7 % of a step; its 3 units of traffic become 1 re-read)
                     GCParams qi = q;
@@ -522,10 +521,7 @@ class Dccrn final : public Model {
             gc_launch_prof(pl, p, st, pf);
         }
         const long CP = (long)co * Fout * T;
-        if (cmb) {
-            if (dst3 && !cmb_sum) gauss_sum(dst, B, co, Fout, T, st);        // S = R + I for the next three-product layer
-            return;
-        }
+        if (cmb) return;
         const bool timed = pf->on;
         if (timed) pf->begin(st);
         hipLaunchKernelGGL(gauss_combine_kernel, dim3(Fout, co, B), dim3(128), 0, st, b.K, dst, co, Fout, T, kz, dst3 ? 3 * CP : 2 * CP,
@@ -536,10 +532,8 @@ class Dccrn final : public Model {
 
     // spec [B][2][257][T] -> mask in b.D[NL] ([B][2][256][T])
     void network(Bufs& b, const float* spec, hipStream_t st) {
-        // (SE_DCCRN_GAUSS_MINB: first batch on the three products - measured at batch 1 ... 32: the form wins at every batch, 4.37
-        // against 4.66 ms for one clip, so the default is 1)
-        static const int gauss_minb = getenv("SE_DCCRN_GAUSS_MINB") ? atoi(getenv("SE_DCCRN_GAUSS_MINB")) : 1;
-        if (gauss_on && b.B >= gauss_minb) {
+        // (at every batch: measured at batch 1 ... 32 the three products win, 4.37 against 4.66 ms for one clip)
+        if (gauss_on) {
             network_gauss(b, spec, st);
             return;
         }

@@ -364,13 +364,10 @@ class FullSubNet final : public Model {
     }
 
     bool graph_capturable() const override { return false; }     // sub-band halves run on two streams
-    // SE_FSN_FUSE_X=0: the sub-band layers' input projections as batched GEMMs into a [T][4H][S] gate tensor (rnn.h step_x)
-    // (from 16 clips on: below, a step launch is a latency-bound K loop of a few workgroups and a K of 768 instead of 384 costs
-    // more than the batched projection it replaces - one clip: 38 vs 30 utt/s)
-    static bool fuse_x_on(int B) {
-        static const bool on = !(getenv("SE_FSN_FUSE_X") && atoi(getenv("SE_FSN_FUSE_X")) == 0);
-        return on && B >= 16;
-    }
+    // the sub-band layers project their inputs inside the step GEMM (rnn.h step_x) from 16 clips on; below, a step launch is a
+    // latency-bound K loop of a few workgroups and a K of 768 instead of 384 costs more than the batched projection into a
+    // [T][4H][S] gate tensor it replaces (one clip: 38 vs 30 utt/s)
+    static bool fuse_x_on(int B) { return B >= 16; }
 
     // mag [B][257][T] -> maskBT [n*B+b][2][T+2]
     void network(Bufs& b, const float* mag, hipStream_t st) {

@@ -140,7 +140,7 @@ class G2Net final : public Model {
     // (with one kernel per TCM block, k_tcm_stream.hip, the dilated convs and FIRs keep their own ring state and the windows
     // only serve the U-Net's one-frame look-back and the iSTFT overlap: 4 columns - rows of 5 floats instead of 21, and a
     // one-frame access touches a fraction of the cache lines)
-    const int SH = tcm_stream_enabled() ? 4 : 20;
+    const int SH = 4;
     bool stream_supported() const override { return cum; }
     int stream_hc() const override { return SH; }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
@@ -267,7 +267,7 @@ class G2Net final : public Model {
                            st_[0].glance.blk[0].fused.w1 && !(pf && pf->on);
         // (offline the fork is captured into a replayed decode's hipGraph like any other work: the auxiliary streams join the
         // capture through the fork event and leave it through the join events)
-        const bool fork = ((sfork_env && stream_ctx() && tcm_chain_enabled() && !ctx.graphs_wanted()) ||
+        const bool fork = ((sfork_env && stream_ctx() && !ctx.graphs_wanted()) ||
                            (ofork && (!ctx.graphs_wanted() || graph_fork_enabled()))) && b.hxg;
         for (int s = 0; s < (int)st_.size(); ++s) {
             if (fork) {

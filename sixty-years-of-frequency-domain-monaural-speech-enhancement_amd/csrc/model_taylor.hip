@@ -150,7 +150,7 @@ class TaylorSENet final : public Model {
     // (with one kernel per TCM block, k_tcm_stream.hip, the dilated convs and FIRs keep their own ring state and the windows
     // only serve the U-Net's one-frame look-back and the iSTFT overlap: 4 columns - rows of 5 floats instead of 37, and a
     // one-frame access touches a fraction of the cache lines)
-    const int SH = tcm_stream_enabled() ? 4 : 36;
+    const int SH = 4;
     bool stream_supported() const override { return cum; }
     int stream_hc() const override { return SH; }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {

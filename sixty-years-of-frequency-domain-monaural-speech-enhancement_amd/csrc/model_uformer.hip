@@ -63,107 +63,9 @@ __global__ __launch_bounds__(256) void uf_fusion_kernel(float* __restrict__ cplx
     mp[0] = m + (1.f / (1.f + fm_exp(-cm)));
 }
 
-// ---- attention along T (t_att_cplx.py:15-40, :58-67): pq [B][nh*48][F][T] rows (q,k,v) x 16 per head.
-// One block = 256 queries of one (b, f); per head K/V [16][T] go through LDS; online softmax; heads are combined with
-// signs into out [B][nout*16][F][T] (complex: heads 0-3 -> real (+,-,-,-), heads 4-7 -> imag (+,+,+,-); real: 1 head).
-__global__ __launch_bounds__(256) void uf_att_t_kernel(const float* __restrict__ pq, float* __restrict__ out, int F, int T,
-                                                       int nh, const int* __restrict__ tlen) {
-    extern __shared__ float kv[];          // K [T][16], V [T][16]
-    float* Ks = kv;
-    float* Vs = kv + HD * T;
-    const int f = blockIdx.x % F, b = blockIdx.x / F;
-    const int Tkeys = tlen ? tlen[b] : T;  // ragged batch: a clip attends to its own frames only
-    const int t = blockIdx.y * 256 + threadIdx.x;
-    const long P = (long)F * T;
-    const float* base = pq + (long)b * nh * 48 * P + (long)f * T;
-    float accr[HD], acci[HD];
-#pragma unroll
-    for (int d = 0; d < HD; ++d) accr[d] = acci[d] = 0.f;
-    for (int h = 0; h < nh; ++h) {
-        const float* hq = base + (long)h * 48 * P;
-        __syncthreads();
-        // K / V of the head as [T][16] in LDS (key-major): the 16 values of a key are four broadcast 16 B reads in the loop
-        // below instead of sixteen 4 B ones - the loop was bound by LDS instruction issue, not by its FMAs
-        for (int i = threadIdx.x; i < HD * T; i += 256) {
-            const int d = i / T, s = i - d * T;
-            Ks[s * HD + d] = hq[(long)(HD + d) * P + s];
-            Vs[s * HD + d] = hq[(long)(2 * HD + d) * P + s];
-        }
-        __syncthreads();
-        if (t < T) {
-            float q[HD], o[HD];
-#pragma unroll
-            for (int d = 0; d < HD; ++d) {
-                q[d] = hq[(long)d * P + t] * 0.25f;       // / hidden_channel ** 0.5
-                o[d] = 0.f;
-            }
-            // online softmax over chunks of 8 keys: one running-maximum update (one rescale of the 16 accumulators) per
-            // chunk instead of per key, hardware exp (v_exp_f32, ~1 ulp: the weights are normalised by their own sum)
-            float mx = -3.0e38f, l = 0.f;
-            for (int s0 = 0; s0 < Tkeys; s0 += 8) {
-                float e[8];
-                float cm = -3.0e38f;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int s = min(s0 + k, T - 1);
-                    float a = 0.f;
-                    const float4* kp = reinterpret_cast<const float4*>(Ks + s * HD);
-#pragma unroll
-                    for (int d4 = 0; d4 < HD / 4; ++d4) {
-                        const float4 kk = kp[d4];
-                        a = fmaf(q[4 * d4 + 0], kk.x, a);
-                        a = fmaf(q[4 * d4 + 1], kk.y, a);
-                        a = fmaf(q[4 * d4 + 2], kk.z, a);
-                        a = fmaf(q[4 * d4 + 3], kk.w, a);
-                    }
-                    e[k] = (s0 + k < Tkeys) ? a : -3.0e38f;
-                    cm = fmaxf(cm, e[k]);
-                }
-                const float mn = fmaxf(mx, cm);
-                const float corr = fm_exp(mx - mn);
-                l *= corr;
-#pragma unroll
-                for (int d = 0; d < HD; ++d) o[d] *= corr;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int s = min(s0 + k, T - 1);
-                    const float pe = fm_exp(e[k] - mn);          // masked keys: exp(-3e38 - mn) = 0
-                    l += pe;
-                    const float4* vp = reinterpret_cast<const float4*>(Vs + s * HD);
-#pragma unroll
-                    for (int d4 = 0; d4 < HD / 4; ++d4) {
-                        const float4 vv = vp[d4];
-                        o[4 * d4 + 0] = fmaf(pe, vv.x, o[4 * d4 + 0]);
-                        o[4 * d4 + 1] = fmaf(pe, vv.y, o[4 * d4 + 1]);
-                        o[4 * d4 + 2] = fmaf(pe, vv.z, o[4 * d4 + 2]);
-                        o[4 * d4 + 3] = fmaf(pe, vv.w, o[4 * d4 + 3]);
-                    }
-                }
-                mx = mn;
-            }
-            const float inv = 1.f / l;
-            const float sg = (nh == 1) ? 1.f : ((h == 0 || (h >= 4 && h < 7)) ? 1.f : -1.f);
-            if (nh == 1 || h < 4) {
-#pragma unroll
-                for (int d = 0; d < HD; ++d) accr[d] += sg * o[d] * inv;
-            } else {
-#pragma unroll
-                for (int d = 0; d < HD; ++d) acci[d] += sg * o[d] * inv;
-            }
-        }
-    }
-    if (t < T) {
-        const int nout = nh == 1 ? 1 : 2;
-        float* ob = out + (long)b * nout * HD * P + (long)f * T + t;
-#pragma unroll
-        for (int d = 0; d < HD; ++d) {
-            ob[(long)d * P] = accr[d];
-            if (nout == 2) ob[(long)(HD + d) * P] = acci[d];
-        }
-    }
-}
-
-// ---- the same attention on the matrix cores (v_mfma_f32_16x16x4_f32, exact fp32 products): scores and P.V of a
+// ---- attention along T (t_att_cplx.py:15-40, :58-67): pq [B][nh*48][F][T] rows (q,k,v) x 16 per head; online softmax;
+// heads are combined with signs into out [B][nout*16][F][T] (complex: heads 0-3 -> real (+,-,-,-), heads 4-7 -> imag
+// (+,+,+,-); real: 1 head).  On the matrix cores (v_mfma_f32_16x16x4_f32, exact fp32 products): scores and P.V of a
 // 16-query x 16-key tile are 4 + 4 MFMAs instead of 2 x 16 x 16 x 16 VALU FMAs fed by LDS broadcast reads.
 //   S^T[key][query] = K[key][:] . Q[query][:]      A = K tile (lane (m = key, g) holds K[key][4j + g]),  B = Q^T
 //   O^T[d][query]  += V^T[d][key] . P^T[key][query] A = V^T (lane (m = d, g) holds V[4g + j][d]),          B = P^T
@@ -173,6 +75,10 @@ __global__ __launch_bounds__(256) void uf_att_t_kernel(const float* __restrict__
 // (4 waves) 64 * QT queries of one (b, f); K ([16][Tk], dim-major) and V ([T][17], key-major) of a head sit in LDS.
 typedef float uf_x4 __attribute__((ext_vector_type(4)));
 constexpr int UF_QT = 2;
+// keys per LDS block (68 KB of K / V per workgroup: two workgroups per CU at any clip length)
+constexpr int UF_ATT_KB = 512;
+static_assert(((size_t)HD * (UF_ATT_KB + 16) + (size_t)UF_ATT_KB * 17) * sizeof(float) <= 150 * 1024,
+              "the time attention's K / V block must fit the LDS");
 __global__ __launch_bounds__(256) void uf_att_t_mfma_kernel(const float* __restrict__ pq, float* __restrict__ out, int F,
                                                             int T, int nh, int Tk, int KB, const int* __restrict__ tlen) {
     extern __shared__ float kv[];
@@ -814,14 +720,6 @@ class Uformer final : public Model {
     static Act4 view3(const float* t3, int C, int F, int T) {      // its [R | I] planes as a 2 C-channel tensor
         return Act4{t3 + (long)C * F * T, 2 * C, F, 3L * C * F * T, (long)F * T, (long)T};
     }
-    void gauss_sum(float* t3, int B, long CP, hipStream_t st) {
-        Profiler* pf = &ctx.prof;
-        const bool timed = pf->on;
-        if (timed) pf->begin(st);
-        hipLaunchKernelGGL(gauss::gauss_sum_kernel, dim3((unsigned)((CP / 4 + 255) / 256 + 1), B), dim3(256), 0, st, t3, CP);
-        SE_HIP(hipGetLastError());
-        if (timed) pf->end(st, 0.0);
-    }
     void gauss_planes23(const float* x2, float* x3, int B, long CP, hipStream_t st) {
         Profiler* pf = &ctx.prof;
         const bool timed = pf->on;
@@ -906,28 +804,17 @@ class Uformer final : public Model {
         ln(a.ln1, x, b.t1, m * B, CC, P, st);
         pw(a.proj, b.t1, m * CC, b.pq, a.nh * 48, nullptr, B, P, st);
         if (along_t) {
-            // SE_UF_ATT_MFMA=0: the round-1 VALU kernel (kept for the A/B measurement in profiles/)
-            static const bool mfma = !(getenv("SE_UF_ATT_MFMA") && atoi(getenv("SE_UF_ATT_MFMA")) == 0);
-            if (mfma) {
-                // key blocks of <= 512 frames (68 KB of K / V per workgroup: two workgroups per CU at any clip length)
-                static const int kbmax = getenv("SE_UF_ATT_KB") ? std::max(16, atoi(getenv("SE_UF_ATT_KB")) / 16 * 16) : 512;
-                const int KB = std::min((T + 15) / 16 * 16, kbmax);
-                int Tk = KB;
-                if (Tk % 32 != 16) Tk += 16;
-                const size_t lds = ((size_t)HD * Tk + (size_t)KB * 17) * sizeof(float);
-                SE_CHECK(lds <= 150 * 1024, "SE_UF_ATT_KB too large for the LDS-resident T-attention K/V block");
-                static bool seen[64] = {};
-                if (first_on_device(seen))
-                    SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(uf_att_t_mfma_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                hipLaunchKernelGGL(uf_att_t_mfma_kernel, dim3(B * F, (T + 64 * UF_QT - 1) / (64 * UF_QT)), dim3(256), lds, st,
-                                   b.pq, b.t2, F, T, a.nh, Tk, KB, ragged_ctx() ? ragged_ctx()->tlen : nullptr);
-            } else {
-                const size_t lds = (size_t)2 * HD * T * sizeof(float);
-                SE_CHECK(lds <= 64 * 1024, "utterance too long for the LDS-resident T-attention K/V tiles");
-                hipLaunchKernelGGL(uf_att_t_kernel, dim3(B * F, (T + 255) / 256), dim3(256), lds, st, b.pq, b.t2, F, T, a.nh,
-                                   ragged_ctx() ? ragged_ctx()->tlen : nullptr);
-            }
+            // key blocks of <= UF_ATT_KB frames
+            const int KB = std::min((T + 15) / 16 * 16, UF_ATT_KB);
+            int Tk = KB;
+            if (Tk % 32 != 16) Tk += 16;
+            const size_t lds = ((size_t)HD * Tk + (size_t)KB * 17) * sizeof(float);
+            static bool seen[64] = {};
+            if (first_on_device(seen))
+                SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(uf_att_t_mfma_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+            hipLaunchKernelGGL(uf_att_t_mfma_kernel, dim3(B * F, (T + 64 * UF_QT - 1) / (64 * UF_QT)), dim3(256), lds, st,
+                               b.pq, b.t2, F, T, a.nh, Tk, KB, ragged_ctx() ? ragged_ctx()->tlen : nullptr);
         } else {
             SE_CHECK(F <= 8, "F-attention kernel is built for the 4-bin bottleneck");
             // SE_UF_ATT_F_MFMA=0: the VALU kernel of rounds 1-4 (one thread per query)
@@ -1005,7 +892,6 @@ class Uformer final : public Model {
                 SE_CHECK(!out3, "Uformer: three-plane encoder tensors need the folded interaction (SE_UF_FOLD=0 with SE_UF_GAUSS=1)");
                 fusion(b.EC[k], b.ER[k], B, CPk, st);
             }
-            if (out3 && !(fold && conv_fold_writes_sum())) gauss_sum(b.EC[k], B, CPk, st);      // S = R + I of the tensor the interaction has just rewritten (else: stored by the fold's epilogue)
             xc = out3 ? view3(b.EC[k], co, F, T) : act4(b.EC[k], 2 * co, F, T);
             xm = act4(b.ER[k], co, F, T);
         }
@@ -1066,7 +952,6 @@ class Uformer final : public Model {
                 SE_CHECK(!out3, "Uformer: three-plane decoder tensors need the folded interaction (SE_UF_FOLD=0 with SE_UF_GAUSS=1)");
                 fusion(b.DC[k], b.DR[k], B, (long)co * F * T, st);
             }
-            if (out3 && !(fold && conv_fold_writes_sum())) gauss_sum(b.DC[k], B, CPo, st);
             c = b.DC[k];
             c3 = out3;
             m = b.DR[k];

@@ -179,7 +179,7 @@ struct LstmBig {
         gin = make_pointwise_plan(w.wih, ACT_NONE, {}, s_hint);
         step = gc_make_plan(4 * H, H, one_tap(), w.whh.w, {}, {}, ACT_NONE, EPI_LSTM, 1, 1, 0, s_hint);
         step.p.gru = gru ? 1 : 0;
-        static const int fuse_i = getenv("SE_LSTM_FUSE_I") ? atoi(getenv("SE_LSTM_FUSE_I")) : 384;
+        constexpr int fuse_i = 384;      // widest input a layer projects inside its step GEMM
         if (fuse_x && !gru && I <= fuse_i) {
             // Layers that run one GEMM launch per step over many sequences (FullSubNet's sub-band LSTMs: 4 x 384 gate rows over
             // 257 * B sequences): the batched input projection writes [T][4H][S] gate pre-activations - 51 GB at 128 clips, read
@@ -210,7 +210,7 @@ struct LstmBig {
     // (97 TFLOP/s on CRN's 4096 x 1024 projections), one useful column of 64 at batch 1 (LSTM model: 0.9 ms per layer for
     // 3.4 GFLOP).  With the features outermost the T * S (frame, sequence) pairs of a feature are ONE contiguous row and
     // the projection is a full-width GEMM whatever the batch; the cooperative recurrence reads / writes through strides.
-    bool fm_ok(int S) const { return has_fm && coop_enabled() && lstm_coop_supported(H, S, 1); }
+    bool fm_ok(int S) const { return has_fm && lstm_coop_supported(H, S, 1); }
     void run_fm(const float* x, float* G, float* cell, float* out, int T, int S, hipStream_t st, Profiler* prof) const {
         const long N = (long)T * S;
         run_pointwise(gin_fm, x, 0, N, G, 0, N, 1, (int)N, st, prof);
@@ -236,13 +236,6 @@ struct LstmBig {
         if (wih_dev) (void)hipFree(wih_dev);
         if (bih_dev) (void)hipFree(bih_dev);
         whh_dev = wih_dev = bih_dev = nullptr;
-    }
-    static bool coop_enabled() {
-        static const int on = [] {
-            const char* e = getenv("SE_LSTM_COOP");
-            return e ? atoi(e) : 1;
-        }();
-        return on != 0;
     }
     // x [T][I][S] -> out [T][H][S];  G scratch [T][4H][S];  cell scratch [H][S]
     void run(const float* x, float* G, float* cell, float* out, int T, int S, hipStream_t st, Profiler* prof) const {
@@ -298,7 +291,7 @@ struct LstmBig {
     void run_cols(const float* x, long x_t, float* G, float* cell, float* out, long out_t, int out_rs, int T, int S, int c0,
                   int Sn, hipStream_t st, Profiler* prof) const {
         run_pointwise_cols(gin, x + c0, x_t, S, G + c0, 4L * H * S, S, T, Sn, st, prof);
-        if (c0 == 0 && Sn == S && whh_dev && coop_enabled() && lstm_coop_supported(H, S, 1)) {
+        if (c0 == 0 && Sn == S && whh_dev && lstm_coop_supported(H, S, 1)) {
             LstmCoopArgs a{};
             a.gx = G; a.whh = whh_dev; a.out = out; a.cell = cell;
             a.gx_z = 0; a.gx_t = 4L * H * S; a.gx_row = S;
@@ -372,7 +365,7 @@ struct LstmBig {
 // cooperative launch, layer l one frame behind layer l - 1 (k_lstm_coop.hip: lstm_stack_kernel).  false: not applicable.
 inline bool lstm_stack_fm(const LstmBig* const* ly, int L, const float* x, float* G, float* out, int T, hipStream_t st,
                           Profiler* prof) {
-    if (L < 2 || L > 3 || !LstmBig::coop_enabled() || !lstm_stack_supported(ly[0]->H, L)) return false;
+    if (L < 2 || L > 3 || !lstm_stack_supported(ly[0]->H, L)) return false;
     for (int l = 0; l < L; ++l)
         if (!ly[l]->has_fm || !ly[l]->whh_dev || ly[l]->H != ly[0]->H || (l > 0 && (!ly[l]->wih_dev || ly[l]->I != ly[0]->H))) return false;
     const int H = ly[0]->H;
@@ -403,7 +396,7 @@ inline bool lstm_stack_fm(const LstmBig* const* ly, int L, const float* x, float
 // layers one after the other).
 inline bool lstm_stack_chunked_fm(const LstmBig* const* ly, int L, const float* x, float* G, float* cells, float* const* outs, int T, int S,
                                   hipStream_t st, Profiler* prof) {
-    if (L < 2 || L > 4 || !LstmBig::coop_enabled()) return false;
+    if (L < 2 || L > 4) return false;
     const int H = ly[0]->H;
     for (int l = 0; l < L; ++l)
         if (!ly[l]->has_fm || !ly[l]->whh_dev || ly[l]->H != H || (l > 0 && ly[l]->I != H)) return false;
@@ -412,9 +405,8 @@ inline bool lstm_stack_chunked_fm(const LstmBig* const* ly, int L, const float* 
     // bound): batches of long clips (H = 1024: T * S >= ~244 k, e.g. 64 clips of 3 800 frames) go back to the per-layer path, whose
     // launchers fall back by themselves
     if ((double)T * S * 4 * H * 4 >= 4.0e9 || (double)T * S * H >= 4.0e9) return false;
-    static const int chunk_env = getenv("SE_LSTM_CHUNK_T") ? atoi(getenv("SE_LSTM_CHUNK_T")) : 0;
     // chunk length: the pipeline runs (L - 1) chunks longer than the sequence, every launch costs ~3 steps' worth of launch + fill
-    int Tc = chunk_env > 0 ? chunk_env : 48;                 // (measured at batch 64, T = 401: 24 / 36 / 48 / 64 -> CRN 4 907 / 5 022 / 5 281 / 5 204 utt/s)
+    int Tc = 48;                                             // (measured at batch 64, T = 401: 24 / 36 / 48 / 64 -> CRN 4 907 / 5 022 / 5 281 / 5 204 utt/s)
     Tc = std::max(2, std::min(Tc, T)) & ~1;                  // even: a chunk keeps the parity of the exchange slabs
     if (T < 2 * Tc) return false;
     const long N = (long)T * S;
@@ -460,7 +452,7 @@ inline void run_lstm_pair(const LstmBig& l0, const LstmBig& l1, const float* whh
                           hipStream_t st, Profiler* prof) {
     const int H = l0.H;
     const long gz = (long)T * 4 * H * S;
-    if (!(whh2 && LstmBig::coop_enabled() && lstm_coop_supported(H, S, 2))) {
+    if (!(whh2 && lstm_coop_supported(H, S, 2))) {
         l0.run_strided(x0, x_t, G, cell, out0, out_t, out_rs, T, S, st, prof);
         l1.run_strided(x1, x_t, G, cell, out0 + out_z, out_t, out_rs, T, S, st, prof);
         return;

@@ -196,7 +196,7 @@ struct UnetModule {     // En_unet_module (TaylorSENet.py:441-496)
     // in0 (+ optional in1 concatenated on channels), both with F = Fin  ->  out [B][64][out_F][T]
     void run(const Act4& in0, const Act4* in1, float* out, const UnetScratch& s, int B, int T, hipStream_t st,
              Profiler* pf) const {
-        if (in_stats_enabled() && fold_ok()) return run_folded(in0, in1, out, s, B, T, st, pf);
+        if (fold_ok()) return run_folded(in0, in1, out, s, B, T, st, pf);
         const int F0 = out_F(in0.F);
         if (de) {
             deconv_norm2d_prelu(in_d.plan, in_d.na, in0, in1, out, out, 64, F0, B, T, st, pf);

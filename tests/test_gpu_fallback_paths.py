@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWITCHES = {
     'SE_DCCRN_GAUSS': '0', 'SE_UF_GAUSS': '0', 'SE_UF_FOLD': '0', 'SE_GC_PW_BM64': '0', 'SE_GC_WIDE128': '0',
     'SE_LSTM_CHUNK': '0', 'SE_COOP16': '0', 'SE_COOP4': '0', 'SE_GC_DBG': '32',
+    'SE_FSN_SPLIT': '1',       # FullSubNet's sub-band LSTMs over all columns on one stream (the profiling method of profiles/)
 }
 
 
@@ -52,7 +53,8 @@ def test_reference_fixtures_with_the_round5_switches_thrown():
 # equal-length batches run with rows of whole 128 B lines (zero-extended: the cLN variants, CRN, GCRN, DPCRN; as ragged rows of one
 # length: the InstanceNorm networks) - the batch-256 and 4 s fixtures run all of that; here the same fixtures with plain tiles and
 # unpadded rows
-SWITCHES_R6 = {'SE_GC_FLAT': '0', 'SE_CLN_PAD': '1', 'SE_IN_PAD': '1', 'SE_G2NET_FORK': '0'}
+SWITCHES_R6 = {'SE_GC_FLAT': '0', 'SE_CLN_PAD': '1', 'SE_IN_PAD': '1', 'SE_G2NET_FORK': '0',
+               'SE_GCRN_FORK': '0'}   # GCRN's imaginary decoder on the caller's stream (the profiling method of profiles/)
 
 
 @pytest.mark.gpu
