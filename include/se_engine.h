@@ -70,6 +70,13 @@ enum se_model_id {
  * spec_i mask_i).  At most one of the two bits. */
 #define SE_CFG_DCCRN_MASK_C 32
 #define SE_CFG_DCCRN_MASK_R 64
+/* DCCRN(use_clstm=False) (DCCRN/DCCRN_cprs.py:95-102; DCCRN-E / -R / -C of its `__main__`, :303-315): the real-LSTM core - the
+ * 256 x 4 encoder features of a frame as ONE vector into nn.LSTM(1024, rnn_units, num_layers=2) (`enhance.*_l0 / _l1`) and
+ * Linear(rnn_units, 1024) (`tranform.*`) - instead of the complex LSTM.  rnn_units and kernel_num[0] are read from the shapes of
+ * enhance.weight_hh_l0 and encoder.0.0.real_conv.weight; se_engine_finalize accepts (rnn_units, kernel_num) = (256 or 128,
+ * [16,32,64,128,256,256]) and (256, [32,64,128,256,256,256]).  Combines with SE_CFG_DCCRN_MASK_C / _R and the two
+ * complexnn conventions above. */
+#define SE_CFG_DCCRN_REAL_LSTM 128
 /* G2Net / TaylorSENet: the constructor's repeat count, bits 8-11 of se_config.flags.
  *   gaf_base(..., stage_num = n)      G2Net_VB/gaf_net_320.py:27,55-58  (n GAF stages `gafs.<s>.`, 1 <= n <= 8)
  *   TaylorSENet(..., order_num = n)   TaylorSENet/TaylorSENet.py:27,66-70 (n high-order blocks `highorderblock_list.<k>.`, 0 <= n <= 8)

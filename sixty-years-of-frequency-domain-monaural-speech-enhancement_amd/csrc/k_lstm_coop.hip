@@ -1161,6 +1161,19 @@ static int coop_n_cu() {
     }
     return n_cu;
 }
+bool lstm_coop256_supported(int S) {
+    // SE_LSTM_COOP256=0: the per-step GEMM launches of LstmBig instead (the A/B of tests/test_gpu_dccrn_real_lstm.py)
+    static const int on = getenv("SE_LSTM_COOP256") ? atoi(getenv("SE_LSTM_COOP256")) : 1;
+    static const int on16 = getenv("SE_COOP16") ? atoi(getenv("SE_COOP16")) : 1;
+    constexpr int H = 256, US = H / 16;
+    if (!on || !on16 || S < 17 || S > 4096) return false;
+    // the conditions launch_c16<256> checks for a time-major Z = 1 layer (gx_row = out_row = S): one workgroup per CU
+    // (__launch_bounds__(256, 1), grid US x SS <= CUs), 32-bit lane offsets, the tiles' cell states in LDS
+    const int n_cu = coop_n_cu(), NT = (S + 15) / 16;
+    if (US > n_cu || (long)S * H * 8 >= (1L << 31) || (double)S * 4 * H * 4 >= 4.0e9) return false;
+    const int SS = std::max(1, std::min(NT, n_cu / US)), ntl_max = (NT + SS - 1) / SS;
+    return ((size_t)2 * 16 * (H + 4) + (size_t)2 * 4 * 256 + (size_t)4 * ntl_max * 64) * sizeof(float) <= 160 * 1024;
+}
 bool lstm_coop_chunk_supported(int H, int S, int n_layers) {
     static const int on = getenv("SE_LSTM_CHUNK") ? atoi(getenv("SE_LSTM_CHUNK")) : 1;
     if (!on || (H != 512 && H != 1024) || n_layers < 2 || n_layers > 4 || S < 17) return false;
@@ -1312,6 +1325,11 @@ void launch_lstm_coop(const LstmCoopArgs& a, hipStream_t s) {
     SE_CHECK(a.Z * std::max(1, std::min((a.S + 15) / 16, n_cu / ((a.H / 16) * a.Z))) <= 256, "cooperative LSTM: too many slices");
     // one tile: every CU on the K-split form (H = 1024: 7.5 -> 5.1 ... 5.9 us per step for 1 ... 16 sequences; H = 512: 4.4 -> 3.8 at
     // one sequence, nothing from 8 on or with two LSTMs per launch - tools/coopbench.cpp)
+    if (a.H == 256) {            // opt-in width (lstm_coop256_supported): 16-sequence tiles only
+        SE_CHECK(a.Z == 1 && lstm_coop256_supported(a.S) && launch_c16<256>(a, n_cu, s),
+                 "cooperative LSTM at H = 256: one LSTM of 17 - 4096 sequences (lstm_coop256_supported)");
+        return;
+    }
     constexpr int ks_z = 2;      // most LSTMs per launch on the K-split form (two, GCRN: 4.4 -> 2.5 ... 3.0 us)
     if (a.S <= (a.H == 1024 ? 16 : 4) && (a.H == 1024 || a.Z <= ks_z) && (a.H / 4) * a.Z <= n_cu && (a.H / 4) * a.Z <= 256) {
         if (a.H == 1024) launch_ks_n<1024>(a, s);

@@ -331,6 +331,10 @@ struct LstmCoopArgs {
     int lz[4], t0[4], Tz[4];
 };
 bool lstm_coop_supported(int H, int S, int Z);
+// H = 256 on lstm_coop16_kernel<256> (16 workgroups of 16 units per LSTM, 64 KB of W_hh in a workgroup's registers): OPT-IN
+// (LstmBig::build(.., coop256 = true), DCCRN's real-LSTM core) - lstm_coop_supported stays false at 256, so no other layer's
+// kernel selection sees it.  true: launch_lstm_coop runs an H = 256, Z = 1 layer of S sequences in one launch.
+bool lstm_coop256_supported(int S);
 // layers of a stack on consecutive chunks of steps in one cooperative launch (k_lstm_coop.hip: lstm_coop16_kernel); false: the
 // shape has no such kernel.  n_layers = layers of the whole stack (sizes the exchange slabs / `cell` = [n_layers][H][S])
 bool lstm_coop_chunk_supported(int H, int S, int n_layers);

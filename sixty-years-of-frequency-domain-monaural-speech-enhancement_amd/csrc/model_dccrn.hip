@@ -16,6 +16,12 @@
 //     time-major [T][feature][sequence] layout, the recurrence is one fused MFMA GEMM + LSTM-cell epilogue per
 //     frame covering both LSTMs (blockIdx.z) and all 2B sequences; r-i / r+i combinations are folded into the
 //     next layer's weights ([W,-W] / [W,W] two-source GEMMs).
+//   * SE_CFG_DCCRN_REAL_LSTM (`use_clstm=False`, :95-102, :187-192; DCCRN-E / -R / -C): the encoder widths come from the state
+//     dict (KN below: the class default [16,32,64,128,256,256] or the decode script's) and the core is ONE real 2-layer LSTM over
+//     the 1024 features c * 4 + d of a frame (both channel halves) + the `tranform` Linear back to 1024: input projections and
+//     `tranform` are gemmconv GEMMs; the recurrence runs as lstm_persist_kernel<128> (rnn_units 128) or, at 256, as one
+//     lstm_coop16_kernel<256> launch per layer from 17 sequences on and one fused GEMM + cell launch per step below that
+//     (LstmBig).  The three-product (Gauss) layers are a DCCRN-CL-only path.
 #include "rnn.h"
 #include "gauss.h"
 #include "../../include/se_engine.h"
@@ -25,7 +31,8 @@ namespace se {
 namespace {
 
 constexpr int NL = 6;
-constexpr int KN[NL + 1] = {2, 32, 64, 128, 256, 256, 256};
+constexpr int KN_CL[NL + 1] = {2, 32, 64, 128, 256, 256, 256};         // kernel_num of dccrn_decode_vb.py:11
+constexpr int KN_DEFAULT[NL + 1] = {2, 16, 32, 64, 128, 256, 256};    // the class default (DCCRN_cprs.py:18)
 constexpr int NFFT = 512, HOP = 128, NBIN = 257;
 
 struct Bufs {
@@ -53,6 +60,10 @@ class Dccrn final : public Model {
         gc_free_plan(proj);
         if (whh1) (void)hipFree(whh1);
         if (whh2) (void)hipFree(whh2);
+        for (auto& l : rl) l.free();
+        gc_free_plan(tran);
+        for (float* w : rl_whh)
+            if (w) (void)hipFree(w);
     }
     StftGeom default_geom() const override { return StftGeom{NFFT, HOP, NFFT}; }
     int padded_samples(int L) const override {
@@ -72,6 +83,20 @@ class Dccrn final : public Model {
         const bool plain_cat = (ctx.flags & SE_CFG_DCCRN_PLAIN_CAT) != 0;
         SE_CHECK(!((ctx.flags & SE_CFG_DCCRN_MASK_C) && (ctx.flags & SE_CFG_DCCRN_MASK_R)), "DCCRN: masking mode 'C' and 'R' are exclusive");
         mask_mode = (ctx.flags & SE_CFG_DCCRN_MASK_C) ? 1 : ((ctx.flags & SE_CFG_DCCRN_MASK_R) ? 2 : 0);      // DCCRN_cprs.py:205-223
+        rlstm = (ctx.flags & SE_CFG_DCCRN_REAL_LSTM) != 0;
+        std::copy(KN_CL, KN_CL + NL + 1, KN);
+        if (rlstm) {      // widths from the shapes: kernel_num[0] (DCCRN_cprs.py:18) and rnn_units (:95-102)
+            SE_CHECK(sd.has("encoder.0.0.real_conv.weight") && sd.has("enhance.weight_hh_l0"),
+                     "DCCRN real-LSTM form: the state dict has no encoder.0.0.real_conv.weight / enhance.weight_hh_l0");
+            const HostTensor& w0 = sd.get("encoder.0.0.real_conv.weight");
+            const HostTensor& hh = sd.get("enhance.weight_hh_l0");
+            const int k0 = w0.shape.size() == 4 ? 2 * (int)w0.shape[0] : 0;
+            rnn_h = hh.shape.size() == 2 ? (int)hh.shape[1] : 0;
+            SE_CHECK((k0 == 16 && (rnn_h == 128 || rnn_h == 256)) || (k0 == 32 && rnn_h == 256),
+                     "DCCRN(use_clstm=False) is built for (rnn_units, kernel_num) = (256 or 128, [16,32,64,128,256,256]) and (256, "
+                     "[32,64,128,256,256,256]); got rnn_units " + std::to_string(rnn_h) + ", kernel_num[0] " + std::to_string(k0));
+            if (k0 == 16) std::copy(KN_DEFAULT, KN_DEFAULT + NL + 1, KN);
+        }
         auto cplx = [&](const DenseW& wr, const DenseW& wi) {
             DenseW w = complex_expand(wr, wi);          // default: real rows get br - bi, imag rows br + bi
             if (bias_per_part) {
@@ -127,7 +152,7 @@ class Dccrn final : public Model {
         // ---- the layers with >= 128 complex output channels also as Gauss' three products (see GaussLayer); not with the plain-concat
         // convention (a decoder input's [real | imag] halves are then not the halves of its two sources)
         static const int gauss_env = getenv("SE_DCCRN_GAUSS") ? atoi(getenv("SE_DCCRN_GAUSS")) : 2;      // 0: four products everywhere; 1: without decoder 2 (2 354 vs 2 421 utt/s at batch 256)
-        gauss_on = gauss_env != 0 && !plain_cat;
+        gauss_on = gauss_env != 0 && !plain_cat && !rlstm;
         gauss_dec = gauss_env >= 2 ? 3 : 2;
         if (gauss_on) {
             auto three = [](const std::vector<float>& r, const std::vector<float>& i) {
@@ -198,6 +223,19 @@ class Dccrn final : public Model {
                 }
                 tail(g, p, wr, wi);
             }
+        }
+        if (rlstm) {      // ---- nn.LSTM(1024, H, num_layers=2) + tranform Linear(H, 1024) (:95-102)
+            const int H = rnn_h;
+            const LstmW w0 = load_lstm(sd, "enhance.", 0, "", 1024, H), w1 = load_lstm(sd, "enhance.", 1, "", H, H);
+            rl[0].build(w0, ctx.max_batch, false, false, /*coop256*/ true);
+            rl[1].build(w1, ctx.max_batch, false, false, /*coop256*/ true);
+            if (H == 128) {
+                rl_whh[0] = to_device(w0.whh.w);
+                rl_whh[1] = to_device(w1.whh.w);
+            }
+            tran = make_pointwise_plan(linear_weights(sd.get("tranform.weight", {1024, H}), &sd.get("tranform.bias", {1024})), ACT_NONE,
+                                       {}, ctx.max_batch);
+            return;
         }
         // ---- complex LSTM x2 (:80-94), NavieComplexLSTM(1024|256 -> 256 [-> proj 1024])
         auto lstm_w = [&](const std::string& p, int in, DenseW& wih, DenseW& whh) {
@@ -292,9 +330,10 @@ class Dccrn final : public Model {
         ss.B = B;
         ss.first = true;
         for (long rows : stream_rows()) ss.hist.push_back(ss.zeros((size_t)B * rows * DHC, st));
-        for (int l = 0; l < 2; ++l) {           // [2 real LSTMs][128][2B]
-            ss.h[l] = ss.zeros((size_t)2 * 128 * 2 * B, st);
-            ss.c[l] = ss.zeros((size_t)2 * 128 * 2 * B, st);
+        for (int l = 0; l < 2; ++l) {           // [2 real LSTMs][128][2B]  (real-LSTM form: [H][B] per layer)
+            const size_t n = rlstm ? (size_t)rnn_h * B : (size_t)2 * 128 * 2 * B;
+            ss.h[l] = ss.zeros(n, st);
+            ss.c[l] = ss.zeros(n, st);
         }
         (void)max_chunk;
     }
@@ -321,6 +360,9 @@ class Dccrn final : public Model {
             F /= 2;
             x = act4(b.E[k], KN[k + 1], F, Tw);
         }
+        if (rlstm) {
+            real_lstm_core(b, b.E[NL - 1] + DHC, b.D[0] + DHC, Tw, n, st, true);
+        } else {
         // complex LSTM over the n new frames, continuing from the carried state
         const int S = 2 * B;
         for (int part = 0; part < 2; ++part)
@@ -354,6 +396,7 @@ class Dccrn final : public Model {
         for (int part = 0; part < 2; ++part)
             launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)part * 512 * Tw + DHC, n, 512, B, 1024L * B, B,
                                  1024L * Tw, Tw, st);
+        }
         F = 4;
         for (int k = 0; k < NL; ++k) {
             const int cin = KN[NL - k], c0 = DHC - (k + 1);
@@ -373,11 +416,16 @@ class Dccrn final : public Model {
 
   private:
     StreamState ss;
-    static std::vector<long> stream_rows() {      // rows (C * F) of spec, E[0..5], D[0..5], est
-        return {2L * NBIN, 32L * 128, 64L * 64, 128L * 32, 256L * 16, 256L * 8, 256L * 4, 1024L, 256L * 8, 256L * 16, 128L * 32,
-                64L * 64, 32L * 128, 2L * NBIN};
+    std::vector<long> stream_rows() const {      // rows (C * F) of spec, E[0..5], D[0..5], est
+        return {2L * NBIN, KN[1] * 128L, KN[2] * 64L, KN[3] * 32L, KN[4] * 16L, KN[5] * 8L, KN[6] * 4L, 1024L, KN[5] * 8L, KN[4] * 16L,
+                KN[3] * 32L, KN[2] * 64L, KN[1] * 128L, 2L * NBIN};
     }
-    GCPlan enc[NL], g1, g2, proj;
+    int KN[NL + 1] = {2, 32, 64, 128, 256, 256, 256};      // 2 + kernel_num (finalize: KN_CL or KN_DEFAULT)
+    bool rlstm = false;                // SE_CFG_DCCRN_REAL_LSTM
+    int rnn_h = 0;                     // its rnn_units (128 / 256)
+    LstmBig rl[2];                     // its two layers (input projection plans; H = 256: the recurrence too)
+    float* rl_whh[2] = {};             // H = 128: [4H][H] gate-interleaved W_hh for lstm_persist_kernel<128>
+    GCPlan enc[NL], g1, g2, proj, tran;
     GaussLayer genc[NL], gdec[3];      // encoder 3 - 5 / decoder 0 - 1 (- 2) as three real products (gauss_on)
     bool gauss_on = false;
     int mask_mode = 0;                 // 0 'E', 1 'C', 2 'R' (SE_CFG_DCCRN_MASK_*)
@@ -423,6 +471,40 @@ class Dccrn final : public Model {
         b.P = a.alloc_f((size_t)T * 1024 * B);
         cur = b;
         return cur;
+    }
+
+    // real-LSTM core (:187-192) on n frames: src = E[5] at its first frame ([B][256 x 4 = 1024][Tw] rows), dst = D[0] likewise.
+    // Time-major X1 [n][1024][B] -> layer 0 -> H1 [n][H][B] -> layer 1 -> H2 -> tranform -> P [n][1024][B] -> D[0].  stream: continue
+    // from / leave the carried (h, c) of both layers (ss.h / ss.c, [H][B] each).
+    void real_lstm_core(Bufs& b, const float* src, float* dst, int Tw, int n, hipStream_t st, bool stream) {
+        const int B = b.B, H = rnn_h;
+        Profiler* pf = &ctx.prof;
+        launch_transpose_akt(src, b.X1, B, 1024, n, 1024L * Tw, Tw, 1024L * B, B, st);
+        const float* x = b.X1;
+        long x_t = 1024L * B;
+        float* outs[2] = {b.H1, b.H2};
+        float* cells[2] = {b.C1, b.C2};
+        for (int l = 0; l < 2; ++l) {
+            if (H == 128) {
+                run_pointwise_cols(rl[l].gin, x, x_t, B, b.G, 4L * H * B, B, n, B, st, pf);
+                LstmPersistArgs a{};
+                a.st_h = stream ? ss.h[l] : nullptr;
+                a.st_c = stream ? ss.c[l] : nullptr;
+                a.gx = b.G; a.whh = rl_whh[l]; a.out = outs[l];
+                a.gx_t = 4L * H * B; a.gx_row = B;
+                a.out_t = (long)H * B; a.out_row = B;
+                a.H = H; a.T = n; a.S = B; a.Z = 1; a.O = 1; a.reverse = 0;
+                launch_lstm_persist(a, st);
+            } else if (stream) {
+                rl[l].run_stream_strided(x, x_t, b.G, ss.c[l], ss.h[l], outs[l], (long)H * B, 1, n, B, ss.first, st, pf);
+            } else {
+                rl[l].run_strided(x, x_t, b.G, cells[l], outs[l], (long)H * B, 1, n, B, st, pf);
+            }
+            x = outs[l];
+            x_t = (long)H * B;
+        }
+        run_pointwise_cols(tran, b.H2, (long)H * B, B, b.P, 1024L * B, B, n, B, st, pf);
+        launch_transpose_akt(b.P, dst, n, 1024, B, 1024L * B, B, 1024L * Tw, Tw, st);
     }
 
     // both real LSTMs (z) x all 2B sequences, all T steps in one persistent launch (k_lstm.hip)
@@ -550,6 +632,9 @@ class Dccrn final : public Model {
             F /= 2;
             x = act4(b.E[k], KN[k + 1], F, T);
         }
+        if (rlstm) {
+            real_lstm_core(b, b.E[NL - 1], b.D[0], T, T, st, false);
+        } else {
         // ---- complex LSTM (:175-185), time-major, sequences s = part*B + b
         const int S = 2 * B;
         for (int part = 0; part < 2; ++part)
@@ -583,6 +668,7 @@ class Dccrn final : public Model {
         for (int part = 0; part < 2; ++part)
             launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)part * 512 * T, T, 512, B, 1024L * B, B,
                                  1024L * T, T, st);
+        }
         launch_zero_tail(b.D[0], B, 1024L, T, st);
         // ---- decoder with two-source skips (:196-199)
         F = 4;

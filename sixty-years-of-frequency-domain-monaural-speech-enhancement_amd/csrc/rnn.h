@@ -173,7 +173,9 @@ struct LstmBig {
     // kernel only knows the LSTM cell)
     // fuse_x: also pack the [W_hh | W_ih] plan of a step that projects its own input (run_cols_x) - opt-in, only FullSubNet's
     // sub-band layers run it (for LSTM / CRN's 1024-wide layers it would be 19-33 MB of dead device memory per layer)
-    void build(const LstmW& w, int s_hint, bool gru = false, bool fuse_x = false) {
+    // coop256: an H = 256 layer keeps W_hh on the device for lstm_coop16_kernel<256> (lstm_coop256_supported) - opt-in, only
+    // DCCRN's real-LSTM core asks for it
+    void build(const LstmW& w, int s_hint, bool gru = false, bool fuse_x = false, bool coop256 = false) {
         I = w.I;
         H = w.H;
         gin = make_pointwise_plan(w.wih, ACT_NONE, {}, s_hint);
@@ -194,6 +196,7 @@ struct LstmBig {
             step_x = gc_make_plan(4 * H, H + I, one_tap(), wcat, w.wih.bias, {}, ACT_NONE, EPI_LSTM, 1, 1, 0, s_hint, 1, H);
             has_x = true;
         }
+        if (!gru && coop256 && H == 256) whh_dev = to_device(w.whh.w);
         if (!gru && (H == 512 || H == 1024)) {
             whh_dev = to_device(w.whh.w);
             if (I == H) {
@@ -291,7 +294,7 @@ struct LstmBig {
     void run_cols(const float* x, long x_t, float* G, float* cell, float* out, long out_t, int out_rs, int T, int S, int c0,
                   int Sn, hipStream_t st, Profiler* prof) const {
         run_pointwise_cols(gin, x + c0, x_t, S, G + c0, 4L * H * S, S, T, Sn, st, prof);
-        if (c0 == 0 && Sn == S && whh_dev && lstm_coop_supported(H, S, 1)) {
+        if (c0 == 0 && Sn == S && whh_dev && (H == 256 ? lstm_coop256_supported(S) : lstm_coop_supported(H, S, 1))) {
             LstmCoopArgs a{};
             a.gx = G; a.whh = whh_dev; a.out = out; a.cell = cell;
             a.gx_z = 0; a.gx_t = 4L * H * S; a.gx_row = S;

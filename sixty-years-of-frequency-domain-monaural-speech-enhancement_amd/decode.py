@@ -50,12 +50,29 @@ def _build(model, checkpoint, state_dict, **kw):
         net = (models_new if model.endswith('_new') else models).CTSNet(**kw)
         sds = state_dict if state_dict is not None else [load_checkpoint(c) for c in (checkpoint or DEFAULT_CKPT[model])]
         return net.load_state_dicts(*sds)
-    net = MODEL_CLASSES[model](**kw)
     sd = state_dict if state_dict is not None else load_checkpoint(checkpoint or DEFAULT_CKPT[model])
     if isinstance(sd, dict) and 'model_state_dict' in sd:        # TaylorSENet/taylorsenet_decode_vb.py:14-15 wraps it
         sd = sd['model_state_dict']
+    ctor = dccrn_real_lstm_config(sd) if model == 'dccrn' else None
+    if ctor is not None:
+        net = models.DCCRN(**ctor, **kw)
+    else:
+        net = MODEL_CLASSES[model](**kw)
     net.load_state_dict(sd)
     return net
+
+
+def dccrn_real_lstm_config(sd):
+    """The constructor arguments of a real-LSTM DCCRN (`use_clstm=False`, DCCRN_cprs.py:95-102) checkpoint, recognised by its keys
+    `enhance.weight_ih_l0` and `tranform.weight`: rnn_units from enhance.weight_hh_l0 ([4 H, H]) and kernel_num[0] from the first
+    encoder conv ([kernel_num[0] / 2, 1, 5, 2]).  None: not such a checkpoint (DCCRN-CL's keys).  masking_mode is not in a state
+    dict: 'E', as the decode script builds."""
+    if not ('enhance.weight_ih_l0' in sd and 'tranform.weight' in sd):
+        return None
+    units = int(tuple(sd['enhance.weight_hh_l0'].shape)[1])
+    k0 = 2 * int(tuple(sd['encoder.0.0.real_conv.weight'].shape)[0])
+    kn = (16, 32, 64, 128, 256, 256) if k0 == 16 else (32, 64, 128, 256, 256, 256)
+    return dict(rnn_units=units, masking_mode='E', use_clstm=False, kernel_num=list(kn if k0 in (16, 32) else (k0,)))
 
 
 RAGGED_MODELS = frozenset(MODELS)        # every model takes clips of different lengths in one call

@@ -91,20 +91,44 @@ class _EngineModule:
 
 
 class DCCRN(_EngineModule):
-    """DCCRN/DCCRN_cprs.py:8 as built by DCCRN/dccrn_decode_vb.py:11.  forward: [B,2,257,T] -> [B,2,257,T]."""
+    """DCCRN/DCCRN_cprs.py:8 as built by DCCRN/dccrn_decode_vb.py:11 (DCCRN-CL: `use_clstm=True`), or with the real-LSTM core of
+    `use_clstm=False` (DCCRN-E / -R / -C, DCCRN_cprs.py:303-315; SE_CFG_DCCRN_REAL_LSTM).  forward: [B,2,257,T] -> [B,2,257,T]."""
     _model = 'dccrn'
+    SE_CFG_DCCRN_MASK_C = 32
+    SE_CFG_DCCRN_MASK_R = 64
+    SE_CFG_DCCRN_REAL_LSTM = 128
+    # use_clstm=False: the (rnn_units, kernel_num) pairs the engine builds
+    REAL_LSTM_CONFIGS = ((256, (16, 32, 64, 128, 256, 256)), (128, (16, 32, 64, 128, 256, 256)),
+                         (256, (32, 64, 128, 256, 256, 256)))
 
     def __init__(self, rnn_layers=2, rnn_units=128, win_len=512, win_inc=128, fft_len=512, win_type='hanning',
                  masking_mode='E', use_clstm=False, use_cbn=False, kernel_size=5,
                  kernel_num=(16, 32, 64, 128, 256, 256), **kw):
         cfg = (rnn_layers, rnn_units, win_len, win_inc, fft_len, masking_mode, use_clstm, use_cbn, kernel_size,
                tuple(kernel_num))
-        if cfg[:5] + cfg[6:] != (2, 256, 512, 128, 512, True, False, 5, (32, 64, 128, 256, 256, 256)) or masking_mode not in ('E', 'C', 'R'):
-            raise NotImplementedError("the engine builds the decode script's DCCRN configuration "
-                                      "(dccrn_decode_vb.py:11) with masking_mode 'E', 'C' or 'R'; got " + repr(cfg))
-        # masking_mode (DCCRN_cprs.py:205-223): SE_CFG_DCCRN_MASK_C = 32, SE_CFG_DCCRN_MASK_R = 64 (include/se_engine.h)
-        kw['flags'] = kw.get('flags', 0) | {'E': 0, 'C': 32, 'R': 64}[masking_mode]
+        clstm_ok = cfg[:5] + cfg[6:] == (2, 256, 512, 128, 512, True, False, 5, (32, 64, 128, 256, 256, 256))
+        # use_clstm=False: nn.LSTM(num_layers=2) whatever rnn_layers says (DCCRN_cprs.py:95-102)
+        real_ok = (not use_clstm and not use_cbn and (win_len, win_inc, fft_len, kernel_size) == (512, 128, 512, 5)
+                   and (rnn_units, tuple(kernel_num)) in self.REAL_LSTM_CONFIGS)
+        if not (clstm_ok or real_ok) or masking_mode not in ('E', 'C', 'R'):
+            raise NotImplementedError("the engine builds DCCRN with masking_mode 'E', 'C' or 'R' as the decode script's DCCRN-CL "
+                                      "(dccrn_decode_vb.py:11: rnn_units=256, use_clstm=True, kernel_num=[32,64,128,256,256,256]) "
+                                      "or with use_clstm=False, use_cbn=False and (rnn_units, kernel_num) in "
+                                      + repr(self.REAL_LSTM_CONFIGS) + "; got " + repr(cfg))
+        # masking_mode (DCCRN_cprs.py:205-223): SE_CFG_DCCRN_MASK_C / _R (include/se_engine.h)
+        kw['flags'] = kw.get('flags', 0) | {'E': 0, 'C': self.SE_CFG_DCCRN_MASK_C, 'R': self.SE_CFG_DCCRN_MASK_R}[masking_mode]
+        if real_ok:
+            kw['flags'] |= self.SE_CFG_DCCRN_REAL_LSTM
+            self._rlstm = (rnn_units, tuple(kernel_num))
+            self.__class__ = _DCCRNRealLSTM       # same engine model, the real-LSTM key schema
         super().__init__(**kw)
+
+
+class _DCCRNRealLSTM(DCCRN):
+    @_class_or_instance_method
+    def state_dict_schema(cls, self):
+        units, kn = getattr(self, '_rlstm', DCCRN.REAL_LSTM_CONFIGS[0])
+        return schemas.dccrn_rlstm_schema(kn, units)
 
 
 class lstm_net(_EngineModule):

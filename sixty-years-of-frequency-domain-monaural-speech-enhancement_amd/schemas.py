@@ -125,6 +125,21 @@ def dccrn_schema(kernel_num=(32, 64, 128, 256, 256, 256), rnn_units=256, fft_len
     return d
 
 
+
+def dccrn_rlstm_schema(kernel_num=(16, 32, 64, 128, 256, 256), rnn_units=256, fft_len=512):
+    """DCCRN/DCCRN_cprs.py:47-137 with `use_clstm=False` (the class default; DCCRN-E / -R / -C of its `__main__`, :303-315):
+    the same complex encoder / decoder, and a real `nn.LSTM(hidden_dim * kernel_num[-1], rnn_units, num_layers=2)` (two layers
+    whatever `rnn_layers` says, :95-102) + `tranform` Linear(rnn_units, hidden_dim * kernel_num[-1]) as the recurrent core."""
+    d = dccrn_schema(kernel_num, rnn_units, fft_len)
+    for k in [k for k in d if k.startswith('enhance.')]:
+        del d[k]
+    kn = [2] + list(kernel_num)
+    inp = fft_len // (2 ** len(kn)) * kn[-1]
+    _lstm(d, 'enhance.', inp, rnn_units, layers=2)
+    d['tranform.weight'] = ((inp, rnn_units), 'f32')
+    d['tranform.bias'] = ((inp,), 'f32')
+    return d
+
 def fullsubnet_schema(gates=4):
     """FullSubNet/fullsubnet_net_sa/model.py:38-56 with the decode script's sizes (fullsubnet_sa_decode_vb.py:11-24);
     gates=3: `sequence_model="GRU"` (sequence_model.py:36-43)."""
@@ -294,5 +309,8 @@ def cln_variant(schema):
     return out
 
 
-SCHEMAS = {'fullsubnet_gru': fullsubnet_gru_schema, 'taylorsenet': taylorsenet_schema, 'uformer': uformer_schema, 'g2net': g2net_schema, 'cts_step1': cts_step1_schema, 'cts_step2': cts_step2_schema, 'gcrn': gcrn_schema, 'fullsubnet': fullsubnet_schema, 'lstm': lstm_schema, 'crn': crn_schema, 'dpcrn': dpcrn_schema, 'dccrn': dccrn_schema}
+SCHEMAS = {'fullsubnet_gru': fullsubnet_gru_schema, 'taylorsenet': taylorsenet_schema, 'uformer': uformer_schema, 'g2net': g2net_schema, 'cts_step1': cts_step1_schema, 'cts_step2': cts_step2_schema, 'gcrn': gcrn_schema, 'fullsubnet': fullsubnet_schema, 'lstm': lstm_schema, 'crn': crn_schema, 'dpcrn': dpcrn_schema, 'dccrn': dccrn_schema,
+           'dccrn_rlstm': dccrn_rlstm_schema,
+           'dccrn_rlstm128': lambda: dccrn_rlstm_schema(rnn_units=128),
+           'dccrn_rlstm_w32': lambda: dccrn_rlstm_schema(kernel_num=(32, 64, 128, 256, 256, 256))}
 SCHEMAS.update({n + '_new': (lambda n=n: cln_variant(SCHEMAS[n]())) for n in ('cts_step1', 'cts_step2', 'taylorsenet', 'g2net')})

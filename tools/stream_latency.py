@@ -26,6 +26,9 @@ def build(name, B, L):
     if name == 'fullsubnet_cum':        # the causal norm (base_model.py:143-166) is what makes FullSubNet streamable
         from se_amd.models import Model
         return Model(max_batch=B, max_samples=L, norm_type='cumulative_laplace_norm').load_synthetic(15)
+    if name == 'dccrn_e':               # DCCRN(rnn_units=256, masking_mode='E'): the real-LSTM core (opt-in: --models dccrn_e)
+        from se_amd.models import DCCRN
+        return DCCRN(rnn_units=256, masking_mode='E', max_batch=B, max_samples=L).load_synthetic(24)
     return MODEL_CLASSES[name](max_batch=B, max_samples=L).load_synthetic(SEEDS[name])
 
 

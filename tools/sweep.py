@@ -15,7 +15,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 GFLOP = {'lstm': 17.5, 'crn': 17.3, 'gcrn': 13.2, 'dpcrn': 4.8, 'dccrn': 53.4, 'fullsubnet': 238.5, 'ctsnet': 25.6,
-         'g2net': 10.7, 'taylorsenet': 31.3, 'uformer': 27.5}      # SURVEY 8(d), per 4 s utterance
+         'g2net': 10.7, 'taylorsenet': 31.3, 'uformer': 27.5,      # SURVEY 8(d), per 4 s utterance
+         'dccrn_e': 24.9}   # DCCRN(rnn_units=256, masking_mode='E') (opt-in: --models dccrn_e), counted as 'dccrn' 
 
 
 SAMPLES = 64000
@@ -29,6 +30,8 @@ def build(name, B):
         return models.CTSNet(**kw).load_synthetic(17, 18)
     if name == 'ctsnet_new':
         return models_new.CTSNet(**kw).load_synthetic(17, 18)
+    if name == 'dccrn_e':
+        return models.DCCRN(rnn_units=256, masking_mode='E', **kw).load_synthetic(1)
     return models.MODEL_CLASSES[name](**kw).load_synthetic(1)
 
 
@@ -52,6 +55,8 @@ def ragged_pass(name, B, n_clips):
     kw = dict(max_batch=eb, max_samples=el)
     if name.startswith('ctsnet'):
         m = (models_new if name.endswith('_new') else models).CTSNet(**kw).load_synthetic(17, 18)
+    elif name == 'dccrn_e':
+        m = models.DCCRN(rnn_units=256, masking_mode='E', **kw).load_synthetic(1)
     else:
         m = models.MODEL_CLASSES[name](**kw).load_synthetic(1)
     base = torch.from_numpy(synth.synth_clip(5, 'speech', el)).cuda()
