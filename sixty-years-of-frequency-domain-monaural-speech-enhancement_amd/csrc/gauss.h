@@ -1,8 +1,9 @@
-// Gauss' three-product complex (de)conv: the kernels and the per-layer record shared by the models that run their wide complex
-// layers this way (model_dccrn.hip, model_uformer.hip).  DESIGN.md 3.6.
+// Gauss' three-product complex (de)conv: the kernels, the per-layer record, its builders and its launchers, shared by the models
+// that run their wide complex layers this way (model_dccrn.hip, model_uformer.hip).  DESIGN.md 3.6.
 #pragma once
 #include "common.h"
 #include "gemmconv.h"
+#include "kernels.h"
 #include "layers.h"
 #include <vector>
 
@@ -88,7 +89,23 @@ struct GaussLayer {
             if (*p) { (void)hipFree(*p); *p = nullptr; }
     }
 };
-
+// the combine's per-row parameters (rows [real; imag] of 2 co): eval BatchNorm and the conv's row bias as scale / shift, the PReLU
+// slopes.  bias and the BatchNorm tensors are [2 co] (a BatchNorm shared by both parts comes duplicated: Uformer's dup2)
+inline void fold_tail(GaussLayer& g, const std::vector<float>& bias, const HostTensor& ga, const HostTensor& be, const HostTensor& mu,
+                      const HostTensor& va, const std::vector<float>& slope) {
+    const int n = 2 * g.co;
+    SE_CHECK((int)bias.size() == n && (int)ga.numel() == n && (int)be.numel() == n && (int)mu.numel() == n && (int)va.numel() == n &&
+                 (int)slope.size() == n, "three-product layer: BatchNorm / bias / PReLU row count");
+    std::vector<float> sc(n), sh(n);
+    for (int m = 0; m < n; ++m) {
+        const double k = (double)ga.data[m] / std::sqrt((double)va.data[m] + 1e-5);
+        sc[m] = (float)k;
+        sh[m] = (float)((double)be.data[m] - (double)mu.data[m] * k + (double)bias[m] * k);
+    }
+    g.sc = to_device(sc);
+    g.sh = to_device(sh);
+    g.slope = to_device(slope);
+}
 
 // a two-plane tensor [B][2 C][P] = [R | I] -> three planes [B][3 C][P] = [R + I | R | I] (a tensor produced by block-form layers
 // that a three-product layer reads)
@@ -164,6 +181,102 @@ inline void make_deconv_plans(GaussLayer& g, const DenseW& wr, const DenseW& wi,
         g.pl.push_back(gc_make_plan(co, ci, ts, three_products(r, i), {}, {}, ACT_NONE, EPI_ACT, 1, 2, par, tout, 3, c0split));
         g.pl.back().flop_scale = 4.0 / 3.0;
     }
+}
+
+// ---- launchers.  A three-plane tensor [B][3 C][F][T]: S = R + I at +0, R at + C F T, I at + 2 C F T
+inline Act4 view3(const float* t3, int C, int F, int T) {      // its [R | I] planes as a 2 C-channel tensor
+    return Act4{t3 + (long)C * F * T, 2 * C, F, 3L * C * F * T, (long)F * T, (long)T};
+}
+static void launch_sum(float* t3, int B, int C, int F, int T, hipStream_t st, Profiler* pf) {      // S = R + I
+    const long CP = (long)C * F * T;
+    const bool timed = pf->on;
+    if (timed) pf->begin(st);
+    hipLaunchKernelGGL(gauss_sum_kernel, dim3((unsigned)((CP / 4 + 255) / 256 + 1), B), dim3(256), 0, st, t3, CP);
+    SE_HIP(hipGetLastError());
+    if (timed) pf->end(st, 0.0);
+}
+static void launch_planes23(const float* x2, float* x3, int B, long CP, hipStream_t st, Profiler* pf) {
+    const bool timed = pf->on;
+    if (timed) pf->begin(st);
+    hipLaunchKernelGGL(gauss_planes23_kernel, dim3((unsigned)((CP / 4 + 255) / 256 + 1), B), dim3(256), 0, st, x2, x3, CP);
+    SE_HIP(hipGetLastError());
+    if (timed) pf->end(st, 0.0);
+}
+// y = PReLU(BN(complex (de)conv(x))) of one layer: the grouped three-product launch(es), then (without the combine epilogue) the
+// combine pass.  src0 / src1: three-plane tensors of C0 / C1 complex channels (src1 = null: one source); dst3: a three-plane output
+// (else [R | I] only); sum_plane (dst3 only): the layer stores S = R + I as well - else its caller does, as Uformer's folded branch
+// interaction must; K: scratch of the products
+static void run_layer(const GaussLayer& g, const float* src0, int C0, const float* src1, int C1, int Fin, int Fout, int B, int T,
+                      float* dst, bool dst3, bool sum_plane, float* K, hipStream_t st, Profiler* pf) {
+    SE_CHECK(dst3 || !sum_plane, "three-product layer: a sum plane needs a three-plane output");
+    const int co = g.co;
+    // SE_GAUSS_CMB=0: three products into scratch + the combine pass (round 4).  Rows of whole 16 B groups only (the combine
+    // epilogue has no trimming variant; PadFrames gives every offline decode such rows)
+    static const bool cmb_env = !(getenv("SE_GAUSS_CMB") && atoi(getenv("SE_GAUSS_CMB")) == 0);
+    const bool cmb = cmb_env && T % 4 == 0 && co >= 64;
+    const long CP = (long)co * Fout * T, kz = (long)B * CP, oR = dst3 ? CP : 0L, oI = dst3 ? 2 * CP : CP;
+    const Ragged* rg = ragged_ctx();
+    for (const GCPlan& pl : g.pl) {
+        GCParams p = pl.p;
+        p.src0 = src0; p.C0 = C0; p.s0_b = 3L * C0 * Fin * T; p.s0_c = (long)Fin * T; p.s0_f = T; p.src0_z = (long)C0 * Fin * T;
+        if (src1) {
+            p.src1 = src1; p.C1 = C1; p.s1_b = 3L * C1 * Fin * T; p.s1_c = (long)Fin * T; p.s1_f = T; p.src1_z = (long)C1 * Fin * T;
+        } else {
+            p.src1 = nullptr; p.C1 = 0;
+        }
+        p.Fin = Fin; p.Tin = T; p.B = B; p.Tout = T;
+        p.Q = (Fout - p.po + p.so - 1) / p.so;
+        p.dst = K; p.d_b = CP; p.d_c = (long)Fout * T; p.d_f = T; p.dst_z = kz;
+        if (rg) p.tlen = rg->tlen;
+        if (!cmb) {
+            gc_launch_prof(pl, p, st, pf);
+            continue;
+        }
+        // k1 = Wr (xr + xi) alone, then k2 / k3 as a grouped launch of two whose epilogue (EPI_CMB) reads k1 and stores the
+        // finished planes: I = f(k1 + k2), R = f(k1 - k3) - no k2 / k3 scratch, no combine pass (round 4: 5 % of a step)
+        GCParams p1 = p;
+        p1.Z = 1;
+        p1.tlen = nullptr;
+        gc_launch_prof(pl, p1, st, pf);
+        GCParams q = p;
+        q.Z = 2;
+        q.A = pl.p.A + pl.p.A_z;
+        q.src0 = p.src0 + p.src0_z;
+        if (src1) q.src1 = p.src1 + p.src1_z;
+        q.epi = EPI_CMB;
+        q.bias = nullptr;
+        q.aux = K; q.x_b = p.d_b; q.x_c = p.d_c; q.x_f = p.d_f; q.aux_z = 0;
+        q.post_scale = g.sc + co; q.post_shift = g.sh + co; q.slope = g.slope + co; q.ps_z = -co;
+        q.cmb_neg = 2;                                   // z = 0: I = f(k1 + k2); z = 1: R = f(k1 - k3)
+        q.dst = dst + oI; q.dst_z = oR - oI; q.d_b = (dst3 ? 3 : 2) * CP;
+        if (!sum_plane) {
+            gc_launch_prof(pl, q, st, pf);
+            continue;
+        }
+        // I first, then R in a launch of its own whose epilogue reads the finished I and writes S = R + I with it - no gauss_sum
+        // pass over the tensor (2.7 % of a DCCRN step; its 3 units of traffic become 1 re-read)
+        GCParams qi = q;
+        qi.Z = 1;
+        gc_launch_prof(pl, qi, st, pf);
+        GCParams qr = q;
+        qr.Z = 1;
+        qr.A = q.A + pl.p.A_z;
+        qr.src0 = q.src0 + p.src0_z;
+        if (src1) qr.src1 = q.src1 + p.src1_z;
+        qr.post_scale = g.sc; qr.post_shift = g.sh; qr.slope = g.slope;
+        qr.cmb_neg = 1;
+        qr.dst = dst + oR;
+        qr.cmb_i = dst + oI;
+        qr.cmb_s = dst;
+        gc_launch_prof(pl, qr, st, pf);
+    }
+    if (cmb) return;
+    const bool timed = pf->on;
+    if (timed) pf->begin(st);
+    hipLaunchKernelGGL(gauss_combine_kernel, dim3(Fout, co, B), dim3(128), 0, st, K, dst, co, Fout, T, kz, dst3 ? 3 * CP : 2 * CP,
+                       sum_plane ? 0L : -1L, oR, oI, g.sc, g.sh, g.slope, rg ? rg->tlen : nullptr);
+    SE_HIP(hipGetLastError());
+    if (timed) pf->end(st, 0.0);
 }
 
 }  // namespace gauss

@@ -28,6 +28,9 @@ DenseW linear_weights(const HostTensor& w, const HostTensor* b);
 // complexnn-style complex layer from its real_conv / imag_conv halves (channels = [real half ; imag half]):
 //   out_r = Wr*x_r - Wi*x_i + (br - bi);  out_i = Wi*x_r + Wr*x_i + (br + bi)
 DenseW complex_expand(const DenseW& wr, const DenseW& wi);
+// permute_cin order of such a layer over two sources a, b of h complex channels each: the reference's per-part concatenation
+// [a_r, b_r | a_i, b_i] -> the engine's two-source order [a_r, a_i | b_r, b_i]
+std::vector<int> complex_cat_perm(int h);
 // eval-mode BatchNorm on the output channels, folded into w / bias.
 void fold_bn(DenseW& d, const HostTensor& gamma, const HostTensor& beta, const HostTensor& mean,
              const HostTensor& var, float eps = 1e-5f);

@@ -104,6 +104,17 @@ DenseW complex_expand(const DenseW& wr, const DenseW& wi) {
     return d;
 }
 
+std::vector<int> complex_cat_perm(int h) {
+    std::vector<int> perm(4 * h);
+    for (int c = 0; c < h; ++c) {
+        perm[c] = c;
+        perm[h + c] = 2 * h + c;
+        perm[2 * h + c] = h + c;
+        perm[3 * h + c] = 3 * h + c;
+    }
+    return perm;
+}
+
 void fold_bn(DenseW& d, const HostTensor& gamma, const HostTensor& beta, const HostTensor& mean, const HostTensor& var,
              float eps) {
     SE_CHECK((int)gamma.numel() == d.M && (int)var.numel() == d.M, "BatchNorm channel count");

@@ -43,10 +43,6 @@ struct Bufs {
     float *X1 = nullptr, *G = nullptr, *H1 = nullptr, *H2 = nullptr, *C1 = nullptr, *C2 = nullptr, *P = nullptr, *K = nullptr;
 };
 
-using gauss::GaussLayer;
-using gauss::gauss_sum_kernel;
-using gauss::gauss_combine_kernel;
-
 class Dccrn final : public Model {
   public:
     explicit Dccrn(EngineCtx& c) : Model(c) {}
@@ -108,6 +104,11 @@ class Dccrn final : public Model {
             }
             return w;
         };
+        // the layers with >= 128 complex output channels also as Gauss' three products (gauss.h): encoder 3 - 5, decoder 0 - 1 (- 2);
+        // not with the plain-concat convention (a decoder input's [real | imag] halves are then not the halves of its two sources)
+        static const int gauss_env = getenv("SE_DCCRN_GAUSS") ? atoi(getenv("SE_DCCRN_GAUSS")) : 2;      // 0: four products everywhere; 1: without decoder 2 (2 354 vs 2 421 utt/s at batch 256)
+        gauss_on = gauss_env != 0 && !plain_cat && !rlstm;
+        gauss_dec = gauss_env >= 2 ? 3 : 2;
         // ---- encoder (DCCRN_cprs.py:62-77): ComplexConv2d(k=(5,2), s=(2,1), pad=(2,1) causal) + BN + PReLU
         for (int k = 0; k < NL; ++k) {
             const std::string p = "encoder." + std::to_string(k) + ".";
@@ -115,9 +116,15 @@ class Dccrn final : public Model {
             DenseW wr = conv_weights(sd.get(p + "0.real_conv.weight", {co, ci, 5, 2}), &sd.get(p + "0.real_conv.bias", {co}), false);
             DenseW wi = conv_weights(sd.get(p + "0.imag_conv.weight", {co, ci, 5, 2}), &sd.get(p + "0.imag_conv.bias", {co}), false);
             DenseW w = cplx(wr, wi);
-            fold_bn(w, sd.get(p + "1.weight", {2 * co}), sd.get(p + "1.bias", {2 * co}), sd.get(p + "1.running_mean", {2 * co}),
-                    sd.get(p + "1.running_var", {2 * co}));
-            enc[k] = make_conv_plan(w, 2, 2, 1, 1, 1, ACT_PRELU, prelu_slopes(sd.get(p + "2.weight"), 2 * co), EPI_ACT, tout);
+            const HostTensor &ga = sd.get(p + "1.weight", {2 * co}), &be = sd.get(p + "1.bias", {2 * co}),
+                             &mu = sd.get(p + "1.running_mean", {2 * co}), &va = sd.get(p + "1.running_var", {2 * co});
+            const std::vector<float> slope = prelu_slopes(sd.get(p + "2.weight"), 2 * co);
+            if (gauss_on && k >= 3) {
+                gauss::make_conv_plans(genc[k], wr, wi, tout);
+                gauss::fold_tail(genc[k], w.bias, ga, be, mu, va, slope);
+            }
+            fold_bn(w, ga, be, mu, va);
+            enc[k] = make_conv_plan(w, 2, 2, 1, 1, 1, ACT_PRELU, slope, EPI_ACT, tout);
         }
         // ---- decoder (:98-137): ComplexConvTranspose2d(k=(5,2), s=(2,1), pad=(2,0), out_pad=(1,0)) [+ BN + PReLU]
         for (int k = 0; k < NL; ++k) {
@@ -130,99 +137,21 @@ class Dccrn final : public Model {
             // reference channel order after complex_cat([out, skip]) (:197): [out_r, skip_r, out_i, skip_i];
             // engine order (two-source K loop): [out_r, out_i | skip_r, skip_i].  SE_CFG_DCCRN_PLAIN_CAT: complex_cat is
             // a plain torch.cat - the reference order is already the engine order
-            const int h = ci / 2;
-            std::vector<int> perm(4 * h);
-            for (int c = 0; c < h; ++c) {
-                perm[c] = c;
-                perm[h + c] = 2 * h + c;
-                perm[2 * h + c] = h + c;
-                perm[3 * h + c] = 3 * h + c;
-            }
-            if (!plain_cat) permute_cin(w, perm);
+            if (!plain_cat) permute_cin(w, complex_cat_perm(ci / 2));
             std::vector<float> slope;
             int act = ACT_NONE;
             if (k < NL - 1) {
-                fold_bn(w, sd.get(p + "1.weight", {2 * co}), sd.get(p + "1.bias", {2 * co}),
-                        sd.get(p + "1.running_mean", {2 * co}), sd.get(p + "1.running_var", {2 * co}));
-                slope = prelu_slopes(sd.get(p + "2.weight"), 2 * co);
-                act = ACT_PRELU;
-            }
-            dec[k] = make_deconv_plan(w, 2, 2, /*toff: out[..., 1:] :199*/ 1, act, slope, tout, /*C0 = out channels*/ 2 * h);
-        }
-        // ---- the layers with >= 128 complex output channels also as Gauss' three products (see GaussLayer); not with the plain-concat
-        // convention (a decoder input's [real | imag] halves are then not the halves of its two sources)
-        static const int gauss_env = getenv("SE_DCCRN_GAUSS") ? atoi(getenv("SE_DCCRN_GAUSS")) : 2;      // 0: four products everywhere; 1: without decoder 2 (2 354 vs 2 421 utt/s at batch 256)
-        gauss_on = gauss_env != 0 && !plain_cat && !rlstm;
-        gauss_dec = gauss_env >= 2 ? 3 : 2;
-        if (gauss_on) {
-            auto three = [](const std::vector<float>& r, const std::vector<float>& i) {
-                std::vector<float> w(3 * r.size());
-                for (size_t k = 0; k < r.size(); ++k) { w[k] = r[k]; w[r.size() + k] = i[k] - r[k]; w[2 * r.size() + k] = r[k] + i[k]; }
-                return w;
-            };
-            auto tail = [&](GaussLayer& g, const std::string& p, const DenseW& wr, const DenseW& wi) {
-                const int co = wr.M;
-                g.co = co;
                 const HostTensor &ga = sd.get(p + "1.weight", {2 * co}), &be = sd.get(p + "1.bias", {2 * co}),
                                  &mu = sd.get(p + "1.running_mean", {2 * co}), &va = sd.get(p + "1.running_var", {2 * co});
-                std::vector<float> sc(2 * co), sh(2 * co);
-                for (int m = 0; m < 2 * co; ++m) {
-                    const int c = m % co;
-                    const float bias = bias_per_part ? (m < co ? wr.bias[c] : wi.bias[c]) : (m < co ? wr.bias[c] - wi.bias[c] : wr.bias[c] + wi.bias[c]);
-                    const double k = (double)ga.data[m] / std::sqrt((double)va.data[m] + 1e-5);
-                    sc[m] = (float)k;
-                    sh[m] = (float)((double)be.data[m] - (double)mu.data[m] * k + (double)bias * k);
+                slope = prelu_slopes(sd.get(p + "2.weight"), 2 * co);
+                if (gauss_on && k < gauss_dec) {      // complex input channels: [previous (ci / 2) | skip (ci / 2)] (:197)
+                    gauss::make_deconv_plans(gdec[k], wr, wi, /*toff*/ 1, /*c0split*/ ci / 2, tout);
+                    gauss::fold_tail(gdec[k], w.bias, ga, be, mu, va, slope);
                 }
-                g.sc = to_device(sc);
-                g.sh = to_device(sh);
-                g.slope = to_device(prelu_slopes(sd.get(p + "2.weight"), 2 * co));
-            };
-            for (int k = 3; k < NL; ++k) {
-                const std::string p = "encoder." + std::to_string(k) + ".";
-                const int ci = KN[k] / 2, co = KN[k + 1] / 2;
-                DenseW wr = conv_weights(sd.get(p + "0.real_conv.weight", {co, ci, 5, 2}), &sd.get(p + "0.real_conv.bias", {co}), false);
-                DenseW wi = conv_weights(sd.get(p + "0.imag_conv.weight", {co, ci, 5, 2}), &sd.get(p + "0.imag_conv.bias", {co}), false);
-                TapSpec ts;
-                ts.ntaps = 10;
-                for (int kf = 0; kf < 5; ++kf)
-                    for (int kt = 0; kt < 2; ++kt) { ts.df[kf * 2 + kt] = kf - 2; ts.dt[kf * 2 + kt] = kt - 1; }       // as make_conv_plan(w, 2, 2, 1, 1, 1, ..)
-                GaussLayer& g = genc[k];
-                g.pl.push_back(gc_make_plan(co, ci, ts, three(wr.w, wi.w), {}, {}, ACT_NONE, EPI_ACT, 2, 1, 0, tout, 3));
-                g.pl.back().flop_scale = 4.0 / 3.0;          // the profiler books the reference's four products
-                tail(g, p, wr, wi);
+                fold_bn(w, ga, be, mu, va);
+                act = ACT_PRELU;
             }
-            for (int k = 0; k < gauss_dec; ++k) {
-                const int idx = NL - k;
-                const std::string p = "decoder." + std::to_string(k) + ".";
-                const int ci = KN[idx], co = KN[idx - 1] / 2;      // complex input channels: [previous (ci / 2) | skip (ci / 2)] (:197)
-                DenseW wr = deconv_weights(sd.get(p + "0.real_conv.weight", {ci, co, 5, 2}), &sd.get(p + "0.real_conv.bias", {co}), false);
-                DenseW wi = deconv_weights(sd.get(p + "0.imag_conv.weight", {ci, co, 5, 2}), &sd.get(p + "0.imag_conv.bias", {co}), false);
-                GaussLayer& g = gdec[k];
-                for (int par = 0; par < 2; ++par) {          // output-parity classes, as make_deconv_plan(w, 2, 2, 1, ..)
-                    TapSpec ts;
-                    std::vector<int> sel;
-                    for (int kf = 0; kf < 5; ++kf) {
-                        const int num = par + 2 - kf;
-                        if (((num % 2) + 2) % 2 != 0) continue;
-                        for (int kt = 0; kt < 2; ++kt) {
-                            ts.df[ts.ntaps] = num / 2;
-                            ts.dt[ts.ntaps] = 1 - kt;
-                            ts.ntaps++;
-                            sel.push_back(kf * 2 + kt);
-                        }
-                    }
-                    std::vector<float> r((size_t)co * ci * ts.ntaps), i(r.size());
-                    for (int m = 0; m < co; ++m)
-                        for (int c = 0; c < ci; ++c)
-                            for (int j = 0; j < ts.ntaps; ++j) {
-                                r[((size_t)m * ci + c) * ts.ntaps + j] = wr.w[((size_t)m * ci + c) * 10 + sel[j]];
-                                i[((size_t)m * ci + c) * ts.ntaps + j] = wi.w[((size_t)m * ci + c) * 10 + sel[j]];
-                            }
-                    g.pl.push_back(gc_make_plan(co, ci, ts, three(r, i), {}, {}, ACT_NONE, EPI_ACT, 1, 2, par, tout, 3, ci / 2));
-                    g.pl.back().flop_scale = 4.0 / 3.0;
-                }
-                tail(g, p, wr, wi);
-            }
+            dec[k] = make_deconv_plan(w, 2, 2, /*toff: out[..., 1:] :199*/ 1, act, slope, tout, /*C0 = out channels*/ ci);
         }
         if (rlstm) {      // ---- nn.LSTM(1024, H, num_layers=2) + tranform Linear(H, 1024) (:95-102)
             const int H = rnn_h;
@@ -426,7 +355,7 @@ class Dccrn final : public Model {
     LstmBig rl[2];                     // its two layers (input projection plans; H = 256: the recurrence too)
     float* rl_whh[2] = {};             // H = 128: [4H][H] gate-interleaved W_hh for lstm_persist_kernel<128>
     GCPlan enc[NL], g1, g2, proj, tran;
-    GaussLayer genc[NL], gdec[3];      // encoder 3 - 5 / decoder 0 - 1 (- 2) as three real products (gauss_on)
+    gauss::GaussLayer genc[NL], gdec[3];      // encoder 3 - 5 / decoder 0 - 1 (- 2) as three real products (gauss_on)
     bool gauss_on = false;
     int mask_mode = 0;                 // 0 'E', 1 'C', 2 'R' (SE_CFG_DCCRN_MASK_*)
     int gauss_dec = 2;                 // decoder layers on the three-product path (SE_DCCRN_GAUSS = 2: 3 of them, = 1: 2)
@@ -522,96 +451,6 @@ class Dccrn final : public Model {
         launch_lstm_persist(a, st);
     }
 
-    // ---- three-product layers: launch helpers.  A three-plane tensor [B][3 C][F][T]: S at +0, R at + C F T, I at + 2 C F T.
-    static Act4 view3(const float* t3, int C, int F, int T) {      // its [R | I] planes as a 2 C-channel tensor
-        return Act4{t3 + (long)C * F * T, 2 * C, F, 3L * C * F * T, (long)F * T, (long)T};
-    }
-    void gauss_sum(float* t3, int B, int C, int F, int T, hipStream_t st) {
-        const long CP = (long)C * F * T;
-        Profiler* pf = &ctx.prof;
-        const bool timed = pf->on;
-        if (timed) pf->begin(st);
-        hipLaunchKernelGGL(gauss_sum_kernel, dim3((unsigned)((CP / 4 + 255) / 256 + 1), B), dim3(256), 0, st, t3, CP);
-        SE_HIP(hipGetLastError());
-        if (timed) pf->end(st, 0.0);
-    }
-    // y = act(BN(complex (de)conv(x))): the grouped three-product launch(es) into b.K, then the combine pass.  src0 / src1:
-    // three-plane tensors of C0 / C1 complex channels (src1 = null: one source); dst3: three-plane output (else [R | I] only)
-    void gauss_layer(const GaussLayer& g, Bufs& b, const float* src0, int C0, const float* src1, int C1, int Fin, int Fout, float* dst,
-                     bool dst3, hipStream_t st) {
-        const int B = b.B, T = b.T, co = g.co;
-        // SE_GAUSS_CMB=0: three products into scratch + the combine pass (round 4).  Rows of whole 16 B groups only (the combine
-        // epilogue has no trimming variant; PadFrames gives every offline decode such rows)
-        static const bool cmb_env = !(getenv("SE_GAUSS_CMB") && atoi(getenv("SE_GAUSS_CMB")) == 0);
-        const bool cmb = cmb_env && T % 4 == 0 && co >= 64;
-        Profiler* pf = &ctx.prof;
-        const long kz = (long)B * co * Fout * T;
-        const Ragged* rg = ragged_ctx();
-        for (const GCPlan& pl : g.pl) {
-            GCParams p = pl.p;
-            p.src0 = src0; p.C0 = C0; p.s0_b = 3L * C0 * Fin * T; p.s0_c = (long)Fin * T; p.s0_f = T; p.src0_z = (long)C0 * Fin * T;
-            if (src1) {
-                p.src1 = src1; p.C1 = C1; p.s1_b = 3L * C1 * Fin * T; p.s1_c = (long)Fin * T; p.s1_f = T; p.src1_z = (long)C1 * Fin * T;
-            } else {
-                p.src1 = nullptr; p.C1 = 0;
-            }
-            p.Fin = Fin; p.Tin = T; p.B = B; p.Tout = T;
-            p.Q = (Fout - p.po + p.so - 1) / p.so;
-            p.dst = b.K; p.d_b = (long)co * Fout * T; p.d_c = (long)Fout * T; p.d_f = T; p.dst_z = kz;
-            if (rg) p.tlen = rg->tlen;
-            if (cmb) {
-                // k1 = Wr (xr + xi) alone, then k2 / k3 as a grouped launch of two whose epilogue (EPI_CMB) reads k1 and stores the
-                // finished planes: I = f(k1 + k2), R = f(k1 - k3) - no k2 / k3 scratch, no combine pass (round 4: 5 % of a step)
-                GCParams p1 = p;
-                p1.Z = 1;
-                p1.tlen = nullptr;
-                gc_launch_prof(pl, p1, st, pf);
-                GCParams q = p;
-                q.Z = 2;
-                q.A = pl.p.A + pl.p.A_z;
-                q.src0 = p.src0 + p.src0_z;
-                if (src1) q.src1 = p.src1 + p.src1_z;
-                q.epi = EPI_CMB;
-                q.bias = nullptr;
-                q.aux = b.K; q.x_b = p.d_b; q.x_c = p.d_c; q.x_f = p.d_f; q.aux_z = 0;
-                q.post_scale = g.sc + co; q.post_shift = g.sh + co; q.slope = g.slope + co; q.ps_z = -co;
-                q.cmb_neg = 2;                                   // z = 0: I = f(k1 + k2); z = 1: R = f(k1 - k3)
-                const long CPo = (long)co * Fout * T, oR = dst3 ? CPo : 0L, oI = dst3 ? 2 * CPo : CPo;
-                q.dst = dst + oI; q.dst_z = oR - oI; q.d_b = (dst3 ? 3 : 2) * CPo;
-                if (dst3) {
-                    // a three-plane output: I first, then R in a launch of its own whose epilogue reads the finished I and writes
-                    // S = R + I with it - no gauss_sum pass over the tensor (2.7 % of a step; its 3 units of traffic become 1 re-read)
-                    GCParams qi = q;
-                    qi.Z = 1;
-                    gc_launch_prof(pl, qi, st, pf);
-                    GCParams qr = q;
-                    qr.Z = 1;
-                    qr.A = q.A + pl.p.A_z;
-                    qr.src0 = q.src0 + p.src0_z;
-                    if (src1) qr.src1 = q.src1 + p.src1_z;
-                    qr.post_scale = g.sc; qr.post_shift = g.sh; qr.slope = g.slope;
-                    qr.cmb_neg = 1;
-                    qr.dst = dst + oR;
-                    qr.cmb_i = dst + oI;
-                    qr.cmb_s = dst;
-                    gc_launch_prof(pl, qr, st, pf);
-                    continue;
-                }
-                gc_launch_prof(pl, q, st, pf);
-                continue;
-            }
-            gc_launch_prof(pl, p, st, pf);
-        }
-        const long CP = (long)co * Fout * T;
-        if (cmb) return;
-        const bool timed = pf->on;
-        if (timed) pf->begin(st);
-        hipLaunchKernelGGL(gauss_combine_kernel, dim3(Fout, co, B), dim3(128), 0, st, b.K, dst, co, Fout, T, kz, dst3 ? 3 * CP : 2 * CP,
-                           dst3 ? 0L : -1L, dst3 ? CP : 0L, dst3 ? 2 * CP : CP, g.sc, g.sh, g.slope, rg ? rg->tlen : nullptr);
-        SE_HIP(hipGetLastError());
-        if (timed) pf->end(st, 0.0);
-    }
-
     // spec [B][2][257][T] -> mask in b.D[NL] ([B][2][256][T])
     void network(Bufs& b, const float* spec, hipStream_t st) {
         // (at every batch: measured at batch 1 ... 32 the three products win, 4.37 against 4.66 ms for one clip)
@@ -696,9 +535,9 @@ class Dccrn final : public Model {
             F /= 2;
             x = act4(b.E[k], KN[k + 1], F, T);
         }
-        gauss_sum(b.E[2], B, KN[3] / 2, F, T, st);
+        gauss::launch_sum(b.E[2], B, KN[3] / 2, F, T, st, pf);
         for (int k = 3; k < NL; ++k) {            // encoder 3 - 5
-            gauss_layer(genc[k], b, b.E[k - 1], KN[k] / 2, nullptr, 0, F, F / 2, b.E[k], true, st);
+            gauss::run_layer(genc[k], b.E[k - 1], KN[k] / 2, nullptr, 0, F, F / 2, B, T, b.E[k], true, true, b.K, st, pf);
             F /= 2;
         }
         // ---- complex LSTM (:175-185), time-major, sequences s = part*B + b; E[5] / D[0] are three-plane (512 rows per plane)
@@ -734,17 +573,18 @@ class Dccrn final : public Model {
         for (int part = 0; part < 2; ++part)
             launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)(1 + part) * 512 * T, T, 512, B, 1024L * B, B, 1536L * T,
                                  T, st);
-        gauss_sum(b.D[0], B, 128, 4, T, st);
+        gauss::launch_sum(b.D[0], B, 128, 4, T, st, pf);
         launch_zero_tail(b.D[0], B, 1536L, T, st);
         // ---- decoder: layers 0 - 1 three products (two sources: previous | skip), 2 - 5 block form
-        gauss_layer(gdec[0], b, b.D[0], 128, b.E[5], 128, 4, 8, b.D[1], true, st);
-        gauss_layer(gdec[1], b, b.D[1], 128, b.E[4], 128, 8, 16, b.D[2], gauss_dec > 2, st);
-        if (gauss_dec > 2) gauss_layer(gdec[2], b, b.D[2], 128, b.E[3], 128, 16, 32, b.D[3], false, st);
+        // (three-plane outputs store their sum plane themselves: sum_plane = dst3)
+        gauss::run_layer(gdec[0], b.D[0], 128, b.E[5], 128, 4, 8, B, T, b.D[1], true, true, b.K, st, pf);
+        gauss::run_layer(gdec[1], b.D[1], 128, b.E[4], 128, 8, 16, B, T, b.D[2], gauss_dec > 2, gauss_dec > 2, b.K, st, pf);
+        if (gauss_dec > 2) gauss::run_layer(gdec[2], b.D[2], 128, b.E[3], 128, 16, 32, B, T, b.D[3], false, false, b.K, st, pf);
         F = gauss_dec > 2 ? 32 : 16;
         for (int k = gauss_dec; k < NL; ++k) {
             const int cin = KN[NL - k];
             Act4 a0 = act4(b.D[k], cin, F, T);
-            Act4 a1 = (NL - 1 - k) >= 2 ? view3(b.E[NL - 1 - k], cin / 2, F, T) : act4(b.E[NL - 1 - k], cin, F, T);
+            Act4 a1 = (NL - 1 - k) >= 2 ? gauss::view3(b.E[NL - 1 - k], cin / 2, F, T) : act4(b.E[NL - 1 - k], cin, F, T);
             run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, T, T, st, pf);
             if (k + 1 < NL && !conv_zeroes_tail(dec[k])) launch_zero_tail(b.D[k + 1], B, (long)KN[NL - k - 1] * (2 * F), T, st);
             F *= 2;

@@ -522,14 +522,7 @@ class Uformer final : public Model {
             DenseW w = cconv(sd, p + "0.", co, 2 * ci, 5, 2, true);
             // reference channel order of the cat([skip, out]) per part: [skip_r, out_r | skip_i, out_i];
             // engine two-source order: [skip_r, skip_i | out_r, out_i]
-            std::vector<int> perm(4 * ci);
-            for (int c = 0; c < ci; ++c) {
-                perm[c] = c;
-                perm[ci + c] = 2 * ci + c;
-                perm[2 * ci + c] = ci + c;
-                perm[3 * ci + c] = 3 * ci + c;
-            }
-            permute_cin(w, perm);
+            permute_cin(w, complex_cat_perm(ci));
             const std::string q = "decoder_real." + std::to_string(k) + ".";
             DenseW r = deconv_weights(sd.get(q + "0.conv.weight", {2 * ci, co, 5, 2}), &sd.get(q + "0.conv.bias", {co}), false);
             std::vector<float> sc, sr;
@@ -547,30 +540,16 @@ class Uformer final : public Model {
         }
         gauss_on = !(getenv("SE_UF_GAUSS") && atoi(getenv("SE_UF_GAUSS")) == 0);
         if (gauss_on) {
-            // BatchNorm3d(C) (both parts alike) + the conv biases (real part b_r - b_i, imaginary b_r + b_i) + PReLU of a layer
-            auto tail = [&](gauss::GaussLayer& g, const std::string& p, const DenseW& wr, const DenseW& wi) {
-                const int co = wr.M;
-                const HostTensor &ga = sd.get(p + "1.weight", {co}), &be = sd.get(p + "1.bias", {co}), &mu = sd.get(p + "1.running_mean", {co}),
-                                 &va = sd.get(p + "1.running_var", {co});
-                std::vector<float> sc(2 * co), sh(2 * co);
-                for (int m = 0; m < 2 * co; ++m) {
-                    const int c = m % co;
-                    const float bias = m < co ? wr.bias[c] - wi.bias[c] : wr.bias[c] + wi.bias[c];
-                    const double k = (double)ga.data[c] / std::sqrt((double)va.data[c] + 1e-5);
-                    sc[m] = (float)k;
-                    sh[m] = (float)((double)be.data[c] - (double)mu.data[c] * k + (double)bias * k);
-                }
-                g.sc = to_device(sc);
-                g.sh = to_device(sh);
-                g.slope = to_device(prelu_slopes(sd.get(p + "2.weight"), 2 * co));
-            };
+            // BatchNorm3d(C) acts on both parts alike (dup2); the row bias is complex_expand's: real part b_r - b_i, imaginary b_r + b_i
             for (int j = 0; j < 2; ++j) {
                 const int k = 4 + j, ci = KN[k], co = KN[k + 1];
                 const std::string p = "encoder." + std::to_string(k) + ".";
                 DenseW wr = conv_weights(sd.get(p + "0.real_conv.weight", {co, ci, 5, 2}), &sd.get(p + "0.real_conv.bias", {co}), false);
                 DenseW wi = conv_weights(sd.get(p + "0.imag_conv.weight", {co, ci, 5, 2}), &sd.get(p + "0.imag_conv.bias", {co}), false);
                 gauss::make_conv_plans(genc[j], wr, wi, 401);
-                tail(genc[j], p, wr, wi);
+                gauss::fold_tail(genc[j], complex_expand(wr, wi).bias, dup2(sd.get(p + "1.weight", {co})), dup2(sd.get(p + "1.bias", {co})),
+                                 dup2(sd.get(p + "1.running_mean", {co})), dup2(sd.get(p + "1.running_var", {co})),
+                                 prelu_slopes(sd.get(p + "2.weight"), 2 * co));
             }
             for (int k = 0; k < 2; ++k) {
                 const int idx = NL - k, ci = KN[idx], co = KN[idx - 1];
@@ -579,7 +558,9 @@ class Uformer final : public Model {
                 DenseW wr = deconv_weights(sd.get(p + "0.real_conv.weight", {2 * ci, co, 5, 2}), &sd.get(p + "0.real_conv.bias", {co}), false);
                 DenseW wi = deconv_weights(sd.get(p + "0.imag_conv.weight", {2 * ci, co, 5, 2}), &sd.get(p + "0.imag_conv.bias", {co}), false);
                 gauss::make_deconv_plans(gdec[k], wr, wi, 0, ci, 401);
-                tail(gdec[k], p, wr, wi);
+                gauss::fold_tail(gdec[k], complex_expand(wr, wi).bias, dup2(sd.get(p + "1.weight", {co})), dup2(sd.get(p + "1.bias", {co})),
+                                 dup2(sd.get(p + "1.running_mean", {co})), dup2(sd.get(p + "1.running_var", {co})),
+                                 prelu_slopes(sd.get(p + "2.weight"), 2 * co));
             }
         }
         const std::string c = "conformer.";
@@ -716,75 +697,6 @@ class Uformer final : public Model {
     void fusion(float* c, float* m, int B, long CP, hipStream_t st) {
         hipLaunchKernelGGL(uf_fusion_kernel, dim3((unsigned)((CP + 255) / 256), B), dim3(256), 0, st, c, m, CP);
     }
-    // ---- three-product layers (gauss.h).  A three-plane tensor [B][3 C][F][T]: S = R + I at +0, R at + C F T, I at + 2 C F T
-    static Act4 view3(const float* t3, int C, int F, int T) {      // its [R | I] planes as a 2 C-channel tensor
-        return Act4{t3 + (long)C * F * T, 2 * C, F, 3L * C * F * T, (long)F * T, (long)T};
-    }
-    void gauss_planes23(const float* x2, float* x3, int B, long CP, hipStream_t st) {
-        Profiler* pf = &ctx.prof;
-        const bool timed = pf->on;
-        if (timed) pf->begin(st);
-        hipLaunchKernelGGL(gauss::gauss_planes23_kernel, dim3((unsigned)((CP / 4 + 255) / 256 + 1), B), dim3(256), 0, st, x2, x3, CP);
-        SE_HIP(hipGetLastError());
-        if (timed) pf->end(st, 0.0);
-    }
-    // y = PReLU(BN(complex (de)conv(x))): the grouped launch(es) into b.K, then the combine pass.  src0 / src1: three-plane tensors of
-    // C0 / C1 complex channels; dst3: three-plane output (else [R | I])
-    void gauss_layer(const gauss::GaussLayer& g, Bufs& b, const float* src0, int C0, const float* src1, int C1, int Fin, int Fout, int T,
-                     float* dst, bool dst3, hipStream_t st) {
-        const int B = b.B, co = g.co;
-        // SE_GAUSS_CMB=0: three products into scratch + the combine pass (round 4).  Rows of whole 16 B groups only (the combine
-        // epilogue has no trimming variant; PadFrames gives every offline decode such rows)
-        static const bool cmb_env = !(getenv("SE_GAUSS_CMB") && atoi(getenv("SE_GAUSS_CMB")) == 0);
-        const bool cmb = cmb_env && T % 4 == 0 && co >= 64;
-        Profiler* pf = &ctx.prof;
-        const long kz = (long)B * co * Fout * T;
-        const Ragged* rg = ragged_ctx();
-        for (const GCPlan& pl : g.pl) {
-            GCParams p = pl.p;
-            p.src0 = src0; p.C0 = C0; p.s0_b = 3L * C0 * Fin * T; p.s0_c = (long)Fin * T; p.s0_f = T; p.src0_z = (long)C0 * Fin * T;
-            if (src1) {
-                p.src1 = src1; p.C1 = C1; p.s1_b = 3L * C1 * Fin * T; p.s1_c = (long)Fin * T; p.s1_f = T; p.src1_z = (long)C1 * Fin * T;
-            } else {
-                p.src1 = nullptr; p.C1 = 0;
-            }
-            p.Fin = Fin; p.Tin = T; p.B = B; p.Tout = T;
-            p.Q = (Fout - p.po + p.so - 1) / p.so;
-            p.dst = b.K; p.d_b = (long)co * Fout * T; p.d_c = (long)Fout * T; p.d_f = T; p.dst_z = kz;
-            if (rg) p.tlen = rg->tlen;
-            if (cmb) {
-                // k1 = Wr (xr + xi) alone, then k2 / k3 as a grouped launch of two whose epilogue (EPI_CMB) reads k1 and stores the
-                // finished planes: I = f(k1 + k2), R = f(k1 - k3) - no k2 / k3 scratch, no combine pass (round 4: 5 % of a step)
-                GCParams p1 = p;
-                p1.Z = 1;
-                p1.tlen = nullptr;
-                gc_launch_prof(pl, p1, st, pf);
-                GCParams q = p;
-                q.Z = 2;
-                q.A = pl.p.A + pl.p.A_z;
-                q.src0 = p.src0 + p.src0_z;
-                if (src1) q.src1 = p.src1 + p.src1_z;
-                q.epi = EPI_CMB;
-                q.bias = nullptr;
-                q.aux = b.K; q.x_b = p.d_b; q.x_c = p.d_c; q.x_f = p.d_f; q.aux_z = 0;
-                q.post_scale = g.sc + co; q.post_shift = g.sh + co; q.slope = g.slope + co; q.ps_z = -co;
-                q.cmb_neg = 2;                                   // z = 0: I = f(k1 + k2); z = 1: R = f(k1 - k3)
-                const long CPo = (long)co * Fout * T, oR = dst3 ? CPo : 0L, oI = dst3 ? 2 * CPo : CPo;
-                q.dst = dst + oI; q.dst_z = oR - oI; q.d_b = (dst3 ? 3 : 2) * CPo;
-                gc_launch_prof(pl, q, st, pf);
-                continue;
-            }
-            gc_launch_prof(pl, p, st, pf);
-        }
-        const long CP = (long)co * Fout * T;
-        if (cmb) return;      // (the sum plane of a three-plane output is refreshed by the caller, behind the folded interaction)
-        const bool timed = pf->on;
-        if (timed) pf->begin(st);
-        hipLaunchKernelGGL(gauss::gauss_combine_kernel, dim3(Fout, co, B), dim3(128), 0, st, b.K, dst, co, Fout, T, kz, dst3 ? 3 * CP : 2 * CP,
-                           -1L, dst3 ? CP : 0L, dst3 ? 2 * CP : CP, g.sc, g.sh, g.slope, rg ? rg->tlen : nullptr);
-        SE_HIP(hipGetLastError());
-        if (timed) pf->end(st, 0.0);
-    }
     // LayerNorm over C of a [Bv][C][P] view
     void ln(const LnW& w, const float* x, float* y, int Bv, int C, long P, hipStream_t st, int post = 0, const float* slope = nullptr,
             const float* res = nullptr) {
@@ -884,7 +796,9 @@ class Uformer final : public Model {
             // three-plane outputs (inputs of the three-product layers 4 / 5 and skips of decoder layers 1 / 2): EC[3], EC[4]
             const bool out3 = gauss_on && (k == 3 || k == 4);
             float* ecR = out3 ? b.EC[k] + CPk : b.EC[k];          // the [R | I] planes
-            if (gauss_on && k >= 4) gauss_layer(genc[k - 4], b, b.EC[k - 1], KN[k], nullptr, 0, 2 * F, F, T, b.EC[k], out3, st);
+            // (a three-product layer leaves the sum plane to the branch interaction's store below: sum_plane = false)
+            if (gauss_on && k >= 4)
+                gauss::run_layer(genc[k - 4], b.EC[k - 1], KN[k], nullptr, 0, 2 * F, F, B, T, b.EC[k], out3, false, b.K, st, pf);
             else run_conv(encC[k], xc, nullptr, ecR, (out3 ? 3 : 2) * co, F, B, T, T, st, pf);      // (dstC only sets the batch stride)
             const bool fold = fold_env() && conv_folds_interaction(encR[k]);
             run_conv(encR[k], xm, nullptr, b.ER[k], co, F, B, T, T, st, pf, nullptr, 0, fold ? ecR : nullptr, out3 ? 3 : 2);
@@ -892,10 +806,10 @@ class Uformer final : public Model {
                 SE_CHECK(!out3, "Uformer: three-plane encoder tensors need the folded interaction (SE_UF_FOLD=0 with SE_UF_GAUSS=1)");
                 fusion(b.EC[k], b.ER[k], B, CPk, st);
             }
-            xc = out3 ? view3(b.EC[k], co, F, T) : act4(b.EC[k], 2 * co, F, T);
+            xc = out3 ? gauss::view3(b.EC[k], co, F, T) : act4(b.EC[k], 2 * co, F, T);
             xm = act4(b.ER[k], co, F, T);
         }
-        if (gauss_on) gauss_planes23(b.EC[NL - 1], b.EC5g, B, (long)CC * 4 * T, st);      // skip of decoder layer 0
+        if (gauss_on) gauss::launch_planes23(b.EC[NL - 1], b.EC5g, B, (long)CC * 4 * T, st, pf);      // skip of decoder layer 0
         // ---- dilated dual-path conformer at [B][128][4][T] (dilated_dualpath_conformer.py:53-78)
         const long P = 4L * T, CP = (long)CC * P;
         const float *c = b.EC[NL - 1], *m = b.ER[NL - 1];
@@ -926,7 +840,7 @@ class Uformer final : public Model {
         m = b.XR[pp];
         // ---- decoder (:225-232): cat([skip, out]) two-source, fusion after every layer
         F = 4;
-        if (gauss_on) gauss_planes23(c, b.XCg, B, CP, st);
+        if (gauss_on) gauss::launch_planes23(c, b.XCg, B, CP, st, pf);
         bool c3 = false;          // `c` is a three-plane tensor
         for (int k = 0; k < NL; ++k) {
             const int ci = KN[NL - k], co = KN[NL - k - 1];
@@ -938,10 +852,10 @@ class Uformer final : public Model {
             if (gauss_on && k < 2) {
                 const float* s0 = k == 0 ? b.EC5g : b.EC[ek];
                 const float* s1 = k == 0 ? b.XCg : b.DC[0];
-                gauss_layer(gdec[k], b, s0, ci, s1, ci, F, 2 * F, T, b.DC[k], out3, st);
+                gauss::run_layer(gdec[k], s0, ci, s1, ci, F, 2 * F, B, T, b.DC[k], out3, false, b.K, st, pf);
             } else {
-                Act4 s0 = skip3 ? view3(b.EC[ek], ci, F, T) : act4(b.EC[ek], 2 * ci, F, T);
-                Act4 s1 = c3 ? view3(c, ci, F, T) : act4(c, 2 * ci, F, T);
+                Act4 s0 = skip3 ? gauss::view3(b.EC[ek], ci, F, T) : act4(b.EC[ek], 2 * ci, F, T);
+                Act4 s1 = c3 ? gauss::view3(c, ci, F, T) : act4(c, 2 * ci, F, T);
                 run_deconv(decC[k], s0, &s1, b.DC[k], 2 * co, 2 * F, B, T, T, st, pf);
             }
             Act4 r0 = act4(b.ER[ek], ci, F, T), r1 = act4(m, ci, F, T);
