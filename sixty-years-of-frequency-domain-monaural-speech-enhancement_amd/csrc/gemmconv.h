@@ -219,6 +219,7 @@ struct GCLaunchRec {
     int flat_nrm_refused = 0;    // the flattened tiles were considered and refused because a normalising tile would span
                                  // more than GC_FLAT_NRM_ROWS rows (value: rows spanned)
     long nblk = 0;               // workgroups
+    int epi = 0, gru = 0;        // the launch's epilogue (EPI_LSTM: one recurrent step; gru: its GRU cell)
 };
 // nullptr (the default): nothing is recorded.  Otherwise every dispatch of this thread appends its record.
 void gc_set_launch_log(std::vector<GCLaunchRec>* log);

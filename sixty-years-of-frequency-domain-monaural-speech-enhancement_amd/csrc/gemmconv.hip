@@ -1489,6 +1489,8 @@ static void gc_log_launch(int family, const GCParams& p, long nblk, int BM = 0, 
     r.ragged = p.tlen ? 1 : 0;
     r.flat_nrm_refused = g_flat_nrm_refused;
     r.nblk = nblk;
+    r.epi = p.epi;
+    r.gru = p.gru;
     g_launch_log->push_back(r);
 }
 int gc_flat_rows_spanned(int B, int upr, int upt) {

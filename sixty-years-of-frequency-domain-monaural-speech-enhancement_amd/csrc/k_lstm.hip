@@ -294,12 +294,21 @@ void launch_lstm_persist(const LstmPersistArgs& a, hipStream_t s) {
     // few sequences: 4 per workgroup (4x4x1 MFMA) fill the chip where 16-sequence tiles would not
     constexpr int p4_max = 128;      // sequence-tile count up to which the 4-sequence kernel is used
     SE_CHECK(!a.st_h || (a.st_c && a.O == 1), "persistent LSTM: carried state needs both tensors and O = 1");
+    LstmLaunchRec r;
+    r.H = a.H;
+    r.Z = a.Z;
     if (a.H == 128 && !a.st_h && ((a.S + 15) / 16) * a.Z * a.O <= p4_max) {
+        r.kernel = "persist4";
+        r.grid = (long)((a.S + 3) / 4) * a.Z * a.O;
+        lstm_log_launch(r);
         hipLaunchKernelGGL(lstm_persist4_kernel<128>, dim3((a.S + 3) / 4, a.Z * a.O), dim3(256), 0, s, a);
         SE_HIP(hipGetLastError());
         return;
     }
     dim3 grid((a.S + 15) / 16, a.Z * a.O);
+    r.kernel = "persist";
+    r.grid = (long)grid.x * grid.y;
+    lstm_log_launch(r);
     if (a.H == 128) hipLaunchKernelGGL(lstm_persist_kernel<128>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(lstm_persist_kernel<64>, grid, dim3(256), 0, s, a);
     SE_HIP(hipGetLastError());

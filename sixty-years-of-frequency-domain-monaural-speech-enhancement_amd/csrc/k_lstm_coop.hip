@@ -1053,6 +1053,23 @@ __global__ __launch_bounds__(256, 1) void lstm_coop16_kernel(const LstmCoopArgs 
 
 char* coop_scratch(size_t need, hipStream_t s) { return device_scratch(0, need, s); }
 
+// the launch-log record of one cooperative dispatch (lstm_set_launch_log)
+void log_coop(const char* kernel, const LstmCoopArgs& a, int H, int NS, int TAG, int LEAD, int NW, long grid, size_t shmem) {
+    LstmLaunchRec r;
+    r.kernel = kernel;
+    r.H = H; r.NS = NS; r.TAG = TAG; r.LEAD = LEAD; r.NW = NW;
+    r.Z = a.Z; r.SS = a.SS;
+    r.chunk = a.pz;
+    for (int z = 0; a.pz && z < a.Z && z < 4; ++z) {
+        r.lz[z] = a.lz[z];
+        r.t0[z] = a.t0[z];
+        r.Tz[z] = a.Tz[z];
+    }
+    r.grid = grid;
+    r.shmem = (long)shmem;
+    lstm_log_launch(r);
+}
+
 template <int H>
 void launch_t(LstmCoopArgs a, int n_cu, hipStream_t s) {
     constexpr int US = H / 16;
@@ -1079,12 +1096,20 @@ void launch_t(LstmCoopArgs a, int n_cu, hipStream_t s) {
         SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop_kernel<H>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     }
+    log_coop("coop", a, H, 0, 0, 0, 0, (long)US * a.SS * a.Z, shmem);
     void* params[] = {&a};
     SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop_kernel<H>), dim3(US * a.SS * a.Z), dim3(256),
                                       params, (unsigned)shmem, s));
 }
 
 }  // namespace
+
+// lstm_set_launch_log: per-thread record of the recurrent dispatches (tests only; off unless a log is set)
+static thread_local std::vector<LstmLaunchRec>* g_lstm_log = nullptr;
+void lstm_set_launch_log(std::vector<LstmLaunchRec>* log) { g_lstm_log = log; }
+void lstm_log_launch(const LstmLaunchRec& r) {
+    if (g_lstm_log) g_lstm_log->push_back(r);
+}
 
 bool lstm_coop_supported(int H, int S, int Z) { return (H == 512 || H == 1024) && (H / 16) * Z <= 256 && S <= 4096; }
 
@@ -1114,6 +1139,7 @@ static void launch_c8(LstmCoopArgs a, hipStream_t s) {
         SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop8_kernel<H, LEAD, NW>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
+    log_coop("coop8", a, H, 0, 0, LEAD, NW, (long)US * a.SS * a.Z, shmem);
     void* params[] = {&a};
     SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop8_kernel<H, LEAD, NW>), dim3(US * a.SS * a.Z),
                                       dim3(64 * NW), params, (unsigned)shmem, s));
@@ -1147,6 +1173,7 @@ static bool launch_c16(LstmCoopArgs a, int n_cu, hipStream_t s) {
         SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop16_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    160 * 1024));
     }
+    log_coop("coop16", a, H, 0, 0, 0, 0, (long)US * a.SS * a.Z, shmem);
     void* params[] = {&a};
     SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop16_kernel<H>), dim3(US * a.SS * a.Z), dim3(256), params,
                                       (unsigned)shmem, s));
@@ -1211,6 +1238,7 @@ static void launch_chunk_t(LstmCoopArgs a, int n_layers, hipStream_t s) {
         SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop16_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    160 * 1024));
     }
+    log_coop("coop16", a, H, 0, 0, 0, 0, (long)US * a.SS * a.Z, shmem);
     void* params[] = {&a};
     SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop16_kernel<H>), dim3(US * a.SS * a.Z), dim3(256), params,
                                       (unsigned)shmem, s));
@@ -1266,6 +1294,7 @@ static void launch_ks(LstmCoopArgs a, hipStream_t s) {
         SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop_ks_kernel<H, NS, TAG>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     }
+    log_coop("ks", a, H, NS, TAG ? 1 : 0, 0, 0, (long)NWG * a.Z, shmem);
     void* params[] = {&a};
     SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop_ks_kernel<H, NS, TAG>), dim3(NWG * a.Z), dim3(256),
                                       params, (unsigned)shmem, s));
@@ -1296,6 +1325,12 @@ static void launch_stack_t(LstmStackArgs a, hipStream_t s) {
         SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_stack_kernel<H, L>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)shmem));
     }
+    LstmLaunchRec r;
+    r.kernel = "stack";
+    r.H = H; r.L = L; r.Z = 1; r.SS = 1;
+    r.grid = NWG;
+    r.shmem = (long)shmem;
+    lstm_log_launch(r);
     void* params[] = {&a};
     SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_stack_kernel<H, L>), dim3(NWG), dim3(256), params,
                                       (unsigned)shmem, s));

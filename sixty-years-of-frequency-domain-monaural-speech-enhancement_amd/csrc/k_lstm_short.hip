@@ -18,6 +18,7 @@
 // No gate tensor exists; x is read once per direction (8 KB per tile and step).
 #include "k_lstm_short.h"
 #include "common.h"
+#include "kernels.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -217,6 +218,12 @@ void launch_lstm_short(const LstmShortArgs& a, hipStream_t s) {
     SE_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
     // one workgroup per CU (192 weight registers per lane: one wave per SIMD), the directions side by side
     const int G = (int)std::min<long>(ntiles, std::max(1, ncu / a.Z));
+    LstmLaunchRec r;
+    r.kernel = "short";
+    r.H = LS_H;
+    r.Z = a.Z;
+    r.grid = (long)G * a.Z;
+    lstm_log_launch(r);
     hipLaunchKernelGGL(lstm_short_kernel, dim3(G, a.Z), dim3(256), 0, s, a);
     SE_HIP(hipGetLastError());
 }

@@ -354,4 +354,19 @@ bool lstm_stack_supported(int H, int L);
 void launch_lstm_stack(const LstmStackArgs& a, hipStream_t s);
 void launch_lstm_coop(const LstmCoopArgs& a, hipStream_t s);
 
+// Form of one recurrent dispatch, for tests that must know which kernel a launch reached (csrc/tests/lstm_probe.hip).  Host-side
+// only: nothing the kernels compute depends on it.  Template values a kernel does not have are 0.
+struct LstmLaunchRec {
+    const char* kernel = "";     // "coop" (lstm_coop_kernel), "ks", "coop8", "coop16", "stack", "persist", "persist4", "short"
+    int H = 0, NS = 0, TAG = 0, LEAD = 0, NW = 0, L = 0;
+    int Z = 0, SS = 0;           // LSTMs (chunk pipeline: layer ranges) per launch, sequence slices
+    int chunk = 0;               // launch_lstm_coop_chunk: lz / t0 / Tz of each z
+    int lz[4] = {}, t0[4] = {}, Tz[4] = {};
+    long grid = 0, shmem = 0;    // workgroups (all grid dimensions), dynamic LDS bytes
+};
+// nullptr (the default): nothing is recorded.  Otherwise every recurrent dispatch of this thread (k_lstm_coop.hip, k_lstm.hip,
+// k_lstm_short.hip) appends its record.
+void lstm_set_launch_log(std::vector<LstmLaunchRec>* log);
+void lstm_log_launch(const LstmLaunchRec& r);
+
 }  // namespace se

@@ -16,21 +16,26 @@ struct LstmW {
     int I = 0, H = 0;
 };
 
-inline LstmW load_lstm(const TrackedSD& sd, const std::string& prefix, int layer, const std::string& suffix, int I,
-                       int H) {
-    const std::string l = "_l" + std::to_string(layer) + suffix;
+// torch.nn.LSTM tensors of one layer (weight_ih [4H][I], weight_hh [4H][H], bias_ih / bias_hh [4H], gate order i, f, g, o) ->
+// the engine's layer (tests/lstm_probe.hip hands it raw tensors)
+inline LstmW lstm_from_torch(const HostTensor& wi, const HostTensor& wh, const HostTensor& bi, const HostTensor& bh, int I, int H) {
     LstmW w;
     w.I = I;
     w.H = H;
-    w.wih = linear_weights(sd.get(prefix + "weight_ih" + l, {4 * H, I}), nullptr);
-    const HostTensor& bi = sd.get(prefix + "bias_ih" + l, {4 * H});
-    const HostTensor& bh = sd.get(prefix + "bias_hh" + l, {4 * H});
+    w.wih = linear_weights(wi, nullptr);
     for (int i = 0; i < 4 * H; ++i) w.wih.bias[i] = bi.data[i] + bh.data[i];
-    w.whh = linear_weights(sd.get(prefix + "weight_hh" + l, {4 * H, H}), nullptr);
+    w.whh = linear_weights(wh, nullptr);
     const auto perm = lstm_gate_perm(H);
     permute_rows(w.wih, perm);
     permute_rows(w.whh, perm);
     return w;
+}
+
+inline LstmW load_lstm(const TrackedSD& sd, const std::string& prefix, int layer, const std::string& suffix, int I,
+                       int H) {
+    const std::string l = "_l" + std::to_string(layer) + suffix;
+    return lstm_from_torch(sd.get(prefix + "weight_ih" + l, {4 * H, I}), sd.get(prefix + "weight_hh" + l, {4 * H, H}),
+                           sd.get(prefix + "bias_ih" + l, {4 * H}), sd.get(prefix + "bias_hh" + l, {4 * H}), I, H);
 }
 
 // torch.nn.GRU layer (FullSubNet `sequence_model="GRU"`, sequence_model.py:36-43) on the LSTM step kernel's 4-rows-per-unit
@@ -38,12 +43,7 @@ inline LstmW load_lstm(const TrackedSD& sd, const std::string& prefix, int layer
 // b_in, and a zero row whose bias is b_hn (the cell epilogue reads it as the constant inside r * (W_hn h + b_hn));
 // recurrent rows: W_hr / W_hz / W_hn and a zero row.  A quarter of the matrix work is padding - the decode scripts never
 // select the GRU (fullsubnet_sa_decode_vb.py:16), it is built for completeness of the north star's "LSTM/GRU time step".
-inline LstmW load_gru(const TrackedSD& sd, const std::string& prefix, int layer, const std::string& suffix, int I, int H) {
-    const std::string l = "_l" + std::to_string(layer) + suffix;
-    const HostTensor& wi = sd.get(prefix + "weight_ih" + l, {3 * H, I});
-    const HostTensor& wh = sd.get(prefix + "weight_hh" + l, {3 * H, H});
-    const HostTensor& bi = sd.get(prefix + "bias_ih" + l, {3 * H});
-    const HostTensor& bh = sd.get(prefix + "bias_hh" + l, {3 * H});
+inline LstmW gru_from_torch(const HostTensor& wi, const HostTensor& wh, const HostTensor& bi, const HostTensor& bh, int I, int H) {
     auto pad4 = [&](const HostTensor& w, int K) {
         HostTensor o;
         o.shape = {4 * H, K};
@@ -66,6 +66,12 @@ inline LstmW load_gru(const TrackedSD& sd, const std::string& prefix, int layer,
         w.wih.bias[4 * u + 3] = bh.data[2 * H + u];
     }
     return w;
+}
+
+inline LstmW load_gru(const TrackedSD& sd, const std::string& prefix, int layer, const std::string& suffix, int I, int H) {
+    const std::string l = "_l" + std::to_string(layer) + suffix;
+    return gru_from_torch(sd.get(prefix + "weight_ih" + l, {3 * H, I}), sd.get(prefix + "weight_hh" + l, {3 * H, H}),
+                          sd.get(prefix + "bias_ih" + l, {3 * H}), sd.get(prefix + "bias_hh" + l, {3 * H}), I, H);
 }
 
 // per-stream state of the frame-online mode: history columns of every chunk tensor, LSTM (h, c).  A new stream on the same
