@@ -104,6 +104,11 @@ void launch_copy4(const float* in, float* out, int B, int C, int I, int J, long 
 
 constexpr int NU = 8;      // independent loads per thread in the streaming passes of the norm kernels
 
+// launch record of the norm / TCM launchers (kernels.h: NormLaunchRec); null outside tests
+static thread_local std::vector<NormLaunchRec>* g_norm_log = nullptr;
+void norm_set_launch_log(std::vector<NormLaunchRec>* log) { g_norm_log = log; }
+std::vector<NormLaunchRec>* norm_launch_log() { return g_norm_log; }
+
 // ---- LayerNorm over (C, F) per (b, t) + residual ------------------------------------------------------------
 // block = 64 frames x 4 row groups: the C*F rows of a frame are split over 4 waves (partial sums meet in LDS), so a
 // launch has 4x the blocks and a quarter of the serial row walk of a thread-per-frame layout
@@ -174,6 +179,7 @@ __global__ __launch_bounds__(256) void layernorm_cf_kernel(const float* __restri
 }
 void launch_layernorm_cf(const float* x, const float* res, const float* w, const float* b, float* out, int B, int C,
                          int F, int T, float eps, hipStream_t s, int post, const float* prelu_slope) {
+    norm_log_launch("layernorm_cf", (long)((T + 63) / 64) * B, 256, 0);
     hipLaunchKernelGGL(layernorm_cf_kernel, dim3((T + 63) / 64, B), dim3(256), 0, s, x, res, w, b, out, C, F, T, eps, post,
                        prelu_slope);
     SE_HIP(hipGetLastError());
@@ -449,6 +455,8 @@ void launch_instnorm_prelu_stats(const float* x, float* y, const float* gamma, c
                                  const float* stats, int nslot, int B, int C, int P, hipStream_t s, const float* res, int T) {
     const Ragged* rg = ragged_ctx();
     SE_CHECK(!rg || (T > 0 && P % T == 0), "ragged InstanceNorm from epilogue statistics needs the frame count of the plane's lines");
+    norm_log_launch("instnorm_prelu_stats", (long)B * C, 256, 0, rg != nullptr);
+    norm_log_res(res);
     hipLaunchKernelGGL(instnorm_prelu_stats_kernel, dim3(B * C), dim3(256), 0, s, x, y, gamma, beta, slope, res, stats, nslot,
                        C, P, rg ? rg->tlen : nullptr, T);
     SE_HIP(hipGetLastError());
@@ -489,6 +497,7 @@ void launch_instnorm_finalize(const float* stats, int nslot, const float* gamma,
     const Ragged* rg = ragged_ctx();
     SE_CHECK(!rg || (T > 0 && P % T == 0), "ragged InstanceNorm from epilogue statistics needs the frame count of the plane's lines");
     const int planes = B * C;
+    norm_log_launch("instnorm_finalize", (planes + 3) / 4, 256, 0, rg != nullptr);
     hipLaunchKernelGGL(instnorm_finalize_kernel, dim3((planes + 3) / 4), dim3(256), 0, s, stats, nslot, gamma, beta, slope, nrm, C, P,
                        planes, rg ? rg->tlen : nullptr, T);
     SE_HIP(hipGetLastError());
@@ -549,6 +558,7 @@ __global__ __launch_bounds__(256) void instnorm_apply2_kernel(const float* xa, c
 }
 void launch_instnorm_apply2(const float* xa, const float* na, const float* xb, const float* nb, float* y, int B, int C, int P,
                             hipStream_t s) {
+    norm_log_launch("instnorm_apply2", (long)B * C, 256, 0);
     hipLaunchKernelGGL(instnorm_apply2_kernel, dim3(B * C), dim3(256), 0, s, xa, na, xb, nb, y, P);
     SE_HIP(hipGetLastError());
 }
@@ -556,11 +566,15 @@ void launch_instnorm_prelu(const float* x, float* y, const float* gamma, const f
                            int C, int P, hipStream_t s, const float* res, int T) {
     if (const Ragged* rg = ragged_ctx()) {
         SE_CHECK(T > 0 && P % T == 0, "ragged InstanceNorm needs the frame count of the plane's lines");
+        norm_log_launch("instnorm_prelu_ragged", (long)B * C, 256, 0, 1);
+        norm_log_res(res);
         hipLaunchKernelGGL(instnorm_prelu_ragged_kernel, dim3(B * C), dim3(256), 0, s, x, y, gamma, beta, slope, res, C, P, T,
                            rg->tlen);
         SE_HIP(hipGetLastError());
         return;
     }
+    norm_log_launch("instnorm_prelu", (long)B * C, 256, 0);
+    norm_log_res(res);
     hipLaunchKernelGGL(instnorm_prelu_kernel, dim3(B * C), dim3(256), 0, s, x, y, gamma, beta, slope, res, C, P);
     SE_HIP(hipGetLastError());
 }
@@ -623,6 +637,7 @@ void launch_tcm_head(const float* x, float* y, const float* slope, const float* 
                      const float* fir, int K, int B, int C, int T, hipStream_t s) {
     SE_CHECK((size_t)T * 4 <= 60000, "TCM row too long for the LDS-resident head kernel");
     const Ragged* rg = ragged_ctx();
+    norm_log_launch("tcm_head", (long)B * C, 256, (size_t)T * 4, rg != nullptr);
     hipLaunchKernelGGL(tcm_head_kernel, dim3(B * C), dim3(256), (size_t)T * 4, s, x, y, slope, gamma, beta, fir, K, C, T,
                        rg ? rg->tlen : nullptr);
     SE_HIP(hipGetLastError());
@@ -697,8 +712,11 @@ __device__ __forceinline__ void cln_wave_scan(double* sc, int T, int c0, double 
             iq += uq;
         }
     }
-    a = a0 + (ia - a);                       // exclusive offset of this lane's segment
-    q = q0 + (iq - q);
+    // exclusive offset of this lane's segment: the inclusive totals of the lane in front.  (Not `ia - a`: a segment that holds frames
+    // behind a ragged row's end would take their NaN - or, by cancellation, their magnitude - into its own live frames.)
+    const double ea = __shfl_up(ia, 1, 64), eq = __shfl_up(iq, 1, 64);
+    a = a0 + (lane ? ea : 0.0);
+    q = q0 + (lane ? eq : 0.0);
     for (int t = lo; t < hi; ++t) {
         a += sc[t];
         q += sc[T + t];
@@ -1132,6 +1150,8 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
         const long tg0 = cx->t0 - cx->H;
         if (K <= 0 && !pre_slope && cx->n <= 2 && (long)R * cx->n <= 256L * 41 * cx->n && R <= 256 * 41 && C <= 256) {
             // (every frame of the chunk is live: tg0 + c0 = the stream index of the first new frame >= 0)
+            norm_log_launch("cln_window_reg", B, 256, 0, 0, c0, 0, cx->n, 41 * cx->n);
+            norm_log_res(res);
             if (cx->n == 1)
                 hipLaunchKernelGGL((cln_window_reg_kernel<1, 41>), dim3(B), dim3(256), 0, s, x, y, gain, bias, post_slope, R, F, T,
                                    c0, tg0, carry, res);
@@ -1144,6 +1164,7 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
         SE_CHECK(!res, "frame-online cLN: the residual rides on the register form only (ask cln_stream_takes_res first)");
         if ((long)R * (T - c0) <= 32768 && (K <= 0 || (size_t)R * (T - c0) * 4 + (size_t)T * 24 <= 60000)) {   // small windows: one launch
             const size_t lds = (size_t)T * 24 + (K > 0 ? (size_t)R * (T - c0) * 4 : 0);
+            norm_log_launch("cln_window", B, 256, lds, 0, c0);
             hipLaunchKernelGGL(cln_window_kernel, dim3(B), dim3(256), lds, s, x, y, gain, bias, pre_slope, post_slope,
                                fir, K, R, F, T, c0, cx->H, tg0, cx->n, carry);
             SE_HIP(hipGetLastError());
@@ -1151,6 +1172,9 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
         }
         int WP = 1;
         while (WP < T - c0 && WP < 64) WP <<= 1;
+        norm_log_launch("cln_stats", (long)((T - c0 + WP - 1) / WP) * B, 256, 0, 0, c0, WP);
+        norm_log_launch("cln_scan", B, 256, (size_t)T * 16, 0, c0);
+        norm_log_launch("cln_apply", (long)((cx->n + 255) / 256) * ((R + 7) / 8) * B, 256, 0, 0, c0);
         hipLaunchKernelGGL(cln_stats_kernel, dim3((T - c0 + WP - 1) / WP, B), dim3(256), 0, s, x, pre_slope, sum, sq, R, F, T, c0,
                            WP);
         hipLaunchKernelGGL(cln_scan_kernel, dim3(B), dim3(256), (size_t)T * 16, s, sum, sq, mean, rstd, R, T, c0, tg0, cx->n,
@@ -1160,15 +1184,20 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
         SE_HIP(hipGetLastError());
         return;
     }
+    norm_log_launch("cln_stats", (long)((T + 63) / 64) * B, 256, 0, 0, 0, 64);
+    norm_log_launch("cln_scan", B, 256, (size_t)T * 16);
     hipLaunchKernelGGL(cln_stats_kernel, dim3((T + 63) / 64, B), dim3(256), 0, s, x, pre_slope, sum, sq, R, F, T, 0, 64);
     hipLaunchKernelGGL(cln_scan_kernel, dim3(B), dim3(256), (size_t)T * 16, s, sum, sq, mean, rstd, R, T, 0, 0L, 0, nullptr);
     static const bool plane_on = !(getenv("SE_CLN_PLANE") && atoi(getenv("SE_CLN_PLANE")) == 0);
     if (K <= 0 && !pre_slope && (plane_on || res)) {
+        norm_log_launch("cln_apply_plane", (long)B * C, 256, (size_t)T * 8);
+        norm_log_res(res);
         hipLaunchKernelGGL(cln_apply_plane_kernel, dim3(B * C), dim3(256), (size_t)T * 8, s, x, y, mean, rstd, gain, bias, post_slope,
                            res, C, F, T);
         SE_HIP(hipGetLastError());
         return;
     }
+    norm_log_launch("cln_apply", (long)((T + 255) / 256) * ((R + 7) / 8) * B, 256, 0);
     hipLaunchKernelGGL(cln_apply_kernel, dim3((T + 255) / 256, (R + 7) / 8, B), dim3(256), 0, s, x, y, mean, rstd, gain,
                        bias, pre_slope, post_slope, fir, K, R, F, T, 0, 0L);
     SE_HIP(hipGetLastError());
@@ -1183,6 +1212,9 @@ void launch_cln_parts(const float* x, float* y, const float* gain, const float* 
     char* stat = device_scratch(1, need, s);
     float* mean = (float*)((double*)stat + 2 * (size_t)B * T);
     float* rstd = mean + (size_t)B * T;
+    norm_log_launch("cln_scan_parts", B, 256, (size_t)T * 16);
+    norm_log_launch("cln_apply_plane", (long)B * C, 256, (size_t)T * 8);
+    norm_log_res(res);
     hipLaunchKernelGGL(cln_scan_parts_kernel, dim3(B), dim3(256), (size_t)T * 16, s, parts, F, mean, rstd, C * F, T);
     hipLaunchKernelGGL(cln_apply_plane_kernel, dim3(B * C), dim3(256), (size_t)T * 8, s, x, y, mean, rstd, gain, bias, post_slope, res, C,
                        F, T);
@@ -1195,6 +1227,7 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, c
     if (i < n) y[i] = a[i] + b[i];
 }
 void launch_add(const float* a, const float* b, float* y, long n, hipStream_t s) {
+    norm_log_launch("add", (n + 255) / 256, 256, 0);
     hipLaunchKernelGGL(add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, b, y, n);
     SE_HIP(hipGetLastError());
 }

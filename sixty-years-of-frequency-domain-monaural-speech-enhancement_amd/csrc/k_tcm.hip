@@ -199,7 +199,10 @@ __global__ __launch_bounds__(512) void tcm_fused_kernel(const TcmFusedArgs a) {
                     const double ts = __shfl_up(ps, o, 64), tq = __shfl_up(pq, o, 64);
                     if (lane >= o) { ps += ts; pq += tq; }
                 }
-                const double bs = ps - as, bq = pq - aq;        // sums of all columns in front of this lane's eight
+                // sums of all columns in front of this lane's eight: the inclusive totals of the lane in front (not `ps - as`: eight
+                // columns that straddle a ragged row's end would take the dead frames' NaN / magnitude into their live frames)
+                const double es = __shfl_up(ps, 1, 64), eq = __shfl_up(pq, 1, 64);
+                const double bs = lane ? es : 0.0, bq = lane ? eq : 0.0;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const int t = lane * 8 + i;
@@ -334,8 +337,10 @@ __global__ __launch_bounds__(512) void tcm_fused_kernel(const TcmFusedArgs a) {
                     }
 #pragma unroll
                     for (int k = 0; k < 16; ++k) {
-                        {
-                            const float w = tp63[k0 + k];          // entry 63 is zero
+                        // entry 63 of the table is a zero that would multiply frame t + 1: behind the last frame of a ragged row
+                        // that is a dead value, and 0 x NaN / Inf would reach the live frame - the last pass has 15 taps
+                        if (k < 15 || q < 3) {
+                            const float w = tp63[k0 + k];
 #pragma unroll
                             for (int i = 0; i < 8; ++i) o[i] = fmaf(w, xw[2 + i + k], o[i]);
                         }
@@ -584,6 +589,12 @@ void launch_tcm_fused(const TcmFusedW& f, const TcmFusedHeads& hd, const float* 
             up(tcm_fused_kernel<3, false, false>); up(tcm_fused_kernel<5, true, true>); up(tcm_fused_kernel<5, false, true>);
             up(tcm_fused_kernel<3, true, true>); up(tcm_fused_kernel<3, false, true>);
         }
+    }
+    if (std::vector<NormLaunchRec>* log = norm_launch_log()) {
+        NormLaunchRec r;
+        r.kernel = "tcm_fused"; r.KS = f.ks; r.GATED = gated; r.CUM = cum; r.strip = a.strip;
+        r.ragged = rg != nullptr; r.grid = B; r.block = 512; r.shmem = (long)lds;
+        log->push_back(r);
     }
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(B), dim3(512), lds, s, a); };
     if (cum) {

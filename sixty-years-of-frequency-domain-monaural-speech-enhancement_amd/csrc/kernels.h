@@ -369,4 +369,36 @@ struct LstmLaunchRec {
 void lstm_set_launch_log(std::vector<LstmLaunchRec>* log);
 void lstm_log_launch(const LstmLaunchRec& r);
 
+// Form of one dispatch of the normalisation passes (k_misc.hip) and of the one-workgroup-per-utterance TCM block (k_tcm.hip), for
+// tests that must know which kernel a launch reached (csrc/tests/norm_probe.hip).  Host-side only: nothing the kernels compute
+// depends on it.  Fields a kernel does not have are 0.
+struct NormLaunchRec {
+    const char* kernel = "";     // the kernel's name without its template list ("cln_window_reg", "tcm_fused", ...)
+    int W = 0, VPT = 0;          // cln_window_reg_kernel<W, VPT>
+    int KS = 0, GATED = 0, CUM = 0, strip = 0;      // tcm_fused_kernel<KS, GATED, CUM>, its epilogue
+    int ragged = 0;              // the launch read the published per-row frame counts
+    int c0 = 0, WP = 0;          // frame-online cLN: first column summed, columns per workgroup of the statistics pass
+    int res = 0;                 // the kernel adds a residual itself ("add": launch_add, the residual added by a launch of its own)
+    long grid = 0;               // workgroups (all grid dimensions)
+    int block = 0;
+    long shmem = 0;              // dynamic LDS bytes
+};
+// nullptr (the default): nothing is recorded.  Otherwise every dispatch of launch_instnorm_*, launch_tcm_head, launch_cln,
+// launch_cln_parts, launch_layernorm_cf, launch_tcm_fused and launch_add on this thread appends its record.
+void norm_set_launch_log(std::vector<NormLaunchRec>* log);
+std::vector<NormLaunchRec>* norm_launch_log();
+inline void norm_log_launch(const char* kernel, long grid, int block, size_t shmem, int ragged = 0, int c0 = 0, int WP = 0, int W = 0,
+                            int VPT = 0) {
+    if (std::vector<NormLaunchRec>* log = norm_launch_log()) {
+        NormLaunchRec r;
+        r.kernel = kernel; r.grid = grid; r.block = block; r.shmem = (long)shmem;
+        r.ragged = ragged; r.c0 = c0; r.WP = WP; r.W = W; r.VPT = VPT;
+        log->push_back(r);
+    }
+}
+inline void norm_log_res(const void* res) {      // the dispatch just recorded takes `res` in its own apply pass
+    if (std::vector<NormLaunchRec>* log = norm_launch_log())
+        if (res && !log->empty()) log->back().res = 1;
+}
+
 }  // namespace se
