@@ -86,6 +86,16 @@ enum se_model_id {
  * R in SE_CFG_REPEATS (1 <= R <= 8), X in bits 12-15 (1 <= X <= 6); 0 in a field = the decode script's 3 / 6
  * (two_stage_com_decode_vb.py:14). */
 #define SE_CFG_REPEATS2(n) ((((n) + 1) & 15) << 12)
+/* DCCRN of `DCCRN_SNR/` (DCCRN_SNR/DCCRN.py:9-183, built at DCCRN_SNR/dccrn_decode_snr.py:12 for the WSJ0-SI84 grid): the same
+ * network as DCCRN/DCCRN_cprs.py except that after every transposed conv the decoder keeps `out[..., :-1]` (DCCRN_SNR/DCCRN.py:159)
+ * where DCCRN_cprs.py:199 keeps `out[..., 1:]` - each decoder layer then looks BACK one frame instead of ahead, and the network is
+ * causal end to end.  The class has the 'E' mask only (DCCRN.py:162-183): the bit does not combine with SE_CFG_DCCRN_MASK_C / _R
+ * (se_engine_create fails); it combines with SE_CFG_DCCRN_REAL_LSTM (the class default `use_clstm=False`, DCCRN.py:82-91) and with
+ * the two complexnn conventions.  Decode semantics are those of dccrn_decode_snr.py:31-67: the same front end (zero pad to a hop
+ * multiple, torch.stft 512 / 128 / 512), torch.istft without `length`, the result cut to the clip's own length (:66) - so
+ * se_output_samples(n) = n, not the hop-padded length of dccrn_decode_vb.py - and se_stream_* finalises every frame with no
+ * extra delay (the `_vb` network: six frames late). */
+#define SE_CFG_DCCRN_CAUSAL_DEC (1 << 16)
 
 typedef struct se_config {
     int32_t model;        /* enum se_model_id */
@@ -135,7 +145,8 @@ int se_uformer_forward(se_engine* e, const float* inputs_dev, const float* src_d
  * unit-RMS normalise -> (tail pad) -> STFT -> compress -> network (+mask) -> decompress -> iSTFT -> /c.
  * wav_in_dev [B][in_pitch] (first n_samples of each row valid), wav_out_dev [B][out_pitch]; the number of
  * output samples per utterance is se_output_samples(e, n_samples) (DCCRN returns the hop-padded length,
- * dccrn_decode_vb.py:59-64; Uformer hop*floor(L/hop); others L). */
+ * dccrn_decode_vb.py:59-64 - with SE_CFG_DCCRN_CAUSAL_DEC it returns L, dccrn_decode_snr.py:66; Uformer hop*floor(L/hop);
+ * others L). */
 int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int32_t batch, int32_t n_samples,
                      float* wav_out_dev, int64_t out_pitch, void* stream);
 int64_t se_output_samples(const se_engine* e, int32_t n_samples);
@@ -167,7 +178,8 @@ int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, i
  *          agree exactly - that is what the tests check.
  *   max_chunk_frames: frames advanced per internal step (latency / efficiency trade-off, default 16).
  * Supported: SE_MODEL_CRN, SE_MODEL_LSTM, SE_MODEL_GCRN, SE_MODEL_DPCRN, SE_MODEL_DCCRN (whose decoder looks six frames ahead:
- * its output is final six frames later than the others'), and SE_MODEL_CTSNET / SE_MODEL_TAYLORSENET / SE_MODEL_G2NET when
+ * its output is final six frames later than the others'; with SE_CFG_DCCRN_CAUSAL_DEC - the DCCRN of DCCRN_SNR/ - it is final
+ * with no extra frames of delay), and SE_MODEL_CTSNET / SE_MODEL_TAYLORSENET / SE_MODEL_G2NET when
  * loaded with the cumulative-LayerNorm weights of the `_new` directories (CTSNet_new/Step1_network.py:213-286 - with the
  * InstanceNorm weights of the base directories the network needs the whole utterance and se_stream_begin fails; the engine
  * then carries up to 128 history frames per dilated conv and the running cLN sums).  Streams are limited to max_samples
@@ -254,7 +266,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bit SE_CFG_DCCRN_CAUSAL_DEC: no new entry point, same number) */
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,11 @@
 //     `tranform` are gemmconv GEMMs; the recurrence runs as lstm_persist_kernel<128> (rnn_units 128) or, at 256, as one
 //     lstm_coop16_kernel<256> launch per layer from 17 sequences on and one fused GEMM + cell launch per step below that
 //     (LstmBig).  The three-product (Gauss) layers are a DCCRN-CL-only path.
+//   * SE_CFG_DCCRN_CAUSAL_DEC (the DCCRN of DCCRN_SNR/DCCRN.py:9-183, decode loop body DCCRN_SNR/dccrn_decode_snr.py:31-67): the
+//     decoder keeps `out[..., :-1]` (DCCRN.py:159) instead of `out[..., 1:]` - the transposed-conv plans take time offset 0, so
+//     every decoder layer looks back one frame, as the encoder does.  Nothing looks ahead any more: ragged rows need no zeros
+//     behind their own last frame, the frame-online mode runs the decoder on the same columns as the encoder (no lag, four
+//     history columns), and the decode returns the clip's own length (`esti_utt[:wav_len]`, :66).
 #include "rnn.h"
 #include "gauss.h"
 #include "../../include/se_engine.h"
@@ -45,7 +50,11 @@ struct Bufs {
 
 class Dccrn final : public Model {
   public:
-    explicit Dccrn(EngineCtx& c) : Model(c) {}
+    explicit Dccrn(EngineCtx& c) : Model(c), causal((c.flags & SE_CFG_DCCRN_CAUSAL_DEC) != 0) {
+        SE_CHECK(!(causal && (c.flags & (SE_CFG_DCCRN_MASK_C | SE_CFG_DCCRN_MASK_R))),
+                 "DCCRN: SE_CFG_DCCRN_CAUSAL_DEC (the DCCRN of DCCRN_SNR/DCCRN.py) has the 'E' mask only - it does not combine with "
+                 "SE_CFG_DCCRN_MASK_C / SE_CFG_DCCRN_MASK_R");
+    }
     ~Dccrn() override {
         for (auto& g : genc) g.free();
         for (auto& g : gdec) g.free();
@@ -67,7 +76,8 @@ class Dccrn final : public Model {
         const int frame_num = (L + HOP - 1) / HOP + 1;
         return (frame_num - 1) * HOP;
     }
-    int64_t output_samples(int L) const override { return padded_samples(L); }   // :59-64 (not trimmed to L)
+    // :59-64 (not trimmed to L); the causal-decoder script cuts to the clip's own length (dccrn_decode_snr.py:66)
+    int64_t output_samples(int L) const override { return causal ? L : padded_samples(L); }
     int frame_multiple() const override { return 16; }
 
     void finalize(const TrackedSD& sd) override {
@@ -127,6 +137,9 @@ class Dccrn final : public Model {
             enc[k] = make_conv_plan(w, 2, 2, 1, 1, 1, ACT_PRELU, slope, EPI_ACT, tout);
         }
         // ---- decoder (:98-137): ComplexConvTranspose2d(k=(5,2), s=(2,1), pad=(2,0), out_pad=(1,0)) [+ BN + PReLU]
+        // of the T + 1 frames a (., 2) transposed conv makes, `out[..., 1:]` (:199) is time offset 1 - output frame t reads input
+        // frames t and t + 1; `out[..., :-1]` (DCCRN_SNR/DCCRN.py:159) is time offset 0 - frames t - 1 and t
+        const int toff = causal ? 0 : 1;
         for (int k = 0; k < NL; ++k) {
             const int idx = NL - k;
             const std::string p = "decoder." + std::to_string(k) + ".";
@@ -145,13 +158,13 @@ class Dccrn final : public Model {
                                  &mu = sd.get(p + "1.running_mean", {2 * co}), &va = sd.get(p + "1.running_var", {2 * co});
                 slope = prelu_slopes(sd.get(p + "2.weight"), 2 * co);
                 if (gauss_on && k < gauss_dec) {      // complex input channels: [previous (ci / 2) | skip (ci / 2)] (:197)
-                    gauss::make_deconv_plans(gdec[k], wr, wi, /*toff*/ 1, /*c0split*/ ci / 2, tout);
+                    gauss::make_deconv_plans(gdec[k], wr, wi, toff, /*c0split*/ ci / 2, tout);
                     gauss::fold_tail(gdec[k], w.bias, ga, be, mu, va, slope);
                 }
                 fold_bn(w, ga, be, mu, va);
                 act = ACT_PRELU;
             }
-            dec[k] = make_deconv_plan(w, 2, 2, /*toff: out[..., 1:] :199*/ 1, act, slope, tout, /*C0 = out channels*/ ci);
+            dec[k] = make_deconv_plan(w, 2, 2, toff, act, slope, tout, /*C0 = out channels*/ ci);
         }
         if (rlstm) {      // ---- nn.LSTM(1024, H, num_layers=2) + tranform Linear(H, 1024) (:95-102)
             const int H = rnn_h;
@@ -227,14 +240,18 @@ class Dccrn final : public Model {
 
     void enhance(const float* wav, long pitch, int B, int L, float* out, long out_pitch, hipStream_t st) override {
         const int Lpad = padded_samples(L);
-        PadFrames pad(ctx, B, L, Lpad, 1 + Lpad / HOP, Lpad, st, 16);   // the decoder looks ahead: rows of whole 16 B groups - and, since round 6, whole 64 B sectors (501 -> 512 frames: whole 128 / 256-column tiles, rows of 2 048 B)
+        const int Lout = (int)output_samples(L);
+        // (the causal decoder keeps this form - equal-length batches as ragged rows of one length - although nothing of it looks
+        // ahead: the three-product layers' combine epilogue wants rows of whole 16 B groups, which zero-extended 501-frame rows
+        // would have to be padded for as well, and the rows the kernels were tuned on are these)
+        PadFrames pad(ctx, B, L, Lpad, 1 + Lpad / HOP, Lout, st, 16);   // the decoder looks ahead: rows of whole 16 B groups - and, since round 6, whole 64 B sectors (501 -> 512 frames: whole 128 / 256-column tiles, rows of 2 048 B)
         const int T = pad.T;
         Bufs& b = bufs(B, T);
         launch_rms_scale(wav, B, L, pitch, b.c, st);                                           // :27
         launch_stft(ctx.geom, wav, pitch, B, L, Lpad, b.c, ctx.p_in, b.spec, nullptr, T, T, st);   // :28-42
         network(b, b.spec, st);                                                                // :44
         launch_dccrn_mask(b.D[NL], b.spec, b.est, B, NBIN, T, T, ctx.p_out, st, mask_mode);    // model :201-225 + :45-58
-        launch_istft(ctx.geom, b.est, B, T, T, b.frames, b.c, out, out_pitch, Lpad, st);       // :59-62
+        launch_istft(ctx.geom, b.est, B, T, T, b.frames, b.c, out, out_pitch, Lout, st);       // :59-62
     }
 
     void plan_buffers(int B, int T) override {
@@ -250,15 +267,21 @@ class Dccrn final : public Model {
     // it six frames late, stream_lag).  The chunk that ends the stream fills the remaining columns with zeros where their
     // future would be - what the offline decode sees past its last frame.  The history columns of all fourteen tensors come
     // back from / go to the state in one launch each.
+    // The causal decoder (SE_CFG_DCCRN_CAUSAL_DEC: `out[..., :-1]`, DCCRN_SNR/DCCRN.py:159) has a schedule of its own: every
+    // tensor is a window of CHC = 4 history columns + the n new frames, and EVERY layer - decoder included - produces columns
+    // [CHC, CHC + n) only; the one column a transposed conv looks back on (CHC - 1) is the layer input's history, restored from
+    // the state like the encoder's.  The estimate of the new frames is final at once (stream_lag 0), the last chunk is a chunk
+    // like any other, and the history only has to cover what the iSTFT overlaps.
     static constexpr int DHC = 12;          // 6 look-ahead + 3 frames of iSTFT overlap (512 / 128), rounded up to a multiple of 4
-    int stream_hc() const override { return DHC; }
-    int stream_lag() const override { return NL; }
+    static constexpr int CHC = 4;           // causal decoder: the 3 frames of iSTFT overlap (>= the 1 frame of look-back), rounded up
+    int stream_hc() const override { return causal ? CHC : DHC; }
+    int stream_lag() const override { return causal ? 0 : NL; }
     bool stream_supported() const override { return true; }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
         ss.release();
         ss.B = B;
         ss.first = true;
-        for (long rows : stream_rows()) ss.hist.push_back(ss.zeros((size_t)B * rows * DHC, st));
+        for (long rows : stream_rows()) ss.hist.push_back(ss.zeros((size_t)B * rows * stream_hc(), st));
         for (int l = 0; l < 2; ++l) {           // [2 real LSTMs][128][2B]  (real-LSTM form: [H][B] per layer)
             const size_t n = rlstm ? (size_t)rnn_h * B : (size_t)2 * 128 * 2 * B;
             ss.h[l] = ss.zeros(n, st);
@@ -267,35 +290,35 @@ class Dccrn final : public Model {
         (void)max_chunk;
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {
-        Bufs& b = bufs(B, DHC + n);
+        Bufs& b = bufs(B, stream_hc() + n);
         *spec = b.spec;
         *mag = nullptr;
         *est = b.est;
     }
     void stream_chunk(int B, int t0, int n, hipStream_t st, bool last) override {
         SE_CHECK(ss.B == B && !ss.hist.empty(), "stream_chunk without stream_begin");
-        const int Tw = DHC + n;
+        const int HC = stream_hc(), Tw = HC + n;      // (history columns of this schedule: 12, or the causal decoder's 4)
         Bufs& b = bufs(B, Tw);
         Profiler* pf = &ctx.prof;
         const std::vector<long> rows = stream_rows();
         float* tens[14] = {b.spec, b.E[0], b.E[1], b.E[2], b.E[3], b.E[4], b.E[5], b.D[0], b.D[1], b.D[2], b.D[3], b.D[4], b.D[5], b.est};
         HistBatch hb;
         for (int k = 0; k < 14; ++k) hb.add(tens[k], ss.hist[k], rows[k]);
-        launch_hist_batch(hb, B, Tw, DHC, false, st);
+        launch_hist_batch(hb, B, Tw, HC, false, st);
         Act4 x{b.spec + Tw, 2, 256, 2L * NBIN * Tw, (long)NBIN * Tw, (long)Tw};
         int F = 256;
         for (int k = 0; k < NL; ++k) {        // only the new frames: the history columns came back from the state
-            run_conv(enc[k], x, nullptr, b.E[k], KN[k + 1], F / 2, B, Tw, Tw, st, pf, nullptr, DHC);
+            run_conv(enc[k], x, nullptr, b.E[k], KN[k + 1], F / 2, B, Tw, Tw, st, pf, nullptr, HC);
             F /= 2;
             x = act4(b.E[k], KN[k + 1], F, Tw);
         }
         if (rlstm) {
-            real_lstm_core(b, b.E[NL - 1] + DHC, b.D[0] + DHC, Tw, n, st, true);
+            real_lstm_core(b, b.E[NL - 1] + HC, b.D[0] + HC, Tw, n, st, true);
         } else {
         // complex LSTM over the n new frames, continuing from the carried state
         const int S = 2 * B;
         for (int part = 0; part < 2; ++part)
-            launch_transpose_akt(b.E[NL - 1] + (size_t)part * 512 * Tw + DHC, b.X1 + (size_t)part * B, B, 512, n, 1024L * Tw, Tw,
+            launch_transpose_akt(b.E[NL - 1] + (size_t)part * 512 * Tw + HC, b.X1 + (size_t)part * B, B, 512, n, 1024L * Tw, Tw,
                                  512L * S, S, st);
         {
             GCParams p = g1.p;
@@ -323,22 +346,27 @@ class Dccrn final : public Model {
             gc_launch_prof(proj, p, st, pf);
         }
         for (int part = 0; part < 2; ++part)
-            launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)part * 512 * Tw + DHC, n, 512, B, 1024L * B, B,
+            launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)part * 512 * Tw + HC, n, 512, B, 1024L * B, B,
                                  1024L * Tw, Tw, st);
         }
         F = 4;
         for (int k = 0; k < NL; ++k) {
-            const int cin = KN[NL - k], c0 = DHC - (k + 1);
+            const int cin = KN[NL - k], c0 = HC - (k + 1);
             Act4 a0 = act4(b.D[k], cin, F, Tw);
             Act4 a1 = act4(b.E[NL - 1 - k], cin, F, Tw);
-            run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, Tw, Tw, st, pf, nullptr, c0, last ? Tw : c0 + n, true);
+            if (causal)      // the new columns only, like the encoder: column HC - 1 of both inputs came back from the state
+                run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, Tw, Tw, st, pf, nullptr, HC);
+            else
+                run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, Tw, Tw, st, pf, nullptr, c0, last ? Tw : c0 + n, true);
             F *= 2;
         }
-        {
-            const int c0 = DHC - NL;
+        if (causal) {
+            launch_dccrn_mask(b.D[NL] + HC, b.spec + HC, b.est + HC, B, NBIN, n, Tw, ctx.p_out, st, mask_mode);
+        } else {
+            const int c0 = HC - NL;
             launch_dccrn_mask(b.D[NL] + c0, b.spec + c0, b.est + c0, B, NBIN, last ? Tw - c0 : n, Tw, ctx.p_out, st, mask_mode);
         }
-        launch_hist_batch(hb, B, Tw, DHC, true, st);
+        launch_hist_batch(hb, B, Tw, HC, true, st);
         ss.first = false;
         (void)t0;
     }
@@ -350,6 +378,7 @@ class Dccrn final : public Model {
                 KN[3] * 32L, KN[2] * 64L, KN[1] * 128L, 2L * NBIN};
     }
     int KN[NL + 1] = {2, 32, 64, 128, 256, 256, 256};      // 2 + kernel_num (finalize: KN_CL or KN_DEFAULT)
+    const bool causal;                 // SE_CFG_DCCRN_CAUSAL_DEC: the decoder of DCCRN_SNR/DCCRN.py:159 (looks back, not ahead)
     bool rlstm = false;                // SE_CFG_DCCRN_REAL_LSTM
     int rnn_h = 0;                     // its rnn_units (128 / 256)
     LstmBig rl[2];                     // its two layers (input projection plans; H = 256: the recurrence too)
@@ -467,7 +496,8 @@ class Dccrn final : public Model {
             run_conv(enc[k], x, nullptr, b.E[k], KN[k + 1], F / 2, B, T, T, st, pf);
             // ragged batch: the decoder looks one frame ahead per layer (`out[..., 1:]`, :199) into its (previous, skip)
             // inputs, and a clip decoded alone has zeros past its last frame
-            if (!conv_zeroes_tail(enc[k])) launch_zero_tail(b.E[k], B, (long)KN[k + 1] * (F / 2), T, st);
+            // (the causal decoder, SE_CFG_DCCRN_CAUSAL_DEC, reads nothing behind a frame: no zero tails anywhere below)
+            if (!causal && !conv_zeroes_tail(enc[k])) launch_zero_tail(b.E[k], B, (long)KN[k + 1] * (F / 2), T, st);
             F /= 2;
             x = act4(b.E[k], KN[k + 1], F, T);
         }
@@ -508,7 +538,7 @@ class Dccrn final : public Model {
             launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)part * 512 * T, T, 512, B, 1024L * B, B,
                                  1024L * T, T, st);
         }
-        launch_zero_tail(b.D[0], B, 1024L, T, st);
+        if (!causal) launch_zero_tail(b.D[0], B, 1024L, T, st);
         // ---- decoder with two-source skips (:196-199)
         F = 4;
         for (int k = 0; k < NL; ++k) {
@@ -516,7 +546,7 @@ class Dccrn final : public Model {
             Act4 a0 = act4(b.D[k], cin, F, T);
             Act4 a1 = act4(b.E[NL - 1 - k], cin, F, T);
             run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, T, T, st, pf);
-            if (k + 1 < NL && !conv_zeroes_tail(dec[k])) launch_zero_tail(b.D[k + 1], B, (long)KN[NL - k - 1] * (2 * F), T, st);
+            if (!causal && k + 1 < NL && !conv_zeroes_tail(dec[k])) launch_zero_tail(b.D[k + 1], B, (long)KN[NL - k - 1] * (2 * F), T, st);
             F *= 2;
         }
     }
@@ -531,7 +561,7 @@ class Dccrn final : public Model {
             const int c = KN[k + 1] / 2;
             float* dst = k == 2 ? b.E[k] + (long)c * (F / 2) * T : b.E[k];
             run_conv(enc[k], x, nullptr, dst, k == 2 ? 3 * c : 2 * c, F / 2, B, T, T, st, pf);
-            if (!conv_zeroes_tail(enc[k])) launch_zero_tail(b.E[k], B, (long)(k == 2 ? 3 * c : 2 * c) * (F / 2), T, st);
+            if (!causal && !conv_zeroes_tail(enc[k])) launch_zero_tail(b.E[k], B, (long)(k == 2 ? 3 * c : 2 * c) * (F / 2), T, st);
             F /= 2;
             x = act4(b.E[k], KN[k + 1], F, T);
         }
@@ -574,7 +604,7 @@ class Dccrn final : public Model {
             launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)(1 + part) * 512 * T, T, 512, B, 1024L * B, B, 1536L * T,
                                  T, st);
         gauss::launch_sum(b.D[0], B, 128, 4, T, st, pf);
-        launch_zero_tail(b.D[0], B, 1536L, T, st);
+        if (!causal) launch_zero_tail(b.D[0], B, 1536L, T, st);
         // ---- decoder: layers 0 - 1 three products (two sources: previous | skip), 2 - 5 block form
         // (three-plane outputs store their sum plane themselves: sum_plane = dst3)
         gauss::run_layer(gdec[0], b.D[0], 128, b.E[5], 128, 4, 8, B, T, b.D[1], true, true, b.K, st, pf);
@@ -586,7 +616,7 @@ class Dccrn final : public Model {
             Act4 a0 = act4(b.D[k], cin, F, T);
             Act4 a1 = (NL - 1 - k) >= 2 ? gauss::view3(b.E[NL - 1 - k], cin / 2, F, T) : act4(b.E[NL - 1 - k], cin, F, T);
             run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, T, T, st, pf);
-            if (k + 1 < NL && !conv_zeroes_tail(dec[k])) launch_zero_tail(b.D[k + 1], B, (long)KN[NL - k - 1] * (2 * F), T, st);
+            if (!causal && k + 1 < NL && !conv_zeroes_tail(dec[k])) launch_zero_tail(b.D[k + 1], B, (long)KN[NL - k - 1] * (2 * F), T, st);
             F *= 2;
         }
     }

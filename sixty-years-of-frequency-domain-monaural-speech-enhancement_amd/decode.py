@@ -31,8 +31,12 @@ DEFAULT_CKPT = {
                    './BEST_MODEL/step2_vb_cts_cprs_model.pth'),
     'taylorsenet_new': './BEST_MODEL/vb_taylor_cprs_model.pth',             # TaylorSENet_new/taylorsenet_decode_vb.py:14
     'g2net_new': './BEST_MODEL/vb_gaf_cprs_model.pth',                      # G2Net_new/com_decode.py:104
+    'dccrn_snr': './BEST_MODEL/wsj0_si84_300h_dccrn_snr_model.pth',         # DCCRN_SNR/dccrn_decode_snr.py:13
 }
 MODELS = sorted(DEFAULT_CKPT)
+# decode scripts that feed the file's samples to the network at whatever rate the file has - no librosa.resample(..., 16000)
+# in front (DCCRN_SNR/dccrn_decode_snr.py:31-33: the WSJ0-SI84 mixtures are 16 kHz files)
+NO_RESAMPLE_MODELS = frozenset({'dccrn_snr'})
 
 
 def load_checkpoint(path):
@@ -53,8 +57,12 @@ def _build(model, checkpoint, state_dict, **kw):
     sd = state_dict if state_dict is not None else load_checkpoint(checkpoint or DEFAULT_CKPT[model])
     if isinstance(sd, dict) and 'model_state_dict' in sd:        # TaylorSENet/taylorsenet_decode_vb.py:14-15 wraps it
         sd = sd['model_state_dict']
-    ctor = dccrn_real_lstm_config(sd) if model == 'dccrn' else None
-    if ctor is not None:
+    ctor = dccrn_real_lstm_config(sd) if model in ('dccrn', 'dccrn_snr') else None
+    if model == 'dccrn_snr':      # DCCRN_SNR/dccrn_decode_snr.py:12, or the class's real-LSTM core recognised by its keys
+        ctor = ctor or dict(rnn_units=256, use_clstm=True, kernel_num=[32, 64, 128, 256, 256, 256])
+        ctor.pop('masking_mode', None)                # (the class has no such argument: 'E' only)
+        net = models.DCCRN_SNR(**ctor, **kw)
+    elif ctor is not None:
         net = models.DCCRN(**ctor, **kw)
     else:
         net = MODEL_CLASSES[model](**kw)
@@ -167,7 +175,8 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
     t_begin = time.perf_counter()
     mix, out_dir = args.mix_file_path, getattr(args, 'esti_clean_file_path', None) or args.esti_file_path
     if getattr(args, 'noise_type', None):
-        # WSJ0-SI84 grid drivers (`*_decode.py`, e.g. CRN/crn_decode.py:28-32): one (noise, seen/unseen, SNR) cell
+        # WSJ0-SI84 grid drivers (`*_decode.py`, e.g. CRN/crn_decode.py:28-32, DCCRN_SNR/dccrn_decode_snr.py:20-27): one
+        # (noise, seen/unseen, SNR) cell
         mix = os.path.join(mix, args.noise_type, args.seen, str(args.snr))
         out_dir = os.path.join(out_dir, args.noise_type, args.seen, str(args.snr))
     os.makedirs(out_dir, exist_ok=True)
@@ -183,6 +192,8 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
             raise ValueError(f'{f}: {ch} channels - the decode scripts read mono clips')
     native = [i[0] for i in info]
     rates = [i[1] for i in info]
+    if model in NO_RESAMPLE_MODELS:
+        rates = [16000] * len(info)                           # samples go in as they are read, whatever the header says
     lengths = [n if fs == 16000 else resample.resample_samples(n, fs, 16000) for n, fs in zip(native, rates)]
     raw16 = all(i[3] == 1 and i[4] == 16 for i in info)       # PCM_16 corpus: raw samples to the device, floats made there
     if batch_samples is None:
@@ -373,9 +384,13 @@ def main():
     parser.add_argument('--noncprs', action='store_true', help='uncompressed variant: exponents 1.0 / 1.0')
     # WSJ0-SI84 grid drivers (`*_decode.py`): decode <mix>/<noise_type>/<seen>/<snr>/
     parser.add_argument('--noise_type', type=str, default=None)
-    parser.add_argument('--seen', type=str, default='unseen')
+    parser.add_argument('--seen', type=str, default=None)
     parser.add_argument('--snr', type=str, default='-5')
     args = parser.parse_args()
+    if args.model == 'dccrn_snr' and args.noise_type is None:
+        args.noise_type = 'cafe'          # this script always decodes one cell of the grid (dccrn_decode_snr.py:118-120)
+    if args.seen is None:
+        args.seen = 'seen' if args.model == 'dccrn_snr' else 'unseen'
     p_in, p_out = (0.5, 2.0) if args.cprs else ((1.0, 1.0) if args.noncprs else (None, None))
     ck = args.checkpoint
     if ck is not None and not args.model.startswith('ctsnet'):

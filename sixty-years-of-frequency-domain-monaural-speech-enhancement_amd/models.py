@@ -131,6 +131,42 @@ class _DCCRNRealLSTM(DCCRN):
         return schemas.dccrn_rlstm_schema(kn, units)
 
 
+class DCCRN_SNR(DCCRN):
+    """DCCRN_SNR/DCCRN.py:9 - the DCCRN of the WSJ0-SI84 grid, built at DCCRN_SNR/dccrn_decode_snr.py:12 as
+    `DCCRN(rnn_units=256, use_clstm=True, kernel_num=[32, 64, 128, 256, 256, 256])`.  The reference's signature: no `masking_mode`
+    (the class has the 'E' mask only) and no `win_type`.  Its decoder keeps `out[..., :-1]` after every transposed conv
+    (DCCRN.py:159) where DCCRN_cprs.py:199 keeps `out[..., 1:]`: the network is causal end to end (SE_CFG_DCCRN_CAUSAL_DEC,
+    include/se_engine.h), the frame-online mode finalises every frame at once, and a decode returns the clip's own length
+    (dccrn_decode_snr.py:66).  The state-dict keys are DCCRN's, per core.  forward: [B,2,257,T] -> [B,2,257,T]."""
+    SE_CFG_DCCRN_CAUSAL_DEC = 1 << 16
+
+    def __init__(self, rnn_layers=2, rnn_units=128, win_len=512, win_inc=128, fft_len=512, use_clstm=False, use_cbn=False,
+                 kernel_size=5, kernel_num=(16, 32, 64, 128, 256, 256), **kw):
+        for k in ('masking_mode', 'win_type'):
+            if k in kw:
+                raise TypeError(f"DCCRN_SNR() has no argument '{k}' (DCCRN_SNR/DCCRN.py:10-21)")
+        if kw.get('flags', 0) & (self.SE_CFG_DCCRN_MASK_C | self.SE_CFG_DCCRN_MASK_R):
+            raise ValueError("DCCRN_SNR has the 'E' mask only (DCCRN_SNR/DCCRN.py:162-183): SE_CFG_DCCRN_MASK_C / _R do not "
+                             "combine with its causal decoder")
+        kw['flags'] = kw.get('flags', 0) | self.SE_CFG_DCCRN_CAUSAL_DEC
+        try:
+            super().__init__(rnn_layers, rnn_units, win_len, win_inc, fft_len, 'hanning', 'E', use_clstm, use_cbn, kernel_size,
+                             kernel_num, **kw)
+        except NotImplementedError:
+            raise NotImplementedError(
+                "the engine builds DCCRN_SNR as the decode script's (dccrn_decode_snr.py:12: rnn_units=256, use_clstm=True, "
+                "kernel_num=[32,64,128,256,256,256]) or with use_clstm=False, use_cbn=False and (rnn_units, kernel_num) in "
+                + repr(self.REAL_LSTM_CONFIGS) + "; got " + repr((rnn_layers, rnn_units, win_len, win_inc, fft_len, use_clstm,
+                                                                  use_cbn, kernel_size, tuple(kernel_num)))) from None
+        self.__class__ = DCCRN_SNR        # (the real-LSTM form re-classes the instance: the schema below covers both cores)
+
+    @_class_or_instance_method
+    def state_dict_schema(cls, self):
+        """Class.state_dict_schema(): the decode script's configuration (complex LSTM); instance: this instance's core."""
+        rl = getattr(self, '_rlstm', None)
+        return schemas.dccrn_rlstm_schema(rl[1], rl[0]) if rl else schemas.SCHEMAS['dccrn']()
+
+
 class lstm_net(_EngineModule):
     """LSTM/LSTM.py:14 `lstm_net()`.  forward: magnitude [B,T,161] -> enhanced magnitude [B,T,161]."""
     _model = 'lstm'

@@ -313,4 +313,7 @@ SCHEMAS = {'fullsubnet_gru': fullsubnet_gru_schema, 'taylorsenet': taylorsenet_s
            'dccrn_rlstm': dccrn_rlstm_schema,
            'dccrn_rlstm128': lambda: dccrn_rlstm_schema(rnn_units=128),
            'dccrn_rlstm_w32': lambda: dccrn_rlstm_schema(kernel_num=(32, 64, 128, 256, 256, 256))}
+# DCCRN_SNR/DCCRN.py:9-122 declares the same modules under the same names as DCCRN/DCCRN_cprs.py (the two files differ in the
+# decoder's time slice, DCCRN.py:159, and in the masks offered - neither is a parameter): its key schemas ARE DCCRN's, per core
+SCHEMAS.update({'dccrn_snr': dccrn_schema, 'dccrn_snr_rlstm': dccrn_rlstm_schema, 'dccrn_snr_rlstm128': SCHEMAS['dccrn_rlstm128']})
 SCHEMAS.update({n + '_new': (lambda n=n: cln_variant(SCHEMAS[n]())) for n in ('cts_step1', 'cts_step2', 'taylorsenet', 'g2net')})

@@ -29,6 +29,10 @@ def build(name, B, L):
     if name == 'dccrn_e':               # DCCRN(rnn_units=256, masking_mode='E'): the real-LSTM core (opt-in: --models dccrn_e)
         from se_amd.models import DCCRN
         return DCCRN(rnn_units=256, masking_mode='E', max_batch=B, max_samples=L).load_synthetic(24)
+    if name == 'dccrn_snr':             # DCCRN_SNR/dccrn_decode_snr.py:12: the causal-decoder DCCRN (opt-in: --models dccrn,dccrn_snr)
+        from se_amd.models import DCCRN_SNR
+        return DCCRN_SNR(rnn_units=256, use_clstm=True, kernel_num=[32, 64, 128, 256, 256, 256], max_batch=B,
+                         max_samples=L).load_synthetic(14)
     return MODEL_CLASSES[name](max_batch=B, max_samples=L).load_synthetic(SEEDS[name])
 
 
@@ -45,7 +49,7 @@ def main():
         for B in map(int, a.batch.split(',')):
             m = build(name, B, L)
             eng = m.engine
-            hop = {'dccrn': 128, 'fullsubnet_cum': 256}.get(name, 160)
+            hop = {'dccrn': 128, 'dccrn_snr': 128, 'fullsubnet_cum': 256}.get(name, 160)
             x = torch.from_numpy(np.stack([synth.synth_clip(900 + b, 'speech', L) for b in range(B)])).cuda()
             c = eng.rms_scale(x)
             for chunk in map(int, a.chunk.split(',')):
