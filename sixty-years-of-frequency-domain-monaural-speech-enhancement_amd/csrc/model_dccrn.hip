@@ -27,6 +27,10 @@
 //     every decoder layer looks back one frame, as the encoder does.  Nothing looks ahead any more: ragged rows need no zeros
 //     behind their own last frame, the frame-online mode runs the decoder on the same columns as the encoder (no lag, four
 //     history columns), and the decode returns the clip's own length (`esti_utt[:wav_len]`, :66).
+//
+// Host structure: ONE network() runs every offline form - encoder() up to the first three-product layer, the three-product layers
+// (gauss_on; empty ranges otherwise), core(), the three-product decoder layers, decoder() from where they stop - and stream_chunk()
+// calls the same encoder() / core() / decoder() on the new columns of its windows.  core() is real_lstm_core() or complex_lstm_core().
 #include "rnn.h"
 #include "gauss.h"
 #include "../../include/se_engine.h"
@@ -39,6 +43,7 @@ constexpr int NL = 6;
 constexpr int KN_CL[NL + 1] = {2, 32, 64, 128, 256, 256, 256};         // kernel_num of dccrn_decode_vb.py:11
 constexpr int KN_DEFAULT[NL + 1] = {2, 16, 32, 64, 128, 256, 256};    // the class default (DCCRN_cprs.py:18)
 constexpr int NFFT = 512, HOP = 128, NBIN = 257;
+constexpr int GENC = 3, GDEC = 3;      // gauss_on: encoder layers GENC .. 5 and decoder layers 0 .. GDEC - 1 run as three products
 
 struct Bufs {
     int B = 0, T = 0;
@@ -114,11 +119,10 @@ class Dccrn final : public Model {
             }
             return w;
         };
-        // the layers with >= 128 complex output channels also as Gauss' three products (gauss.h): encoder 3 - 5, decoder 0 - 1 (- 2);
+        // the layers with >= 128 complex output channels also as Gauss' three products (gauss.h): encoder 3 - 5, decoder 0 - 2;
         // not with the plain-concat convention (a decoder input's [real | imag] halves are then not the halves of its two sources)
-        static const int gauss_env = getenv("SE_DCCRN_GAUSS") ? atoi(getenv("SE_DCCRN_GAUSS")) : 2;      // 0: four products everywhere; 1: without decoder 2 (2 354 vs 2 421 utt/s at batch 256)
-        gauss_on = gauss_env != 0 && !plain_cat && !rlstm;
-        gauss_dec = gauss_env >= 2 ? 3 : 2;
+        static const bool gauss_env = !(getenv("SE_DCCRN_GAUSS") && atoi(getenv("SE_DCCRN_GAUSS")) == 0);      // 0: four products everywhere
+        gauss_on = gauss_env && !plain_cat && !rlstm;
         // ---- encoder (DCCRN_cprs.py:62-77): ComplexConv2d(k=(5,2), s=(2,1), pad=(2,1) causal) + BN + PReLU
         for (int k = 0; k < NL; ++k) {
             const std::string p = "encoder." + std::to_string(k) + ".";
@@ -129,7 +133,7 @@ class Dccrn final : public Model {
             const HostTensor &ga = sd.get(p + "1.weight", {2 * co}), &be = sd.get(p + "1.bias", {2 * co}),
                              &mu = sd.get(p + "1.running_mean", {2 * co}), &va = sd.get(p + "1.running_var", {2 * co});
             const std::vector<float> slope = prelu_slopes(sd.get(p + "2.weight"), 2 * co);
-            if (gauss_on && k >= 3) {
+            if (gauss_on && k >= GENC) {
                 gauss::make_conv_plans(genc[k], wr, wi, tout);
                 gauss::fold_tail(genc[k], w.bias, ga, be, mu, va, slope);
             }
@@ -157,7 +161,7 @@ class Dccrn final : public Model {
                 const HostTensor &ga = sd.get(p + "1.weight", {2 * co}), &be = sd.get(p + "1.bias", {2 * co}),
                                  &mu = sd.get(p + "1.running_mean", {2 * co}), &va = sd.get(p + "1.running_var", {2 * co});
                 slope = prelu_slopes(sd.get(p + "2.weight"), 2 * co);
-                if (gauss_on && k < gauss_dec) {      // complex input channels: [previous (ci / 2) | skip (ci / 2)] (:197)
+                if (gauss_on && k < GDEC) {      // complex input channels: [previous (ci / 2) | skip (ci / 2)] (:197)
                     gauss::make_deconv_plans(gdec[k], wr, wi, toff, /*c0split*/ ci / 2, tout);
                     gauss::fold_tail(gdec[k], w.bias, ga, be, mu, va, slope);
                 }
@@ -190,10 +194,7 @@ class Dccrn final : public Model {
             permute_rows(wih, perm);
             permute_rows(whh, perm);
         };
-        TapSpec one;
-        one.ntaps = 1;
-        one.df[0] = 0;
-        one.dt[0] = 0;
+        const TapSpec one = one_tap();
         auto stack_z = [](const DenseW& a, const DenseW& b, std::vector<float>& w, std::vector<float>& bias) {
             w = a.w;
             w.insert(w.end(), b.w.begin(), b.w.end());
@@ -299,73 +300,18 @@ class Dccrn final : public Model {
         SE_CHECK(ss.B == B && !ss.hist.empty(), "stream_chunk without stream_begin");
         const int HC = stream_hc(), Tw = HC + n;      // (history columns of this schedule: 12, or the causal decoder's 4)
         Bufs& b = bufs(B, Tw);
-        Profiler* pf = &ctx.prof;
         const std::vector<long> rows = stream_rows();
         float* tens[14] = {b.spec, b.E[0], b.E[1], b.E[2], b.E[3], b.E[4], b.E[5], b.D[0], b.D[1], b.D[2], b.D[3], b.D[4], b.D[5], b.est};
         HistBatch hb;
         for (int k = 0; k < 14; ++k) hb.add(tens[k], ss.hist[k], rows[k]);
         launch_hist_batch(hb, B, Tw, HC, false, st);
-        Act4 x{b.spec + Tw, 2, 256, 2L * NBIN * Tw, (long)NBIN * Tw, (long)Tw};
-        int F = 256;
-        for (int k = 0; k < NL; ++k) {        // only the new frames: the history columns came back from the state
-            run_conv(enc[k], x, nullptr, b.E[k], KN[k + 1], F / 2, B, Tw, Tw, st, pf, nullptr, HC);
-            F /= 2;
-            x = act4(b.E[k], KN[k + 1], F, Tw);
-        }
-        if (rlstm) {
-            real_lstm_core(b, b.E[NL - 1] + HC, b.D[0] + HC, Tw, n, st, true);
-        } else {
-        // complex LSTM over the n new frames, continuing from the carried state
-        const int S = 2 * B;
-        for (int part = 0; part < 2; ++part)
-            launch_transpose_akt(b.E[NL - 1] + (size_t)part * 512 * Tw + HC, b.X1 + (size_t)part * B, B, 512, n, 1024L * Tw, Tw,
-                                 512L * S, S, st);
-        {
-            GCParams p = g1.p;
-            p.src0 = b.X1; p.s0_b = 512L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 512; p.C1 = 0;
-            p.Fin = 1; p.Tin = S; p.B = n; p.Q = 1; p.Tout = S;
-            p.dst = b.G; p.d_b = 1024L * S; p.d_c = S; p.d_f = 0;
-            gc_launch_prof(g1, p, st, pf);
-        }
-        lstm_steps(whh1, b.H1, b.G, n, S, st, ss.h[0], ss.c[0]);
-        {
-            GCParams p = g2.p;
-            p.src0 = b.H1; p.src0_z = B; p.s0_b = 256L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 128;
-            p.src1 = b.H1 + 128L * S + B; p.src1_z = -(long)B; p.s1_b = 256L * S; p.s1_c = S; p.s1_f = 0; p.C1 = 128;
-            p.Fin = 1; p.Tin = B; p.B = n; p.Q = 1; p.Tout = B;
-            p.dst = b.G; p.dst_z = B; p.d_b = 1024L * S; p.d_c = S; p.d_f = 0;
-            gc_launch_prof(g2, p, st, pf);
-        }
-        lstm_steps(whh2, b.H2, b.G, n, S, st, ss.h[1], ss.c[1]);
-        {
-            GCParams p = proj.p;
-            p.src0 = b.H2; p.src0_z = B; p.s0_b = 256L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 128;
-            p.src1 = b.H2 + 128L * S + B; p.src1_z = -(long)B; p.s1_b = 256L * S; p.s1_c = S; p.s1_f = 0; p.C1 = 128;
-            p.Fin = 1; p.Tin = B; p.B = n; p.Q = 1; p.Tout = B;
-            p.dst = b.P; p.dst_z = 512L * B; p.d_b = 1024L * B; p.d_c = B; p.d_f = 0;
-            gc_launch_prof(proj, p, st, pf);
-        }
-        for (int part = 0; part < 2; ++part)
-            launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)part * 512 * Tw + HC, n, 512, B, 1024L * B, B,
-                                 1024L * Tw, Tw, st);
-        }
-        F = 4;
-        for (int k = 0; k < NL; ++k) {
-            const int cin = KN[NL - k], c0 = HC - (k + 1);
-            Act4 a0 = act4(b.D[k], cin, F, Tw);
-            Act4 a1 = act4(b.E[NL - 1 - k], cin, F, Tw);
-            if (causal)      // the new columns only, like the encoder: column HC - 1 of both inputs came back from the state
-                run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, Tw, Tw, st, pf, nullptr, HC);
-            else
-                run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, Tw, Tw, st, pf, nullptr, c0, last ? Tw : c0 + n, true);
-            F *= 2;
-        }
-        if (causal) {
-            launch_dccrn_mask(b.D[NL] + HC, b.spec + HC, b.est + HC, B, NBIN, n, Tw, ctx.p_out, st, mask_mode);
-        } else {
-            const int c0 = HC - NL;
-            launch_dccrn_mask(b.D[NL] + c0, b.spec + c0, b.est + c0, B, NBIN, last ? Tw - c0 : n, Tw, ctx.p_out, st, mask_mode);
-        }
+        // only the new frames: the history columns came back from the state.  Look-ahead decoder: layer k runs k + 1 columns behind
+        // them - up to the end of the window (c1 beyond every layer's lag) in the chunk that ends the stream; causal: no lag
+        encoder(b, b.spec, 0, NL, Tw, HC, false, st);
+        core(b, b.E[NL - 1] + HC, 1024L * Tw, b.D[0] + HC, 1024L * Tw, Tw, n, st, true);
+        decoder(b, 0, NL, Tw, HC, last ? Tw + NL : Tw, causal ? 0 : 1, false, st);
+        const int cm = HC - stream_lag();      // the estimate's first new column
+        launch_dccrn_mask(b.D[NL] + cm, b.spec + cm, b.est + cm, B, NBIN, last ? Tw - cm : n, Tw, ctx.p_out, st, mask_mode);
         launch_hist_batch(hb, B, Tw, HC, true, st);
         ss.first = false;
         (void)t0;
@@ -384,10 +330,9 @@ class Dccrn final : public Model {
     LstmBig rl[2];                     // its two layers (input projection plans; H = 256: the recurrence too)
     float* rl_whh[2] = {};             // H = 128: [4H][H] gate-interleaved W_hh for lstm_persist_kernel<128>
     GCPlan enc[NL], g1, g2, proj, tran;
-    gauss::GaussLayer genc[NL], gdec[3];      // encoder 3 - 5 / decoder 0 - 1 (- 2) as three real products (gauss_on)
+    gauss::GaussLayer genc[NL], gdec[GDEC];      // encoder GENC - 5 / decoder 0 - 2 as three real products (gauss_on)
     bool gauss_on = false;
     int mask_mode = 0;                 // 0 'E', 1 'C', 2 'R' (SE_CFG_DCCRN_MASK_*)
-    int gauss_dec = 2;                 // decoder layers on the three-product path (SE_DCCRN_GAUSS = 2: 3 of them, = 1: 2)
     float *whh1 = nullptr, *whh2 = nullptr;
     DeconvPlan dec[NL];
     Bufs cur;
@@ -404,7 +349,7 @@ class Dccrn final : public Model {
         b.spec = a.alloc_f(BT * 2 * NBIN);
         b.est = a.alloc_f(BT * 2 * NBIN);
         b.frames = nullptr;      // the fused iSTFT keeps its frames in LDS (k_stft.hip); kept in the struct for the launcher signature
-        // (gauss_on: E[2..5], D[0], D[1] hold THREE planes per complex channel in the offline decode - [xr + xi | xr | xi], the
+        // (gauss_on: E[2..5], D[0..2] hold THREE planes per complex channel in the offline decode - [xr + xi | xr | xi], the
         // sources of the three-product layers - and K the three products of one layer; the frame-online mode uses the same
         // memory as plain [real | imag] tensors)
         int F = 256;
@@ -416,7 +361,7 @@ class Dccrn final : public Model {
         b.D[0] = a.alloc_f(BT * 256 * 4 * (gauss_on ? 3 : 2) / 2);
         for (int k = 0; k < NL; ++k) {
             F *= 2;
-            b.D[k + 1] = a.alloc_f(BT * KN[NL - k - 1] * F * ((gauss_on && k + 1 < gauss_dec) ? 3 : 2) / 2);
+            b.D[k + 1] = a.alloc_f(BT * KN[NL - k - 1] * F * ((gauss_on && k + 1 < GDEC) ? 3 : 2) / 2);
         }
         b.K = gauss_on ? a.alloc_f(BT * 3 * 128 * 16) : nullptr;      // (decoder 2: 64 x 32 rows per product - the same)
         const size_t S = 2 * (size_t)B;
@@ -431,20 +376,27 @@ class Dccrn final : public Model {
         return cur;
     }
 
-    // real-LSTM core (:187-192) on n frames: src = E[5] at its first frame ([B][256 x 4 = 1024][Tw] rows), dst = D[0] likewise.
-    // Time-major X1 [n][1024][B] -> layer 0 -> H1 [n][H][B] -> layer 1 -> H2 -> tranform -> P [n][1024][B] -> D[0].  stream: continue
-    // from / leave the carried (h, c) of both layers (ss.h / ss.c, [H][B] each).
-    void real_lstm_core(Bufs& b, const float* src, float* dst, int Tw, int n, hipStream_t st, bool stream) {
+    // ---- the recurrent core on n frames.  src = the real plane of E[5] at its first frame (rows of Tw frames; batch stride src_b:
+    // 1024 Tw, or 1536 Tw in a three-plane tensor), dst / dst_b = D[0] likewise.  stream: continue from / leave the carried (h, c) of
+    // both layers in ss.h / ss.c.
+    void core(Bufs& b, const float* src, long src_b, float* dst, long dst_b, int Tw, int n, hipStream_t st, bool stream) {
+        if (rlstm) real_lstm_core(b, src, src_b, dst, dst_b, Tw, n, st, stream);
+        else complex_lstm_core(b, src, src_b, dst, dst_b, Tw, n, st, stream);
+    }
+
+    // real-LSTM core (:187-192): the 1024 rows of a frame are one feature vector.  Time-major X1 [n][1024][B] -> layer 0 -> H1 [n][H][B]
+    // -> layer 1 -> H2 -> tranform -> P [n][1024][B] -> dst.  Carried state: [H][B] per layer.
+    void real_lstm_core(Bufs& b, const float* src, long src_b, float* dst, long dst_b, int Tw, int n, hipStream_t st, bool stream) {
         const int B = b.B, H = rnn_h;
         Profiler* pf = &ctx.prof;
-        launch_transpose_akt(src, b.X1, B, 1024, n, 1024L * Tw, Tw, 1024L * B, B, st);
+        launch_transpose_akt(src, b.X1, B, 1024, n, src_b, Tw, 1024L * B, B, st);
         const float* x = b.X1;
         long x_t = 1024L * B;
         float* outs[2] = {b.H1, b.H2};
         float* cells[2] = {b.C1, b.C2};
         for (int l = 0; l < 2; ++l) {
             if (H == 128) {
-                run_pointwise_cols(rl[l].gin, x, x_t, B, b.G, 4L * H * B, B, n, B, st, pf);
+                run_pointwise(rl[l].gin, x, x_t, B, b.G, 4L * H * B, B, n, B, st, pf);
                 LstmPersistArgs a{};
                 a.st_h = stream ? ss.h[l] : nullptr;
                 a.st_c = stream ? ss.c[l] : nullptr;
@@ -461,13 +413,40 @@ class Dccrn final : public Model {
             x = outs[l];
             x_t = (long)H * B;
         }
-        run_pointwise_cols(tran, b.H2, (long)H * B, B, b.P, 1024L * B, B, n, B, st, pf);
-        launch_transpose_akt(b.P, dst, n, 1024, B, 1024L * B, B, 1024L * Tw, Tw, st);
+        run_pointwise(tran, b.H2, (long)H * B, B, b.P, 1024L * B, B, n, B, st, pf);
+        launch_transpose_akt(b.P, dst, n, 1024, B, 1024L * B, B, dst_b, Tw, st);
+    }
+
+    // complex-LSTM core (:175-185): rows [real 512 | imag 512], time-major, sequences s = part * B + b.  X1 [n][512][S] -> G [n][1024][S] =
+    // [Wih_real; Wih_imag] x X1 -> both first-layer LSTMs -> H1 [n][2][128][S] -> G -> both second-layer LSTMs -> H2 -> r_trans / i_trans
+    // -> P [n][part'][512][B] -> dst.  Carried state: [2 real LSTMs][128][S] per layer.
+    void complex_lstm_core(Bufs& b, const float* src, long src_b, float* dst, long dst_b, int Tw, int n, hipStream_t st, bool stream) {
+        const int B = b.B, S = 2 * B;
+        for (int part = 0; part < 2; ++part)
+            launch_transpose_akt(src + (size_t)part * 512 * Tw, b.X1 + (size_t)part * B, B, 512, n, src_b, Tw, 512L * S, S, st);
+        run_pointwise(g1, b.X1, 512L * S, S, b.G, 1024L * S, S, n, S, st, &ctx.prof);
+        lstm_steps(whh1, b.H1, b.G, n, S, st, stream ? ss.h[0] : nullptr, stream ? ss.c[0] : nullptr);
+        cross_gemm(g2, b.H1, b.G, B, 1024L * S, S, n, B, st);
+        lstm_steps(whh2, b.H2, b.G, n, S, st, stream ? ss.h[1] : nullptr, stream ? ss.c[1] : nullptr);
+        cross_gemm(proj, b.H2, b.P, 512L * B, 1024L * B, B, n, B, st);
+        for (int part = 0; part < 2; ++part)
+            launch_transpose_akt(b.P + (size_t)part * 512 * B, dst + (size_t)part * 512 * Tw, n, 512, B, 1024L * B, B, dst_b, Tw, st);
+    }
+
+    // the two-source GEMM behind a pair of LSTMs, h = [n][lstm][128][S = part * B + b]: z = output part'; src0 = (lstm 0, part z),
+    // src1 = (lstm 1, part 1 - z) - the pairs whose difference (z = 0, weights [W, -W]) / sum (z = 1, [W, W]) part' is (file header)
+    void cross_gemm(const GCPlan& pl, const float* h, float* dst, long dst_z, long d_b, long d_c, int n, int B, hipStream_t st) {
+        const int S = 2 * B;
+        GCParams p = pl.p;
+        p.src0 = h; p.src0_z = B; p.s0_b = 256L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 128;
+        p.src1 = h + 128L * S + B; p.src1_z = -(long)B; p.s1_b = 256L * S; p.s1_c = S; p.s1_f = 0; p.C1 = 128;
+        p.Fin = 1; p.Tin = B; p.B = n; p.Q = 1; p.Tout = B;
+        p.dst = dst; p.dst_z = dst_z; p.d_b = d_b; p.d_c = d_c; p.d_f = 0;
+        gc_launch_prof(pl, p, st, &ctx.prof);
     }
 
     // both real LSTMs (z) x all 2B sequences, all T steps in one persistent launch (k_lstm.hip)
-    void lstm_steps(const float* whh, float* H, const float* G, int T, int S, hipStream_t st, float* st_h = nullptr,
-                    float* st_c = nullptr) {
+    void lstm_steps(const float* whh, float* H, const float* G, int T, int S, hipStream_t st, float* st_h, float* st_c) {
         LstmPersistArgs a{};
         a.st_h = st_h;          // frame-online mode: continue from / leave the carried state ([2][128][S])
         a.st_c = st_c;
@@ -480,145 +459,54 @@ class Dccrn final : public Model {
         launch_lstm_persist(a, st);
     }
 
-    // spec [B][2][257][T] -> mask in b.D[NL] ([B][2][256][T])
-    void network(Bufs& b, const float* spec, hipStream_t st) {
-        // (at every batch: measured at batch 1 ... 32 the three products win, 4.37 against 4.66 ms for one clip)
-        if (gauss_on) {
-            network_gauss(b, spec, st);
-            return;
+    // ---- the block-form layers [k0, k1) on rows of Tw frames.  e2_planes3 (the offline three-product form): E[2] is a three-plane
+    // tensor - encoder layer 2 writes its [R | I] planes, decoder layer 3 reads them as its skip.
+    // Ragged batch: the decoder looks one frame ahead per layer (`out[..., 1:]`, :199) into its (previous, skip) inputs, and a clip
+    // decoded alone has zeros past its last frame - launch_zero_tail behind the layers that do not store them themselves (it launches
+    // nothing without a ragged context, as in a stream chunk).  The causal decoder reads nothing behind a frame: no zero tails.
+    // encoder: output columns [c0, Tw); layer 0 reads bins 1..256 of spec [B][2][257][Tw] (:166)
+    void encoder(Bufs& b, const float* spec, int k0, int k1, int Tw, int c0, bool e2_planes3, hipStream_t st) {
+        for (int k = k0; k < k1; ++k) {
+            const int F = 256 >> k, c = KN[k + 1] / 2;
+            const bool p3 = e2_planes3 && k == 2;
+            const Act4 x = k == 0 ? Act4{spec + Tw, 2, 256, 2L * NBIN * Tw, (long)NBIN * Tw, (long)Tw} : act4(b.E[k - 1], KN[k], F, Tw);
+            const int dstC = p3 ? 3 * c : 2 * c;
+            run_conv(enc[k], x, nullptr, p3 ? b.E[k] + (long)c * (F / 2) * Tw : b.E[k], dstC, F / 2, b.B, Tw, Tw, st, &ctx.prof, nullptr, c0);
+            if (!causal && !conv_zeroes_tail(enc[k])) launch_zero_tail(b.E[k], b.B, (long)dstC * (F / 2), Tw, st);
         }
-        const int B = b.B, T = b.T;
-        Profiler* pf = &ctx.prof;
-        // encoder; first layer reads bins 1..256 (:166)
-        Act4 x{spec + T, 2, 256, 2L * NBIN * T, (long)NBIN * T, (long)T};
-        int F = 256;
-        for (int k = 0; k < NL; ++k) {
-            run_conv(enc[k], x, nullptr, b.E[k], KN[k + 1], F / 2, B, T, T, st, pf);
-            // ragged batch: the decoder looks one frame ahead per layer (`out[..., 1:]`, :199) into its (previous, skip)
-            // inputs, and a clip decoded alone has zeros past its last frame
-            // (the causal decoder, SE_CFG_DCCRN_CAUSAL_DEC, reads nothing behind a frame: no zero tails anywhere below)
-            if (!causal && !conv_zeroes_tail(enc[k])) launch_zero_tail(b.E[k], B, (long)KN[k + 1] * (F / 2), T, st);
-            F /= 2;
-            x = act4(b.E[k], KN[k + 1], F, T);
-        }
-        if (rlstm) {
-            real_lstm_core(b, b.E[NL - 1], b.D[0], T, T, st, false);
-        } else {
-        // ---- complex LSTM (:175-185), time-major, sequences s = part*B + b
-        const int S = 2 * B;
-        for (int part = 0; part < 2; ++part)
-            launch_transpose_akt(b.E[NL - 1] + (size_t)part * 512 * T, b.X1 + (size_t)part * B, B, 512, T, 1024L * T, T,
-                                 512L * S, S, st);
-        {   // G1[t][1024][S] = [Wih_real; Wih_imag] x X1[t]
-            GCParams p = g1.p;
-            p.src0 = b.X1; p.s0_b = 512L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 512; p.C1 = 0;
-            p.Fin = 1; p.Tin = S; p.B = T; p.Q = 1; p.Tout = S;
-            p.dst = b.G; p.d_b = 1024L * S; p.d_c = S; p.d_f = 0;
-            gc_launch_prof(g1, p, st, pf);
-        }
-        lstm_steps(whh1, b.H1, b.G, T, S, st);
-        {   // G2: z = output part';  src0/src1 select (lstm, part) pairs, see file header
-            GCParams p = g2.p;
-            p.src0 = b.H1; p.src0_z = B; p.s0_b = 256L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 128;
-            p.src1 = b.H1 + 128L * S + B; p.src1_z = -(long)B; p.s1_b = 256L * S; p.s1_c = S; p.s1_f = 0; p.C1 = 128;
-            p.Fin = 1; p.Tin = B; p.B = T; p.Q = 1; p.Tout = B;
-            p.dst = b.G; p.dst_z = B; p.d_b = 1024L * S; p.d_c = S; p.d_f = 0;
-            gc_launch_prof(g2, p, st, pf);
-        }
-        lstm_steps(whh2, b.H2, b.G, T, S, st);
-        {   // projection r_trans / i_trans -> P[t][part'][512][B]
-            GCParams p = proj.p;
-            p.src0 = b.H2; p.src0_z = B; p.s0_b = 256L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 128;
-            p.src1 = b.H2 + 128L * S + B; p.src1_z = -(long)B; p.s1_b = 256L * S; p.s1_c = S; p.s1_f = 0; p.C1 = 128;
-            p.Fin = 1; p.Tin = B; p.B = T; p.Q = 1; p.Tout = B;
-            p.dst = b.P; p.dst_z = 512L * B; p.d_b = 1024L * B; p.d_c = B; p.d_f = 0;
-            gc_launch_prof(proj, p, st, pf);
-        }
-        for (int part = 0; part < 2; ++part)
-            launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)part * 512 * T, T, 512, B, 1024L * B, B,
-                                 1024L * T, T, st);
-        }
-        if (!causal) launch_zero_tail(b.D[0], B, 1024L, T, st);
-        // ---- decoder with two-source skips (:196-199)
-        F = 4;
-        for (int k = 0; k < NL; ++k) {
-            const int cin = KN[NL - k];
-            Act4 a0 = act4(b.D[k], cin, F, T);
-            Act4 a1 = act4(b.E[NL - 1 - k], cin, F, T);
-            run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, T, T, st, pf);
-            if (!causal && k + 1 < NL && !conv_zeroes_tail(dec[k])) launch_zero_tail(b.D[k + 1], B, (long)KN[NL - k - 1] * (2 * F), T, st);
-            F *= 2;
+    }
+    // decoder with two-source skips (:196-199): layer k writes columns [c0 - lag (k + 1), min(c1 - lag (k + 1), Tw)) - lag 1 (the
+    // look-ahead stream schedule): every layer one column behind its input, whose look-ahead column is there by then
+    void decoder(Bufs& b, int k0, int k1, int Tw, int c0, int c1, int lag, bool e2_planes3, hipStream_t st) {
+        for (int k = k0; k < k1; ++k) {
+            const int F = 4 << k, cin = KN[NL - k], cout = KN[NL - k - 1], back = lag * (k + 1);
+            const Act4 a0 = act4(b.D[k], cin, F, Tw);
+            const Act4 a1 = e2_planes3 && NL - 1 - k == 2 ? gauss::view3(b.E[2], cin / 2, F, Tw) : act4(b.E[NL - 1 - k], cin, F, Tw);
+            run_deconv(dec[k], a0, &a1, b.D[k + 1], cout, 2 * F, b.B, Tw, Tw, st, &ctx.prof, nullptr, c0 - back, std::min(c1 - back, Tw),
+                       lag != 0);
+            if (!causal && k + 1 < NL && !conv_zeroes_tail(dec[k])) launch_zero_tail(b.D[k + 1], b.B, (long)cout * (2 * F), Tw, st);
         }
     }
 
-    // the same network with encoder 3 - 5 and decoder 0 - 1 as three real products; E[2..5], D[0], D[1] are three-plane tensors
-    void network_gauss(Bufs& b, const float* spec, hipStream_t st) {
+    // spec [B][2][257][T] -> mask in b.D[NL] ([B][2][256][T]).  gauss_on: encoder GENC - 5 and decoder 0 - 2 as three real products
+    // (at every batch: measured at batch 1 ... 32 they win, 4.37 against 4.66 ms for one clip); E[2..5] and D[0..2] are then three-plane
+    // tensors [S | R | I] (a three-plane output stores its sum plane itself; behind block-form layers and the core launch_sum does)
+    void network(Bufs& b, const float* spec, hipStream_t st) {
         const int B = b.B, T = b.T;
         Profiler* pf = &ctx.prof;
-        Act4 x{spec + T, 2, 256, 2L * NBIN * T, (long)NBIN * T, (long)T};
-        int F = 256;
-        for (int k = 0; k < 3; ++k) {             // encoder 0 - 2: block form; layer 2 writes the [R | I] planes of E[2]
-            const int c = KN[k + 1] / 2;
-            float* dst = k == 2 ? b.E[k] + (long)c * (F / 2) * T : b.E[k];
-            run_conv(enc[k], x, nullptr, dst, k == 2 ? 3 * c : 2 * c, F / 2, B, T, T, st, pf);
-            if (!causal && !conv_zeroes_tail(enc[k])) launch_zero_tail(b.E[k], B, (long)(k == 2 ? 3 * c : 2 * c) * (F / 2), T, st);
-            F /= 2;
-            x = act4(b.E[k], KN[k + 1], F, T);
-        }
-        gauss::launch_sum(b.E[2], B, KN[3] / 2, F, T, st, pf);
-        for (int k = 3; k < NL; ++k) {            // encoder 3 - 5
-            gauss::run_layer(genc[k], b.E[k - 1], KN[k] / 2, nullptr, 0, F, F / 2, B, T, b.E[k], true, true, b.K, st, pf);
-            F /= 2;
-        }
-        // ---- complex LSTM (:175-185), time-major, sequences s = part*B + b; E[5] / D[0] are three-plane (512 rows per plane)
-        const int S = 2 * B;
-        for (int part = 0; part < 2; ++part)
-            launch_transpose_akt(b.E[NL - 1] + (size_t)(1 + part) * 512 * T, b.X1 + (size_t)part * B, B, 512, T, 1536L * T, T, 512L * S,
-                                 S, st);
-        {
-            GCParams p = g1.p;
-            p.src0 = b.X1; p.s0_b = 512L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 512; p.C1 = 0;
-            p.Fin = 1; p.Tin = S; p.B = T; p.Q = 1; p.Tout = S;
-            p.dst = b.G; p.d_b = 1024L * S; p.d_c = S; p.d_f = 0;
-            gc_launch_prof(g1, p, st, pf);
-        }
-        lstm_steps(whh1, b.H1, b.G, T, S, st);
-        {
-            GCParams p = g2.p;
-            p.src0 = b.H1; p.src0_z = B; p.s0_b = 256L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 128;
-            p.src1 = b.H1 + 128L * S + B; p.src1_z = -(long)B; p.s1_b = 256L * S; p.s1_c = S; p.s1_f = 0; p.C1 = 128;
-            p.Fin = 1; p.Tin = B; p.B = T; p.Q = 1; p.Tout = B;
-            p.dst = b.G; p.dst_z = B; p.d_b = 1024L * S; p.d_c = S; p.d_f = 0;
-            gc_launch_prof(g2, p, st, pf);
-        }
-        lstm_steps(whh2, b.H2, b.G, T, S, st);
-        {
-            GCParams p = proj.p;
-            p.src0 = b.H2; p.src0_z = B; p.s0_b = 256L * S; p.s0_c = S; p.s0_f = 0; p.C0 = 128;
-            p.src1 = b.H2 + 128L * S + B; p.src1_z = -(long)B; p.s1_b = 256L * S; p.s1_c = S; p.s1_f = 0; p.C1 = 128;
-            p.Fin = 1; p.Tin = B; p.B = T; p.Q = 1; p.Tout = B;
-            p.dst = b.P; p.dst_z = 512L * B; p.d_b = 1024L * B; p.d_c = B; p.d_f = 0;
-            gc_launch_prof(proj, p, st, pf);
-        }
-        for (int part = 0; part < 2; ++part)
-            launch_transpose_akt(b.P + (size_t)part * 512 * B, b.D[0] + (size_t)(1 + part) * 512 * T, T, 512, B, 1024L * B, B, 1536L * T,
-                                 T, st);
-        gauss::launch_sum(b.D[0], B, 128, 4, T, st, pf);
-        if (!causal) launch_zero_tail(b.D[0], B, 1536L, T, st);
-        // ---- decoder: layers 0 - 1 three products (two sources: previous | skip), 2 - 5 block form
-        // (three-plane outputs store their sum plane themselves: sum_plane = dst3)
-        gauss::run_layer(gdec[0], b.D[0], 128, b.E[5], 128, 4, 8, B, T, b.D[1], true, true, b.K, st, pf);
-        gauss::run_layer(gdec[1], b.D[1], 128, b.E[4], 128, 8, 16, B, T, b.D[2], gauss_dec > 2, gauss_dec > 2, b.K, st, pf);
-        if (gauss_dec > 2) gauss::run_layer(gdec[2], b.D[2], 128, b.E[3], 128, 16, 32, B, T, b.D[3], false, false, b.K, st, pf);
-        F = gauss_dec > 2 ? 32 : 16;
-        for (int k = gauss_dec; k < NL; ++k) {
-            const int cin = KN[NL - k];
-            Act4 a0 = act4(b.D[k], cin, F, T);
-            Act4 a1 = (NL - 1 - k) >= 2 ? gauss::view3(b.E[NL - 1 - k], cin / 2, F, T) : act4(b.E[NL - 1 - k], cin, F, T);
-            run_deconv(dec[k], a0, &a1, b.D[k + 1], KN[NL - k - 1], 2 * F, B, T, T, st, pf);
-            if (!causal && k + 1 < NL && !conv_zeroes_tail(dec[k])) launch_zero_tail(b.D[k + 1], B, (long)KN[NL - k - 1] * (2 * F), T, st);
-            F *= 2;
-        }
+        const int ge = gauss_on ? GENC : NL, gd = gauss_on ? GDEC : 0;      // block-form encoder [0, ge), decoder [gd, NL)
+        encoder(b, spec, 0, ge, T, 0, gauss_on, st);
+        if (gauss_on) gauss::launch_sum(b.E[ge - 1], B, KN[ge] / 2, 256 >> ge, T, st, pf);
+        for (int k = ge; k < NL; ++k)
+            gauss::run_layer(genc[k], b.E[k - 1], KN[k] / 2, nullptr, 0, 256 >> k, 128 >> k, B, T, b.E[k], true, true, b.K, st, pf);
+        const long rows = gauss_on ? 1536 : 1024, re = gauss_on ? 512L * T : 0;      // E[5] / D[0]: rows ([S |] R | I), offset of R
+        core(b, b.E[NL - 1] + re, rows * T, b.D[0] + re, rows * T, T, T, st, false);
+        if (gauss_on) gauss::launch_sum(b.D[0], B, 128, 4, T, st, pf);
+        if (!causal) launch_zero_tail(b.D[0], B, rows, T, st);
+        for (int k = 0; k < gd; ++k)      // two sources: previous | skip; the last one's output is [R | I] for the block form
+            gauss::run_layer(gdec[k], b.D[k], KN[NL - k] / 2, b.E[NL - 1 - k], KN[NL - k] / 2, 4 << k, 8 << k, B, T, b.D[k + 1], k + 1 < gd,
+                             k + 1 < gd, b.K, st, pf);
+        decoder(b, gd, NL, T, 0, T, 0, gauss_on, st);
     }
 };
 

@@ -138,7 +138,8 @@ inline GCPlan make_pointwise_plan(const DenseW& d, int act, const std::vector<fl
     return gc_make_plan(d.M, d.Cin, one_tap(), d.w, d.bias, slope, act, epi, 1, 1, 0, tout_hint);
 }
 
-// Launch a pointwise plan on a time-major / generic 3-level tensor: element (o, c, n) at o*s_o + c*s_c + n.
+// Launch a pointwise plan on a time-major / generic 3-level tensor: element (o, c, n) at o*s_o + c*s_c + n (the row length N is
+// free of the pitches: a column range of wider rows runs the same way).
 inline void run_pointwise(const GCPlan& pl, const float* src, long s_o, long s_c, float* dst, long d_o, long d_c, int O,
                           int N, hipStream_t st, Profiler* prof) {
     GCParams p = pl.p;
@@ -157,12 +158,6 @@ inline void run_pointwise(const GCPlan& pl, const float* src, long s_o, long s_c
     p.d_c = d_c;
     p.d_f = 0;
     gc_launch_prof(pl, p, st, prof);
-}
-
-// the same with the row length N decoupled from the row pitches (a column range of wider rows)
-inline void run_pointwise_cols(const GCPlan& pl, const float* src, long s_o, long s_c, float* dst, long d_o, long d_c, int O,
-                               int N, hipStream_t st, Profiler* prof) {
-    run_pointwise(pl, src, s_o, s_c, dst, d_o, d_c, O, N, st, prof);
 }
 
 // LSTM layer with a hidden size too large for register-resident weights (H = 1024 in LSTM/CRN): input projection
@@ -267,7 +262,7 @@ struct LstmBig {
     // per-step stride out_t; h_state stays a dense [H][S] tensor
     void run_stream_strided(const float* x, long x_t, float* G, float* cell, float* h_state, float* out, long out_t, int out_rs,
                             int T, int S, bool first, hipStream_t st, Profiler* prof) const {
-        run_pointwise_cols(gin, x, x_t, S, G, 4L * H * S, S, T, S, st, prof);
+        run_pointwise(gin, x, x_t, S, G, 4L * H * S, S, T, S, st, prof);
         for (int t = 0; t < T; ++t) {
             GCParams p = step.p;
             p.first_step = (first && t == 0);
@@ -299,7 +294,7 @@ struct LstmBig {
     // so disjoint column ranges can run concurrently on different streams (FullSubNet's 257 * B sub-band sequences)
     void run_cols(const float* x, long x_t, float* G, float* cell, float* out, long out_t, int out_rs, int T, int S, int c0,
                   int Sn, hipStream_t st, Profiler* prof) const {
-        run_pointwise_cols(gin, x + c0, x_t, S, G + c0, 4L * H * S, S, T, Sn, st, prof);
+        run_pointwise(gin, x + c0, x_t, S, G + c0, 4L * H * S, S, T, Sn, st, prof);
         if (c0 == 0 && Sn == S && whh_dev && (H == 256 ? lstm_coop256_supported(S) : lstm_coop_supported(H, S, 1))) {
             LstmCoopArgs a{};
             a.gx = G; a.whh = whh_dev; a.out = out; a.cell = cell;
