@@ -96,6 +96,14 @@ enum se_model_id {
  * se_output_samples(n) = n, not the hop-padded length of dccrn_decode_vb.py - and se_stream_* finalises every frame with no
  * extra delay (the `_vb` network: six frames late). */
 #define SE_CFG_DCCRN_CAUSAL_DEC (1 << 16)
+/* Frame-online streams (se_stream_*) that outlive max_samples: the engine keeps only the samples some not-yet-transformed
+ * frame still needs, in a window of max_samples + n_fft + hop floats per row (two such buffers: a slide copies the live tail
+ * from one into the other), instead of every sample since se_stream_begin.  A stream may then run to 2^31 - 1 - max_samples
+ * samples (37 hours at 16 kHz; engines with max_samples < n_fft + 32 hop: 2^31 - 1 - n_fft - 32 hop), where se_stream_push
+ * refuses; a single push may carry at most max_samples samples.  max_samples keeps its other meanings (offline limit, arena
+ * size, cap on max_chunk_frames).  Any model that streams, se_stream_begin and se_stream_begin_running alike; the offline
+ * calls are not affected, and a model that cannot stream still cannot. */
+#define SE_CFG_STREAM_SLIDING (1 << 17)
 
 typedef struct se_config {
     int32_t model;        /* enum se_model_id */
@@ -182,8 +190,9 @@ int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, i
  * with no extra frames of delay), and SE_MODEL_CTSNET / SE_MODEL_TAYLORSENET / SE_MODEL_G2NET when
  * loaded with the cumulative-LayerNorm weights of the `_new` directories (CTSNet_new/Step1_network.py:213-286 - with the
  * InstanceNorm weights of the base directories the network needs the whole utterance and se_stream_begin fails; the engine
- * then carries up to 128 history frames per dilated conv and the running cLN sums).  Streams are limited to max_samples
- * of se_config. */
+ * then carries up to 128 history frames per dilated conv and the running cLN sums).  A stream ends at max_samples of se_config
+ * at the latest (se_stream_push refuses the push that would pass it) unless the engine was created with
+ * SE_CFG_STREAM_SLIDING: then it may run to 2^31 - 1 - max_samples samples, fed at most max_samples samples per push. */
 int se_stream_begin(se_engine* e, int32_t batch, int32_t max_chunk_frames, const float* c_dev, void* stream);
 /* The same, for a caller that has no scale to give: the stream runs on a RUNNING unit-RMS scale.  After every push
  * c = sqrt(samples so far / their sum of squares) - the decode scripts' `c = np.sqrt(len(x) / np.sum(x ** 2.0))`
@@ -266,7 +275,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bit SE_CFG_DCCRN_CAUSAL_DEC: no new entry point, same number) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number) */
 
 #ifdef __cplusplus
 }

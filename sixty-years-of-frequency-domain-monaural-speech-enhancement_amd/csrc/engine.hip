@@ -1,6 +1,7 @@
 // C ABI of the engine (include/se_engine.h): handle, strict state-dict load, stage hooks.
 #include "../../include/se_engine.h"
 #include "model.h"
+#include "stream_window.h"
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -48,10 +49,15 @@ struct se_engine {
     std::unique_ptr<EngineCtx> ctx2[MAX_TWINS];
     std::unique_ptr<Model> twin[MAX_TWINS];
     hipEvent_t ev_tfork = nullptr, ev_tjoin[MAX_TWINS] = {};
-    // se_stream_*: the samples received so far ([batch][max_samples]), frames transformed, samples emitted
+    // se_stream_*: the samples received so far ([batch][max_samples]), frames transformed, samples emitted.
+    // SE_CFG_STREAM_SLIDING: `wav` is a window [batch][pitch] whose column 0 holds the absolute sample w0 (stream_window.h);
+    // a slide copies the live tail into `wav2` and swaps the two
     struct Stream {
         bool active = false;
         int batch = 0, max_chunk = 0, n_total = 0, t_done = 0, o_done = 0;
+        int w0 = 0;
+        long pitch = 0;          // floats per row of wav (max_samples, or stream_window_pitch())
+        float* wav2 = nullptr;
         int carve_B = -1, carve_n = -1;      // (batch, chunk frames) the arena was last carved and zero-filled for
         // running unit-RMS scale (se_stream_begin_running): sum of squares so far per stream, 1 / c per frame in a ring
         bool running = false;
@@ -229,6 +235,7 @@ int se_engine_destroy(se_engine* e) {
         (void)hipEventDestroy(e->ev_join);
     }
     if (e->strm.wav) (void)hipFree(e->strm.wav);
+    if (e->strm.wav2) (void)hipFree(e->strm.wav2);
     if (e->strm.c) (void)hipFree(e->strm.c);
     if (e->strm.sumsq) (void)hipFree(e->strm.sumsq);
     if (e->strm.frame_inv) (void)hipFree(e->strm.frame_inv);
@@ -564,7 +571,7 @@ static void stream_process(se_engine* e, int t_end, bool last, float* out_dev, i
             S.carve_B = B;
             S.carve_n = n;
         }
-        launch_stft(g, S.wav, e->ctx.max_samples, B, S.n_total, Lpad, S.c, e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC);
+        launch_stft(g, S.wav, S.pitch, B, S.n_total, Lpad, S.c, e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, S.w0);
         e->model->stream_chunk(B, t0, n, st, last && t0 + n == t_end);
         S.t_done = t0 + n;
         const bool end = last && S.t_done == t_end;
@@ -607,7 +614,10 @@ static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_fram
         if (S.has_last && S.last_st != st && S.ev_order) SE_HIP(hipStreamWaitEvent(st, S.ev_order, 0));
         S.max_chunk = std::max(1, std::min(max_chunk_frames > 0 ? max_chunk_frames : 16, e->plan_frames - e->model->stream_hc()));
         if (!S.wav) {
-            SE_HIP(hipMalloc(&S.wav, (size_t)e->ctx.max_batch * e->ctx.max_samples * sizeof(float)));
+            const bool sliding = (e->cfg.flags & SE_CFG_STREAM_SLIDING) != 0;
+            S.pitch = sliding ? stream_window_pitch(e->ctx.max_samples, g.n_fft, g.hop) : e->ctx.max_samples;
+            SE_HIP(hipMalloc(&S.wav, (size_t)e->ctx.max_batch * S.pitch * sizeof(float)));
+            if (sliding) SE_HIP(hipMalloc(&S.wav2, (size_t)e->ctx.max_batch * S.pitch * sizeof(float)));
             SE_HIP(hipMalloc(&S.c, (size_t)e->ctx.max_batch * sizeof(float)));
         }
         if (c_dev) SE_HIP(hipMemcpyAsync(S.c, c_dev, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -624,7 +634,7 @@ static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_fram
             launch_fill(S.frame_inv, (long)batch * S.ring, 1.f, st);
         }
         S.batch = batch;
-        S.n_total = S.t_done = S.o_done = 0;
+        S.n_total = S.t_done = S.o_done = S.w0 = 0;
         S.carve_B = S.carve_n = -1;
         e->model->stream_begin(batch, S.max_chunk, st);
         S.active = true;
@@ -647,12 +657,33 @@ int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_
         SE_CHECK(S.active, "se_stream_push without se_stream_begin");
         SE_CHECK(wav_dev && out_dev && n_out && n_new >= 0, "bad argument");
         SE_CHECK(S.batch == 1 || pitch >= n_new, "se_stream_push: input row pitch smaller than n_new");
-        SE_CHECK(S.n_total + n_new <= e->ctx.max_samples, "stream longer than max_samples given at create");
+        const StftGeom& g = e->ctx.geom;
+        const bool sliding = (e->cfg.flags & SE_CFG_STREAM_SLIDING) != 0;
+        int keep = S.w0;
+        if (sliding) {
+            SE_CHECK(n_new <= e->ctx.max_samples, "se_stream_push: a single push may carry at most max_samples samples");
+            SE_CHECK((int64_t)S.n_total + n_new <= stream_sample_limit(e->ctx.max_samples, g.n_fft, g.hop),
+                     "sliding stream longer than 2^31 - 1 - max_samples samples");
+            // the new samples do not fit behind the live tail: drop what no later launch reads (stream_window.h)
+            if ((long)(S.n_total - S.w0) + n_new > S.pitch) {
+                keep = stream_keep_from(g.n_fft, g.hop, S.t_done, S.n_total);
+                SE_CHECK(keep >= S.w0 && keep <= S.n_total && (long)(S.n_total - keep) + n_new <= S.pitch,
+                         "se_stream_push: the stream window cannot hold this push behind the samples still to be transformed");
+            }
+        } else {
+            SE_CHECK(S.n_total + n_new <= e->ctx.max_samples, "stream longer than max_samples given at create");
+        }
         hipStream_t st = static_cast<hipStream_t>(stream);
         StreamMarkScope sms(e, st);
-        const StftGeom& g = e->ctx.geom;
+        if (keep != S.w0) {
+            // [keep, n_total) of every row to column 0 of the other buffer (whole float4s: up to three columns past the tail
+            // travel along, inside the row - the append below overwrites them)
+            launch_stream_slide(S.wav, S.wav2, S.pitch, S.batch, keep - S.w0, (S.n_total - keep + 3) & ~3, st);
+            std::swap(S.wav, S.wav2);
+            S.w0 = keep;
+        }
         if (n_new > 0)
-            SE_HIP(hipMemcpy2DAsync(S.wav + S.n_total, (size_t)e->ctx.max_samples * sizeof(float), wav_dev,
+            SE_HIP(hipMemcpy2DAsync(S.wav + (S.n_total - S.w0), (size_t)S.pitch * sizeof(float), wav_dev,
                                     (size_t)pitch * sizeof(float), (size_t)n_new * sizeof(float), S.batch,
                                     hipMemcpyDeviceToDevice, st));
         S.n_total += n_new;
@@ -660,8 +691,8 @@ int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_
         // left half needs sample n_fft / 2 as well)
         const int t_avail = S.n_total > g.n_fft / 2 ? (S.n_total - g.n_fft / 2 - 1) / g.hop + 1 : 0;
         if (S.running)      // c of the frames this push releases: sqrt(samples so far / their sum of squares)
-            launch_stream_rms(S.wav, e->ctx.max_samples, S.batch, S.n_total, n_new, S.sumsq, S.c, S.frame_inv, S.ring, S.t_done,
-                              std::max(t_avail, S.t_done), st);
+            launch_stream_rms(S.wav, S.pitch, S.batch, S.n_total, n_new, S.sumsq, S.c, S.frame_inv, S.ring, S.t_done,
+                              std::max(t_avail, S.t_done), st, S.w0);
         int written = 0;
         const int will = std::max(0, std::min(S.n_total, (t_avail - e->model->stream_lag()) * g.hop - g.n_fft / 2) - S.o_done);
         SE_CHECK(out_pitch >= will, "output row pitch too small for the samples this push completes");
@@ -683,8 +714,8 @@ int se_stream_flush(se_engine* e, float* out_dev, int64_t out_pitch, int32_t* n_
         StreamMarkScope sms(e, static_cast<hipStream_t>(stream));
         e->ctx.prof_reset();
         if (S.running)
-            launch_stream_rms(S.wav, e->ctx.max_samples, S.batch, S.n_total, 0, S.sumsq, S.c, S.frame_inv, S.ring, S.t_done,
-                              e->model->num_frames(S.n_total), static_cast<hipStream_t>(stream));
+            launch_stream_rms(S.wav, S.pitch, S.batch, S.n_total, 0, S.sumsq, S.c, S.frame_inv, S.ring, S.t_done,
+                              e->model->num_frames(S.n_total), static_cast<hipStream_t>(stream), S.w0);
         stream_process(e, e->model->num_frames(S.n_total), true, out_dev, out_pitch, &written, static_cast<hipStream_t>(stream));
         *n_out = written;
         S.active = false;

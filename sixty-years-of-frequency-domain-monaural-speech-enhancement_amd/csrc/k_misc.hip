@@ -1260,11 +1260,11 @@ void launch_zero_tail(float* x, int B, long rows, int T, hipStream_t s) {
 // it in the iSTFT (ring of 1 / c per frame).  A push that delivers the whole utterance at once therefore IS the offline decode.
 __global__ __launch_bounds__(256) void stream_rms_kernel(const float* __restrict__ wav, long pitch, int n_total, int n_new,
                                                          double* __restrict__ sumsq, float* __restrict__ c,
-                                                         float* __restrict__ frame_inv, int ring, int t0, int t1) {
+                                                         float* __restrict__ frame_inv, int ring, int t0, int t1, int w0) {
     __shared__ double sh[256];
     __shared__ float s_inv;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float* x = wav + (long)b * pitch + (n_total - n_new);
+    const float* x = wav + (long)b * pitch + (n_total - n_new - w0);      // column 0 of a row holds sample w0
     double s = 0.0;
     for (int i = tid; i < n_new; i += 256) s += (double)x[i] * x[i];
     sh[tid] = s;
@@ -1284,8 +1284,30 @@ __global__ __launch_bounds__(256) void stream_rms_kernel(const float* __restrict
     for (int t = t0 + tid; t < t1; t += 256) frame_inv[(long)b * ring + (t & (ring - 1))] = s_inv;
 }
 void launch_stream_rms(const float* wav, long pitch, int B, int n_total, int n_new, double* sumsq, float* c, float* frame_inv,
-                       int ring, int t0, int t1, hipStream_t s) {
-    hipLaunchKernelGGL(stream_rms_kernel, dim3(B), dim3(256), 0, s, wav, pitch, n_total, n_new, sumsq, c, frame_inv, ring, t0, t1);
+                       int ring, int t0, int t1, hipStream_t s, int w0) {
+    SE_CHECK(n_total - n_new >= w0, "launch_stream_rms: the new samples start below the sample origin");
+    hipLaunchKernelGGL(stream_rms_kernel, dim3(B), dim3(256), 0, s, wav, pitch, n_total, n_new, sumsq, c, frame_inv, ring, t0, t1, w0);
+    SE_HIP(hipGetLastError());
+}
+
+// ---- sliding input window of a frame-online stream (SE_CFG_STREAM_SLIDING, stream_window.h) --------------------------------
+// The live tail of every row moves to column 0 of the OTHER buffer of the pair: source and destination never alias, so the
+// copy needs no order.  One float4 per thread, grid (segment of 256 float4, row).
+__global__ __launch_bounds__(256) void stream_slide_kernel(const float* __restrict__ src, float* __restrict__ dst, long pitch,
+                                                           int shift, int n4) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const float4* s4 = reinterpret_cast<const float4*>(src + (long)blockIdx.y * pitch + shift);
+    float4* d4 = reinterpret_cast<float4*>(dst + (long)blockIdx.y * pitch);
+    d4[i] = s4[i];
+}
+void launch_stream_slide(const float* src, float* dst, long pitch, int B, int shift, int n, hipStream_t s) {
+    SE_CHECK(src != dst && shift >= 0 && n >= 0 && ((shift | n) & 3) == 0 && (pitch & 3) == 0 && (long)shift + n <= pitch,
+             "launch_stream_slide: bad range");
+    SE_CHECK(((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0, "launch_stream_slide: rows not 16 B aligned");
+    if (n == 0) return;
+    const int n4 = n / 4;
+    hipLaunchKernelGGL(stream_slide_kernel, dim3((n4 + 255) / 256, B), dim3(256), 0, s, src, dst, pitch, shift, n4);
     SE_HIP(hipGetLastError());
 }
 

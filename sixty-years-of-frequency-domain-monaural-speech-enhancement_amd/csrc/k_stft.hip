@@ -113,11 +113,12 @@ void launch_rms_scale(const float* wav, int B, int L, long pitch, float* c_out, 
 }
 
 void launch_stft(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale,
-                 float p_in, float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0) {
+                 float p_in, float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0, int w0) {
     SE_CHECK(t_first >= 0 && t_first < T, "launch_stft: empty frame range");
+    SE_CHECK(w0 >= 0 && (w0 == 0 || (long)t_first * g.hop - g.n_fft / 2 >= w0), "launch_stft: frames reach below the sample origin");
     SE_CHECK(g.n_fft == 512 || g.n_fft == 320, "unsupported n_fft (320 and 512 are the reference geometries)");
     StageScope prof(STAGE_STFT, s, 4.0 * L * B + (spec_ri ? 8.0 : 0.0) * g.F() * T * B + (mag ? 4.0 : 0.0) * g.F() * T * B);
-    launch_stft2(g, wav, pitch, B, L, Lpad, c_scale, p_in, spec_ri, mag, T, Tp, s, t_first, col0);
+    launch_stft2(g, wav, pitch, B, L, Lpad, c_scale, p_in, spec_ri, mag, T, Tp, s, t_first, col0, w0);
 }
 
 void launch_istft(const StftGeom& g, const float* spec_ri, int B, int T, int Tp, float* /*frames: unused since the fused kernel*/,

@@ -194,6 +194,7 @@ struct Stft2Args {
     const int *len, *lpad, *tlen;
     int t_first, col0;
     const float* tab;
+    int w0;      // sample origin: column 0 of `wav` holds the absolute sample w0 (0 offline; the sliding window of a stream)
 };
 
 // ------------------------------------------------------------------------------------------------ forward
@@ -232,7 +233,9 @@ __global__ __launch_bounds__(Shape<false>::NT) void stft2_kernel(const Stft2Args
 #pragma unroll
     for (int j = 0; j < R1; ++j) wn[j] = wtab[lane + 64 * j];
     const float c = a.c_scale ? a.c_scale[b] : 1.f;
-    const float* x = a.wav + (long)b * a.pitch;
+    // sample positions below are absolute (reflection, zero pad and the fast path's test are those of origin 0); every read is
+    // x[idx] = wav[idx - w0] - a sliding stream window never holds less than the frames of this launch reach (stream_window.h)
+    const float* x = a.wav + (long)b * a.pitch - a.w0;
     auto sample = [&](int t, int n, float w) {
         float v = 0.f;
         if (t < Tb) {
@@ -525,11 +528,11 @@ void set_lds(Kern kernel, size_t bytes) {
 }  // namespace
 
 void launch_stft2(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale, float p_in,
-                  float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0) {
+                  float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0, int w0) {
     const Ragged* rg = ragged_ctx();
     Stft2Args a{wav, pitch, B, L, Lpad, c_scale, p_in, spec_ri, mag, T, Tp, g.hop,
                 rg ? rg->len : nullptr, rg ? rg->lpad : nullptr, rg ? rg->tlen : nullptr, t_first, col0,
-                fft_table(g.n_fft, g.win)};
+                fft_table(g.n_fft, g.win), w0};
     dim3 grid((T - t_first + NFB - 1) / NFB, B);
     // (every variant stays below the 64 KB of LDS a kernel may use without raising its limit)
     const int cp = p_in == 1.f ? 0 : (p_in == 0.5f ? 1 : 2);

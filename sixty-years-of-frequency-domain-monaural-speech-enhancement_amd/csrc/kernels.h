@@ -67,9 +67,11 @@ void launch_rms_scale(const float* wav, int B, int L, long pitch, float* c_out, 
 // magnitude power-compression |X|^p * e^{j angle X}.
 //   wav [B][pitch] (first L samples valid; samples in [L, Lpad) are the decode scripts' zero tail pad)
 //   spec_ri [B][2][F][Tp]   (may be null)     mag [B][F][Tp] = |X|^p (may be null)
-// Streaming: only frames [t_first, T) are transformed, frame t lands in column t - t_first + col0 of the Tp-pitch rows.
+// Streaming: only frames [t_first, T) are transformed, frame t lands in column t - t_first + col0 of the Tp-pitch rows;
+// w0 (sliding stream windows, stream_window.h): column 0 of a wav row holds the absolute sample w0 - L, Lpad and the frame
+// numbers stay absolute, and no frame of the launch may start below w0.
 void launch_stft(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale,
-                 float p_in, float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first = 0, int col0 = 0);
+                 float p_in, float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first = 0, int col0 = 0, int w0 = 0);
 
 // Inverse: spec_ri [B][2][F][Tp] -> windowed frames [B][T][n_fft] (scratch) -> overlap-add, divide by the
 // overlap-added squared window, drop n_fft/2 head, write Lout samples, divide by c.
@@ -83,14 +85,17 @@ void launch_istft(const StftGeom& g, const float* spec_ri, int B, int T, int Tp,
 // released (se_stream_begin_running); c_scale is then null
 
 // running unit-RMS scale of frame-online streams (k_misc.hip): sumsq[b] += the n_new newest samples squared, c[b] =
-// sqrt(n_total / sumsq[b]), frames [t0, t1) get 1 / c[b] in the ring frame_inv [B][ring]
+// sqrt(n_total / sumsq[b]), frames [t0, t1) get 1 / c[b] in the ring frame_inv [B][ring]; w0: the sample origin of wav
 void launch_stream_rms(const float* wav, long pitch, int B, int n_total, int n_new, double* sumsq, float* c, float* frame_inv,
-                       int ring, int t0, int t1, hipStream_t s);
+                       int ring, int t0, int t1, hipStream_t s, int w0 = 0);
+// sliding stream window: dst[b][i] = src[b][shift + i], i < n, for B rows of `pitch` floats in two DIFFERENT buffers (the
+// engine ping-pongs between them).  shift, n and pitch are multiples of 4 and both bases 16 B aligned: 16 B accesses only.
+void launch_stream_slide(const float* src, float* dst, long pitch, int B, int shift, int n, hipStream_t s);
 
 // the kernels behind the two launchers above (k_stft2.hip): FFT points in registers, two LDS exchanges, 32-frame tiles
 // moved through LDS so that the [F][T]-major spectrogram is touched in 128 B runs
 void launch_stft2(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale, float p_in,
-                  float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0);
+                  float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0, int w0 = 0);
 void launch_istft2(const StftGeom& g, const float* spec_ri, int B, int T, int Tp, const float* c_scale, float* wav_out,
                    long out_pitch, int Lout, hipStream_t s, int t_off, int t_lo, int o_lo, const float* frame_inv = nullptr,
                    int ring = 0);

@@ -13,17 +13,21 @@ class EngineError(RuntimeError):
 class Engine:
     """One engine handle = one model replica on one GPU (one per rank)."""
 
+    SE_CFG_STREAM_SLIDING = 1 << 17      # include/se_engine.h
+
     def __init__(self, model, device=0, max_batch=1, max_samples=64000, p_in=1.0, p_out=1.0,
-                 n_fft=0, hop=0, win=0, graphs=False, flags=0):
+                 n_fft=0, hop=0, win=0, graphs=False, flags=0, sliding_stream=False):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.model = model
         cfg = _lib.SeConfig(_lib.MODEL_IDS[model], device, max_batch, max_samples, p_in, p_out, n_fft, hop, win,
-                            (1 if graphs else 0) | int(flags))        # SE_CFG_GRAPHS | model-specific SE_CFG_* bits
+                            (1 if graphs else 0) | int(flags) | (self.SE_CFG_STREAM_SLIDING if sliding_stream else 0))
+        # SE_CFG_GRAPHS | model-specific SE_CFG_* bits | SE_CFG_STREAM_SLIDING (frame-online streams may outlive max_samples)
         if self._lib.se_engine_create(C.byref(cfg), C.byref(self._h)):
             raise EngineError(self._lib.se_last_error(None).decode())
         self.device = device
         self.max_batch, self.max_samples = max_batch, max_samples
+        self.sliding_stream = bool(cfg.flags & self.SE_CFG_STREAM_SLIDING)
         self.finalized = False
         self._stream_batch = 0          # rows of the open frame-online stream (0 = none)
 
@@ -192,6 +196,9 @@ class Engine:
             raise EngineError("stream_push without stream_begin")
         if B != self._stream_batch:      # the engine reads and writes exactly the stream's rows
             raise EngineError(f"stream_push: {B} rows pushed into a stream of {self._stream_batch}")
+        if self.sliding_stream and n > self.max_samples:      # the stream window holds one push of max_samples behind its live tail
+            raise EngineError(f"stream_push: {n} samples in one push, a sliding stream takes at most max_samples "
+                              f"({self.max_samples}) at a time")
         out = torch.empty((B, n + 1024), dtype=torch.float32, device=wav.device)
         n_out = C.c_int32(0)
         pitch = wav.stride(0) if B > 1 else max(n, 1)

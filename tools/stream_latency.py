@@ -2,7 +2,10 @@
 streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, chunk):
   ms_per_push, frames per push, x_realtime = audio time of the push / its wall time (per stream), host_enqueue_ms = the part of it the
   call itself takes (everything enqueued, nothing waited for); launches are not counted.
-Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8]"""
+--sliding N: engines made for max_samples = N with `sliding_stream=True` (SE_CFG_STREAM_SLIDING) instead of max_samples = the clip: the
+  stream outlives the engine's window and slides it; the line then also carries `slides`, the number of slides among the timed pushes,
+  and `mean_ms` (the median of a run in which one push in ~26 slides does not see them).
+Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000]"""
 import argparse
 import json
 import os
@@ -18,22 +21,35 @@ from se_amd import synth  # noqa: E402
 SEEDS = {'crn': 12, 'lstm': 11, 'gcrn': 16, 'dpcrn': 13, 'dccrn': 14, 'taylorsenet_new': 19, 'g2net_new': 20}
 
 
-def build(name, B, L):
+def build(name, B, L, **kw):
     from se_amd import models_new
     from se_amd.models import MODEL_CLASSES
     if name == 'ctsnet_new':
-        return models_new.CTSNet(max_batch=B, max_samples=L).load_synthetic(17, 18)
+        return models_new.CTSNet(max_batch=B, max_samples=L, **kw).load_synthetic(17, 18)
     if name == 'fullsubnet_cum':        # the causal norm (base_model.py:143-166) is what makes FullSubNet streamable
         from se_amd.models import Model
-        return Model(max_batch=B, max_samples=L, norm_type='cumulative_laplace_norm').load_synthetic(15)
+        return Model(max_batch=B, max_samples=L, norm_type='cumulative_laplace_norm', **kw).load_synthetic(15)
     if name == 'dccrn_e':               # DCCRN(rnn_units=256, masking_mode='E'): the real-LSTM core (opt-in: --models dccrn_e)
         from se_amd.models import DCCRN
-        return DCCRN(rnn_units=256, masking_mode='E', max_batch=B, max_samples=L).load_synthetic(24)
+        return DCCRN(rnn_units=256, masking_mode='E', max_batch=B, max_samples=L, **kw).load_synthetic(24)
     if name == 'dccrn_snr':             # DCCRN_SNR/dccrn_decode_snr.py:12: the causal-decoder DCCRN (opt-in: --models dccrn,dccrn_snr)
         from se_amd.models import DCCRN_SNR
         return DCCRN_SNR(rnn_units=256, use_clstm=True, kernel_num=[32, 64, 128, 256, 256, 256], max_batch=B,
-                         max_samples=L).load_synthetic(14)
-    return MODEL_CLASSES[name](max_batch=B, max_samples=L).load_synthetic(SEEDS[name])
+                         max_samples=L, **kw).load_synthetic(14)
+    return MODEL_CLASSES[name](max_batch=B, max_samples=L, **kw).load_synthetic(SEEDS[name])
+
+
+def count_slides(L, piece, first, max_samples, n_fft, hop):
+    """slides among the pushes from index `first` on: the engine's own rule (csrc/stream_window.h) replayed on the host"""
+    pitch = (max_samples + n_fft + hop + 3) // 4 * 4
+    w0 = n = slides = 0
+    for k, p in enumerate(range(0, L - piece + 1, piece)):
+        if n - w0 + piece > pitch:
+            t_done = (n - n_fft // 2 - 1) // hop + 1 if n > n_fft // 2 else 0
+            w0 = max(0, min(t_done * hop - n_fft // 2, n - n_fft // 2 - 1)) // 4 * 4
+            slides += k >= first
+        n += piece
+    return slides
 
 
 def main():
@@ -43,11 +59,12 @@ def main():
     ap.add_argument('--batch', default='1,16')
     ap.add_argument('--chunk', default='1,8')
     ap.add_argument('--seconds', type=float, default=2.0)
+    ap.add_argument('--sliding', type=int, default=0, help='max_samples of a sliding-stream engine (0: a bounded engine as long as the clip)')
     a = ap.parse_args()
     L = int(a.seconds * 16000)
     for name in a.models.split(','):
         for B in map(int, a.batch.split(',')):
-            m = build(name, B, L)
+            m = build(name, B, a.sliding, sliding_stream=True) if a.sliding else build(name, B, L)
             eng = m.engine
             hop = {'dccrn': 128, 'dccrn_snr': 128, 'fullsubnet_cum': 256}.get(name, 160)
             x = torch.from_numpy(np.stack([synth.synth_clip(900 + b, 'speech', L) for b in range(B)])).cuda()
@@ -68,7 +85,12 @@ def main():
                         enq.append(t1 - t0)
                     eng.stream_flush()
                 t = float(np.median(times[4:]))
-                print(json.dumps({'model': name, 'streams': B, 'frames_per_push': chunk, 'ms_per_push': round(t * 1e3, 3),
+                extra = {}
+                if a.sliding:
+                    n_fft = 320 if hop == 160 else 512
+                    extra = {'sliding_max_samples': a.sliding, 'slides': count_slides(L, piece, 4, a.sliding, n_fft, hop),
+                             'pushes': len(times[4:]), 'mean_ms': round(float(np.mean(times[4:])) * 1e3, 3)}
+                print(json.dumps({'model': name, 'streams': B, 'frames_per_push': chunk, 'ms_per_push': round(t * 1e3, 3), **extra,
                                   'p95_ms': round(float(np.percentile(times[4:], 95)) * 1e3, 3),
                                   'host_enqueue_ms': round(float(np.median(enq[4:])) * 1e3, 3),
                                   'x_realtime_per_stream': round(piece / 16000 / t, 2),
