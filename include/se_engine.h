@@ -206,6 +206,24 @@ int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_
                    int32_t* n_out, void* stream);
 int se_stream_flush(se_engine* e, float* out_dev, int64_t out_pitch, int32_t* n_out, void* stream);
 
+/* se_enhance_batch for clips LONGER than max_samples (any length; shorter ones take the same path): `batch` equal-length clips
+ * resident on the device, decoded in windows of max_chunk_frames frames through the frame-online machinery above - conv history,
+ * TCM rings, LSTM (h, c) and the running norm sums carried from window to window - under the WHOLE clip's unit-RMS scale, so
+ * the workspace stays the one planned for max_samples whatever n_samples is.  Row b of wav_out_dev receives
+ * se_output_samples(e, n_samples) samples: what se_enhance_batch returns on an engine created with max_samples >= n_samples,
+ * up to the fp32 rounding of the differently tiled recurrence (the streamed-vs-offline agreement of se_stream_flush).
+ *   n_samples: n_fft ... 2^31 - 1 - n_fft - 32 hop (the position counters; independent of max_samples); batch <= max_batch.
+ *   max_chunk_frames: frames per window; 0 = the largest the workspace was planned for (an offline caller wants large
+ *                     windows, not the frame-online default of 16); larger values are clamped to that.
+ * The input rows are read in place (pitch in_pitch, no copy, no stream window: SE_CFG_STREAM_SLIDING is not needed and the
+ * buffers of se_stream_* are not allocated).  Only the models se_stream_begin accepts - a network that needs the whole
+ * utterance (Uformer; FullSubNet with offline_laplace_norm or the GRU; CTSNet / G2Net / TaylorSENet with InstanceNorm weights)
+ * is refused with the reason in se_last_error.  The call ENDS any stream running on the handle: a later se_stream_push /
+ * se_stream_flush fails with "... without se_stream_begin" (a REFUSED call touches nothing: the stream goes on).  Ordered against frame-online calls on other hipStreams like the
+ * other offline calls. */
+int se_enhance_long(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int32_t batch, int32_t n_samples,
+                    int32_t max_chunk_frames, float* wav_out_dev, int64_t out_pitch, void* stream);
+
 /* Stage hooks, so each oracle-pinned stage can be diffed alone (engine-internal spectrogram layout
  * [B][2][F][T] re/im planes, T contiguous, row pitch = T).
  *   se_stft     : torch.stft / librosa.stft call of the model's decode script, fused with x*c and |X|^p_in.
@@ -275,7 +293,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long: an added entry point, nothing existing changes, same number) */
 
 #ifdef __cplusplus
 }

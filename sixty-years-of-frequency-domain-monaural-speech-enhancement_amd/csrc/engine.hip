@@ -549,8 +549,10 @@ int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, i
 }
 
 // frames [e->strm.t_done, t_end) of the stream through the network, then every output sample they complete (all of them up to
-// the end when `last`); the samples are appended to out row b at out_dev[b * out_pitch + *written ...]
-static void stream_process(se_engine* e, int t_end, bool last, float* out_dev, int64_t out_pitch, int* written, hipStream_t st) {
+// the end when `last`); the samples are appended to out row b at out_dev[b * out_pitch + *written ...].  The input rows are the
+// stream's own window (wav = S.wav, pitch = S.pitch, origin w0 = S.w0) or, for se_enhance_long, the caller's resident clip (origin 0)
+static void stream_process(se_engine* e, const float* wav, long pitch, int w0, int t_end, bool last, float* out_dev,
+                           int64_t out_pitch, int* written, hipStream_t st) {
     se_engine::Stream& S = e->strm;
     const StftGeom& g = e->ctx.geom;
     const int HC = e->model->stream_hc(), LAG = e->model->stream_lag(), B = S.batch;
@@ -571,7 +573,7 @@ static void stream_process(se_engine* e, int t_end, bool last, float* out_dev, i
             S.carve_B = B;
             S.carve_n = n;
         }
-        launch_stft(g, S.wav, S.pitch, B, S.n_total, Lpad, S.c, e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, S.w0);
+        launch_stft(g, wav, pitch, B, S.n_total, Lpad, S.c, e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, w0);
         e->model->stream_chunk(B, t0, n, st, last && t0 + n == t_end);
         S.t_done = t0 + n;
         const bool end = last && S.t_done == t_end;
@@ -618,8 +620,8 @@ static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_fram
             S.pitch = sliding ? stream_window_pitch(e->ctx.max_samples, g.n_fft, g.hop) : e->ctx.max_samples;
             SE_HIP(hipMalloc(&S.wav, (size_t)e->ctx.max_batch * S.pitch * sizeof(float)));
             if (sliding) SE_HIP(hipMalloc(&S.wav2, (size_t)e->ctx.max_batch * S.pitch * sizeof(float)));
-            SE_HIP(hipMalloc(&S.c, (size_t)e->ctx.max_batch * sizeof(float)));
         }
+        if (!S.c) SE_HIP(hipMalloc(&S.c, (size_t)e->ctx.max_batch * sizeof(float)));      // (se_enhance_long may have made it already)
         if (c_dev) SE_HIP(hipMemcpyAsync(S.c, c_dev, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, st));
         else launch_fill(S.c, batch, 1.f, st);
         S.running = running;
@@ -697,7 +699,7 @@ int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_
         const int will = std::max(0, std::min(S.n_total, (t_avail - e->model->stream_lag()) * g.hop - g.n_fft / 2) - S.o_done);
         SE_CHECK(out_pitch >= will, "output row pitch too small for the samples this push completes");
         e->ctx.prof_reset();
-        stream_process(e, std::max(t_avail, S.t_done), false, out_dev, out_pitch, &written, st);
+        stream_process(e, S.wav, S.pitch, S.w0, std::max(t_avail, S.t_done), false, out_dev, out_pitch, &written, st);
         *n_out = written;
     });
 }
@@ -716,9 +718,74 @@ int se_stream_flush(se_engine* e, float* out_dev, int64_t out_pitch, int32_t* n_
         if (S.running)
             launch_stream_rms(S.wav, S.pitch, S.batch, S.n_total, 0, S.sumsq, S.c, S.frame_inv, S.ring, S.t_done,
                               e->model->num_frames(S.n_total), static_cast<hipStream_t>(stream), S.w0);
-        stream_process(e, e->model->num_frames(S.n_total), true, out_dev, out_pitch, &written, static_cast<hipStream_t>(stream));
+        stream_process(e, S.wav, S.pitch, S.w0, e->model->num_frames(S.n_total), true, out_dev, out_pitch, &written,
+                       static_cast<hipStream_t>(stream));
         *n_out = written;
         S.active = false;
+    });
+}
+
+// why a model that has no frame-online mode has none: the windowed decode of se_enhance_long is the same walk
+static std::string why_not_causal(const se_engine* e) {
+    switch (e->cfg.model) {
+        case SE_MODEL_UFORMER:
+            return "Uformer attends over every frame of the utterance and its dilated convolutions look ahead in time";
+        case SE_MODEL_FULLSUBNET:
+            if (e->cfg.flags & SE_CFG_FSN_GRU) return "the GRU FullSubNet (SE_CFG_FSN_GRU) has no frame-online mode";
+            return "FullSubNet with offline_laplace_norm divides every frame by a mean over the whole utterance "
+                   "(cumulative_laplace_norm, SE_CFG_FSN_CUMULATIVE, does not)";
+        case SE_MODEL_CTSNET:
+        case SE_MODEL_G2NET:
+        case SE_MODEL_TAYLORSENET:
+            return "the model was loaded with InstanceNorm weights, whose statistics span the whole utterance (the "
+                   "cumulative-LayerNorm weights of the `_new` directories do not)";
+        default: return "the model has no frame-online mode";
+    }
+}
+
+int se_enhance_long(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int32_t batch, int32_t n_samples,
+                    int32_t max_chunk_frames, float* wav_out_dev, int64_t out_pitch, void* stream) {
+    if (!e) return 1;
+    return guard(e, [&] {
+        SE_CHECK(e->finalized, "engine not finalized");
+        se_engine::Stream& S = e->strm;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        SE_CHECK(wav_in_dev && wav_out_dev, "null argument");
+        SE_CHECK(e->model->stream_supported(),
+                 "se_enhance_long decodes in windows, which needs a network that is causal end to end: " + why_not_causal(e));
+        SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
+        const StftGeom& g = e->ctx.geom;
+        SE_CHECK(n_samples >= g.n_fft, "se_enhance_long: n_samples shorter than one FFT frame (n_fft)");
+        // no push follows, so the headroom of the position counters is the kernels' own reach (stream_window.h), whatever max_samples
+        SE_CHECK(n_samples <= stream_sample_limit(0, g.n_fft, g.hop),
+                 "se_enhance_long: n_samples above the position bound 2^31 - 1 - n_fft - 32 hop");
+        SE_CHECK(batch == 1 || in_pitch >= n_samples, "se_enhance_long: input row pitch smaller than n_samples");
+        SE_CHECK(out_pitch >= e->model->output_samples(n_samples), "se_enhance_long: output row pitch smaller than se_output_samples(n_samples)");
+        SE_CHECK(max_chunk_frames >= 0, "se_enhance_long: negative max_chunk_frames");
+        SE_CHECK((g.n_fft + g.hop - 1) / g.hop - 1 + e->model->stream_lag() <= e->model->stream_hc(),
+                 "front end overlap + look-ahead exceed the history the model keeps");
+        // every refusal is above: a refused call leaves a stream running on this handle as it was.  From here the call takes over
+        // the stream state, so that stream ends
+        S.active = false;
+        S.carve_B = -1;
+        stream_order_wait(e, st);
+        StreamMarkScope sms(e, st);
+        // the whole clip's unit-RMS scale first, then the stream's begin step and one walk over every frame, the last window
+        // included (right-edge reflection, hop-multiple tail pad); the STFT reads the caller's rows, nothing is copied
+        const int room = std::max(1, e->plan_frames - e->model->stream_hc());
+        S.max_chunk = max_chunk_frames > 0 ? std::min(max_chunk_frames, room) : room;
+        if (!S.c) SE_HIP(hipMalloc(&S.c, (size_t)e->ctx.max_batch * sizeof(float)));
+        e->ctx.prof_reset();
+        launch_rms_scale(wav_in_dev, batch, n_samples, in_pitch, S.c, st);
+        S.running = false;
+        S.batch = batch;
+        S.n_total = n_samples;
+        S.t_done = S.o_done = S.w0 = 0;
+        S.carve_n = -1;
+        e->model->stream_begin(batch, S.max_chunk, st);
+        int written = 0;
+        stream_process(e, wav_in_dev, in_pitch, 0, e->model->num_frames(n_samples), true, wav_out_dev, out_pitch, &written, st);
+        S.carve_B = -1;
     });
 }
 

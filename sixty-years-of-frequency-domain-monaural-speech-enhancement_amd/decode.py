@@ -109,6 +109,26 @@ def plan_batches(lengths, max_batch, batch_samples, ragged, max_pad=0.15):
     return batches
 
 
+# models whose network is causal end to end as the driver builds them: a clip longer than the engine's max_samples can be decoded
+# in windows (Engine.enhance_long).  The others need the whole utterance at once (Uformer's attention and look-ahead convs,
+# FullSubNet's offline_laplace_norm, the InstanceNorm weights of the base CTSNet / G2Net / TaylorSENet directories).
+LONG_MODELS = frozenset({'lstm', 'crn', 'gcrn', 'dpcrn', 'dccrn', 'dccrn_snr', 'ctsnet_new', 'taylorsenet_new', 'g2net_new'})
+
+
+def plan_long(lengths, max_seconds, fs=16000):
+    """Split clip indices by the engine bound.  max_seconds None: no bound - (longest clip, every index, []).  Else the engine
+    is made for min(longest clip, max_seconds * fs) samples; -> (that size, indices of the clips that fit, indices of the
+    longer ones, which are decoded one at a time in windows)."""
+    longest = max(lengths) if lengths else 0
+    if max_seconds is None:
+        return longest, list(range(len(lengths))), []
+    bound = int(max_seconds * fs)
+    if bound < 1:
+        raise ValueError(f'max_seconds = {max_seconds}: the bound must be at least one sample')
+    short = [i for i, n in enumerate(lengths) if n <= bound]
+    return min(longest, bound), short, [i for i, n in enumerate(lengths) if n > bound]
+
+
 def shard_clips(lengths, rank, world):
     """Clips -> ranks: the length-sorted clip list dealt round-robin (clip k of the sorted order goes to rank k % world), so
     every rank gets the same number of clips (+-1), the same length distribution and therefore the same number of frames
@@ -150,7 +170,7 @@ class _Slot:
 
 
 def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_batch=64, state_dict=None,
-            batch_samples=None, max_pad=0.15, rank=None, world=None, verbose=True, stats=None, readers=4):
+            batch_samples=None, max_pad=0.15, rank=None, world=None, verbose=True, stats=None, readers=4, max_seconds=None):
     """The file -> file decode of a directory (`enhance(args)` of every `*_decode_vb.py`), as a pipeline:
 
       plan     lengths come from the WAV headers only; the length-sorted clip list is dealt round-robin to the ranks and every
@@ -164,7 +184,15 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
                (se_pcm16_encode) and one asynchronous D2H of 2-byte samples;
       writer   a thread writes each clip's `<out>/<same file name>` as soon as its call's samples have landed.
     p_in / p_out None -> the exponents checked in at the model's decode script (host class defaults).  `stats` (a dict)
-    receives the timing of the run (tools/corpus_bench.py)."""
+    receives the timing of the run (tools/corpus_bench.py).
+    max_seconds: bound on the engine's max_samples (and so on its workspace) - the engine is made for min(longest clip,
+    max_seconds); this rank's longer clips are decoded one at a time after the batched calls, in windows (Engine.enhance_long:
+    the same result, the state carried from window to window), and counted in stats['long_clips'].  Those clips bypass the
+    reader / writer pipeline: each is read (wavio.read_wav, also in a PCM_16 corpus), uploaded, decoded, quantised, fetched and
+    written in turn on the calling thread - meant for the rare long recording, not for a corpus of them.  Their time is part
+    of pipeline_s / total_s and clips_per_s counts them, but no stage_busy_s entry does; calls_rank, pad_frac, pad_over_audio
+    and audio_s_rank describe the batched calls only, stats['long_audio_s'] is the audio of the long clips.  A model that
+    cannot be decoded in windows (LONG_MODELS) raises before any file is written.  None: the engine is made for the longest clip."""
     import queue
     import threading
     import time
@@ -199,26 +227,37 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
     if batch_samples is None:
         batch_samples = max_batch * 64000                     # the padded size of a call of max_batch 4 s clips
     own = shard_clips(lengths, rank, world)
-    mine = [[own[k] for k in b] for b in plan_batches([lengths[i] for i in own], max_batch, batch_samples,
-                                                       model in RAGGED_MODELS, max_pad)]
+    eng_samples, fit, over = plan_long([lengths[i] for i in own], max_seconds)
+    long_own, short_own = [own[k] for k in over], [own[k] for k in fit]
+    if long_own and model not in LONG_MODELS:
+        raise ValueError(f'{model} needs a whole utterance in one call and cannot be decoded in windows: '
+                         f'{", ".join(files[i] for i in long_own)} exceed max_seconds = {max_seconds} '
+                         f'({", ".join("%.1f s" % (lengths[i] / 16000.0) for i in long_own)})')
+    mine = [[short_own[k] for k in b] for b in plan_batches([lengths[i] for i in short_own], max_batch, batch_samples,
+                                                             model in RAGGED_MODELS, max_pad)]
     if stats is not None:
-        pad, use = sum(len(b) * max(lengths[i] for i in b) for b in mine), sum(lengths[i] for i in own)
+        pad, use = sum(len(b) * max(lengths[i] for i in b) for b in mine), sum(lengths[i] for i in short_own)
         stats.update(files=len(files), files_rank=len(own), calls_rank=len(mine), world=world,
                      pad_frac=round(1.0 - use / max(pad, 1), 4), pad_over_audio=round(pad / max(use, 1) - 1.0, 4),
                      audio_s_rank=round(use / 16000.0, 2))      # pad_frac: the planner's definition (share of padded rows' samples
                                                                 # that is padding, capped by max_pad); pad_over_audio: extra work / audio
-    if not mine:
+        if max_seconds is not None:
+            # (the figures above are the batched calls'; the clips above the bound, decoded one at a time afterwards, are counted here)
+            stats.update(long_clips=len(long_own), long_audio_s=round(sum(lengths[i] for i in long_own) / 16000.0, 2),
+                         engine_samples=eng_samples)
+    if not mine and not long_own:
         return 0
     # ---- engine: the workspace is sized for the calls this rank actually makes, not for max_batch x the longest clip
-    eng_batch = max(len(b) for b in mine)
-    eng_len = max(lengths[i] for b in mine for i in b)
-    nat_len = max(native[i] for b in mine for i in b)
-    net = _build(model, checkpoint, state_dict, device=device, max_batch=eng_batch, max_samples=max(eng_len, 512),
-                 p_in=p_in, p_out=p_out)
+    # (with max_seconds: for the bound when a clip exceeds it - those clips go through the same workspace in windows afterwards)
+    eng_batch = max((len(b) for b in mine), default=1)
+    eng_len = max((lengths[i] for b in mine for i in b), default=0)
+    nat_len = max((native[i] for b in mine for i in b), default=0)
+    net = _build(model, checkpoint, state_dict, device=device, max_batch=eng_batch,
+                 max_samples=max(eng_samples if long_own else eng_len, 512), p_in=p_in, p_out=p_out)
     eng = net.engine
     lib = _lib.load()
     n_out_max = eng.output_samples(eng_len)
-    NS = 3
+    NS = 3 if mine else 0
     slots = [_Slot(torch, eng_batch, nat_len, eng_len, n_out_max, device, raw16) for _ in range(NS)]
     free = queue.Queue()
     for sl in slots:
@@ -363,6 +402,25 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
         tr.join(timeout=30.0 if not (aborted or errors) else 5.0)
     if errors and not aborted:
         raise errors[0]
+    # ---- the clips above max_seconds, one at a time: the whole clip on the device, decoded in windows by the same engine
+    dev = torch.device('cuda', device)
+    for i in long_own:
+        x = np.ascontiguousarray(wavio.read_wav(os.path.join(mix, files[i]))[0], dtype=np.float32)
+        wav = torch.from_numpy(x).to(dev)
+        st = C.c_void_p(main.cuda_stream)
+        if rates[i] != 16000:
+            nat, wav = wav, torch.empty(lengths[i], dtype=torch.float32, device=dev)
+            _check(lib.se_resample(C.c_void_p(nat.data_ptr()), native[i], 1, native[i], rates[i], 16000,
+                                   C.c_void_p(wav.data_ptr()), lengths[i], st))
+        out = eng.enhance_long(wav.view(1, -1))
+        n = out.shape[1]
+        q = torch.empty(n, dtype=torch.int16, device=dev)
+        _check(lib.se_pcm16_encode(C.c_void_p(out.data_ptr()), n, 1, n, C.c_void_p(q.data_ptr()), n, st))
+        with open(os.path.join(out_dir, files[i]), 'wb', buffering=0) as f:
+            f.write(wavio.wav_header_pcm16(2 * n, args.fs) + q.cpu().numpy().tobytes())
+        cnt[0] += 1
+        if verbose:
+            print(' The %d utterance has been decoded!' % cnt[0])
     if stats is not None:
         t_end = time.perf_counter()
         stats.update(decoded=cnt[0], setup_s=round(t_ready - t_begin, 3), pipeline_s=round(t_end - t_ready, 3),
@@ -371,7 +429,7 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
     return cnt[0]
 
 
-def main():
+def build_parser():
     parser = argparse.ArgumentParser('Recovering audio')
     parser.add_argument('--mix_file_path', type=str, required=True)
     parser.add_argument('--esti_clean_file_path', '--esti_file_path', dest='esti_clean_file_path', type=str, required=True)
@@ -386,7 +444,14 @@ def main():
     parser.add_argument('--noise_type', type=str, default=None)
     parser.add_argument('--seen', type=str, default=None)
     parser.add_argument('--snr', type=str, default='-5')
-    args = parser.parse_args()
+    parser.add_argument('--max-seconds', '--max_seconds', dest='max_seconds', type=float, default=None,
+                        help='make the engine for clips of at most this many seconds (at 16 kHz) instead of the longest of the '
+                             'directory; longer clips are decoded one at a time in windows (models that are causal end to end)')
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if args.model == 'dccrn_snr' and args.noise_type is None:
         args.noise_type = 'cafe'          # this script always decodes one cell of the grid (dccrn_decode_snr.py:118-120)
     if args.seen is None:
@@ -400,7 +465,7 @@ def main():
     import torch
     if 'LOCAL_RANK' in os.environ:
         torch.cuda.set_device(int(os.environ['LOCAL_RANK']) % max(torch.cuda.device_count(), 1))
-    enhance(args, args.model, ck, p_in, p_out, max_batch=args.max_batch)
+    enhance(args, args.model, ck, p_in, p_out, max_batch=args.max_batch, max_seconds=args.max_seconds)
 
 
 if __name__ == '__main__':

@@ -165,6 +165,34 @@ class Engine:
                                                 C.c_void_p(out.data_ptr()), out_pitch, self._stream()))
         return out
 
+    def enhance_long(self, wav, out=None, max_chunk_frames=0):
+        """wav [B, L] float32 cuda tensor, L of any length (max_samples does not bound it) -> [B, output_samples(L)]: the offline
+        decode of the whole clips, run in windows of max_chunk_frames frames (0 = the largest the workspace holds) with the
+        network state carried from window to window (se_enhance_long).  Models that stream only; ends a stream running on
+        this engine."""
+        import torch
+        self._check_tensor(wav, 'enhance_long input', 2)
+        B, L = wav.shape
+        if B < 1 or B > self.max_batch:
+            raise EngineError(f"enhance_long input: {B} rows outside 1..max_batch ({self.max_batch})")
+        if B > 1 and wav.stride(0) < L:
+            raise EngineError(f"enhance_long input: rows of {L} samples overlap (strides {wav.stride()})")
+        max_chunk_frames = int(max_chunk_frames)
+        if max_chunk_frames < 0:
+            raise EngineError(f"enhance_long: max_chunk_frames {max_chunk_frames} is negative (0 = the largest window)")
+        n_out = self.output_samples(L)
+        if out is None:
+            out = torch.empty((B, n_out), dtype=torch.float32, device=wav.device)
+        else:
+            self._check_tensor(out, 'enhance_long output', 2)
+            if out.shape[0] != B or out.shape[1] < n_out:
+                raise EngineError(f"enhance_long output: need [{B}, >= {n_out}], got {tuple(out.shape)}")
+        in_pitch = wav.stride(0) if B > 1 else L
+        out_pitch = out.stride(0) if B > 1 else n_out
+        self._check(self._lib.se_enhance_long(self._h, C.c_void_p(wav.data_ptr()), in_pitch, B, L, max_chunk_frames,
+                                              C.c_void_p(out.data_ptr()), out_pitch, self._stream()))
+        return out
+
     # ------------------------------------------------------------------ frame-online decoding
     def stream_begin(self, batch, c=None, max_chunk_frames=16, running_rms=False):
         """Start `batch` parallel streams; c: per-stream scale tensor (what rms_scale() returns offline) or None = 1.

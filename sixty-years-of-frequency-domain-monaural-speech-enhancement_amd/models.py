@@ -89,6 +89,10 @@ class _EngineModule:
     def enhance_batch(self, wav):
         return self.engine.enhance_batch(wav)
 
+    def enhance_long(self, wav, out=None, max_chunk_frames=0):
+        """enhance_batch for clips of any length, decoded in windows (Engine.enhance_long): models that stream only."""
+        return self.engine.enhance_long(wav, out, max_chunk_frames)
+
     def enhance_ragged(self, wav, lengths):
         return self.engine.enhance_ragged(wav, lengths)
 
@@ -305,6 +309,10 @@ class CTSNet:
 
     def enhance_batch(self, wav):
         return self.engine.enhance_batch(wav)
+
+    def enhance_long(self, wav, out=None, max_chunk_frames=0):
+        """Both stages over clips of any length, in windows (Engine.enhance_long): the cumulative-LayerNorm (`_new`) weights only."""
+        return self.engine.enhance_long(wav, out, max_chunk_frames)
 
     def enhance_ragged(self, wav, lengths):
         return self.engine.enhance_ragged(wav, lengths)
