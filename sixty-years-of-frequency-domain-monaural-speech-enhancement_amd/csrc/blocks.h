@@ -1,5 +1,6 @@
 // Building blocks shared by the TCM / gated-U-Net models (CTSNet, TaylorSENet, G2Net).
 #pragma once
+#include "decode_frame.h"
 #include "rnn.h"
 #include <cmath>
 
@@ -170,7 +171,21 @@ struct TcmBlock {      // Glu / glu (Step1_network.py:158-188, Step2_network.py:
 
 struct TcmScratch {
     float *h, *a, *r, *m;     // [B][64][T] each
+    void alloc(Arena& ar, size_t BT) {
+        for (float** p : {&h, &a, &r, &m}) *p = ar.alloc_f(BT * 64);
+    }
 };
+
+// Linear(F, F) over the frequency axis of x [B][1][F][T] - an F-channel pointwise layer - into one F x T plane per utterance
+// at dst + b * dst_b; t_base: first frame produced (a frame-online chunk that publishes no StreamCtx)
+inline void run_linear_f(const GCPlan& fc, const float* x, float* dst, long dst_b, int F, int B, int T, hipStream_t st, Profiler* pf,
+                         int t_base = 0) {
+    GCParams p = fc.p;
+    p.src0 = x; p.s0_b = (long)F * T; p.s0_c = T; p.s0_f = 0; p.src1 = nullptr;
+    p.Fin = 1; p.Tin = T; p.B = B; p.Q = 1; p.Tout = T; p.t_base = t_base;
+    p.dst = dst; p.d_b = dst_b; p.d_c = T; p.d_f = 0;
+    gc_launch_prof(fc, p, st, pf);
+}
 
 // x [B][256][T] -> y [B][256][T]
 // batch from which one workgroup per utterance beats the multi-launch path (96)

@@ -10,6 +10,7 @@
 // Engine mapping: convs / deconvs are tap-table implicit GEMMs with BatchNorm folded and the activation in the
 // epilogue, skip concatenations are two-source K loops; the 1024-wide LSTMs run time-major ([T][feature][B]) as one
 // input-projection GEMM over all frames plus one fused GEMM + cell-update launch per frame.
+#include "decode_frame.h"
 #include "rnn.h"
 #include <algorithm>
 #include <vector>
@@ -19,6 +20,21 @@ namespace se {
 namespace {
 
 constexpr int NFFT = 320, HOP = 160, NBIN = 161;
+constexpr int EC[5] = {16, 32, 64, 128, 256}, EF[5] = {80, 39, 19, 9, 4};          // CRN: encoder channels / bins per level
+constexpr int DCo[5] = {128, 64, 32, 16, 1}, DF[5] = {9, 19, 39, 80, 161};         // ... decoder
+
+// Feature-major LSTM layers ly[0..n) over x [I][T][B] (rnn.h run_fm), layer l into outs[l]: one clip - all layers as one
+// wavefront launch (which writes the last layer's output only); up to 64 clips - the layers as a pipeline over chunks of frames,
+// one cooperative launch per chunk; otherwise layer by layer
+void lstm_layers_fm(const LstmBig* const* ly, int n, const float* x, float* G, float* cell, float* const* outs, int T, int B,
+                    hipStream_t st, Profiler* pf) {
+    if (B == 1 && lstm_stack_fm(ly, n, x, G, outs[n - 1], T, st, pf)) return;
+    if (lstm_stack_chunked_fm(ly, n, x, G, cell, outs, T, B, st, pf)) return;
+    for (int l = 0; l < n; ++l) {
+        ly[l]->run_fm(x, G, cell, outs[l], T, B, st, pf);
+        x = outs[l];
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ CRN
 class Crn final : public Model {
@@ -32,10 +48,9 @@ class Crn final : public Model {
     StftGeom default_geom() const override { return StftGeom{NFFT, HOP, NFFT}; }
 
     void finalize(const TrackedSD& sd) override {
-        const int EC[6] = {1, 16, 32, 64, 128, 256};
         for (int i = 0; i < 5; ++i) {   // CRN.py:35-71  pad(top 1 frame) + Conv2d((2,3),(1,2)) + BN + ELU
             const std::string p = "en.en_module." + std::to_string(i) + ".";
-            DenseW w = conv_weights(sd.get(p + "1.weight", {EC[i + 1], EC[i], 2, 3}), &sd.get(p + "1.bias", {EC[i + 1]}), true);
+            DenseW w = conv_weights(sd.get(p + "1.weight", {EC[i], i ? EC[i - 1] : 1, 2, 3}), &sd.get(p + "1.bias", {EC[i]}), true);
             fold_bn(w, sd.get(p + "2.weight"), sd.get(p + "2.bias"), sd.get(p + "2.running_mean"), sd.get(p + "2.running_var"));
             enc[i] = make_conv_plan(w, 2, 0, 1, 1, 1, ACT_ELU, {}, EPI_ACT, 401);
         }
@@ -69,23 +84,19 @@ class Crn final : public Model {
         launch_transpose_akt(b.D[5], out, NBIN, B, T, T, (long)NBIN * T, NBIN, (long)T * NBIN, st);
     }
 
-    // (the network is causal end to end - eval BatchNorm is folded - so an equal-length batch runs with its rows zero-extended to
-    // whole 128 B lines, model.h causal_work_frames; the LSTMs still walk the clip's own T frames: Bufs::Tl)
+    // causal end to end: eval BatchNorm is folded (decode_frame.h WorkFrames; the LSTMs walk the clip's own frames, Bufs::Tl)
     int frame_multiple() const override { return causal_frame_multiple(true); }
     void enhance(const float* wav, long pitch, int B, int L, float* out, long out_pitch, hipStream_t st) override {
-        const int T = 1 + L / HOP;
-        const int Tw = causal_work_frames(T, true);
-        const bool rag = ragged_ctx() != nullptr;
-        const int Ts = rag ? Tw : T;          // frames the STFT / iSTFT walk (ragged rows: zeros behind a row's own last frame)
+        WorkFrames wf(ctx, B, L, L, 1 + L / HOP, st, true);
+        const int Tw = wf.Tw, Ts = wf.Ts;
         Bufs& b = bufs(B, Tw);
-        b.Tl = T;
+        wf.own_frames(b.Tl);
         launch_rms_scale(wav, B, L, pitch, b.c, st);                                               // crn_decode_vb.py:34-35
-        if (Tw != T && !rag) SE_HIP(hipMemsetAsync(b.mag, 0, (size_t)B * NBIN * Tw * sizeof(float), st));
+        wf.zero_rows(b.mag, NBIN, st);
         launch_stft(ctx.geom, wav, pitch, B, L, L, b.c, ctx.p_in, b.spec, b.mag, Ts, Tw, st);       // :36-39
         network(b, st);                                                                            // :43
         launch_mag_phase(b.D[5], b.spec, b.est, B, NBIN, Tw, ctx.p_out, st);                       // :46-49
         launch_istft(ctx.geom, b.est, B, Ts, Tw, b.frames, b.c, out, out_pitch, L, st);             // :50-52
-        b.Tl = 0;
     }
 
     // ---- frame-online mode (model.h): every conv / deconv looks back exactly one frame (CRN.py:38 ConstantPad2d top 1 +
@@ -120,25 +131,12 @@ class Crn final : public Model {
         HistBatch hb;
         for (int k = 0; k < 13; ++k) hb.add(tens[k], ss.hist[k], rows[k]);
         launch_hist_batch(hb, B, Tw, HC, false, st);
-        const int EC[5] = {16, 32, 64, 128, 256}, EF[5] = {80, 39, 19, 9, 4};
-        Act4 x = act4(b.mag, 1, NBIN, Tw);
-        for (int i = 0; i < 5; ++i) {
-            run_conv(enc[i], x, nullptr, b.E[i], EC[i], EF[i], B, Tw, Tw, st, pf, nullptr, HC);
-            x = act4(b.E[i], EC[i], EF[i], Tw);
-        }
+        encoder(b, HC, st);
         launch_transpose_akt(b.E[4] + HC, b.X, B, 1024, n, 1024L * Tw, Tw, 1024L * B, B, st);
         lstm[0].run_stream(b.X, b.G, ss.c[0], ss.h[0], b.Hs[0], n, B, ss.first, st, pf);
         lstm[1].run_stream(b.Hs[0], b.G, ss.c[1], ss.h[1], b.Hs[1], n, B, ss.first, st, pf);
         launch_transpose_akt(b.Hs[1], b.D[0] + HC, n, 1024, B, 1024L * B, B, 1024L * Tw, Tw, st);
-        const int DCo[5] = {128, 64, 32, 16, 1}, DF[5] = {9, 19, 39, 80, 161};
-        int cin = 256, fin = 4;
-        for (int i = 0; i < 5; ++i) {
-            Act4 a0 = act4(b.D[i], cin, fin, Tw);
-            Act4 a1 = act4(b.E[4 - i], cin, fin, Tw);
-            run_deconv(dec[i], a0, &a1, b.D[i + 1], DCo[i], DF[i], B, Tw, Tw, st, pf, nullptr, HC);
-            cin = DCo[i];
-            fin = DF[i];
-        }
+        decoder(b, HC, st);
         launch_mag_phase(b.D[5], b.spec, b.est, B, NBIN, Tw, ctx.p_out, st);     // history columns come out as last time
         launch_hist_batch(hb, B, Tw, HC, true, st);
         ss.first = false;
@@ -173,9 +171,7 @@ class Crn final : public Model {
         b.mag = a.alloc_f(BT * NBIN);
         b.est = a.alloc_f(BT * 2 * NBIN);
         b.frames = nullptr;      // the fused iSTFT keeps its frames in LDS (k_stft.hip); kept in the struct for the launcher signature
-        const int EC[5] = {16, 32, 64, 128, 256}, EF[5] = {80, 39, 19, 9, 4};
         for (int i = 0; i < 5; ++i) b.E[i] = a.alloc_f(BT * EC[i] * EF[i]);
-        const int DCo[5] = {128, 64, 32, 16, 1}, DF[5] = {9, 19, 39, 80, 161};
         b.D[0] = a.alloc_f(BT * 1024);
         for (int i = 0; i < 5; ++i) b.D[i + 1] = a.alloc_f(BT * DCo[i] * DF[i]);
         b.X = a.alloc_f(BT * 1024);
@@ -187,31 +183,40 @@ class Crn final : public Model {
         return cur;
     }
 
+    // b.mag [B][161][T] -> b.E[0..4], b.D[0] [B][256][4][T] + skips -> b.D[5] [B][1][161][T];  tb: first frame produced (0
+    // offline, STREAM_HC in a frame-online chunk, whose history columns come from the state)
+    void encoder(Bufs& b, int tb, hipStream_t st) {
+        const int B = b.B, T = b.T;
+        Act4 x = act4(b.mag, 1, NBIN, T);
+        for (int i = 0; i < 5; ++i) {
+            run_conv(enc[i], x, nullptr, b.E[i], EC[i], EF[i], B, T, T, st, &ctx.prof, nullptr, tb);
+            x = act4(b.E[i], EC[i], EF[i], T);
+        }
+    }
+    void decoder(Bufs& b, int tb, hipStream_t st) {
+        const int B = b.B, T = b.T;
+        int cin = 256, fin = 4;
+        for (int i = 0; i < 5; ++i) {
+            Act4 a0 = act4(b.D[i], cin, fin, T);
+            Act4 a1 = act4(b.E[4 - i], cin, fin, T);
+            run_deconv(dec[i], a0, &a1, b.D[i + 1], DCo[i], DF[i], B, T, T, st, &ctx.prof, nullptr, tb);
+            cin = DCo[i];
+            fin = DF[i];
+        }
+    }
+
     // b.mag [B][161][T] -> b.D[5] [B][1][161][T]
     void network(Bufs& b, hipStream_t st) {
         const int B = b.B, T = b.T;
         const int Tl = b.Tl > 0 ? b.Tl : T;      // frames the recurrent section walks (rows may be zero-extended: enhance())
         Profiler* pf = &ctx.prof;
-        const int EC[5] = {16, 32, 64, 128, 256}, EF[5] = {80, 39, 19, 9, 4};
-        Act4 x = act4(b.mag, 1, NBIN, T);
-        for (int i = 0; i < 5; ++i) {
-            run_conv(enc[i], x, nullptr, b.E[i], EC[i], EF[i], B, T, T, st, pf);
-            x = act4(b.E[i], EC[i], EF[i], T);
-        }
+        encoder(b, 0, st);
         // CRN.py:27-31  [B,256,T,4] -> [B,T,1024] -> LSTM x2 -> back;  engine: [B][1024][T] <-> [T][1024][B]
         if (lstm[0].fm_ok(B) && lstm[1].fm_ok(B)) {
             // feature-major [1024][T][B] (rnn.h run_fm): the two 4096 x 1024 input projections are full-width GEMMs
             launch_transpose_akt(b.E[4], b.X, B, 1024, Tl, 1024L * T, T, B, (long)Tl * B, st);
             const LstmBig* ly[2] = {&lstm[0], &lstm[1]};
-            float* outs2[2] = {b.Hs[0], b.Hs[1]};
-            if (B == 1 && lstm_stack_fm(ly, 2, b.X, b.G, b.Hs[1], Tl, st, pf)) {
-                // (one clip: both layers as one wavefront launch, rnn.h)
-            } else if (lstm_stack_chunked_fm(ly, 2, b.X, b.G, b.cell, outs2, Tl, B, st, pf)) {
-                // (up to 64 clips: the two layers as a pipeline over chunks of frames, one cooperative launch per chunk, rnn.h)
-            } else {
-                lstm[0].run_fm(b.X, b.G, b.cell, b.Hs[0], Tl, B, st, pf);
-                lstm[1].run_fm(b.Hs[0], b.G, b.cell, b.Hs[1], Tl, B, st, pf);
-            }
+            lstm_layers_fm(ly, 2, b.X, b.G, b.cell, b.Hs, Tl, B, st, pf);
             launch_transpose_akt(b.Hs[1], b.D[0], Tl, 1024, B, B, (long)Tl * B, 1024L * T, T, st);
         } else {
             launch_transpose_akt(b.E[4], b.X, B, 1024, Tl, 1024L * T, T, 1024L * B, B, st);
@@ -219,15 +224,7 @@ class Crn final : public Model {
             lstm[1].run(b.Hs[0], b.G, b.cell, b.Hs[1], Tl, B, st, pf);
             launch_transpose_akt(b.Hs[1], b.D[0], Tl, 1024, B, 1024L * B, B, 1024L * T, T, st);
         }
-        const int DCo[5] = {128, 64, 32, 16, 1}, DF[5] = {9, 19, 39, 80, 161};
-        int cin = 256, fin = 4;
-        for (int i = 0; i < 5; ++i) {
-            Act4 a0 = act4(b.D[i], cin, fin, T);
-            Act4 a1 = act4(b.E[4 - i], cin, fin, T);
-            run_deconv(dec[i], a0, &a1, b.D[i + 1], DCo[i], DF[i], B, T, T, st, pf);
-            cin = DCo[i];
-            fin = DF[i];
-        }
+        decoder(b, 0, st);
     }
 };
 
@@ -375,16 +372,8 @@ class LstmNet final : public Model {
         const long N = (long)T * B;
         Profiler* pf = &ctx.prof;
         const LstmBig* ly[3] = {&lstm[0], &lstm[1], &lstm[2]};
-        float* outs3[3] = {b.Hs[0], b.Hs[1], b.Hs[0]};
-        if (B == 1 && lstm_stack_fm(ly, 3, b.X, b.G, b.Hs[0], T, st, pf)) {
-            // (one clip: the three layers as one wavefront launch, rnn.h)
-        } else if (lstm_stack_chunked_fm(ly, 3, b.X, b.G, b.cell, outs3, T, B, st, pf)) {
-            // (up to 64 clips: the three layers as a pipeline over chunks of frames, rnn.h)
-        } else {
-            lstm[0].run_fm(b.X, b.G, b.cell, b.Hs[0], T, B, st, pf);
-            lstm[1].run_fm(b.Hs[0], b.G, b.cell, b.Hs[1], T, B, st, pf);
-            lstm[2].run_fm(b.Hs[1], b.G, b.cell, b.Hs[0], T, B, st, pf);
-        }
+        float* outs[3] = {b.Hs[0], b.Hs[1], b.Hs[0]};
+        lstm_layers_fm(ly, 3, b.X, b.G, b.cell, outs, T, B, st, pf);
         run_pointwise(fc_fm, b.Hs[0], 0, N, b.Y, 0, N, 1, (int)N, st, pf);
     }
     // b.X [T][161][B] -> b.Y [T][161][B]

@@ -74,11 +74,7 @@ struct GatedDecoder {
             deconv_norm2d_prelu(dc[i], na[i], a0, &a1, D[i], D[i], co, DF[i], B, T, st, pf);
             a0 = act4(D[i], co, DF[i], T);
         }
-        GCParams p = fc.p;    // Linear(161,161) over F
-        p.src0 = D[4]; p.s0_b = (long)NBIN * T; p.s0_c = T; p.s0_f = 0; p.src1 = nullptr;
-        p.Fin = 1; p.Tin = T; p.B = B; p.Q = 1; p.Tout = T;
-        p.dst = out; p.d_b = out_b; p.d_c = T; p.d_f = 0;
-        gc_launch_prof(fc, p, st, pf);
+        run_linear_f(fc, D[4], out, out_b, NBIN, B, T, st, pf);
     }
 };
 
@@ -153,18 +149,13 @@ class CtsNet final : public Model {
     int frame_multiple() const override { return causal_frame_multiple(cum && has1 && has2); }
     void enhance(const float* wav, long pitch, int B, int L, float* out, long out_pitch, hipStream_t st) override {
         SE_CHECK(has1 && has2, "CTSNet decode needs both stages' weights");
-        const int Lpad = padded_samples(L), T = 1 + Lpad / HOP;
-        // InstanceNorm weights: rows of whole 128 B lines as ragged rows of one length; cLN weights: zero-extended (model.h)
-        PadFrames pad(ctx, B, L, Lpad, T, L, st, cum ? 1 : in_pad_multiple());
-        const int Tw = cum ? causal_work_frames(T, true) : pad.T;
-        const bool rag = ragged_ctx() != nullptr;
-        const int Ts = (cum && !rag) ? T : Tw;          // frames the STFT / iSTFT walk (ragged rows: zeros behind a row's own last frame)
+        const int Lpad = padded_samples(L);
+        WorkFrames wf(ctx, B, L, Lpad, 1 + Lpad / HOP, st, cum);
+        const int Tw = wf.Tw, Ts = wf.Ts;
         Bufs& b = bufs(B, Tw);
         launch_rms_scale(wav, B, L, pitch, b.c, st);                                               // :63-64
-        if (Tw != T && cum && !rag) {
-            SE_HIP(hipMemsetAsync(b.spec, 0, (size_t)B * 2 * NBIN * Tw * sizeof(float), st));
-            SE_HIP(hipMemsetAsync(b.mag, 0, (size_t)B * NBIN * Tw * sizeof(float), st));
-        }
+        wf.zero_rows(b.spec, 2 * NBIN, st);
+        wf.zero_rows(b.mag, NBIN, st);
         launch_stft(ctx.geom, wav, pitch, B, L, Lpad, b.c, ctx.p_in, b.spec, b.mag, Ts, Tw, st);    // :65-76
         step1(b, b.mag, b.est1, st);                                                               // :79
         launch_mag_phase(b.est1, b.spec, b.s1, B, NBIN, Tw, 1.f, st);                              // :80-81
@@ -174,37 +165,29 @@ class CtsNet final : public Model {
         launch_istft(ctx.geom, b.est, B, Ts, Tw, b.frames, b.c, out, out_pitch, L, st);             // :93-96 ([:wav_len])
     }
 
-    // ---- frame-online mode (CTSNet_new: every norm is a cumulative LayerNorm, so the whole network is causal).  The chunk
-    // runs the same launch sequence as enhance() on windows of SH history columns + n new frames; the shared helpers keep
-    // the per-layer history and the cLN sums (kernels.h: StreamCtx).  SH = the deepest look-back: (5 - 1) * 32 frames of
-    // the last dilated conv of a TCM group (its ShareSepConv reaches 62 back).
-    // (with one kernel per TCM block, k_tcm_stream.hip, the dilated convs and FIRs keep their own ring state and the windows
-    // only serve the U-Net's one-frame look-back and the iSTFT overlap: 4 columns - rows of 5 floats instead of 129, and a
-    // one-frame access touches a fraction of the cache lines)
-    const int SH = 4;
+    // ---- frame-online mode (CTSNet_new: every norm is a cumulative LayerNorm, so the whole network is causal): the launch
+    // sequence of enhance() on windows of STREAM_HC history columns + n new frames (decode_frame.h stream_estimate)
     bool stream_supported() const override { return has1 && has2 && cum; }
-    int stream_hc() const override { return SH; }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
         SE_CHECK(stream_supported(), "frame-online CTSNet needs the cumulative-LayerNorm (`_new`) weights of both stages");
         slots.begin(B, st);
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {
-        Bufs& b = bufs(B, SH + n);
+        Bufs& b = bufs(B, STREAM_HC + n);
         *spec = b.spec;
         *mag = b.mag;
         *est = b.est;
     }
     void stream_chunk(int B, int t0, int n, hipStream_t st, bool last) override {
         (void)last;
-        Bufs& b = bufs(B, SH + n);
+        Bufs& b = bufs(B, STREAM_HC + n);
         const int T = b.T;
-        StreamScope sc(slots, SH, n, t0, B);
+        StreamScope sc(slots, STREAM_HC, n, t0, B);
         step1(b, b.mag, b.est1, st);
         launch_mag_phase(b.est1, b.spec, b.s1, B, NBIN, T, 1.f, st);
         step2(b, b.spec, b.s1, b.est, st);
         launch_add(b.est, b.s1, b.est, (long)B * 2 * NBIN * T, st);
-        launch_polar_pow(b.est, b.est, B, NBIN, T, ctx.p_out, st);
-        stream_exchange(b.est, 2L * NBIN * T, (long)NBIN * T, T, B, 2, NBIN, 2, st);      // the iSTFT overlaps one frame back
+        stream_estimate(b.est, b.est, B, NBIN, T, ctx.p_out, st);
     }
 
   private:
@@ -244,10 +227,7 @@ class CtsNet final : public Model {
         b.X[0] = a.alloc_f(BT * 256);
         b.X[1] = a.alloc_f(BT * 256);
         b.acc = a.alloc_f(BT * 256);
-        b.ts.h = a.alloc_f(BT * 64);
-        b.ts.a = a.alloc_f(BT * 64);
-        b.ts.r = a.alloc_f(BT * 64);
-        b.ts.m = a.alloc_f(BT * 64);
+        b.ts.alloc(a, BT);
         cur = b;
         return cur;
     }
@@ -281,17 +261,11 @@ class CtsNet final : public Model {
         static const bool sfork_env = !(getenv("SE_CTSNET_STREAM_FORK") && atoi(getenv("SE_CTSNET_STREAM_FORK")) == 0);
         if (const StreamCtx* scx = stream_ctx()) {
             const bool fork = sfork_env && scx->n <= 2 && b.D2[0] && !ctx.graphs_wanted();
-            if (fork) {
-                hipStream_t s2 = ctx.aux_stream(0);
-                SE_HIP(hipEventRecord(ctx.ev_fork, st));
-                SE_HIP(hipStreamWaitEvent(s2, ctx.ev_fork, 0));
-                de2i.run(b.acc, b.E, b.D2, est + (long)NBIN * b.T, 2L * NBIN * b.T, b.B, b.T, s2, &ctx.aux_prof[0]);
-                SE_HIP(hipEventRecord(ctx.ev_join[0], s2));
-            } else {
-                de2i.run(b.acc, b.E, b.D, est + (long)NBIN * b.T, 2L * NBIN * b.T, b.B, b.T, st, &ctx.prof);
-            }
+            Fork fk(ctx, st, fork);
+            de2i.run(b.acc, b.E, fork ? b.D2 : b.D, est + (long)NBIN * b.T, 2L * NBIN * b.T, b.B, b.T, fk.to(0), fk.prof(0));
+            fk.done(0);
             de2r.run(b.acc, b.E, b.D, est, 2L * NBIN * b.T, b.B, b.T, st, &ctx.prof);
-            if (fork) SE_HIP(hipStreamWaitEvent(st, ctx.ev_join[0], 0));
+            fk.join(0);
             return;
         }
         de2r.run(b.acc, b.E, b.D, est, 2L * NBIN * b.T, b.B, b.T, st, &ctx.prof);

@@ -10,6 +10,7 @@
 //     (contiguous t), both directions in one launch (blockIdx.y);
 //   * inter-frame LSTM (over T, :77-82): transposed to time-major [T][128][B*4], same persistent kernel;
 //   * LayerNorm([4,128]) + residual fused in one kernel; complex mask + decode-script decompress fused.
+#include "decode_frame.h"
 #include "rnn.h"
 #include "k_lstm_short.h"
 
@@ -18,6 +19,8 @@ namespace se {
 namespace {
 
 constexpr int NFFT = 320, HOP = 160, NBIN = 161, CH = 128, NF = 4;
+constexpr int EC[5] = {32, 32, 32, 64, 128}, EF[5] = {80, 39, 19, 9, 4};          // encoder channels / bins per level
+constexpr int DCo[5] = {64, 32, 32, 32, 2}, DF[5] = {9, 19, 39, 80, 161};         // ... decoder
 
 class Dpcrn final : public Model {
   public:
@@ -36,12 +39,11 @@ class Dpcrn final : public Model {
     StftGeom default_geom() const override { return StftGeom{NFFT, HOP, NFFT}; }
 
     void finalize(const TrackedSD& sd) override {
-        const int EC[6] = {2, 32, 32, 32, 64, 128};
         for (int i = 0; i < 5; ++i) {   // DPCRN.py:94-130
             const std::string p = "en.en_module." + std::to_string(i) + ".";
-            DenseW w = conv_weights(sd.get(p + "1.weight", {EC[i + 1], EC[i], 2, 3}), &sd.get(p + "1.bias", {EC[i + 1]}), true);
+            DenseW w = conv_weights(sd.get(p + "1.weight", {EC[i], i ? EC[i - 1] : 2, 2, 3}), &sd.get(p + "1.bias", {EC[i]}), true);
             fold_bn(w, sd.get(p + "2.weight"), sd.get(p + "2.bias"), sd.get(p + "2.running_mean"), sd.get(p + "2.running_var"));
-            enc[i] = make_conv_plan(w, 2, 0, 1, 1, 1, ACT_PRELU, prelu_slopes(sd.get(p + "3.weight"), EC[i + 1]), EPI_ACT, 401);
+            enc[i] = make_conv_plan(w, 2, 0, 1, 1, 1, ACT_PRELU, prelu_slopes(sd.get(p + "3.weight"), EC[i]), EPI_ACT, 401);
         }
         // ---- DPRNN (DPCRN.py:44-57)
         for (int l = 0; l < 2; ++l) {
@@ -104,24 +106,20 @@ class Dpcrn final : public Model {
         launch_transpose_akt(b.est, out, NBIN, 2 * B, T, T, (long)NBIN * T, NBIN, (long)T * NBIN, st);
     }
 
-    // (causal end to end - eval BatchNorm folded, the intra-frame BiLSTM and both LayerNorms work inside one frame - so an
-    // equal-length batch runs with its rows zero-extended to whole 128 B lines, model.h causal_work_frames; the inter-frame LSTMs
-    // walk the clip's own frames: Bufs::Tl)
+    // causal end to end: eval BatchNorm is folded, the intra-frame BiLSTM and both LayerNorms work inside one frame
+    // (decode_frame.h WorkFrames; the inter-frame LSTMs walk the clip's own frames, Bufs::Tl)
     int frame_multiple() const override { return causal_frame_multiple(true); }
     void enhance(const float* wav, long pitch, int B, int L, float* out, long out_pitch, hipStream_t st) override {
-        const int T = 1 + L / HOP;
-        const int Tw = causal_work_frames(T, true);
-        const bool rag = ragged_ctx() != nullptr;
-        const int Ts = rag ? Tw : T;          // frames the STFT / iSTFT walk (ragged rows: zeros behind a row's own last frame)
+        WorkFrames wf(ctx, B, L, L, 1 + L / HOP, st, true);
+        const int Tw = wf.Tw, Ts = wf.Ts;
         Bufs& b = bufs(B, Tw);
-        b.Tl = T;
+        wf.own_frames(b.Tl);
         launch_rms_scale(wav, B, L, pitch, b.c, st);                                               // dpcrn_decode_vb.py:34-35
-        if (Tw != T && !rag) SE_HIP(hipMemsetAsync(b.spec, 0, (size_t)B * 2 * NBIN * Tw * sizeof(float), st));
+        wf.zero_rows(b.spec, 2 * NBIN, st);
         launch_stft(ctx.geom, wav, pitch, B, L, L, b.c, ctx.p_in, b.spec, nullptr, Ts, Tw, st);     // :37-45
         network(b, st);                                                                            // :47
         launch_cmask_apply(b.D[5], b.spec, b.est, B, NBIN, Tw, ctx.p_out, st);                     // model :33-42 + :48-57
         launch_istft(ctx.geom, b.est, B, Ts, Tw, b.frames, b.c, out, out_pitch, L, st);             // :58-60
-        b.Tl = 0;
     }
 
     // ---- frame-online mode (model.h): (de)convs look back one frame (DPCRN.py:94-166, same pad / chomp scheme as CRN), the
@@ -150,7 +148,6 @@ class Dpcrn final : public Model {
         SE_CHECK(ss.B == B && !ss.hist.empty(), "stream_chunk without stream_begin");
         const int HC = STREAM_HC, Tw = HC + n;
         Bufs& b = bufs(B, Tw);
-        Profiler* pf = &ctx.prof;
         const std::vector<long> rows = stream_rows();
         float* tens[13] = {b.spec, b.E[0], b.E[1], b.E[2], b.E[3], b.E[4], b.P1, b.D[0], b.D[1], b.D[2], b.D[3], b.D[4], b.D[5]};
         auto restore = [&](int k) { launch_hist_restore(tens[k], ss.hist[k], B, rows[k], Tw, HC, st); };
@@ -161,25 +158,12 @@ class Dpcrn final : public Model {
             if (k != 6 && k != 7) hb.add(tens[k], ss.hist[k], rows[k]);
         }
         launch_hist_batch(hb, B, Tw, HC, false, st);
-        const int EC[5] = {32, 32, 32, 64, 128}, EF[5] = {80, 39, 19, 9, 4};
-        Act4 x = act4(b.spec, 2, NBIN, Tw);
-        for (int i = 0; i < 5; ++i) {
-            run_conv(enc[i], x, nullptr, b.E[i], EC[i], EF[i], B, Tw, Tw, st, pf, nullptr, HC);
-            x = act4(b.E[i], EC[i], EF[i], Tw);
-        }
+        encoder(b, HC, st);
         dprnn(b, b.E[4], b.P1, st, n, 0);
         restore(6);                              // the history columns of a DPRNN output saw no inter-frame LSTM
         dprnn(b, b.P1, b.D[0], st, n, 1);
         restore(7);
-        const int DCo[5] = {64, 32, 32, 32, 2}, DF[5] = {9, 19, 39, 80, 161};
-        int cin = CH, fin = NF;
-        for (int i = 0; i < 5; ++i) {
-            Act4 a0 = act4(b.D[i], cin, fin, Tw);
-            Act4 a1 = act4(b.E[4 - i], cin, fin, Tw);
-            run_deconv(dec[i], a0, &a1, b.D[i + 1], DCo[i], DF[i], B, Tw, Tw, st, pf, nullptr, HC);
-            cin = DCo[i];
-            fin = DF[i];
-        }
+        decoder(b, HC, st);
         launch_cmask_apply(b.D[5], b.spec, b.est, B, NBIN, Tw, ctx.p_out, st);
         launch_hist_batch(hb_all, B, Tw, HC, true, st);
         ss.first = false;
@@ -216,9 +200,7 @@ class Dpcrn final : public Model {
         b.spec = a.alloc_f(BT * 2 * NBIN);
         b.est = a.alloc_f(BT * 2 * NBIN);
         b.frames = nullptr;      // the fused iSTFT keeps its frames in LDS (k_stft.hip); kept in the struct for the launcher signature
-        const int EC[5] = {32, 32, 32, 64, 128}, EF[5] = {80, 39, 19, 9, 4};
         for (int i = 0; i < 5; ++i) b.E[i] = a.alloc_f(BT * EC[i] * EF[i]);
-        const int DCo[5] = {64, 32, 32, 32, 2}, DF[5] = {9, 19, 39, 80, 161};
         b.D[0] = a.alloc_f(BT * CH * NF);
         for (int i = 0; i < 5; ++i) b.D[i + 1] = a.alloc_f(BT * DCo[i] * DF[i]);
         const size_t act = BT * CH * NF;
@@ -309,27 +291,34 @@ class Dpcrn final : public Model {
         launch_layernorm_cf(b.R2, b.R1, ln_w[1], ln_b[1], out, B, CH, NF, T, 1e-5f, st);           // :87-88
     }
 
-    // b.spec [B][2][161][T] -> mask b.D[5] [B][2][161][T]
-    void network(Bufs& b, hipStream_t st) {
+    // b.spec [B][2][161][T] -> b.E[0..4], b.D[0] [B][128][4][T] + skips -> b.D[5] [B][2][161][T];  tb: first frame produced (0
+    // offline, STREAM_HC in a frame-online chunk, whose history columns come from the state)
+    void encoder(Bufs& b, int tb, hipStream_t st) {
         const int B = b.B, T = b.T;
-        Profiler* pf = &ctx.prof;
-        const int EC[5] = {32, 32, 32, 64, 128}, EF[5] = {80, 39, 19, 9, 4};
         Act4 x = act4(b.spec, 2, NBIN, T);
         for (int i = 0; i < 5; ++i) {
-            run_conv(enc[i], x, nullptr, b.E[i], EC[i], EF[i], B, T, T, st, pf);
+            run_conv(enc[i], x, nullptr, b.E[i], EC[i], EF[i], B, T, T, st, &ctx.prof, nullptr, tb);
             x = act4(b.E[i], EC[i], EF[i], T);
         }
-        dprnn(b, b.E[4], b.P1, st);
-        dprnn(b, b.P1, b.D[0], st);            // second application with the same weights (DPCRN.py:28-29)
-        const int DCo[5] = {64, 32, 32, 32, 2}, DF[5] = {9, 19, 39, 80, 161};
+    }
+    void decoder(Bufs& b, int tb, hipStream_t st) {
+        const int B = b.B, T = b.T;
         int cin = CH, fin = NF;
         for (int i = 0; i < 5; ++i) {
             Act4 a0 = act4(b.D[i], cin, fin, T);
             Act4 a1 = act4(b.E[4 - i], cin, fin, T);
-            run_deconv(dec[i], a0, &a1, b.D[i + 1], DCo[i], DF[i], B, T, T, st, pf);
+            run_deconv(dec[i], a0, &a1, b.D[i + 1], DCo[i], DF[i], B, T, T, st, &ctx.prof, nullptr, tb);
             cin = DCo[i];
             fin = DF[i];
         }
+    }
+
+    // b.spec [B][2][161][T] -> mask b.D[5] [B][2][161][T]
+    void network(Bufs& b, hipStream_t st) {
+        encoder(b, 0, st);
+        dprnn(b, b.E[4], b.P1, st);
+        dprnn(b, b.P1, b.D[0], st);            // second application with the same weights (DPCRN.py:28-29)
+        decoder(b, 0, st);
     }
 };
 

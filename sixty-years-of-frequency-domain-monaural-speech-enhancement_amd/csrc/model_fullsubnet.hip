@@ -13,6 +13,7 @@
 //   sub-band LSTM   : [T+2][32][257*B]   (sequence s = n*B + b: sub-band n of utterance b, hidden 384) - the one
 //                     place a recurrent step is a large GEMM (M = 1536, K = 384, N = 257*B), run on f32 MFMA with the
 //                     LSTM cell fused in the epilogue.
+#include "decode_frame.h"
 #include "rnn.h"
 #include "../../include/se_engine.h"
 
@@ -418,22 +419,13 @@ class FullSubNet final : public Model {
             else sbl[1].run_cols(b.h[0], 384L * S, b.G, cell, b.h[1], 384L * S, 1, Tp, S, c0, Sn, s, p);
             run_pointwise(sb_fc, b.h[1] + c0, 384L * S, S, b.maskT + c0, 2L * S, S, Tp, Sn, s, p);
         };
-        if (parts > 1) {
-            for (int i = 1; i < parts; ++i) (void)ctx.aux_stream(i - 1);
-            SE_HIP(hipEventRecord(ctx.ev_fork, st));
-            for (int i = 1; i < parts; ++i) {
-                const int c0 = i * Sp, Sn = std::min(Sp, S - c0);
-                if (Sn <= 0) break;
-                SE_HIP(hipStreamWaitEvent(ctx.aux[i - 1], ctx.ev_fork, 0));
-                part(c0, Sn, ctx.aux[i - 1], &ctx.aux_prof[i - 1]);
-                SE_HIP(hipEventRecord(ctx.ev_join[i - 1], ctx.aux[i - 1]));
-            }
-            part(0, std::min(Sp, S), st, pf);
-            for (int i = 1; i < parts; ++i)
-                if (i * Sp < S) SE_HIP(hipStreamWaitEvent(st, ctx.ev_join[i - 1], 0));
-        } else {
-            part(0, S, st, pf);
+        Fork fk(ctx, st, true);      // (one part: no auxiliary stream is asked for, Sp >= S)
+        for (int i = 1; i < parts && i * Sp < S; ++i) {
+            part(i * Sp, std::min(Sp, S - i * Sp), fk.to(i - 1), fk.prof(i - 1));
+            fk.done(i - 1);
         }
+        part(0, std::min(Sp, S), st, pf);
+        for (int i = 1; i < parts && i * Sp < S; ++i) fk.join(i - 1);
         // [Tp][2][S] -> [S][2][Tp]
         launch_transpose_akt(b.maskT, b.maskBT, Tp, 2, S, 2L * S, S, 2L * Tp, Tp, st);
     }

@@ -119,48 +119,35 @@ class G2Net final : public Model {
 
     int frame_multiple() const override { return causal_frame_multiple(cum); }
     void enhance(const float* wav, long pitch, int B, int L, float* out, long out_pitch, hipStream_t st) override {
-        const int T = 1 + L / HOP;
-        // InstanceNorm weights: rows of whole 128 B lines as ragged rows of one length; cLN weights: zero-extended (model.h)
-        PadFrames pad(ctx, B, L, L, T, L, st, cum ? 1 : in_pad_multiple());
-        const int Tw = cum ? causal_work_frames(T, true) : pad.T;
-        const bool rag = ragged_ctx() != nullptr;
-        const int Ts = (cum && !rag) ? T : Tw;          // frames the STFT / iSTFT walk (ragged rows: zeros behind a row's own last frame)
+        WorkFrames wf(ctx, B, L, L, 1 + L / HOP, st, cum);
+        const int Tw = wf.Tw, Ts = wf.Ts;
         Bufs& b = bufs(B, Tw);
         launch_rms_scale(wav, B, L, pitch, b.c, st);        // c_engine = 1 / RMS: x * c_engine == x / RMS (:43-44), y / c_engine == y * RMS (:88)
-        if (Tw != T && cum && !rag) SE_HIP(hipMemsetAsync(b.spec, 0, (size_t)B * 2 * NBIN * Tw * sizeof(float), st));
+        wf.zero_rows(b.spec, 2 * NBIN, st);
         launch_stft(ctx.geom, wav, pitch, B, L, L, b.c, ctx.p_in, b.spec, nullptr, Ts, Tw, st);     // :49-61
         const float* y = network(b, st);                                                           // :66-69
         launch_polar_pow(y, b.est, B, NBIN, Tw, ctx.p_out, st);                                    // :76-82
         launch_istft(ctx.geom, b.est, B, Ts, Tw, b.frames, b.c, out, out_pitch, L, st);             // :86-88
     }
 
-    // ---- frame-online mode (G2Net_new: cumulative LayerNorms only).  Windows of SH history columns + n new frames through
-    // the same launch sequence; history / cLN sums are kept by the shared helpers (kernels.h: StreamCtx).  SH covers the
-    // deepest look-back, (3 - 1) * 9 frames of the widest dilated conv.
-    // (with one kernel per TCM block, k_tcm_stream.hip, the dilated convs and FIRs keep their own ring state and the windows
-    // only serve the U-Net's one-frame look-back and the iSTFT overlap: 4 columns - rows of 5 floats instead of 21, and a
-    // one-frame access touches a fraction of the cache lines)
-    const int SH = 4;
+    // ---- frame-online mode (G2Net_new: cumulative LayerNorms only): the launch sequence of enhance() on windows of STREAM_HC
+    // history columns + n new frames (decode_frame.h stream_estimate)
     bool stream_supported() const override { return cum; }
-    int stream_hc() const override { return SH; }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
         SE_CHECK(cum, "frame-online G2Net needs the cumulative-LayerNorm (`_new`) weights");
         slots.begin(B, st);
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {
-        Bufs& b = bufs(B, SH + n);
+        Bufs& b = bufs(B, STREAM_HC + n);
         *spec = b.spec;
         *mag = nullptr;
         *est = b.est;
     }
     void stream_chunk(int B, int t0, int n, hipStream_t st, bool last) override {
         (void)last;
-        Bufs& b = bufs(B, SH + n);
-        const int T = b.T;
-        StreamScope sc(slots, SH, n, t0, B);
-        const float* y = network(b, st);
-        launch_polar_pow(y, b.est, B, NBIN, T, ctx.p_out, st);
-        stream_exchange(b.est, 2L * NBIN * T, (long)NBIN * T, T, B, 2, NBIN, 2, st);      // the iSTFT overlaps one frame back
+        Bufs& b = bufs(B, STREAM_HC + n);
+        StreamScope sc(slots, STREAM_HC, n, t0, B);
+        stream_estimate(network(b, st), b.est, B, NBIN, b.T, ctx.p_out, st);
     }
 
   private:
@@ -178,6 +165,11 @@ class G2Net final : public Model {
     } cur;
     U2Encoder en;
     std::vector<GafStage> st_;
+    // SE_G2NET_FORK=0: the offline decode stays on one stream (network()) and the workspace has no second / third set
+    static bool ofork_on() {
+        static const bool on = !(getenv("SE_G2NET_FORK") && atoi(getenv("SE_G2NET_FORK")) == 0);
+        return on;
+    }
 
     Bufs& bufs(int B, int T) {
         if (cur.B == B && cur.T == T) return cur;
@@ -201,36 +193,18 @@ class G2Net final : public Model {
         b.X[0] = a.alloc_f(BT * 256);
         b.X[1] = a.alloc_f(BT * 256);
         b.us.alloc(a, BT, B);
-        b.ts.h = a.alloc_f(BT * 64);
-        b.ts.a = a.alloc_f(BT * 64);
-        b.ts.r = a.alloc_f(BT * 64);
-        b.ts.m = a.alloc_f(BT * 64);
-        static const bool ofork_env = !(getenv("SE_G2NET_FORK") && atoi(getenv("SE_G2NET_FORK")) == 0);
-        if (T <= 64 || ofork_env) {
+        b.ts.alloc(a, BT);
+        if (T <= 64 || ofork_on()) {
             b.hxg = a.alloc_f(BT * 256);
             for (float** X : {b.Xg, b.Xi}) {
                 X[0] = a.alloc_f(BT * 256);
                 X[1] = a.alloc_f(BT * 256);
             }
-            for (TcmScratch* t : {&b.tsg, &b.tsi}) {
-                t->h = a.alloc_f(BT * 64);
-                t->a = a.alloc_f(BT * 64);
-                t->r = a.alloc_f(BT * 64);
-                t->m = a.alloc_f(BT * 64);
-            }
+            b.tsg.alloc(a, BT);
+            b.tsi.alloc(a, BT);
         }
         cur = b;
         return cur;
-    }
-
-    void gate_in(const GCPlan& pl, const float* feat, const float* pre, float* dst, int B, int T, hipStream_t st,
-                 Profiler* pf = nullptr) {
-        GCParams p = pl.p;
-        p.src0 = feat; p.s0_b = 256L * T; p.s0_c = T; p.s0_f = 0; p.C0 = 256;
-        p.src1 = pre; p.s1_b = 2L * NBIN * T; p.s1_c = T; p.s1_f = 0; p.C1 = 2 * NBIN;
-        p.Fin = 1; p.Tin = T; p.B = B; p.Q = 1; p.Tout = T;
-        p.dst = dst; p.d_b = 256L * T; p.d_c = T; p.d_f = 0;
-        gc_launch_prof(pl, p, st, pf ? pf : &ctx.prof);
     }
 
     // b.spec [B][2][161][T] -> pointer to the last stage output [B][2][161][T]
@@ -252,7 +226,7 @@ class G2Net final : public Model {
         // half of the time (3.3); the neighbours' launches and the 1 x 1 layers in between fill the gaps: G2Net 6 376 / 6 384 ->
         // 6 579 / 6 577 utt/s at batch 256, G2Net_new 6 387 -> 6 597 (+ 3.1 ... 3.3 %; 0.76 GB more arena).  SE_G2NET_FORK=0: one
         // stream (also under the profiler: its kernel summaries are single-stream durations).
-        static const bool ofork_env = !(getenv("SE_G2NET_FORK") && atoi(getenv("SE_G2NET_FORK")) == 0);
+        const bool ofork_env = ofork_on();
         // With three sequences in flight that kernel wins from ONE clip on (batch 1 ... 4: even; 8: + 4.5 %, 32: + 12 %, 64: + 25 %,
         // 96: + 40 %, 128: + 29 %; G2Net_new one clip 5.77 -> 4.20 ms, batch 8 + 38 %, 64 + 36 %), so the model lowers the batch
         // threshold of blocks.h: run_tcm to 1 for its own calls (CTSNet / TaylorSENet, whose TCM groups feed each other, keep 96).
@@ -269,30 +243,32 @@ class G2Net final : public Model {
         // capture through the fork event and leave it through the join events)
         const bool fork = ((sfork_env && stream_ctx() && !ctx.graphs_wanted()) ||
                            (ofork && (!ctx.graphs_wanted() || graph_fork_enabled()))) && b.hxg;
+        // forked, the glance branch and the imaginary focus sequence work in their own tensors
+        float* const hxg = fork ? b.hxg : b.hx;
+        float* const* const Xg = fork ? b.Xg : b.X;
+        float* const* const Xi = fork ? b.Xi : b.X;
+        const TcmScratch &tsg = fork ? b.tsg : b.ts, &tsi = fork ? b.tsi : b.ts;
         for (int s = 0; s < (int)st_.size(); ++s) {
+            Fork fk(ctx, st, fork);
+            hipStream_t sg = fk.to(0);
+            run_fuse_1x1(st_[s].gin, feat, pre, 2 * NBIN, hxg, B, T, sg, fk.prof(0));
+            st_[s].glance.run(hxg, Xg, tsg, b.gain, plane, B, T, sg, fk.prof(0));
+            fk.done(0);
+            run_fuse_1x1(st_[s].fin, feat, pre, 2 * NBIN, b.hx, B, T, st, pf);
+            // the imaginary sequence starts behind the focus branch's input conv, not at the fork point: auxiliary stream 1 waits
+            // for a marker on st (the third join event, whose stream runs nothing) - the one wait Fork has no call for
+            hipStream_t si = st;
             if (fork) {
-                hipStream_t sg = ctx.aux_stream(0), si = ctx.aux_stream(1);
-                (void)ctx.aux_stream(2);                                   // (its join event marks "focus input ready")
-                SE_HIP(hipEventRecord(ctx.ev_fork, st));
-                SE_HIP(hipStreamWaitEvent(sg, ctx.ev_fork, 0));
-                gate_in(st_[s].gin, feat, pre, b.hxg, B, T, sg, &ctx.aux_prof[0]);
-                st_[s].glance.run(b.hxg, b.Xg, b.tsg, b.gain, plane, B, T, sg, &ctx.aux_prof[0]);
-                SE_HIP(hipEventRecord(ctx.ev_join[0], sg));
-                gate_in(st_[s].fin, feat, pre, b.hx, B, T, st);
+                si = ctx.aux_stream(1);
+                (void)ctx.aux_stream(2);
                 SE_HIP(hipEventRecord(ctx.ev_join[2], st));
-                st_[s].fr.run(b.hx, b.X, b.ts, b.resi, 2 * plane, B, T, st, pf);
-                SE_HIP(hipStreamWaitEvent(si, ctx.ev_join[2], 0));
-                st_[s].fi.run(b.hx, b.Xi, b.tsi, b.resi + plane, 2 * plane, B, T, si, &ctx.aux_prof[1]);
-                SE_HIP(hipEventRecord(ctx.ev_join[1], si));
-                SE_HIP(hipStreamWaitEvent(st, ctx.ev_join[0], 0));
-                SE_HIP(hipStreamWaitEvent(st, ctx.ev_join[1], 0));
-            } else {
-                gate_in(st_[s].gin, feat, pre, b.hx, B, T, st);
-                st_[s].glance.run(b.hx, b.X, b.ts, b.gain, plane, B, T, st, pf);
-                gate_in(st_[s].fin, feat, pre, b.hx, B, T, st);
-                st_[s].fr.run(b.hx, b.X, b.ts, b.resi, 2 * plane, B, T, st, pf);
-                st_[s].fi.run(b.hx, b.X, b.ts, b.resi + plane, 2 * plane, B, T, st, pf);
             }
+            st_[s].fr.run(b.hx, b.X, b.ts, b.resi, 2 * plane, B, T, st, pf);
+            if (fork) SE_HIP(hipStreamWaitEvent(si, ctx.ev_join[2], 0));
+            st_[s].fi.run(b.hx, Xi, tsi, b.resi + plane, 2 * plane, B, T, si, fk.prof(1));
+            fk.done(1);
+            fk.join(0);
+            fk.join(1);
             float* nxt = b.pre[s & 1];
             hipLaunchKernelGGL(gaf_combine_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, b.gain, pre, b.resi, nxt,
                                plane, tot);

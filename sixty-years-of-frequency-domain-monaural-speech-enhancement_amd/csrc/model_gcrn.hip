@@ -8,7 +8,7 @@
 // eval-BatchNorm that follows it and the ELU run in the epilogue; the reference's `elu(cat(y, skip))` re-applies
 // ELU to the skip tensors, so elu(e_k) is materialised once and shared by both decoders; the grouped LSTM runs
 // time-major with one fused GEMM + cell launch per step and group, group outputs interleaved by row stride.
-#include "rnn.h"
+#include "blocks.h"
 
 namespace se {
 
@@ -100,23 +100,20 @@ class Gcrn final : public Model {
         launch_transpose_akt(b.est, out, NBIN, 2 * B, T, T, (long)NBIN * T, NBIN, (long)T * NBIN, st);
     }
 
-    // (causal end to end - the convs have no extent in time, eval BatchNorm is folded, LayerNorm is per frame - so an equal-length
-    // batch runs with its rows zero-extended to whole 128 B lines, model.h causal_work_frames; the LSTMs walk the clip's own frames)
+    // causal end to end: the convs have no extent in time, eval BatchNorm is folded, LayerNorm is per frame (decode_frame.h
+    // WorkFrames; the LSTMs walk the clip's own frames, Bufs::Tl)
     int frame_multiple() const override { return causal_frame_multiple(true); }
     void enhance(const float* wav, long pitch, int B, int L, float* out, long out_pitch, hipStream_t st) override {
-        const int T = 1 + L / HOP;
-        const int Tw = causal_work_frames(T, true);
-        const bool rag = ragged_ctx() != nullptr;
-        const int Ts = rag ? Tw : T;          // frames the STFT / iSTFT walk (ragged rows: zeros behind a row's own last frame)
+        WorkFrames wf(ctx, B, L, L, 1 + L / HOP, st, true);
+        const int Tw = wf.Tw, Ts = wf.Ts;
         Bufs& b = bufs(B, Tw);
-        b.Tl = T;
+        wf.own_frames(b.Tl);
         launch_rms_scale(wav, B, L, pitch, b.c, st);                                               // gcrn_decode_vb.py:35-36
-        if (Tw != T && !rag) SE_HIP(hipMemsetAsync(b.spec, 0, (size_t)B * 2 * NBIN * Tw * sizeof(float), st));
+        wf.zero_rows(b.spec, 2 * NBIN, st);
         launch_stft(ctx.geom, wav, pitch, B, L, L, b.c, ctx.p_in, b.spec, nullptr, Ts, Tw, st);     // :37-44
         network(b, st);                                                                            // :46
         launch_polar_pow(b.est, b.est, B, NBIN, Tw, ctx.p_out, st);                                // :47-55
         launch_istft(ctx.geom, b.est, B, Ts, Tw, b.frames, b.c, out, out_pitch, L, st);             // :56-58
-        b.Tl = 0;
     }
 
     // ---- frame-online mode (model.h): the (1,3) convs have no extent in time (GCRN_noncprs.py:42-83), LayerNorm is per
@@ -277,25 +274,14 @@ class Gcrn final : public Model {
                 a0 = act4(b.D[br][i], DCO[i], DF[i], T);
                 if (i < 4) a1 = act4(b.EE[3 - i], EC[4 - i], EF[3 - i], T);
             }
-            // Linear(161,161) over F (:161-162): the [B][1][161][T] map is a 161-channel pointwise layer
-            GCParams p = fc[br].p;
-            p.src0 = b.D[br][4]; p.s0_b = (long)NBIN * T; p.s0_c = T; p.s0_f = 0; p.src1 = nullptr;
-            p.Fin = 1; p.Tin = T; p.B = B; p.Q = 1; p.Tout = T; p.t_base = tb;
-            p.dst = b.est + (long)br * NBIN * T; p.d_b = 2L * NBIN * T; p.d_c = T; p.d_f = 0;
-            gc_launch_prof(fc[br], p, sd, pd);
+            run_linear_f(fc[br], b.D[br][4], b.est + (long)br * NBIN * T, 2L * NBIN * T, NBIN, B, T, sd, pd, tb);      // :161-162
         };
-        if (fork) {
-            hipStream_t s2 = ctx.aux_stream(0);
-            SE_HIP(hipEventRecord(ctx.ev_fork, st));
-            SE_HIP(hipStreamWaitEvent(s2, ctx.ev_fork, 0));
-            decoder(1, s2, &ctx.aux_prof[0]);
-            SE_HIP(hipEventRecord(ctx.ev_join[0], s2));
-            decoder(0, st, pf);
-            SE_HIP(hipStreamWaitEvent(st, ctx.ev_join[0], 0));
-        } else {
-            decoder(0, st, pf);
-            decoder(1, st, pf);
-        }
+        // (forked: the imaginary decoder is enqueued first, on the auxiliary stream; one stream: real, then imaginary)
+        Fork fk(ctx, st, fork);
+        decoder(fork ? 1 : 0, fk.to(0), fk.prof(0));
+        fk.done(0);
+        decoder(fork ? 0 : 1, st, pf);
+        fk.join(0);
     }
 };
 

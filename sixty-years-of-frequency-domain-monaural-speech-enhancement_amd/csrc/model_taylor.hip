@@ -129,47 +129,37 @@ class TaylorSENet final : public Model {
 
     int frame_multiple() const override { return causal_frame_multiple(cum); }
     void enhance(const float* wav, long pitch, int B, int L, float* out, long out_pitch, hipStream_t st) override {
-        const int Lpad = padded_samples(L), T = 1 + Lpad / HOP;
-        // InstanceNorm weights: rows of whole 128 B lines as ragged rows of one length; cLN weights: zero-extended (model.h)
-        PadFrames pad(ctx, B, L, Lpad, T, L, st, cum ? 1 : in_pad_multiple());
-        const int Tw = cum ? causal_work_frames(T, true) : pad.T;
-        const bool rag = ragged_ctx() != nullptr;
-        const int Ts = (cum && !rag) ? T : Tw;          // frames the STFT / iSTFT walk (ragged rows: zeros behind a row's own last frame)
+        const int Lpad = padded_samples(L);
+        WorkFrames wf(ctx, B, L, Lpad, 1 + Lpad / HOP, st, cum);
+        const int Tw = wf.Tw, Ts = wf.Ts;
         Bufs& b = bufs(B, Tw);
         launch_rms_scale(wav, B, L, pitch, b.c, st);                                               // :27-28
-        if (Tw != T && cum && !rag) SE_HIP(hipMemsetAsync(b.spec, 0, (size_t)B * 2 * NBIN * Tw * sizeof(float), st));
+        wf.zero_rows(b.spec, 2 * NBIN, st);
         launch_stft(ctx.geom, wav, pitch, B, L, Lpad, b.c, ctx.p_in, b.spec, nullptr, Ts, Tw, st);  // :30-41
         network(b, st);                                                                            // :42
         launch_polar_pow(b.est, b.est, B, NBIN, Tw, ctx.p_out, st);                                // :44-45
         launch_istft(ctx.geom, b.est, B, Ts, Tw, b.frames, b.c, out, out_pitch, L, st);             // :48-51
     }
 
-    // ---- frame-online mode (TaylorSENet_new: cumulative LayerNorms only).  Windows of SH history columns + n new frames
-    // through the same launch sequence; history / cLN sums are kept by the shared helpers (kernels.h: StreamCtx).  SH is the
-    // deepest look-back, (5 - 1) * 9 frames of the widest dilated conv.
-    // (with one kernel per TCM block, k_tcm_stream.hip, the dilated convs and FIRs keep their own ring state and the windows
-    // only serve the U-Net's one-frame look-back and the iSTFT overlap: 4 columns - rows of 5 floats instead of 37, and a
-    // one-frame access touches a fraction of the cache lines)
-    const int SH = 4;
+    // ---- frame-online mode (TaylorSENet_new: cumulative LayerNorms only): the launch sequence of enhance() on windows of
+    // STREAM_HC history columns + n new frames (decode_frame.h stream_estimate)
     bool stream_supported() const override { return cum; }
-    int stream_hc() const override { return SH; }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
         SE_CHECK(cum, "frame-online TaylorSENet needs the cumulative-LayerNorm (`_new`) weights");
         slots.begin(B, st);
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {
-        Bufs& b = bufs(B, SH + n);
+        Bufs& b = bufs(B, STREAM_HC + n);
         *spec = b.spec;
         *mag = nullptr;
         *est = b.est;
     }
     void stream_chunk(int B, int t0, int n, hipStream_t st, bool last) override {
         (void)last;
-        Bufs& b = bufs(B, SH + n);
-        StreamScope sc(slots, SH, n, t0, B);
+        Bufs& b = bufs(B, STREAM_HC + n);
+        StreamScope sc(slots, STREAM_HC, n, t0, B);
         network(b, st);
-        launch_polar_pow(b.est, b.est, B, NBIN, b.T, ctx.p_out, st);
-        stream_exchange(b.est, 2L * NBIN * b.T, (long)NBIN * b.T, b.T, B, 2, NBIN, 2, st);   // the iSTFT overlaps one frame back
+        stream_estimate(b.est, b.est, B, NBIN, b.T, ctx.p_out, st);
     }
 
   private:
@@ -217,10 +207,7 @@ class TaylorSENet final : public Model {
         b.X[1] = a.alloc_f(BT * 256);
         b.us.alloc(a, BT, B);
         b.us2.alloc(a, BT, B);
-        b.ts.h = a.alloc_f(BT * 64);
-        b.ts.a = a.alloc_f(BT * 64);
-        b.ts.r = a.alloc_f(BT * 64);
-        b.ts.m = a.alloc_f(BT * 64);
+        b.ts.alloc(a, BT);
         cur = b;
         return cur;
     }
@@ -245,14 +232,11 @@ class TaylorSENet final : public Model {
                           (!scx || (sfork_env && scx->n <= 2));
         const bool sen_first = fork || scx;
         const bool turns = scx || fork;
+        Fork fk(ctx, st, fork);
         if (turns) {
             // (the two encoders are enqueued module by module in turn: the host is ~3.5 us per launch ahead of nothing - a chain
             // whose ~80 launches are enqueued behind the other's starts 0.27 ms late; offline that is 5 % of a single clip's decode)
-            hipStream_t s2 = fork ? ctx.aux_stream(0) : st;
-            if (fork) {
-                SE_HIP(hipEventRecord(ctx.ev_fork, st));
-                SE_HIP(hipStreamWaitEvent(s2, ctx.ev_fork, 0));
-            }
+            hipStream_t s2 = fk.to(0);
             const int EF[5] = {79, 39, 19, 9, 4};
             for (int i = 0; i < 5; ++i)
                 for (int which = 0; which < 2; ++which) {
@@ -260,12 +244,12 @@ class TaylorSENet final : public Model {
                     float* const* ens = which ? b.ens : b.sens;
                     const UnetScratch& us = (which || !fork) ? b.us : b.us2;
                     hipStream_t s = which ? st : s2;
-                    Profiler* p = (which || !fork) ? pf : &ctx.aux_prof[0];
+                    Profiler* p = which ? pf : fk.prof(0);
                     const Act4 x = i == 0 ? act4(b.spec, 2, NBIN, T) : act4(ens[i - 1], 64, EF[i - 1], T);
                     if (i < 4) e.m[i].run(x, nullptr, ens[i], us, B, T, s, p);
                     else conv_norm2d_prelu(e.last.plan, e.last.na, x, nullptr, ens[4], ens[4], 64, 4, B, T, s, p);
                 }
-            if (fork) SE_HIP(hipEventRecord(ctx.ev_join[0], s2));
+            fk.done(0);
         }
         // ---- zero-order block (:139-153)
         if (!turns) zen.run(act4(b.spec, 2, NBIN, T), b.ens, b.us, B, T, st, pf);
@@ -288,16 +272,11 @@ class TaylorSENet final : public Model {
         hipLaunchKernelGGL(taylor_zero_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, b.gain, b.spec, b.zero, b.est,
                            plane, tot);
         // ---- separate encoder (:78-82) and the high-order recurrence (:84-93); `zero` doubles as pre_term
-        if (fork) SE_HIP(hipStreamWaitEvent(st, ctx.ev_join[0], 0));
-        else if (!sen_first) sen.run(act4(b.spec, 2, NBIN, T), b.sens, b.us, B, T, st, pf);
+        fk.join(0);
+        if (!sen_first) sen.run(act4(b.spec, 2, NBIN, T), b.sens, b.us, B, T, st, pf);
         float fact = 1.f;
         for (int k = 0; k < (int)htcm.size(); ++k) {
-            GCParams p = h_in[k].p;      // in_conv over cat(feature_head [B][256][T], pre [B][322][T])
-            p.src0 = b.sens[4]; p.s0_b = 256L * T; p.s0_c = T; p.s0_f = 0; p.C0 = 256;
-            p.src1 = b.zero; p.s1_b = 2L * NBIN * T; p.s1_c = T; p.s1_f = 0; p.C1 = 2 * NBIN;
-            p.Fin = 1; p.Tin = T; p.B = B; p.Q = 1; p.Tout = T;
-            p.dst = b.hx; p.d_b = 256L * T; p.d_c = T; p.d_f = 0;
-            gc_launch_prof(h_in[k], p, st, pf);
+            run_fuse_1x1(h_in[k], b.sens[4], b.zero, 2 * NBIN, b.hx, B, T, st, pf);      // in_conv over cat(feature_head, pre)
             const float* y = htcm[k].run(b.hx, b.X, b.ts, B, T, st, pf);
             run_pointwise(h_out[k], y, 256L * T, T, b.hob, 2L * NBIN * T, T, B, T, st, pf);
             fact *= (float)(k + 1);

@@ -9,6 +9,18 @@
 
 namespace se {
 
+// 1 x 1 layer over cat(feat [B][256][T], prev [B][C1][T]) -> dst [B][256][T]: one two-source GEMM (a GAF branch's gated input
+// conv over the previous stage's estimate, a high-order block's in_conv over the previous Taylor term)
+inline void run_fuse_1x1(const GCPlan& pl, const float* feat, const float* prev, int C1, float* dst, int B, int T, hipStream_t st,
+                         Profiler* pf) {
+    GCParams p = pl.p;
+    p.src0 = feat; p.s0_b = 256L * T; p.s0_c = T; p.s0_f = 0; p.C0 = 256;
+    p.src1 = prev; p.s1_b = (long)C1 * T; p.s1_c = T; p.s1_f = 0; p.C1 = C1;
+    p.Fin = 1; p.Tin = T; p.B = B; p.Q = 1; p.Tout = T;
+    p.dst = dst; p.d_b = 256L * T; p.d_c = T; p.d_f = 0;
+    gc_launch_prof(pl, p, st, pf);
+}
+
 struct ConvIN {        // conv (plain or gated) -> InstanceNorm2d -> PReLU
     GCPlan plan;
     NormAct na;
