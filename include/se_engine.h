@@ -224,6 +224,26 @@ int se_stream_flush(se_engine* e, float* out_dev, int64_t out_pitch, int32_t* n_
 int se_enhance_long(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int32_t batch, int32_t n_samples,
                     int32_t max_chunk_frames, float* wav_out_dev, int64_t out_pitch, void* stream);
 
+/* se_enhance_long for `batch` resident clips of DIFFERENT lengths, any of them longer than max_samples: one walk over the
+ * windows of the longest row, every row under its own sizes.  `lengths` is a HOST array of `batch` sample counts, each in
+ * n_fft ... 2^31 - 1 - n_fft - 32 hop (independent of max_samples; shorter clips take the same path).  Row b of wav_in_dev
+ * holds lengths[b] valid samples and nothing past them is read; row b of wav_out_dev receives se_output_samples(e, lengths[b])
+ * samples followed by zeros up to se_output_samples(e, max lengths).  Each row gets what se_enhance_long returns for that clip
+ * alone, up to the fp32 rounding of the differently tiled recurrence: its own whole-clip unit-RMS scale, its own right-edge
+ * reflection / tail pad and frame count (in whichever window holds its end), frames at or past its own last one transformed
+ * to zeros and never overlap-added into its samples (every window's STFT / iSTFT launch sees the rows' frame counts clipped to the
+ * frames that launch owns, derived on the device without a host synchronisation).  The networks are causal, so what a row's state holds after its end
+ * never reaches a sample of it, and no operator on these paths reduces over the batch.  FullSubNet with the cumulative norm
+ * looks two frames ahead at its input only and sees there the zero frames of the STFT, as it does when the row is decoded alone.
+ * NOT accepted here: SE_MODEL_DCCRN with the look-ahead decoder (without SE_CFG_DCCRN_CAUSAL_DEC) - its decoder looks one frame
+ * ahead per layer into tensors that are not zero behind a row's own last frame, and the per-layer zeroing a row that ends
+ * mid-walk needs is not built yet; the call refuses it with that reason (se_enhance_long and se_enhance_ragged decode it as before).
+ *   max_chunk_frames: as se_enhance_long.  in_pitch >= max lengths (batch > 1), out_pitch >= se_output_samples(e, max lengths),
+ *   batch <= max_batch.  Models, refusal reasons and the effect on a running stream: as se_enhance_long (a refused call
+ *   touches nothing, an accepted one ends the stream). */
+int se_enhance_long_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int32_t batch, const int32_t* lengths,
+                           int32_t max_chunk_frames, float* wav_out_dev, int64_t out_pitch, void* stream);
+
 /* Stage hooks, so each oracle-pinned stage can be diffed alone (engine-internal spectrogram layout
  * [B][2][F][T] re/im planes, T contiguous, row pitch = T).
  *   se_stft     : torch.stft / librosa.stft call of the model's decode script, fused with x*c and |X|^p_in.
@@ -293,7 +313,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long: an added entry point, nothing existing changes, same number) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number) */
 
 #ifdef __cplusplus
 }

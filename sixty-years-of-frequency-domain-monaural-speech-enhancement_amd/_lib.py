@@ -20,6 +20,7 @@ SYMBOLS = [
     'se_istft', 'se_num_frames', 'se_num_bins', 'se_set_profiling', 'se_get_profile', 'se_resample',
     'se_resample_samples', 'se_enhance_ragged', 'se_get_stage_profile', 'se_stream_begin', 'se_stream_begin_running', 'se_stream_push', 'se_stream_flush',
     'se_uformer_forward', 'se_pcm16_decode', 'se_pcm16_encode', 'se_frontend', 'se_backend', 'se_enhance_long',
+    'se_enhance_long_ragged',
 ]
 
 
@@ -63,6 +64,7 @@ def load():
     lib.se_enhance_batch.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp]
     lib.se_enhance_ragged.argtypes = [vp, vp, i64, i32, C.POINTER(i32), vp, i64, vp]
     lib.se_enhance_long.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp]
+    lib.se_enhance_long_ragged.argtypes = [vp, vp, i64, i32, C.POINTER(i32), i32, vp, i64, vp]
     lib.se_output_samples.restype = i64
     lib.se_output_samples.argtypes = [vp, i32]
     lib.se_rms_scale.argtypes = [vp, vp, i64, i32, i32, vp, vp]

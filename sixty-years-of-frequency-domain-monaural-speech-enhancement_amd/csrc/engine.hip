@@ -2,6 +2,7 @@
 #include "../../include/se_engine.h"
 #include "model.h"
 #include "stream_window.h"
+#include "window_rows.h"
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -35,6 +36,7 @@ struct se_engine {
     int* rag_dev = nullptr;        // device [RAG_SLOTS][4 * max_batch]
     hipEvent_t rag_ev[RAG_SLOTS] = {};
     int rag_next = 0;
+    int* rag_win = nullptr;        // device [4 * max_batch]: the rows' sizes as the current window launch of se_enhance_long_ragged sees them
     hipStream_t cap_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // Two half-batches side by side (round 6: Uformer, DPCRN, CTSNet, TaylorSENet): a second instance of the model with its own context and
@@ -242,6 +244,7 @@ int se_engine_destroy(se_engine* e) {
     if (e->strm.ev_order) (void)hipEventDestroy(e->strm.ev_order);
     if (e->rag_host) (void)hipHostFree(e->rag_host);
     if (e->rag_dev) (void)hipFree(e->rag_dev);
+    if (e->rag_win) (void)hipFree(e->rag_win);
     for (auto& ev : e->rag_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (e->hook_buf) (void)hipFree(e->hook_buf);
@@ -496,6 +499,44 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
     });
 }
 
+// the per-row sizes of a ragged call (len | lpad | tlen | olen of rows 0..batch-1), host -> device through the next pinned slot
+static Ragged upload_row_sizes(se_engine* e, int batch, const int32_t* lengths, hipStream_t st) {
+    const int MB = e->ctx.max_batch;
+    if (!e->rag_host) {
+        SE_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->rag_host), sizeof(int) * 4 * MB * se_engine::RAG_SLOTS, hipHostMallocDefault));
+        SE_HIP(hipMalloc(reinterpret_cast<void**>(&e->rag_dev), sizeof(int) * 4 * MB * se_engine::RAG_SLOTS));
+        for (auto& ev : e->rag_ev) SE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    const int slot = e->rag_next;
+    e->rag_next = (slot + 1) % se_engine::RAG_SLOTS;
+    SE_HIP(hipEventSynchronize(e->rag_ev[slot]));      // the copy that last used this slot has run (no-op when unused)
+    int* h = e->rag_host + (size_t)slot * 4 * MB;
+    int* d = e->rag_dev + (size_t)slot * 4 * MB;
+    const int hop = e->ctx.geom.hop;
+    for (int b = 0; b < batch; ++b) {
+        const int L = lengths[b], Lp = e->model->padded_samples(L);
+        h[b] = L;
+        h[MB + b] = Lp;
+        h[2 * MB + b] = 1 + Lp / hop;
+        h[3 * MB + b] = (int)e->model->output_samples(L);
+    }
+    SE_HIP(hipMemcpyAsync(d, h, sizeof(int) * 4 * MB, hipMemcpyHostToDevice, st));
+    SE_HIP(hipEventRecord(e->rag_ev[slot], st));
+    return Ragged{d, d + MB, d + 2 * MB, d + 3 * MB};
+}
+// the per-row sizes are visible to the launchers only while this scope enqueues work (null: nothing is published)
+struct RaggedScope {
+    const bool on;
+    explicit RaggedScope(const Ragged* r) : on(r != nullptr) {
+        if (on) set_ragged_ctx(r);
+    }
+    ~RaggedScope() {
+        if (on) set_ragged_ctx(nullptr);
+    }
+    RaggedScope(const RaggedScope&) = delete;
+    RaggedScope& operator=(const RaggedScope&) = delete;
+};
+
 int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int32_t batch, const int32_t* lengths,
                       float* wav_out_dev, int64_t out_pitch, void* stream) {
     if (!e) return 1;
@@ -516,34 +557,10 @@ int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, i
         }
         SE_CHECK(in_pitch >= Lmax && out_pitch >= e->model->output_samples(Lmax), "row pitch too small");
         hipStream_t st = static_cast<hipStream_t>(stream);
-        const int MB = e->ctx.max_batch;
-        if (!e->rag_host) {
-            SE_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->rag_host), sizeof(int) * 4 * MB * se_engine::RAG_SLOTS, hipHostMallocDefault));
-            SE_HIP(hipMalloc(reinterpret_cast<void**>(&e->rag_dev), sizeof(int) * 4 * MB * se_engine::RAG_SLOTS));
-            for (auto& ev : e->rag_ev) SE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        }
-        const int slot = e->rag_next;
-        e->rag_next = (slot + 1) % se_engine::RAG_SLOTS;
-        SE_HIP(hipEventSynchronize(e->rag_ev[slot]));      // the copy that last used this slot has run (no-op when unused)
-        int* h = e->rag_host + (size_t)slot * 4 * MB;
-        int* d = e->rag_dev + (size_t)slot * 4 * MB;
-        const int hop = e->ctx.geom.hop;
-        for (int b = 0; b < batch; ++b) {
-            const int L = lengths[b], Lp = e->model->padded_samples(L);
-            h[b] = L;
-            h[MB + b] = Lp;
-            h[2 * MB + b] = 1 + Lp / hop;
-            h[3 * MB + b] = (int)e->model->output_samples(L);
-        }
-        SE_HIP(hipMemcpyAsync(d, h, sizeof(int) * 4 * MB, hipMemcpyHostToDevice, st));
-        SE_HIP(hipEventRecord(e->rag_ev[slot], st));
+        const Ragged rg = upload_row_sizes(e, batch, lengths, st);
         e->ctx.prof_reset();
         StageProfScope sps(e);
-        Ragged rg{d, d + MB, d + 2 * MB, d + 3 * MB};
-        struct Scope {          // the per-row sizes are visible to the launchers only while this call enqueues work
-            explicit Scope(const Ragged* r) { set_ragged_ctx(r); }
-            ~Scope() { set_ragged_ctx(nullptr); }
-        } scope(&rg);
+        RaggedScope scope(&rg);
         e->model->enhance(wav_in_dev, in_pitch, batch, Lmax, wav_out_dev, out_pitch, st);
     });
 }
@@ -551,8 +568,20 @@ int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, i
 // frames [e->strm.t_done, t_end) of the stream through the network, then every output sample they complete (all of them up to
 // the end when `last`); the samples are appended to out row b at out_dev[b * out_pitch + *written ...].  The input rows are the
 // stream's own window (wav = S.wav, pitch = S.pitch, origin w0 = S.w0) or, for se_enhance_long, the caller's resident clip (origin 0)
+// `rows` (se_enhance_long_ragged; null otherwise): the rows' own sizes over their whole clips, absolute.  S.n_total / t_end are then
+// those of the LONGEST row.  The STFT and the iSTFT count frames and samples absolutely inside a window too, so a row's sample
+// counts (len, lpad, olen) mean in a window what they mean offline: its reflected edge and tail pad fall into whichever window holds
+// its end, its samples from olen[b] on are zeros in every window.  Its FRAME count does not carry over as it is: a window launch owns
+// the frames below its own bound only (the STFT's t0 + n, the iSTFT's t_fin) - with the whole-clip count the forward transform would
+// pair the window's last frame with a frame of the next window, and the inverse would load and transform columns past the window.
+// Each of the two launches therefore gets a view with tlen[b] = min(tlen[b], its bound), made on the device in stream order
+// (window_rows.h): a row that has not ended sees the bound an equal-length launch has, a row that has ended its own last frame - its
+// frames from there on are written as zeros and never overlap-added.  The network is causal and runs as for rows of one length,
+// without per-row sizes: past its end a row is fed zero frames.  That is exact for a look-ahead at the network's INPUT (FullSubNet,
+// cumulative norm: the zero frames `last` appends are the ones the STFT wrote); a model that looks ahead behind its input layer (the
+// `_vb` DCCRN's decoder) needs zeros behind every layer, which is not built yet: the caller refuses it.
 static void stream_process(se_engine* e, const float* wav, long pitch, int w0, int t_end, bool last, float* out_dev,
-                           int64_t out_pitch, int* written, hipStream_t st) {
+                           int64_t out_pitch, int* written, hipStream_t st, const Ragged* rows = nullptr) {
     se_engine::Stream& S = e->strm;
     const StftGeom& g = e->ctx.geom;
     const int HC = e->model->stream_hc(), LAG = e->model->stream_lag(), B = S.batch;
@@ -560,6 +589,12 @@ static void stream_process(se_engine* e, const float* wav, long pitch, int w0, i
     // (se_stream_push only releases frames whose last sample has arrived); at the end the decode script's padded length
     const int Lpad = last ? e->model->padded_samples(S.n_total) : S.n_total;
     const int n_final = last ? (int)e->model->output_samples(S.n_total) : S.n_total;
+    const int MB = e->ctx.max_batch;
+    if (rows && !e->rag_win) SE_HIP(hipMalloc(reinterpret_cast<void**>(&e->rag_win), sizeof(int) * 4 * MB));
+    // (one buffer: a view, the launch that reads it and the next view follow one another on `st`; rows->len is the base of the
+    // uploaded [4][MB] block, upload_row_sizes)
+    const Ragged win{e->rag_win, e->rag_win + MB, e->rag_win + 2 * MB, e->rag_win + 3 * MB};
+    const Ragged* view = rows ? &win : nullptr;
     while (S.t_done < t_end) {
         const int t0 = S.t_done, n = std::min(S.max_chunk, t_end - t0), Tw = HC + n;
         float *spec = nullptr, *mag = nullptr, *est = nullptr;
@@ -573,7 +608,11 @@ static void stream_process(se_engine* e, const float* wav, long pitch, int w0, i
             S.carve_B = B;
             S.carve_n = n;
         }
-        launch_stft(g, wav, pitch, B, S.n_total, Lpad, S.c, e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, w0);
+        {
+            if (rows) launch_window_rows(rows->len, e->rag_win, MB, B, t0 + n, st);
+            RaggedScope rs(view);
+            launch_stft(g, wav, pitch, B, S.n_total, Lpad, S.c, e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, w0);
+        }
         e->model->stream_chunk(B, t0, n, st, last && t0 + n == t_end);
         S.t_done = t0 + n;
         const bool end = last && S.t_done == t_end;
@@ -582,6 +621,8 @@ static void stream_process(se_engine* e, const float* wav, long pitch, int w0, i
         const int t_fin = end ? S.t_done : S.t_done - LAG;
         const int o_hi = end ? n_final : std::min(S.n_total, t_fin * g.hop - g.n_fft / 2);
         if (o_hi > S.o_done) {
+            if (rows && t_fin != t0 + n) launch_window_rows(rows->len, e->rag_win, MB, B, t_fin, st);      // (else the STFT's view holds)
+            RaggedScope rs(view);
             launch_istft(g, est, B, t_fin, Tw, nullptr, S.running ? nullptr : S.c, out_dev + *written, out_pitch, o_hi, st, t0 - HC,
                          std::max(0, t0 - HC), S.o_done, S.running ? S.frame_inv : nullptr, S.ring);
             *written += o_hi - S.o_done;
@@ -785,6 +826,62 @@ int se_enhance_long(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int
         e->model->stream_begin(batch, S.max_chunk, st);
         int written = 0;
         stream_process(e, wav_in_dev, in_pitch, 0, e->model->num_frames(n_samples), true, wav_out_dev, out_pitch, &written, st);
+        S.carve_B = -1;
+    });
+}
+
+int se_enhance_long_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int32_t batch, const int32_t* lengths,
+                           int32_t max_chunk_frames, float* wav_out_dev, int64_t out_pitch, void* stream) {
+    if (!e) return 1;
+    return guard(e, [&] {
+        SE_CHECK(e->finalized, "engine not finalized");
+        se_engine::Stream& S = e->strm;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        SE_CHECK(wav_in_dev && wav_out_dev && lengths, "null argument");
+        SE_CHECK(e->model->stream_supported(),
+                 "se_enhance_long_ragged decodes in windows, which needs a network that is causal end to end: " + why_not_causal(e));
+        SE_CHECK(!(e->cfg.model == SE_MODEL_DCCRN && e->model->stream_lag() > 0),
+                 "se_enhance_long_ragged: DCCRN's look-ahead decoder reads one frame ahead per layer into tensors that are not zero "
+                 "behind a row's own last frame; the per-layer zeroing that rows of different lengths need is not built yet: decode "
+                 "them one at a time with se_enhance_long (the causal decoder, SE_CFG_DCCRN_CAUSAL_DEC, is accepted)");
+        SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
+        const StftGeom& g = e->ctx.geom;
+        int Lmax = 0;
+        for (int b = 0; b < batch; ++b) {
+            SE_CHECK(lengths[b] >= g.n_fft, "se_enhance_long_ragged: lengths[" + std::to_string(b) + "] shorter than one FFT frame (n_fft)");
+            SE_CHECK(lengths[b] <= stream_sample_limit(0, g.n_fft, g.hop),
+                     "se_enhance_long_ragged: lengths[" + std::to_string(b) + "] above the position bound 2^31 - 1 - n_fft - 32 hop");
+            Lmax = std::max(Lmax, (int)lengths[b]);
+        }
+        SE_CHECK(batch == 1 || in_pitch >= Lmax, "se_enhance_long_ragged: input row pitch smaller than the longest row");
+        SE_CHECK(out_pitch >= e->model->output_samples(Lmax),
+                 "se_enhance_long_ragged: output row pitch smaller than se_output_samples(longest row)");
+        SE_CHECK(max_chunk_frames >= 0, "se_enhance_long_ragged: negative max_chunk_frames");
+        SE_CHECK((g.n_fft + g.hop - 1) / g.hop - 1 + e->model->stream_lag() <= e->model->stream_hc(),
+                 "front end overlap + look-ahead exceed the history the model keeps");
+        // every refusal is above (se_enhance_long): from here the call takes over the stream state, so a running stream ends
+        S.active = false;
+        S.carve_B = -1;
+        stream_order_wait(e, st);
+        StreamMarkScope sms(e, st);
+        const int room = std::max(1, e->plan_frames - e->model->stream_hc());
+        S.max_chunk = max_chunk_frames > 0 ? std::min(max_chunk_frames, room) : room;
+        if (!S.c) SE_HIP(hipMalloc(&S.c, (size_t)e->ctx.max_batch * sizeof(float)));
+        e->ctx.prof_reset();
+        // the rows' sizes go up once; every row's scale is that of its own whole clip; then one walk over the frames of the longest row
+        const Ragged rg = upload_row_sizes(e, batch, lengths, st);
+        {
+            RaggedScope rs(&rg);
+            launch_rms_scale(wav_in_dev, batch, Lmax, in_pitch, S.c, st);
+        }
+        S.running = false;
+        S.batch = batch;
+        S.n_total = Lmax;
+        S.t_done = S.o_done = S.w0 = 0;
+        S.carve_n = -1;
+        e->model->stream_begin(batch, S.max_chunk, st);
+        int written = 0;
+        stream_process(e, wav_in_dev, in_pitch, 0, e->model->num_frames(Lmax), true, wav_out_dev, out_pitch, &written, st, &rg);
         S.carve_B = -1;
     });
 }

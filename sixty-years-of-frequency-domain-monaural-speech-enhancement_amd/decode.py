@@ -115,6 +115,11 @@ def plan_batches(lengths, max_batch, batch_samples, ragged, max_pad=0.15):
 LONG_MODELS = frozenset({'lstm', 'crn', 'gcrn', 'dpcrn', 'dccrn', 'dccrn_snr', 'ctsnet_new', 'taylorsenet_new', 'g2net_new'})
 
 
+# ... and of those, the models whose long clips may share a window walk (Engine.enhance_long_ragged): all but the `_vb` DCCRN, whose
+# decoder looks ahead behind the input layer (include/se_engine.h)
+LONG_RAGGED_MODELS = LONG_MODELS - {'dccrn'}
+
+
 def plan_long(lengths, max_seconds, fs=16000):
     """Split clip indices by the engine bound.  max_seconds None: no bound - (longest clip, every index, []).  Else the engine
     is made for min(longest clip, max_seconds * fs) samples; -> (that size, indices of the clips that fit, indices of the
@@ -127,6 +132,29 @@ def plan_long(lengths, max_seconds, fs=16000):
         raise ValueError(f'max_seconds = {max_seconds}: the bound must be at least one sample')
     short = [i for i, n in enumerate(lengths) if n <= bound]
     return min(longest, bound), short, [i for i, n in enumerate(lengths) if n > bound]
+
+
+def plan_long_groups(lengths, long_batch=1, max_pad=0.15):
+    """Clips above the engine bound -> the calls that decode them in windows: lists of indices into `lengths`.  long_batch <= 1:
+    one clip per call, in the order given (Engine.enhance_long).  Else the clips, sorted by length, are taken greedily into
+    groups of at most long_batch rows that share one window walk (Engine.enhance_long_ragged: each row gets what it gets alone)
+    as long as the group's padding share sum(max - len) / (n * max) stays within max_pad - the walk is as long as the longest
+    row's, a row that has ended rides along as zeros.  A clip that fits no group goes alone."""
+    if long_batch <= 1:
+        return [[i] for i in range(len(lengths))]
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+    groups, cur, tot = [], [], 0
+    for i in order:
+        n = lengths[i]                                 # (ascending: the newcomer is the group's longest row)
+        ok = len(cur) < long_batch and (len(cur) + 1) * n - (tot + n) <= max_pad * (len(cur) + 1) * n
+        if cur and not ok:
+            groups.append(cur)
+            cur, tot = [], 0
+        cur.append(i)
+        tot += n
+    if cur:
+        groups.append(cur)
+    return groups
 
 
 def shard_clips(lengths, rank, world):
@@ -170,7 +198,8 @@ class _Slot:
 
 
 def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_batch=64, state_dict=None,
-            batch_samples=None, max_pad=0.15, rank=None, world=None, verbose=True, stats=None, readers=4, max_seconds=None):
+            batch_samples=None, max_pad=0.15, rank=None, world=None, verbose=True, stats=None, readers=4, max_seconds=None,
+            long_batch=1):
     """The file -> file decode of a directory (`enhance(args)` of every `*_decode_vb.py`), as a pipeline:
 
       plan     lengths come from the WAV headers only; the length-sorted clip list is dealt round-robin to the ranks and every
@@ -192,7 +221,15 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
     written in turn on the calling thread - meant for the rare long recording, not for a corpus of them.  Their time is part
     of pipeline_s / total_s and clips_per_s counts them, but no stage_busy_s entry does; calls_rank, pad_frac, pad_over_audio
     and audio_s_rank describe the batched calls only, stats['long_audio_s'] is the audio of the long clips.  A model that
-    cannot be decoded in windows (LONG_MODELS) raises before any file is written.  None: the engine is made for the longest clip."""
+    cannot be decoded in windows (LONG_MODELS) raises before any file is written.  None: the engine is made for the longest clip.
+    long_batch: rows per windowed call.  1 (the default): one long clip at a time, as above.  N > 1: the long clips are grouped by
+    length (plan_long_groups: at most min(N, max_batch) rows, padding within max_pad) and each group shares one window walk
+    (Engine.enhance_long_ragged - every row gets what it gets alone, up to fp32 rounding); the engine is then made for the
+    largest call of either kind; a model outside LONG_RAGGED_MODELS (the `_vb` DCCRN) raises before any file is written.
+    Like the one-at-a-time path, a group bypasses the reader / writer pipeline: its clips are read, uploaded and resampled one after
+    another on the calling thread, and the group's rows plus each clip's temporaries are resident together while it is assembled -
+    sized for the occasional long recordings of a corpus, not for a corpus made of them.
+    stats['long_calls'] counts the windowed calls (= long_clips when long_batch is 1)."""
     import queue
     import threading
     import time
@@ -233,6 +270,11 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
         raise ValueError(f'{model} needs a whole utterance in one call and cannot be decoded in windows: '
                          f'{", ".join(files[i] for i in long_own)} exceed max_seconds = {max_seconds} '
                          f'({", ".join("%.1f s" % (lengths[i] / 16000.0) for i in long_own)})')
+    if long_own and long_batch > 1 and model not in LONG_RAGGED_MODELS:
+        raise ValueError(f'{model} cannot decode long clips of different lengths in one call (long_batch = {long_batch}): '
+                         f'its decoder looks ahead in time; use long_batch = 1')
+    long_groups = [[long_own[k] for k in grp]
+                   for grp in plan_long_groups([lengths[i] for i in long_own], min(int(long_batch), max_batch), max_pad)]
     mine = [[short_own[k] for k in b] for b in plan_batches([lengths[i] for i in short_own], max_batch, batch_samples,
                                                              model in RAGGED_MODELS, max_pad)]
     if stats is not None:
@@ -244,12 +286,12 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
         if max_seconds is not None:
             # (the figures above are the batched calls'; the clips above the bound, decoded one at a time afterwards, are counted here)
             stats.update(long_clips=len(long_own), long_audio_s=round(sum(lengths[i] for i in long_own) / 16000.0, 2),
-                         engine_samples=eng_samples)
+                         engine_samples=eng_samples, long_calls=len(long_groups))
     if not mine and not long_own:
         return 0
     # ---- engine: the workspace is sized for the calls this rank actually makes, not for max_batch x the longest clip
     # (with max_seconds: for the bound when a clip exceeds it - those clips go through the same workspace in windows afterwards)
-    eng_batch = max((len(b) for b in mine), default=1)
+    eng_batch = max((len(b) for b in mine + long_groups), default=1)
     eng_len = max((lengths[i] for b in mine for i in b), default=0)
     nat_len = max((native[i] for b in mine for i in b), default=0)
     net = _build(model, checkpoint, state_dict, device=device, max_batch=eng_batch,
@@ -402,25 +444,40 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
         tr.join(timeout=30.0 if not (aborted or errors) else 5.0)
     if errors and not aborted:
         raise errors[0]
-    # ---- the clips above max_seconds, one at a time: the whole clip on the device, decoded in windows by the same engine
+    # ---- the clips above max_seconds, one call per group (one clip at a time unless long_batch says otherwise): the whole clips on
+    # the device, decoded in windows by the same engine
     dev = torch.device('cuda', device)
-    for i in long_own:
+
+    def resident(i):
         x = np.ascontiguousarray(wavio.read_wav(os.path.join(mix, files[i]))[0], dtype=np.float32)
         wav = torch.from_numpy(x).to(dev)
-        st = C.c_void_p(main.cuda_stream)
         if rates[i] != 16000:
             nat, wav = wav, torch.empty(lengths[i], dtype=torch.float32, device=dev)
             _check(lib.se_resample(C.c_void_p(nat.data_ptr()), native[i], 1, native[i], rates[i], 16000,
-                                   C.c_void_p(wav.data_ptr()), lengths[i], st))
-        out = eng.enhance_long(wav.view(1, -1))
-        n = out.shape[1]
-        q = torch.empty(n, dtype=torch.int16, device=dev)
-        _check(lib.se_pcm16_encode(C.c_void_p(out.data_ptr()), n, 1, n, C.c_void_p(q.data_ptr()), n, st))
-        with open(os.path.join(out_dir, files[i]), 'wb', buffering=0) as f:
-            f.write(wavio.wav_header_pcm16(2 * n, args.fs) + q.cpu().numpy().tobytes())
-        cnt[0] += 1
-        if verbose:
-            print(' The %d utterance has been decoded!' % cnt[0])
+                                   C.c_void_p(wav.data_ptr()), lengths[i], C.c_void_p(main.cuda_stream)))
+        return wav
+
+    for grp in long_groups:
+        st = C.c_void_p(main.cuda_stream)
+        if len(grp) == 1:
+            out = eng.enhance_long(resident(grp[0]).view(1, -1))
+        else:
+            lens = [lengths[i] for i in grp]
+            rows = torch.empty((len(grp), max(lens)), dtype=torch.float32, device=dev)      # (nothing past a row's length is read)
+            for r, i in enumerate(grp):
+                rows[r, :lengths[i]].copy_(resident(i))
+            out = eng.enhance_long_ragged(rows, lens)
+        nb, n = out.shape
+        q = torch.empty((nb, n), dtype=torch.int16, device=dev)
+        _check(lib.se_pcm16_encode(C.c_void_p(out.data_ptr()), n, nb, n, C.c_void_p(q.data_ptr()), n, st))
+        q = q.cpu().numpy()
+        for r, i in enumerate(grp):
+            ni = eng.output_samples(lengths[i])
+            with open(os.path.join(out_dir, files[i]), 'wb', buffering=0) as f:
+                f.write(wavio.wav_header_pcm16(2 * ni, args.fs) + q[r, :ni].tobytes())
+            cnt[0] += 1
+            if verbose:
+                print(' The %d utterance has been decoded!' % cnt[0])
     if stats is not None:
         t_end = time.perf_counter()
         stats.update(decoded=cnt[0], setup_s=round(t_ready - t_begin, 3), pipeline_s=round(t_end - t_ready, 3),
@@ -447,6 +504,9 @@ def build_parser():
     parser.add_argument('--max-seconds', '--max_seconds', dest='max_seconds', type=float, default=None,
                         help='make the engine for clips of at most this many seconds (at 16 kHz) instead of the longest of the '
                              'directory; longer clips are decoded one at a time in windows (models that are causal end to end)')
+    parser.add_argument('--long-batch', '--long_batch', dest='long_batch', type=int, default=1,
+                        help='clips above --max-seconds per windowed call: 1 = one at a time; N > 1 = groups of up to N clips of '
+                             'similar length share one window walk (each clip gets the result it gets alone)')
     return parser
 
 
@@ -465,7 +525,8 @@ def main(argv=None):
     import torch
     if 'LOCAL_RANK' in os.environ:
         torch.cuda.set_device(int(os.environ['LOCAL_RANK']) % max(torch.cuda.device_count(), 1))
-    enhance(args, args.model, ck, p_in, p_out, max_batch=args.max_batch, max_seconds=args.max_seconds)
+    enhance(args, args.model, ck, p_in, p_out, max_batch=args.max_batch, max_seconds=args.max_seconds,
+            long_batch=args.long_batch)
 
 
 if __name__ == '__main__':

@@ -193,6 +193,41 @@ class Engine:
                                               C.c_void_p(out.data_ptr()), out_pitch, self._stream()))
         return out
 
+    def enhance_long_ragged(self, wav, lengths, max_chunk_frames=0, out=None):
+        """wav [B, >= max(lengths)] float32 cuda tensor, lengths: B sample counts (host ints, each of any length from n_fft on) ->
+        [B, output_samples(max(lengths))]: every row decoded in windows as enhance_long decodes it alone - its own unit-RMS
+        scale, right edge and frame count - in ONE walk over the windows of the longest row (se_enhance_long_ragged).  Row b
+        holds output_samples(lengths[b]) samples, then zeros; nothing past lengths[b] is read.  Models that stream only; ends a
+        stream running on this engine."""
+        import torch
+        self._check_tensor(wav, 'enhance_long_ragged input', 2)
+        B, W = wav.shape
+        if B < 1 or B > self.max_batch:
+            raise EngineError(f"enhance_long_ragged input: {B} rows outside 1..max_batch ({self.max_batch})")
+        lengths = [int(n) for n in lengths]
+        if len(lengths) != B:
+            raise EngineError(f"enhance_long_ragged: {len(lengths)} lengths for a batch of {B} rows")
+        if min(lengths) < 1 or max(lengths) > W:
+            raise EngineError(f"enhance_long_ragged: lengths {min(lengths)}..{max(lengths)} outside rows of {W} samples")
+        if B > 1 and wav.stride(0) < max(lengths):
+            raise EngineError(f"enhance_long_ragged input: rows of {max(lengths)} samples overlap (strides {wav.stride()})")
+        max_chunk_frames = int(max_chunk_frames)
+        if max_chunk_frames < 0:
+            raise EngineError(f"enhance_long_ragged: max_chunk_frames {max_chunk_frames} is negative (0 = the largest window)")
+        n_out = self.output_samples(max(lengths))
+        if out is None:
+            out = torch.empty((B, n_out), dtype=torch.float32, device=wav.device)
+        else:
+            self._check_tensor(out, 'enhance_long_ragged output', 2)
+            if out.shape[0] != B or out.shape[1] < n_out:
+                raise EngineError(f"enhance_long_ragged output: need [{B}, >= {n_out}], got {tuple(out.shape)}")
+        in_pitch = wav.stride(0) if B > 1 else W
+        out_pitch = out.stride(0) if B > 1 else out.shape[1]
+        arr = (C.c_int32 * B)(*lengths)
+        self._check(self._lib.se_enhance_long_ragged(self._h, C.c_void_p(wav.data_ptr()), in_pitch, B, arr, max_chunk_frames,
+                                                     C.c_void_p(out.data_ptr()), out_pitch, self._stream()))
+        return out
+
     # ------------------------------------------------------------------ frame-online decoding
     def stream_begin(self, batch, c=None, max_chunk_frames=16, running_rms=False):
         """Start `batch` parallel streams; c: per-stream scale tensor (what rms_scale() returns offline) or None = 1.

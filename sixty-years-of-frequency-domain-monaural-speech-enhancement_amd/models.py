@@ -93,6 +93,10 @@ class _EngineModule:
         """enhance_batch for clips of any length, decoded in windows (Engine.enhance_long): models that stream only."""
         return self.engine.enhance_long(wav, out, max_chunk_frames)
 
+    def enhance_long_ragged(self, wav, lengths, max_chunk_frames=0, out=None):
+        """enhance_long for rows of different lengths in one walk (Engine.enhance_long_ragged): each row as if decoded alone."""
+        return self.engine.enhance_long_ragged(wav, lengths, max_chunk_frames, out)
+
     def enhance_ragged(self, wav, lengths):
         return self.engine.enhance_ragged(wav, lengths)
 
@@ -313,6 +317,10 @@ class CTSNet:
     def enhance_long(self, wav, out=None, max_chunk_frames=0):
         """Both stages over clips of any length, in windows (Engine.enhance_long): the cumulative-LayerNorm (`_new`) weights only."""
         return self.engine.enhance_long(wav, out, max_chunk_frames)
+
+    def enhance_long_ragged(self, wav, lengths, max_chunk_frames=0, out=None):
+        """enhance_long for rows of different lengths in one walk (Engine.enhance_long_ragged): each row as if decoded alone."""
+        return self.engine.enhance_long_ragged(wav, lengths, max_chunk_frames, out)
 
     def enhance_ragged(self, wav, lengths):
         return self.engine.enhance_ragged(wav, lengths)

@@ -8,7 +8,13 @@ engine is created to after its first decode: weights + activation arena + lazily
 rms(windowed - whole) / rms(whole).  The two engines are alive one after the other, never together.  Where the engine made for the
 whole clip refuses it (the offline cLN scan of the `_new` variants holds at most 3 750 frames, 37.5 s), the line carries its error
 text instead of the second set of figures.
-Usage: python tools/long_decode_bench.py [--models crn,dccrn,g2net_new] [--seconds 60] [--bound 64000] [--chunk 0] [--reps 5]"""
+Usage: python tools/long_decode_bench.py [--models crn,dccrn,g2net_new] [--seconds 60] [--bound 64000] [--chunk 0] [--reps 5]
+
+--ragged: --clips (8) clips of different lengths, spread evenly over --span (20,60) seconds, through ONE engine of max_samples =
+--bound and max_batch = --group: once one at a time (se_enhance_long, a call per clip) and once in groups of up to --group rows
+(se_enhance_long_ragged, the groups of se_amd.decode.plan_long_groups within --max-pad).  Same box, same binary, same engine.  One
+JSON line per model: calls, median wall ms, clips / s and audio seconds / s of both, their ratio, and the largest
+rms(grouped row - its one-at-a-time decode) / rms(the latter) over the clips."""
 import argparse
 import gc
 import json
@@ -46,6 +52,53 @@ def measure(torch, name, max_samples, x, call, reps):
     return float(np.median(times)), int(took), out
 
 
+def ragged(torch, a):
+    from se_amd import decode
+    lo, hi = (float(v) for v in a.span.split(','))
+    secs = [lo + (hi - lo) * k / max(a.clips - 1, 1) for k in range(a.clips)]
+    lens = [int(s * 16000) + 37 * k for k, s in enumerate(secs)]            # (no multiples of a hop)
+    clips = [torch.from_numpy(synth.synth_clip(900 + k, 'speech', L)).cuda() for k, L in enumerate(lens)]
+    groups = decode.plan_long_groups(lens, a.group, a.max_pad)
+    batches = []
+    for g in groups:
+        rows = torch.empty((len(g), max(lens[i] for i in g)), dtype=torch.float32, device='cuda')
+        for r, i in enumerate(g):
+            rows[r, :lens[i]].copy_(clips[i])
+        batches.append((g, rows, [lens[i] for i in g]))
+    audio = sum(lens) / 16000.0
+    for name in a.models.split(','):
+        m = build(name, a.group, a.bound)
+        eng = m.engine
+        one = lambda: [eng.enhance_long(c.view(1, -1), None, a.chunk) for c in clips]
+        grouped = lambda: [eng.enhance_long_ragged(rows, ls, a.chunk) for _, rows, ls in batches]
+
+        def timed(f):
+            f()
+            times = []
+            for _ in range(a.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                y = f()
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+            return float(np.median(times)), y
+        t1, y1 = timed(one)
+        tg, yg = timed(grouped)
+        err = 0.0
+        for (g, _, _), y in zip(batches, yg):
+            for r, i in enumerate(g):
+                ref = y1[i][0].cpu().numpy()
+                got = y[r, :ref.shape[0]].cpu().numpy()
+                err = max(err, float(np.sqrt(np.mean((got - ref) ** 2)) / max(np.sqrt(np.mean(ref ** 2)), 1e-12)))
+        eng.close()
+        side = lambda t, calls: {'calls': calls, 'ms': round(t * 1e3, 2), 'clips_per_s': round(len(lens) / t, 2),
+                                 'audio_s_per_s': round(audio / t, 1)}
+        print(json.dumps({'model': name, 'clips': len(lens), 'seconds': [round(L / 16000.0, 2) for L in lens], 'audio_s': round(audio, 2),
+                          'max_samples': a.bound, 'max_chunk_frames': a.chunk, 'group': a.group, 'max_pad': a.max_pad,
+                          'groups': [len(g) for g in groups], 'one_at_a_time': side(t1, len(lens)),
+                          'grouped': side(tg, len(groups)), 'speedup_grouped': round(t1 / tg, 3), 'max_rel_rms_diff': err}), flush=True)
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -54,7 +107,14 @@ def main():
     ap.add_argument('--bound', type=int, default=64000, help='max_samples of the bounded engine')
     ap.add_argument('--chunk', type=int, default=0, help='frames per window of the bounded engine (0 = the largest it holds)')
     ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--ragged', action='store_true', help='clips of different lengths: one at a time against grouped')
+    ap.add_argument('--clips', type=int, default=8)
+    ap.add_argument('--span', default='20,60', help='shortest,longest clip of --ragged in seconds')
+    ap.add_argument('--group', type=int, default=8, help='rows per grouped call of --ragged (and max_batch of its engine)')
+    ap.add_argument('--max-pad', dest='max_pad', type=float, default=0.15, help='padding cap of a group of --ragged')
     a = ap.parse_args()
+    if a.ragged:
+        return ragged(torch, a)
     L = int(a.seconds * 16000)
     x = torch.from_numpy(synth.synth_clip(900, 'speech', L)[None]).cuda()
     y0 = torch.empty((1, L + 1024), dtype=torch.float32, device='cuda')          # both outputs exist before anything is measured
