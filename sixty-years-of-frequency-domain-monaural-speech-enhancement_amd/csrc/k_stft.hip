@@ -13,12 +13,18 @@
 // points in registers) are in k_stft2.hip.
 #include "kernels.h"
 #include "common.h"
+#include "fe_launch.h"
+#include <algorithm>
 
 namespace se {
 
 static thread_local const Ragged* g_ragged = nullptr;
 const Ragged* ragged_ctx() { return g_ragged; }
 void set_ragged_ctx(const Ragged* r) { g_ragged = r; }
+
+static thread_local std::vector<FeLaunchRec>* g_fe_log = nullptr;
+void fe_set_launch_log(std::vector<FeLaunchRec>* log) { g_fe_log = log; }
+std::vector<FeLaunchRec>* fe_launch_log() { return g_fe_log; }
 
 static thread_local StageProf* g_stage_prof = nullptr;
 StageProf* stage_prof() { return g_stage_prof; }
@@ -119,6 +125,15 @@ void launch_stft(const StftGeom& g, const float* wav, long pitch, int B, int L, 
     SE_CHECK(g.n_fft == 512 || g.n_fft == 320, "unsupported n_fft (320 and 512 are the reference geometries)");
     StageScope prof(STAGE_STFT, s, 4.0 * L * B + (spec_ri ? 8.0 : 0.0) * g.F() * T * B + (mag ? 4.0 : 0.0) * g.F() * T * B);
     launch_stft2(g, wav, pitch, B, L, Lpad, c_scale, p_in, spec_ri, mag, T, Tp, s, t_first, col0, w0);
+    // (the record restates launch_stft2's selection from the arguments passed on: k_stft2.hip, 32 frames and 4 waves per block)
+    if (std::vector<FeLaunchRec>* log = fe_launch_log()) {
+        FeLaunchRec r;
+        r.kernel = "stft2"; r.N = g.n_fft; r.MAG = mag != nullptr; r.CP = p_in == 1.f ? 0 : (p_in == 0.5f ? 1 : 2);
+        r.gx = (T - t_first + 31) / 32; r.gy = B; r.block = 256;
+        r.shmem = (long)std::max((size_t)4 * g.n_fft * 8, (size_t)g.F() * 33 * 4);
+        r.ragged = ragged_ctx() != nullptr;
+        log->push_back(r);
+    }
 }
 
 void launch_istft(const StftGeom& g, const float* spec_ri, int B, int T, int Tp, float* /*frames: unused since the fused kernel*/,
@@ -128,6 +143,18 @@ void launch_istft(const StftGeom& g, const float* spec_ri, int B, int T, int Tp,
     SE_CHECK(Lout > o_lo, "launch_istft: empty output range");
     SE_CHECK(g.n_fft == 512 || g.n_fft == 320, "unsupported n_fft");
     launch_istft2(g, spec_ri, B, T, Tp, c_scale, wav_out, out_pitch, Lout, s, t_off, t_lo, o_lo, frame_inv, ring);
+    // (as above: 32 frames per block of which `halo` are shared with the block below, 8 waves)
+    if (std::vector<FeLaunchRec>* log = fe_launch_log()) {
+        FeLaunchRec r;
+        int halo = (g.n_fft + g.hop - 1) / g.hop - 1;
+        halo += halo & 1;
+        const int span = (32 - halo) * g.hop, pos_base = (o_lo + g.n_fft / 2) / g.hop * g.hop;
+        r.kernel = "istft2"; r.N = g.n_fft; r.FSC = frame_inv != nullptr;
+        r.gx = (g.n_fft / 2 + Lout - pos_base + span - 1) / span; r.gy = B; r.block = 512;
+        r.shmem = (long)(std::max((size_t)32 * g.n_fft * 4, (size_t)g.F() * 33 * 4) + (size_t)g.n_fft * 4);
+        r.ragged = ragged_ctx() != nullptr;
+        log->push_back(r);
+    }
 }
 
 }  // namespace se
