@@ -303,6 +303,45 @@ int64_t se_resample_samples(int32_t n_in, int32_t sr_in, int32_t sr_out);
 int se_resample(const float* in_dev, int64_t in_pitch, int32_t batch, int32_t n_in, int32_t sr_in, int32_t sr_out,
                 float* out_dev, int64_t out_pitch, void* stream);
 
+/* The same conversion for a signal that arrives piecewise - in front of se_stream_*, whose 16 kHz input a live source delivers at
+ * 48 / 44.1 / 32 kHz.  A stand-alone object next to the engine (no engine handle, errors through se_last_error(NULL)); one
+ * object serves `batch` <= max_batch parallel rows that advance together, on the device that is current at create.  All device
+ * memory (two history buffers of max_batch x 2 * reach floats, the filter table, for non-integer ratios a ring of read positions)
+ * is allocated at create; push and flush allocate nothing.  A handle is not thread-safe.
+ *   CONTRACT: for any split of a signal of n samples into pushes of 1 ... max_push samples, the outputs of the pushes followed by
+ *   the output of the flush, concatenated, are the se_resample_samples(n, sr_in, sr_out) samples se_resample returns for the
+ *   whole signal - equal as numbers, sample for sample (the same float64 sum in the same order at the same read positions),
+ *   the zero tail of librosa's fix_length included.
+ *   se_resampler_begin: starts (or restarts: all state is reset) a signal of `batch` rows.
+ *   se_resampler_push : in_dev [batch][in_pitch], n_new new samples per row (0 ... max_push; 0 does nothing); the output samples
+ *                       this push makes final - those whose filter taps have all arrived - go to the start of each row of out_dev
+ *                       [batch][out_pitch].  *n_out (a HOST value, the same for all rows, 0 is normal) = their count =
+ *                       se_resampler_ready_samples(after) - se_resampler_ready_samples(before), at most ceil(n_new * sr_out /
+ *                       sr_in) + 1.  Pitches are ignored when batch == 1.
+ *   se_resampler_flush: the signal has ended: the remaining outputs (right filter wing cut at the end, as offline) and the zero
+ *                       tail, at most ceil((reach + 1) * sr_out / sr_in) + 2 per row; the object then waits for the next begin.
+ *   sr_in == sr_out   : the input is copied through - n_out = n_new, flush returns 0.
+ *   LATENCY: the filter looks floor(32769 / step) input samples ahead, step = floor(512 min(1, sr_out / sr_in)): 192 samples
+ *   = 4 ms at 48 -> 16 kHz (128 at 32 -> 16 kHz, 177 at 44.1 -> 16 kHz, 64 when upsampling) - the algorithmic latency.  The
+ *   release rule rounds it up and is one sample late: the output read at input position p is returned by the push that brings
+ *   sample p + reach, reach = floor(32769 / step) + 1 (193 at 48 -> 16 kHz) - so a signal of up to reach samples comes out of
+ *   the flush alone.
+ *   WAITS: when sr_in is a multiple of sr_out (48 / 32 -> 16 kHz) a push enqueues one kernel and calls nothing that waits for the
+ *   device.  Other ratios carry resampy's running float64 read position on the host and hand a push's positions to the device
+ *   through a ring of 8 pinned slots; the host waits (hipEventSynchronize) only for the copy enqueued 8 pushes earlier.
+ *   ERRORS (a refused call changes no state: the signal goes on): n_new above max_push; batch above max_batch; push or flush
+ *   without begin; a total length beyond what se_resample accepts (2^31 - 1 samples, in or out); a row pitch below the row.
+ * se_resampler_ready_samples is stateless and host-only: how many output samples are final once n_in input samples of a signal
+ * that has not ended have arrived (-1: bad arguments).  For sr_in % sr_out != 0 it walks the running sum, O(n_in). */
+typedef struct se_resampler se_resampler;
+int se_resampler_create(int32_t sr_in, int32_t sr_out, int32_t max_batch, int32_t max_push, se_resampler** out);
+int se_resampler_destroy(se_resampler* r);
+int se_resampler_begin(se_resampler* r, int32_t batch, void* stream);
+int se_resampler_push(se_resampler* r, const float* in_dev, int64_t in_pitch, int32_t n_new, float* out_dev, int64_t out_pitch,
+                      int32_t* n_out, void* stream);
+int se_resampler_flush(se_resampler* r, float* out_dev, int64_t out_pitch, int32_t* n_out, void* stream);
+int64_t se_resampler_ready_samples(int64_t n_in, int32_t sr_in, int32_t sr_out);
+
 /* The two ends of `enhance(args)`: `feat_wav, orig_fs = sf.read(path)` hands out int16 / 32768 as floats, and
  * `sf.write(path, y, fs)` stores PCM_16 (soundfile's default subtype for .wav: round to nearest, clipped) - e.g.
  * DCCRN/dccrn_decode_vb.py:25,64.  Both conversions are exact in fp32, so they run on the device and the host moves raw
@@ -313,7 +352,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise) */
 
 #ifdef __cplusplus
 }

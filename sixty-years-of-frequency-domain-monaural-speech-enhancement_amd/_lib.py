@@ -20,7 +20,8 @@ SYMBOLS = [
     'se_istft', 'se_num_frames', 'se_num_bins', 'se_set_profiling', 'se_get_profile', 'se_resample',
     'se_resample_samples', 'se_enhance_ragged', 'se_get_stage_profile', 'se_stream_begin', 'se_stream_begin_running', 'se_stream_push', 'se_stream_flush',
     'se_uformer_forward', 'se_pcm16_decode', 'se_pcm16_encode', 'se_frontend', 'se_backend', 'se_enhance_long',
-    'se_enhance_long_ragged',
+    'se_enhance_long_ragged', 'se_resampler_create', 'se_resampler_destroy', 'se_resampler_begin', 'se_resampler_push',
+    'se_resampler_flush', 'se_resampler_ready_samples',
 ]
 
 
@@ -88,5 +89,12 @@ def load():
     lib.se_pcm16_decode.argtypes = [vp, i64, i32, i32, vp, i64, vp]
     lib.se_pcm16_encode.argtypes = [vp, i64, i32, i32, vp, i64, vp]
     lib.se_resample.argtypes = [vp, i64, i32, i32, i32, i32, vp, i64, vp]
+    lib.se_resampler_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
+    lib.se_resampler_destroy.argtypes = [vp]
+    lib.se_resampler_begin.argtypes = [vp, i32, vp]
+    lib.se_resampler_push.argtypes = [vp, vp, i64, i32, vp, i64, C.POINTER(i32), vp]
+    lib.se_resampler_flush.argtypes = [vp, vp, i64, C.POINTER(i32), vp]
+    lib.se_resampler_ready_samples.restype = i64
+    lib.se_resampler_ready_samples.argtypes = [i64, i32, i32]
     _lib = lib
     return lib

@@ -1,6 +1,7 @@
 // C ABI of the engine (include/se_engine.h): handle, strict state-dict load, stage hooks.
 #include "../../include/se_engine.h"
 #include "model.h"
+#include "resampler.h"
 #include "stream_window.h"
 #include "window_rows.h"
 #include <algorithm>
@@ -119,6 +120,41 @@ int se_resample(const float* in_dev, int64_t in_pitch, int32_t batch, int32_t n_
         SE_CHECK(in_pitch >= n_in && out_pitch >= se::resample_out_samples(n_in, sr_in, sr_out), "row pitch too small");
         se::launch_resample(in_dev, in_pitch, batch, n_in, sr_in, sr_out, out_dev, out_pitch, static_cast<hipStream_t>(stream));
     });
+}
+
+// the stateful resampler: an object of its own next to the engine (k_resample.hip), errors through se_last_error(NULL)
+static se::StreamResampler* rs_of(se_resampler* r) { return reinterpret_cast<se::StreamResampler*>(r); }
+
+int se_resampler_create(int32_t sr_in, int32_t sr_out, int32_t max_batch, int32_t max_push, se_resampler** out) {
+    return guard(nullptr, [&] {
+        SE_CHECK(out, "null argument");
+        *out = reinterpret_cast<se_resampler*>(se::stream_resampler_create(sr_in, sr_out, max_batch, max_push));
+    });
+}
+int se_resampler_destroy(se_resampler* r) {
+    return guard(nullptr, [&] { se::stream_resampler_destroy(rs_of(r)); });
+}
+int se_resampler_begin(se_resampler* r, int32_t batch, void* stream) {
+    return guard(nullptr, [&] {
+        SE_CHECK(r, "null argument");
+        se::stream_resampler_begin(rs_of(r), batch, static_cast<hipStream_t>(stream));
+    });
+}
+int se_resampler_push(se_resampler* r, const float* in_dev, int64_t in_pitch, int32_t n_new, float* out_dev, int64_t out_pitch,
+                      int32_t* n_out, void* stream) {
+    return guard(nullptr, [&] {
+        SE_CHECK(r && n_out, "null argument");
+        *n_out = se::stream_resampler_push(rs_of(r), in_dev, in_pitch, n_new, out_dev, out_pitch, static_cast<hipStream_t>(stream));
+    });
+}
+int se_resampler_flush(se_resampler* r, float* out_dev, int64_t out_pitch, int32_t* n_out, void* stream) {
+    return guard(nullptr, [&] {
+        SE_CHECK(r && n_out, "null argument");
+        *n_out = se::stream_resampler_flush(rs_of(r), out_dev, out_pitch, static_cast<hipStream_t>(stream));
+    });
+}
+int64_t se_resampler_ready_samples(int64_t n_in, int32_t sr_in, int32_t sr_out) {
+    return se::resample_ready_samples(n_in, sr_in, sr_out);
 }
 
 int se_pcm16_decode(const int16_t* in_dev, int64_t in_pitch, int32_t batch, int32_t n, float* out_dev, int64_t out_pitch,

@@ -5,8 +5,31 @@
 // published resampy 'kaiser_best' algorithm - Kaiser-windowed sinc table (64 zero crossings x 512 samples), linear
 // interpolation between table entries, float64 accumulation - restated in oracle/resample.py; parity is pinned to
 // that restatement only.  One thread per output sample; the table (256 KB of doubles) lives in L2.
+//
+// Two kernels share the tap arithmetic (resample_taps): resample_kernel, stateless, for a whole clip, and
+// resample_stream_kernel for the stateful StreamResampler below, which is fed piecewise and returns, push by push, the very
+// numbers resample_kernel gives for the whole signal - the same float64 sum term by term, at the same read positions.
+//   window   : per row the last 2 * reach input samples ("history": reach = the taps one wing can span, resample_pos.h - an
+//              output not yet released sits at most reach samples before the end and looks less than reach further back)
+//              in one of two buffers; a push reads [history | the caller's new samples] in place and writes the next
+//              history into the OTHER buffer in the same launch, so nothing is read and written at once.  Both buffers, the
+//              scaled table and the position ring are allocated at create; push and flush allocate nothing.
+//   wings    : clamped by absolute position as offline - the left one by n + 1, the right one by the samples that have
+//              arrived.  A push releases an output only when its whole right wing has arrived, so the right clamp bites at
+//              flush alone, where the arrived samples are the final length.  History is never assumed to be zero-filled.
+//   positions: integer decimation (48 / 32 -> 16 kHz): t * inc in the kernel; a push then enqueues one launch and calls
+//              nothing that waits for the device.  Other ratios: resampy's running sum, carried across pushes on the host; the
+//              few positions of a push travel through a ring of 8 pinned slots (hipMemcpyAsync, one event per slot).  The one
+//              wait left on that path: hipEventSynchronize on a slot's event before the host rewrites the slot, i.e. on the
+//              copy enqueued 8 pushes earlier - it blocks only a caller that runs 8 pushes ahead of the device.
+//   launch   : one output per thread, 64-thread blocks.  A 10 ms push at 48 kHz makes 160 outputs per row: three waves of
+//              ~384 dependent float64 steps each.  The launch is bound by that chain's latency, not by occupancy or f64
+//              rate, so the outputs are spread over as many CUs as there are waves instead of filling one 256-thread block.
 #include "kernels.h"
 #include "common.h"
+#include "resample_pos.h"
+#include "resampler.h"
+#include <climits>
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -15,7 +38,6 @@ namespace se {
 
 namespace {
 
-constexpr int RS_ZEROS = 64, RS_BITS = 512, RS_NWIN = RS_ZEROS * RS_BITS + 1;
 constexpr double RS_ROLLOFF = 0.9475937167399596, RS_BETA = 14.769656459379492;
 
 double bessel_i0(double x) {
@@ -55,6 +77,47 @@ struct ResampleArgs {
     int index_step;
 };
 
+// x by absolute sample position: a whole clip, or a stream's [history | new samples]
+struct ClipAt {
+    const float* __restrict__ x;
+    __device__ float operator()(int p) const { return x[p]; }
+};
+struct WindowAt {
+    const float* __restrict__ hist;   // hist[0] is sample w0
+    const float* __restrict__ in;     // in[0] is sample split (never read when nothing is new)
+    int w0, split;
+    __device__ float operator()(int p) const { return p < split ? hist[p - w0] : in[p - split]; }
+};
+
+// One output sample: the taps around input position n + pos_frac of a signal of n_in samples - table look-up with linear
+// interpolation, float64 accumulation, left wing then right wing.
+template <typename X>
+__device__ __forceinline__ double resample_taps(const X& x, const double* __restrict__ win, int n, double pos_frac, int n_in,
+                                                double scale, int index_step) {
+    double acc = 0.0;
+    const double frac = scale * pos_frac;
+    const double index_frac = frac * RS_BITS;
+    const int offset = (int)index_frac;
+    const double eta = index_frac - offset;
+    const int i_max = min(n + 1, (RS_NWIN - offset) / index_step);
+    for (int i = 0; i < i_max; ++i) {
+        const int idx = offset + i * index_step;
+        const double d = idx + 1 < RS_NWIN ? win[idx + 1] - win[idx] : 0.0;
+        acc += (win[idx] + eta * d) * (double)x(n - i);
+    }
+    const double frac2 = scale - frac;
+    const double index_frac2 = frac2 * RS_BITS;
+    const int offset2 = (int)index_frac2;
+    const double eta2 = index_frac2 - offset2;
+    const int k_max = min(n_in - n - 1, (RS_NWIN - offset2) / index_step);
+    for (int k = 0; k < k_max; ++k) {
+        const int idx = offset2 + k * index_step;
+        const double d = idx + 1 < RS_NWIN ? win[idx + 1] - win[idx] : 0.0;
+        acc += (win[idx] + eta2 * d) * (double)x(n + k + 1);
+    }
+    return acc;
+}
+
 __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= a.n_out) return;
@@ -63,34 +126,49 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
         yp[t] = 0.f;
         return;
     }
-    const float* __restrict__ x = a.x + (long)blockIdx.y * a.in_pitch;
-    const double* __restrict__ win = a.win;
+    const ClipAt x{a.x + (long)blockIdx.y * a.in_pitch};
     const double tr = a.treg ? a.treg[t] : (double)t * a.inc;
     const int n = (int)tr;
-    double acc = 0.0;
-    {
-        const double frac = a.scale * (tr - n);
-        const double index_frac = frac * RS_BITS;
-        const int offset = (int)index_frac;
-        const double eta = index_frac - offset;
-        const int i_max = min(n + 1, (RS_NWIN - offset) / a.index_step);
-        for (int i = 0; i < i_max; ++i) {
-            const int idx = offset + i * a.index_step;
-            const double d = idx + 1 < RS_NWIN ? win[idx + 1] - win[idx] : 0.0;
-            acc += (win[idx] + eta * d) * (double)x[n - i];
-        }
-        const double frac2 = a.scale - frac;
-        const double index_frac2 = frac2 * RS_BITS;
-        const int offset2 = (int)index_frac2;
-        const double eta2 = index_frac2 - offset2;
-        const int k_max = min(a.n_in - n - 1, (RS_NWIN - offset2) / a.index_step);
-        for (int k = 0; k < k_max; ++k) {
-            const int idx = offset2 + k * a.index_step;
-            const double d = idx + 1 < RS_NWIN ? win[idx + 1] - win[idx] : 0.0;
-            acc += (win[idx] + eta2 * d) * (double)x[n + k + 1];
-        }
+    yp[t] = (float)resample_taps(x, a.win, n, tr - n, a.n_in, a.scale, a.index_step);
+}
+
+// One push (or the flush) of a StreamResampler: blocks [0, out_blocks) compute outputs t0 .. t0 + n_emit, blocks behind them
+// copy the samples from w0_next on into the other history buffer.
+struct ResampleStreamArgs {
+    const float* hist; float* hist_next; long hist_pitch;
+    const float* in; long in_pitch;
+    float* y; long out_pitch;
+    const double* win;
+    const double* treg;      // [n_calc] read positions of this launch's outputs, or nullptr -> (t0 + j) * inc
+    double inc, scale;
+    int index_step;
+    int w0, split, n_total;  // absolute positions: first history sample, first new sample, samples arrived (new ones included)
+    int w0_next;             // first sample of the next history (n_total: no history is written)
+    int t0, n_calc, n_emit;  // first output; outputs computed; outputs written (the rest is the fix_length zero tail, at flush)
+    int out_blocks;
+};
+
+constexpr int RS_STREAM_BLOCK = 64;
+
+__global__ __launch_bounds__(RS_STREAM_BLOCK) void resample_stream_kernel(const ResampleStreamArgs a) {
+    const long b = blockIdx.y;
+    const WindowAt x{a.hist + b * a.hist_pitch, a.in ? a.in + b * a.in_pitch : nullptr, a.w0, a.split};
+    if ((int)blockIdx.x >= a.out_blocks) {
+        const int j = ((int)blockIdx.x - a.out_blocks) * RS_STREAM_BLOCK + threadIdx.x;
+        if (j < a.n_total - a.w0_next) a.hist_next[b * a.hist_pitch + j] = x(a.w0_next + j);
+        return;
     }
-    yp[t] = (float)acc;
+    const int j = blockIdx.x * RS_STREAM_BLOCK + threadIdx.x;
+    if (j >= a.n_emit) return;
+    float* yp = a.y + b * a.out_pitch;
+    if (j >= a.n_calc) {
+        yp[j] = 0.f;
+        return;
+    }
+    const int t = a.t0 + j;
+    const double tr = a.treg ? a.treg[j] : (double)t * a.inc;
+    const int n = (int)tr;
+    yp[j] = (float)resample_taps(x, a.win, n, tr - n, a.n_total, a.scale, a.index_step);
 }
 
 struct Tables {
@@ -200,6 +278,249 @@ void launch_resample(const float* x, long in_pitch, int batch, int n_in, int sr_
     }
     hipLaunchKernelGGL(resample_kernel, dim3((a.n_out + 255) / 256, batch), dim3(256), 0, s, a);
     SE_HIP(hipGetLastError());
+}
+
+// ---- the stateful resampler (se_resampler_* of include/se_engine.h; layout and rules in the header comment of this file)
+namespace {
+struct DeviceScope {          // the object's device is current while a call runs; the caller's is restored on the way out
+    int prev = -1;
+    explicit DeviceScope(int dev) {
+        SE_HIP(hipGetDevice(&prev));
+        if (prev != dev) SE_HIP(hipSetDevice(dev));
+        else prev = -1;
+    }
+    ~DeviceScope() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+}  // namespace
+
+class StreamResampler {
+  public:
+    StreamResampler(int sr_in, int sr_out, int max_batch, int max_push);
+    ~StreamResampler() { release(); }
+    void begin(int batch, hipStream_t s);
+    int push(const float* in, long in_pitch, int n_new, float* out, long out_pitch, hipStream_t s);
+    int flush(float* out, long out_pitch, hipStream_t s);
+
+  private:
+    static constexpr int RING = 8;
+    void release();
+    void order_behind_last(hipStream_t s);
+    const double* upload_positions(ResamplePos& pos, int64_t n_in, int64_t t_end, int64_t count, hipStream_t s);
+    void launch(const float* in, long in_pitch, float* out, long out_pitch, int n_total, int w0_next, int t0, int n_calc,
+                int n_emit, const double* treg, hipStream_t s);
+
+    int sr_in_, sr_out_, max_batch_, max_push_, dev_ = 0;
+    ResamplePlan plan_{};
+    bool pass_;                      // sr_in == sr_out: samples are copied through, nothing else is allocated
+    long pitch_ = 0;                 // floats per row of a history buffer (2 * reach, rounded up to 4)
+    float* hist_[2] = {nullptr, nullptr};
+    double* win_ = nullptr;          // the table, scaled by the ratio when downsampling
+    double* ring_host_ = nullptr;    // pinned [RING][ring_cap_]
+    double* ring_dev_ = nullptr;     // device [RING][ring_cap_]
+    long ring_cap_ = 0;              // the most outputs one push or the flush can release
+    hipEvent_t ring_ev_[RING] = {};
+    int ring_next_ = 0;
+    hipEvent_t ev_order_ = nullptr;
+    bool has_last_ = false;
+    hipStream_t last_st_ = nullptr;
+    // the stream: rows, which buffer holds the history, samples arrived, first sample of the history, next output
+    bool active_ = false;
+    int batch_ = 0, cur_ = 0, w0_ = 0;
+    int64_t n_total_ = 0;
+    ResamplePos pos_;
+};
+
+StreamResampler::StreamResampler(int sr_in, int sr_out, int max_batch, int max_push)
+    : sr_in_(sr_in), sr_out_(sr_out), max_batch_(max_batch), max_push_(max_push), pass_(sr_in == sr_out) {
+    SE_CHECK(sr_in > 0 && sr_out > 0 && max_batch > 0 && max_push > 0, "se_resampler_create: bad arguments");
+    plan_ = resample_plan(sr_in, sr_out);
+    SE_CHECK(pass_ || plan_.index_step > 0, "se_resampler_create: sr_out / sr_in below the table's resolution");
+    SE_HIP(hipGetDevice(&dev_));
+    if (pass_) return;
+    try {
+        const long hist = 2L * plan_.reach;
+        pitch_ = (hist + 3) / 4 * 4;
+        SE_CHECK((double)max_batch * (double)pitch_ < 1e9, "se_resampler_create: max_batch too large");
+        for (auto& h : hist_) SE_HIP(hipMalloc(&h, sizeof(float) * (size_t)max_batch * pitch_));
+        std::vector<double> w = build_window();
+        if (plan_.ratio < 1.0)
+            for (auto& v : w) v *= plan_.ratio;                         // interp_win *= sample_ratio
+        SE_HIP(hipMalloc(&win_, RS_NWIN * sizeof(double)));
+        SE_HIP(hipMemcpy(win_, w.data(), RS_NWIN * sizeof(double), hipMemcpyHostToDevice));
+        ring_cap_ = (long)std::ceil((double)std::max(max_push, plan_.reach + 1) * plan_.ratio) + 2;
+        if (!plan_.exact) {
+            SE_HIP(hipHostMalloc(reinterpret_cast<void**>(&ring_host_), sizeof(double) * ring_cap_ * RING, hipHostMallocDefault));
+            SE_HIP(hipMalloc(&ring_dev_, sizeof(double) * ring_cap_ * RING));
+            for (auto& ev : ring_ev_) SE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        }
+        SE_HIP(hipEventCreateWithFlags(&ev_order_, hipEventDisableTiming));
+    } catch (...) {
+        release();
+        throw;
+    }
+}
+
+void StreamResampler::release() {
+    for (auto& h : hist_) {
+        if (h) (void)hipFree(h);
+        h = nullptr;
+    }
+    if (win_) (void)hipFree(win_);
+    if (ring_host_) (void)hipHostFree(ring_host_);
+    if (ring_dev_) (void)hipFree(ring_dev_);
+    for (auto& ev : ring_ev_) {
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
+    if (ev_order_) (void)hipEventDestroy(ev_order_);
+    win_ = ring_host_ = ring_dev_ = nullptr;
+    ev_order_ = nullptr;
+}
+
+// a call on ANOTHER hipStream than the last one re-uses the history buffers: it is ordered behind the work in flight there
+void StreamResampler::order_behind_last(hipStream_t s) {
+    if (has_last_ && last_st_ != s) SE_HIP(hipStreamWaitEvent(s, ev_order_, 0));
+}
+
+void StreamResampler::begin(int batch, hipStream_t s) {
+    SE_CHECK(batch >= 1 && batch <= max_batch_, "se_resampler_begin: batch " + std::to_string(batch) + " outside 1..max_batch (" +
+                                                    std::to_string(max_batch_) + ")");
+    if (!pass_) {
+        DeviceScope ds(dev_);
+        order_behind_last(s);
+    }
+    active_ = true;
+    batch_ = batch;
+    cur_ = w0_ = 0;
+    n_total_ = 0;
+    pos_ = ResamplePos{};
+}
+
+// the read positions of the next `count` outputs, host -> device through the next pinned slot; `pos` moves past them
+const double* StreamResampler::upload_positions(ResamplePos& pos, int64_t n_in, int64_t t_end, int64_t count, hipStream_t s) {
+    const int slot = ring_next_;
+    ring_next_ = (slot + 1) % RING;
+    SE_HIP(hipEventSynchronize(ring_ev_[slot]));      // the copy that last used this slot has run (no-op when unused)
+    double* h = ring_host_ + (size_t)slot * ring_cap_;
+    double* d = ring_dev_ + (size_t)slot * ring_cap_;
+    const int64_t k = resample_advance(plan_, pos, n_in, t_end, h, count);
+    SE_CHECK(k == count, "resampler: position count changed between two walks");
+    SE_HIP(hipMemcpyAsync(d, h, sizeof(double) * count, hipMemcpyHostToDevice, s));
+    SE_HIP(hipEventRecord(ring_ev_[slot], s));
+    return d;
+}
+
+void StreamResampler::launch(const float* in, long in_pitch, float* out, long out_pitch, int n_total, int w0_next, int t0,
+                             int n_calc, int n_emit, const double* treg, hipStream_t s) {
+    ResampleStreamArgs a{};
+    a.hist = hist_[cur_]; a.hist_next = hist_[cur_ ^ 1]; a.hist_pitch = pitch_;
+    a.in = in; a.in_pitch = in_pitch; a.y = out; a.out_pitch = out_pitch;
+    a.win = win_; a.treg = treg; a.inc = plan_.inc; a.scale = plan_.scale; a.index_step = plan_.index_step;
+    a.w0 = w0_; a.split = (int)n_total_; a.n_total = n_total; a.w0_next = w0_next;
+    a.t0 = t0; a.n_calc = n_calc; a.n_emit = n_emit;
+    a.out_blocks = (n_emit + RS_STREAM_BLOCK - 1) / RS_STREAM_BLOCK;
+    const int keep = n_total - w0_next;
+    // what the kernel indexes, checked where the sizes are known: the history it reads, the history it writes
+    SE_CHECK(w0_ >= 0 && a.split - w0_ <= pitch_ && w0_next >= w0_ && keep >= 0 && keep <= pitch_, "resampler: window out of range");
+    const int blocks = a.out_blocks + (keep + RS_STREAM_BLOCK - 1) / RS_STREAM_BLOCK;
+    if (blocks == 0) return;
+    hipLaunchKernelGGL(resample_stream_kernel, dim3(blocks, batch_), dim3(RS_STREAM_BLOCK), 0, s, a);
+    SE_HIP(hipGetLastError());
+}
+
+int StreamResampler::push(const float* in, long in_pitch, int n_new, float* out, long out_pitch, hipStream_t s) {
+    // every refusal comes before the first change of state
+    SE_CHECK(active_, "se_resampler_push without se_resampler_begin");
+    SE_CHECK(n_new >= 0 && n_new <= max_push_, "se_resampler_push: " + std::to_string(n_new) + " samples in one push, the object takes 0..max_push (" +
+                                                   std::to_string(max_push_) + ")");
+    SE_CHECK(in && out, "null argument");
+    SE_CHECK(batch_ == 1 || in_pitch >= n_new, "input row pitch too small");
+    const int64_t n_after = n_total_ + n_new;
+    SE_CHECK(n_after <= INT_MAX && std::ceil((double)n_after * plan_.ratio) <= (double)INT_MAX,
+             "se_resampler_push: the stream would pass the " + std::to_string(INT_MAX) + " samples (in or out) se_resample accepts");
+    if (n_new == 0) return 0;
+    if (pass_) {
+        SE_CHECK(batch_ == 1 || out_pitch >= n_new, "output row pitch too small");
+        SE_HIP(hipMemcpy2DAsync(out, sizeof(float) * (batch_ == 1 ? n_new : out_pitch), in, sizeof(float) * (batch_ == 1 ? n_new : in_pitch),
+                                sizeof(float) * n_new, batch_, hipMemcpyDeviceToDevice, s));
+        n_total_ = n_after;
+        return n_new;
+    }
+    ResamplePos pos = pos_;
+    const int64_t count = resample_advance(plan_, pos, n_after, INT64_MAX, nullptr, 0);
+    SE_CHECK(count <= ring_cap_, "resampler: a push released more outputs than planned");
+    SE_CHECK(batch_ == 1 || out_pitch >= count, "output row pitch too small");
+    // the oldest tap of the first output lies inside the history
+    SE_CHECK(count == 0 || std::max<int64_t>(0, (int64_t)resample_pos_of(plan_, pos_) - (plan_.reach - 2)) >= w0_,
+             "resampler: history too short");
+    DeviceScope ds(dev_);
+    order_behind_last(s);
+    const double* treg = nullptr;
+    if (!plan_.exact && count > 0) {
+        pos = pos_;
+        treg = upload_positions(pos, n_after, INT64_MAX, count, s);
+    }
+    const int w0_next = (int)std::max<int64_t>(0, n_after - 2L * plan_.reach);
+    launch(in, in_pitch, out, out_pitch, (int)n_after, w0_next, (int)pos_.t, (int)count, (int)count, treg, s);
+    SE_HIP(hipEventRecord(ev_order_, s));
+    has_last_ = true;
+    last_st_ = s;
+    cur_ ^= 1;
+    w0_ = w0_next;
+    n_total_ = n_after;
+    pos_ = pos;
+    return (int)count;
+}
+
+int StreamResampler::flush(float* out, long out_pitch, hipStream_t s) {
+    SE_CHECK(active_, "se_resampler_flush without se_resampler_begin");
+    if (pass_ || n_total_ == 0) {
+        active_ = false;
+        return 0;
+    }
+    const int64_t n_calc = resample_calc_samples(plan_, n_total_) - pos_.t;                    // still to compute
+    const int64_t n_emit = resample_out_samples((int)n_total_, sr_in_, sr_out_) - pos_.t;      // + the fix_length zero tail
+    SE_CHECK(n_calc >= 0 && n_emit >= n_calc && n_emit <= ring_cap_, "resampler: the flush holds more outputs than planned");
+    SE_CHECK(out || n_emit == 0, "null argument");
+    SE_CHECK(batch_ == 1 || out_pitch >= n_emit, "output row pitch too small");
+    SE_CHECK(n_calc == 0 || std::max<int64_t>(0, (int64_t)resample_pos_of(plan_, pos_) - (plan_.reach - 2)) >= w0_,
+             "resampler: history too short");
+    // every remaining output reads at a position inside the signal: n + reach < n_total_ + reach
+    const int64_t n_lim = n_total_ + plan_.reach;
+    ResamplePos pos = pos_;
+    SE_CHECK(resample_advance(plan_, pos, n_lim, pos_.t + n_calc, nullptr, 0) == n_calc, "resampler: a read position past the end");
+    DeviceScope ds(dev_);
+    order_behind_last(s);
+    const double* treg = nullptr;
+    if (!plan_.exact && n_calc > 0) {
+        pos = pos_;
+        treg = upload_positions(pos, n_lim, pos_.t + n_calc, n_calc, s);
+    }
+    // the right wing is clamped by n_total_, now the final length; no history is written (w0_next = n_total_)
+    launch(nullptr, 0, out, out_pitch, (int)n_total_, (int)n_total_, (int)pos_.t, (int)n_calc, (int)n_emit, treg, s);
+    SE_HIP(hipEventRecord(ev_order_, s));
+    has_last_ = true;
+    last_st_ = s;
+    active_ = false;
+    return (int)n_emit;
+}
+
+StreamResampler* stream_resampler_create(int sr_in, int sr_out, int max_batch, int max_push) {
+    return new StreamResampler(sr_in, sr_out, max_batch, max_push);
+}
+void stream_resampler_destroy(StreamResampler* r) { delete r; }
+void stream_resampler_begin(StreamResampler* r, int batch, hipStream_t s) { r->begin(batch, s); }
+int stream_resampler_push(StreamResampler* r, const float* in, long in_pitch, int n_new, float* out, long out_pitch, hipStream_t s) {
+    return r->push(in, in_pitch, n_new, out, out_pitch, s);
+}
+int stream_resampler_flush(StreamResampler* r, float* out, long out_pitch, hipStream_t s) { return r->flush(out, out_pitch, s); }
+long resample_ready_samples(long n_in, int sr_in, int sr_out) {
+    if (n_in < 0 || sr_in <= 0 || sr_out <= 0) return -1;
+    if (sr_in == sr_out) return n_in;
+    const ResamplePlan p = resample_plan(sr_in, sr_out);
+    return p.index_step > 0 ? (long)resample_ready(p, n_in) : -1;
 }
 
 }  // namespace se

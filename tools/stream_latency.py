@@ -5,7 +5,9 @@ streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, 
 --sliding N: engines made for max_samples = N with `sliding_stream=True` (SE_CFG_STREAM_SLIDING) instead of max_samples = the clip: the
   stream outlives the engine's window and slides it; the line then also carries `slides`, the number of slides among the timed pushes,
   and `mean_ms` (the median of a run in which one push in ~26 slides does not see them).
-Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000]"""
+--source-rate SR: the pushes arrive at SR Hz (48000, 44100, 32000) through se_amd.source_stream.SourceRateStream - a StreamResampler
+  in front of the engine's stream; a push then carries the source samples of `chunk` frames and its time includes the resampling.
+Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000]"""
 import argparse
 import json
 import os
@@ -52,6 +54,37 @@ def count_slides(L, piece, first, max_samples, n_fft, hop):
     return slides
 
 
+def time_source_rate(a, name, B, L, hop, eng, c):
+    """--source-rate: the same measurement with every push made at the source rate through SourceRateStream"""
+    import torch
+    from se_amd.source_stream import SourceRateStream
+    sr = a.source_rate
+    for chunk in map(int, a.chunk.split(',')):
+        piece = round(chunk * hop * sr / 16000)                 # source samples of `chunk` frames
+        Ls = L * sr // 16000 // piece * piece                   # as many whole pieces as fit the engine's max_samples at 16 kHz
+        xs = torch.from_numpy(np.stack([synth.synth_clip(900 + b, 'speech', Ls, fs=sr) for b in range(B)])).cuda()
+        src = SourceRateStream(eng, sr, max_push=piece)
+        for rep in range(2):
+            src.begin(B, c=c, max_chunk_frames=chunk)
+            times, enq = [], []
+            for p in range(0, Ls, piece):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                src.push(xs[:, p:p + piece])
+                t1 = time.perf_counter()
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+                enq.append(t1 - t0)
+            src.flush()
+        src.close()
+        t = float(np.median(times[4:]))
+        print(json.dumps({'model': name, 'streams': B, 'frames_per_push': chunk, 'source_rate': sr, 'samples_per_push': piece,
+                          'ms_per_push': round(t * 1e3, 3), 'p95_ms': round(float(np.percentile(times[4:], 95)) * 1e3, 3),
+                          'host_enqueue_ms': round(float(np.median(enq[4:])) * 1e3, 3),
+                          'x_realtime_per_stream': round(piece / sr / t, 2),
+                          'x_realtime_all_streams': round(B * piece / sr / t, 1)}), flush=True)
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -60,6 +93,7 @@ def main():
     ap.add_argument('--chunk', default='1,8')
     ap.add_argument('--seconds', type=float, default=2.0)
     ap.add_argument('--sliding', type=int, default=0, help='max_samples of a sliding-stream engine (0: a bounded engine as long as the clip)')
+    ap.add_argument('--source-rate', type=int, default=0, help='push at this sample rate through SourceRateStream (0: push 16 kHz samples)')
     a = ap.parse_args()
     L = int(a.seconds * 16000)
     for name in a.models.split(','):
@@ -69,6 +103,10 @@ def main():
             hop = {'dccrn': 128, 'dccrn_snr': 128, 'fullsubnet_cum': 256}.get(name, 160)
             x = torch.from_numpy(np.stack([synth.synth_clip(900 + b, 'speech', L) for b in range(B)])).cuda()
             c = eng.rms_scale(x)
+            if a.source_rate:
+                time_source_rate(a, name, B, L, hop, eng, c)
+                del m, eng
+                continue
             for chunk in map(int, a.chunk.split(',')):
                 piece = chunk * hop
                 times = []
