@@ -1,15 +1,19 @@
 // C ABI of the engine (include/se_engine.h): handle, strict state-dict load, stage hooks.
 #include "../../include/se_engine.h"
+#include "hip_owned.h"
 #include "model.h"
 #include "resampler.h"
 #include "stream_window.h"
 #include "window_rows.h"
 #include <algorithm>
+#include <climits>
 #include <cstring>
 #include <mutex>
 
 using namespace se;
 
+// Every device buffer, pinned buffer, event and stream below is an owner (hip_owned.h): `delete e` releases them, and members are
+// destroyed in reverse order of declaration - each model is declared behind the context it refers to
 struct se_engine {
     se_config cfg{};
     EngineCtx ctx;
@@ -27,19 +31,19 @@ struct se_engine {
     };
     std::vector<GraphEntry> graphs;
     std::vector<std::pair<int, int>> warmed;
-    float *stage_in = nullptr, *stage_out = nullptr;
-    float* hook_buf = nullptr;     // se_backend: the decompressed spectrum between the mask stage and the iSTFT (grows, never shrinks)
+    DevBuf<float> stage_in, stage_out;
+    DevBuf<float> hook_buf;        // se_backend: the decompressed spectrum between the mask stage and the iSTFT (grows, never shrinks)
     size_t hook_cap = 0;
     // se_enhance_ragged: per-row sizes (len | lpad | tlen | olen, max_batch ints each) go host -> device through a small
     // ring of pinned slots, so back-to-back calls never wait for each other's copy
     static constexpr int RAG_SLOTS = 8;
-    int* rag_host = nullptr;       // pinned [RAG_SLOTS][4 * max_batch]
-    int* rag_dev = nullptr;        // device [RAG_SLOTS][4 * max_batch]
-    hipEvent_t rag_ev[RAG_SLOTS] = {};
+    PinnedBuf<int> rag_host;       // pinned [RAG_SLOTS][4 * max_batch]
+    DevBuf<int> rag_dev;           // device [RAG_SLOTS][4 * max_batch]
+    Event rag_ev[RAG_SLOTS];
     int rag_next = 0;
-    int* rag_win = nullptr;        // device [4 * max_batch]: the rows' sizes as the current window launch of se_enhance_long_ragged sees them
-    hipStream_t cap_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    DevBuf<int> rag_win;           // device [4 * max_batch]: the rows' sizes as the current window launch of se_enhance_long_ragged sees them
+    OwnedStream cap_stream;
+    Event ev_fork, ev_join;
     // Two half-batches side by side (round 6: Uformer, DPCRN, CTSNet, TaylorSENet): a second instance of the model with its own context and
     // workspace decodes rows [B / 2, B) of a se_enhance_batch call on a process-wide auxiliary stream while the first decodes
     // rows [0, B / 2) on the caller's - a decode is ~400 launches of very different shapes, two of them in flight fill each
@@ -50,8 +54,8 @@ struct se_engine {
     static constexpr int MAX_TWINS = 2;
     int ntwins = 0;
     std::unique_ptr<EngineCtx> ctx2[MAX_TWINS];
-    std::unique_ptr<Model> twin[MAX_TWINS];
-    hipEvent_t ev_tfork = nullptr, ev_tjoin[MAX_TWINS] = {};
+    std::unique_ptr<Model> twin[MAX_TWINS];      // (behind ctx2: the models go before their contexts)
+    Event ev_tfork, ev_tjoin[MAX_TWINS];
     // se_stream_*: the samples received so far ([batch][max_samples]), frames transformed, samples emitted.
     // SE_CFG_STREAM_SLIDING: `wav` is a window [batch][pitch] whose column 0 holds the absolute sample w0 (stream_window.h);
     // a slide copies the live tail into `wav2` and swaps the two
@@ -60,20 +64,31 @@ struct se_engine {
         int batch = 0, max_chunk = 0, n_total = 0, t_done = 0, o_done = 0;
         int w0 = 0;
         long pitch = 0;          // floats per row of wav (max_samples, or stream_window_pitch())
-        float* wav2 = nullptr;
+        DevBuf<float> wav, wav2;
+        // se_enhance_long / _ragged: the caller's resident rows (origin 0, not owned), read in place of `wav`; null in a stream
+        const float* ext = nullptr;
+        long ext_pitch = 0;
         int carve_B = -1, carve_n = -1;      // (batch, chunk frames) the arena was last carved and zero-filled for
         // running unit-RMS scale (se_stream_begin_running): sum of squares so far per stream, 1 / c per frame in a ring
         bool running = false;
-        double* sumsq = nullptr;
-        float* frame_inv = nullptr;
+        DevBuf<double> sumsq;
+        DevBuf<float> frame_inv;
         int ring = 0;
-        float* wav = nullptr;
-        float* c = nullptr;
+        DevBuf<float> c;
         // the hipStream the last push / flush / begin of this handle ran on: a new stream that starts on ANOTHER hipStream
         // re-uses (and clears) the parked state buffers, so it must be ordered behind the work still in flight there
         bool has_last = false;
         hipStream_t last_st = nullptr;
-        hipEvent_t ev_order = nullptr;
+        Event ev_order;
+        // a stream or a windowed decode starts: nothing received (or a whole clip of n_total_ samples), nothing done, no carve
+        void start(int batch_, int n_total_, bool running_) {
+            batch = batch_;
+            n_total = n_total_;
+            running = running_;
+            t_done = o_done = w0 = 0;
+            carve_B = carve_n = -1;
+            ext = nullptr;
+        }
     } strm;
 };
 
@@ -236,7 +251,6 @@ int se_engine_create(const se_config* cfg, se_engine** out) {
         if (split && e->ctx.max_batch >= 64) {
             const int parts = (cfg->model == SE_MODEL_UFORMER || cfg->model == SE_MODEL_DPCRN) ? 3 : 2;
             e->ntwins = parts - 1;
-            SE_HIP(hipEventCreateWithFlags(&e->ev_tfork, hipEventDisableTiming));
             for (int i = 0; i < e->ntwins; ++i) {
                 e->ctx2[i].reset(new EngineCtx());
                 e->ctx2[i]->max_batch = (e->ctx.max_batch + i + 1) / (i + 2);      // the first: a half (two-part calls), the second: a third
@@ -246,7 +260,6 @@ int se_engine_create(const se_config* cfg, se_engine** out) {
                 e->ctx2[i]->flags = e->ctx.flags;
                 e->twin[i] = make_model(cfg->model, *e->ctx2[i]);
                 e->ctx2[i]->geom = e->ctx.geom;
-                SE_HIP(hipEventCreateWithFlags(&e->ev_tjoin[i], hipEventDisableTiming));
             }
         }
         *out = e;
@@ -267,33 +280,10 @@ int se_engine_destroy(se_engine* e) {
     (void)hipDeviceSynchronize();
     for (auto& g : e->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (e->cap_stream) {
-        (void)hipStreamDestroy(e->cap_stream);
-        (void)hipEventDestroy(e->ev_fork);
-        (void)hipEventDestroy(e->ev_join);
-    }
-    if (e->strm.wav) (void)hipFree(e->strm.wav);
-    if (e->strm.wav2) (void)hipFree(e->strm.wav2);
-    if (e->strm.c) (void)hipFree(e->strm.c);
-    if (e->strm.sumsq) (void)hipFree(e->strm.sumsq);
-    if (e->strm.frame_inv) (void)hipFree(e->strm.frame_inv);
-    if (e->strm.ev_order) (void)hipEventDestroy(e->strm.ev_order);
-    if (e->rag_host) (void)hipHostFree(e->rag_host);
-    if (e->rag_dev) (void)hipFree(e->rag_dev);
-    if (e->rag_win) (void)hipFree(e->rag_win);
-    for (auto& ev : e->rag_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (e->hook_buf) (void)hipFree(e->hook_buf);
-    if (e->stage_in) (void)hipFree(e->stage_in);
-    if (e->stage_out) (void)hipFree(e->stage_out);
+    // (the tile kernels' over-read ranges are dropped before `delete e` releases the arenas they name)
     if (e->ctx.arena.base()) gc_unregister_overread_range(e->ctx.arena.base());
-    if (e->ev_tfork) (void)hipEventDestroy(e->ev_tfork);
-    for (int i = 0; i < se_engine::MAX_TWINS; ++i) {
-        if (e->ctx2[i] && e->ctx2[i]->arena.base()) gc_unregister_overread_range(e->ctx2[i]->arena.base());
-        if (e->ev_tjoin[i]) (void)hipEventDestroy(e->ev_tjoin[i]);
-        e->twin[i].reset();          // (the model before its context)
-        e->ctx2[i].reset();
-    }
+    for (auto& c2 : e->ctx2)
+        if (c2 && c2->arena.base()) gc_unregister_overread_range(c2->arena.base());
     const int dev = e->cfg.device;
     delete e;
     scratch_engine_destroyed(dev);      // the device's last engine takes the engine-lifetime scratch slots with it
@@ -376,26 +366,40 @@ int se_engine_finalize(se_engine* e) {
     });
 }
 
-// an offline decode re-carves the arena: it is ordered behind the last frame-online call made on ANOTHER hipStream (the event
-// stream_mark() recorded there), so that it cannot overwrite windows that call is still reading
-static void stream_order_wait(se_engine* e, hipStream_t st) {
-    se_engine::Stream& S = e->strm;
-    if (S.has_last && S.last_st != st && S.ev_order) SE_HIP(hipStreamWaitEvent(st, S.ev_order, 0));
+// The preamble and the epilogue of every call that enqueues work on the arena, in one scope.
+// A call that re-carves the arena (RECARVE: every offline decode; TAKE_OVER: the windowed decodes, which also end a running
+// stream) first tells a stream running on this handle to zero-fill its next windows (carve_B), then orders itself behind the
+// last call made on ANOTHER hipStream - the event stream_mark() recorded there - so that it cannot overwrite windows that call
+// is still reading.  se_stream_push / _flush only mark (MARK_ONLY).
+// ... and the other direction: EVERY such call leaves the ordering event behind its last launch, also when it
+// throws after enqueueing, so that a se_stream_begin issued on another hipStream right after it cannot re-carve or zero-fill
+// the arena under it
+static void stream_mark(se_engine::Stream& S, hipStream_t st) {
+    SE_HIP(hipEventRecord(S.ev_order.get(), st));
+    S.has_last = true;
+    S.last_st = st;
 }
-// ... and the other direction: EVERY call that enqueues work on the arena - offline decodes as well - leaves the
-// ordering event behind its last launch, also when it throws after enqueueing, so that a se_stream_begin issued on another
-// hipStream right after an offline decode cannot re-carve or zero-fill the arena under it
-static void stream_mark(se_engine::Stream& S, hipStream_t st);
-struct StreamMarkScope {
-    se_engine* e;
+static void stream_order_wait(se_engine::Stream& S, hipStream_t st) {
+    if (S.has_last && S.last_st != st) SE_HIP(hipStreamWaitEvent(st, S.ev_order.get(), 0));
+}
+struct ArenaCall {
+    enum Mode { MARK_ONLY, RECARVE, TAKE_OVER };
+    se_engine::Stream& S;
     hipStream_t st;
-    StreamMarkScope(se_engine* e_, hipStream_t st_) : e(e_), st(st_) {}
-    ~StreamMarkScope() {
+    ArenaCall(se_engine* e, hipStream_t st_, Mode mode = RECARVE) : S(e->strm), st(st_) {
+        if (mode == MARK_ONLY) return;
+        if (mode == TAKE_OVER) S.active = false;
+        S.carve_B = -1;
+        stream_order_wait(S, st);
+    }
+    ~ArenaCall() {
         try {
-            stream_mark(e->strm, st);
+            stream_mark(S, st);
         } catch (const std::exception&) {      // (a failed record leaves the previous event in place)
         }
     }
+    ArenaCall(const ArenaCall&) = delete;
+    ArenaCall& operator=(const ArenaCall&) = delete;
 };
 
 int se_forward(se_engine* e, const float* in_dev, const int64_t* in_shape, int32_t in_ndim, float* out_dev,
@@ -403,9 +407,7 @@ int se_forward(se_engine* e, const float* in_dev, const int64_t* in_shape, int32
     if (!e) return 1;
     return guard(e, [&] {
         SE_CHECK(e->finalized, "engine not finalized");
-        e->strm.carve_B = -1;          // (any decode re-carves the arena: a stream running on this handle zero-fills its next windows)
-        stream_order_wait(e, static_cast<hipStream_t>(stream));
-        StreamMarkScope sms(e, static_cast<hipStream_t>(stream));
+        ArenaCall call(e, static_cast<hipStream_t>(stream));
         SE_CHECK(in_dev && out_dev && in_shape, "null argument");
         e->ctx.prof_reset();
         e->model->forward(in_dev, in_shape, in_ndim, out_dev, static_cast<hipStream_t>(stream));
@@ -417,9 +419,7 @@ int se_uformer_forward(se_engine* e, const float* inputs_dev, const float* src_d
     if (!e) return 1;
     return guard(e, [&] {
         SE_CHECK(e->finalized, "engine not finalized");
-        e->strm.carve_B = -1;          // (any decode re-carves the arena: a stream running on this handle zero-fills its next windows)
-        stream_order_wait(e, static_cast<hipStream_t>(stream));
-        StreamMarkScope sms(e, static_cast<hipStream_t>(stream));
+        ArenaCall call(e, static_cast<hipStream_t>(stream));
         SE_CHECK(inputs_dev && output_dev, "null argument");
         SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
         SE_CHECK(n_samples >= e->ctx.geom.n_fft && n_samples <= e->ctx.max_samples, "n_samples outside [n_fft, max_samples]");
@@ -434,9 +434,7 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
     if (!e) return 1;
     return guard(e, [&] {
         SE_CHECK(e->finalized, "engine not finalized");
-        e->strm.carve_B = -1;          // (any decode re-carves the arena: a stream running on this handle zero-fills its next windows)
-        stream_order_wait(e, static_cast<hipStream_t>(stream));
-        StreamMarkScope sms(e, static_cast<hipStream_t>(stream));
+        ArenaCall call(e, static_cast<hipStream_t>(stream));
         SE_CHECK(wav_in_dev && wav_out_dev, "null argument");
         SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
         SE_CHECK(n_samples >= e->ctx.geom.n_fft && n_samples <= e->ctx.max_samples,
@@ -457,20 +455,31 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
                     Active() { batch_split_active() = true; }
                     ~Active() { batch_split_active() = false; }
                 } active;
-                SE_HIP(hipEventRecord(e->ev_tfork, st));
-                int njoin = 0;
+                // the caller's stream joins every twin recorded so far, also when a later enhance() throws: their work still
+                // reads wav_in and writes wav_out; a failing wait is swallowed, as a failing mark is
+                struct TwinJoin {
+                    se_engine* e;
+                    hipStream_t st;
+                    int n = 0;
+                    ~TwinJoin() {
+                        try {
+                            for (int i = 0; i < n; ++i) (void)hipStreamWaitEvent(st, e->ev_tjoin[i].get(), 0);
+                        } catch (const std::exception&) {
+                        }
+                    }
+                } join{e, st};
+                SE_HIP(hipEventRecord(e->ev_tfork.get(), st));
                 for (int i = 0; i < parts - 1; ++i) {
                     const int r0 = (i + 1) * Bp, nr = std::min(Bp, batch - r0);
                     if (nr <= 0) break;
                     hipStream_t s2 = twin_stream(e->cfg.device, i);
-                    SE_HIP(hipStreamWaitEvent(s2, e->ev_tfork, 0));
+                    SE_HIP(hipStreamWaitEvent(s2, e->ev_tfork.get(), 0));
                     e->twin[i]->enhance(wav_in_dev + (size_t)r0 * in_pitch, in_pitch, nr, n_samples, wav_out_dev + (size_t)r0 * out_pitch,
                                         out_pitch, s2);
-                    SE_HIP(hipEventRecord(e->ev_tjoin[i], s2));
-                    njoin = i + 1;
+                    SE_HIP(hipEventRecord(e->ev_tjoin[i].get(), s2));
+                    join.n = i + 1;
                 }
                 e->model->enhance(wav_in_dev, in_pitch, std::min(Bp, batch), n_samples, wav_out_dev, out_pitch, st);
-                for (int i = 0; i < njoin; ++i) SE_HIP(hipStreamWaitEvent(st, e->ev_tjoin[i], 0));
                 return;
             }
             e->model->enhance(wav_in_dev, in_pitch, batch, n_samples, wav_out_dev, out_pitch, st);
@@ -482,35 +491,30 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
             if (g.batch == batch && g.samples == n_samples) ge = &g;
         if (!ge) {
             const std::pair<int, int> key(batch, n_samples);
-            if (!e->cap_stream) {
-                SE_HIP(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
-                SE_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-                SE_HIP(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-            }
+            // capture on the engine-owned stream: the caller's stream may be the legacy default stream, which cannot capture
+            hipStream_t cs = e->cap_stream.get();
             if (std::find(e->warmed.begin(), e->warmed.end(), key) == e->warmed.end()) {
                 // first call of a shape: eager, but on the capture stream (fork / join around the caller's stream) so that
                 // the lazily grown scratch buffers - keyed by stream - already exist when the shape is captured
                 e->warmed.push_back(key);
-                SE_HIP(hipEventRecord(e->ev_fork, st));
-                SE_HIP(hipStreamWaitEvent(e->cap_stream, e->ev_fork, 0));
-                e->model->enhance(wav_in_dev, in_pitch, batch, n_samples, wav_out_dev, out_pitch, e->cap_stream);
-                SE_HIP(hipEventRecord(e->ev_join, e->cap_stream));
-                SE_HIP(hipStreamWaitEvent(st, e->ev_join, 0));
+                SE_HIP(hipEventRecord(e->ev_fork.get(), st));
+                SE_HIP(hipStreamWaitEvent(cs, e->ev_fork.get(), 0));
+                e->model->enhance(wav_in_dev, in_pitch, batch, n_samples, wav_out_dev, out_pitch, cs);
+                SE_HIP(hipEventRecord(e->ev_join.get(), cs));
+                SE_HIP(hipStreamWaitEvent(st, e->ev_join.get(), 0));
                 return;
             }
             if (!e->stage_in) {
                 const int64_t max_out = e->model->output_samples(e->ctx.max_samples);
-                SE_HIP(hipMalloc(&e->stage_in, (size_t)e->ctx.max_batch * e->ctx.max_samples * sizeof(float)));
-                SE_HIP(hipMalloc(&e->stage_out, (size_t)e->ctx.max_batch * max_out * sizeof(float)));
+                e->stage_in.alloc((size_t)e->ctx.max_batch * e->ctx.max_samples);
+                e->stage_out.alloc((size_t)e->ctx.max_batch * max_out);
             }
             hipGraph_t graph = nullptr;
             hipGraphExec_t exec = nullptr;
-            // capture on the engine-owned stream: the caller's stream may be the legacy default stream, which cannot capture
-            hipStream_t cs = e->cap_stream;
             SE_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
             bool ok = true;
             try {
-                e->model->enhance(e->stage_in, n_samples, batch, n_samples, e->stage_out, n_out, cs);
+                e->model->enhance(e->stage_in.get(), n_samples, batch, n_samples, e->stage_out.get(), n_out, cs);
             } catch (const std::exception&) {
                 ok = false;
             }
@@ -527,10 +531,10 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
             e->model->enhance(wav_in_dev, in_pitch, batch, n_samples, wav_out_dev, out_pitch, st);
             return;
         }
-        SE_HIP(hipMemcpy2DAsync(e->stage_in, (size_t)n_samples * sizeof(float), wav_in_dev, (size_t)in_pitch * sizeof(float),
+        SE_HIP(hipMemcpy2DAsync(e->stage_in.get(), (size_t)n_samples * sizeof(float), wav_in_dev, (size_t)in_pitch * sizeof(float),
                                 (size_t)n_samples * sizeof(float), batch, hipMemcpyDeviceToDevice, st));
         SE_HIP(hipGraphLaunch(ge->exec, st));
-        SE_HIP(hipMemcpy2DAsync(wav_out_dev, (size_t)out_pitch * sizeof(float), e->stage_out, (size_t)n_out * sizeof(float),
+        SE_HIP(hipMemcpy2DAsync(wav_out_dev, (size_t)out_pitch * sizeof(float), e->stage_out.get(), (size_t)n_out * sizeof(float),
                                 (size_t)n_out * sizeof(float), batch, hipMemcpyDeviceToDevice, st));
     });
 }
@@ -539,15 +543,14 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
 static Ragged upload_row_sizes(se_engine* e, int batch, const int32_t* lengths, hipStream_t st) {
     const int MB = e->ctx.max_batch;
     if (!e->rag_host) {
-        SE_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->rag_host), sizeof(int) * 4 * MB * se_engine::RAG_SLOTS, hipHostMallocDefault));
-        SE_HIP(hipMalloc(reinterpret_cast<void**>(&e->rag_dev), sizeof(int) * 4 * MB * se_engine::RAG_SLOTS));
-        for (auto& ev : e->rag_ev) SE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        e->rag_host.alloc((size_t)4 * MB * se_engine::RAG_SLOTS);
+        e->rag_dev.alloc((size_t)4 * MB * se_engine::RAG_SLOTS);
     }
     const int slot = e->rag_next;
     e->rag_next = (slot + 1) % se_engine::RAG_SLOTS;
-    SE_HIP(hipEventSynchronize(e->rag_ev[slot]));      // the copy that last used this slot has run (no-op when unused)
-    int* h = e->rag_host + (size_t)slot * 4 * MB;
-    int* d = e->rag_dev + (size_t)slot * 4 * MB;
+    SE_HIP(hipEventSynchronize(e->rag_ev[slot].get()));      // the copy that last used this slot has run (no-op when unused)
+    int* h = e->rag_host.get() + (size_t)slot * 4 * MB;
+    int* d = e->rag_dev.get() + (size_t)slot * 4 * MB;
     const int hop = e->ctx.geom.hop;
     for (int b = 0; b < batch; ++b) {
         const int L = lengths[b], Lp = e->model->padded_samples(L);
@@ -557,7 +560,7 @@ static Ragged upload_row_sizes(se_engine* e, int batch, const int32_t* lengths, 
         h[3 * MB + b] = (int)e->model->output_samples(L);
     }
     SE_HIP(hipMemcpyAsync(d, h, sizeof(int) * 4 * MB, hipMemcpyHostToDevice, st));
-    SE_HIP(hipEventRecord(e->rag_ev[slot], st));
+    SE_HIP(hipEventRecord(e->rag_ev[slot].get(), st));
     return Ragged{d, d + MB, d + 2 * MB, d + 3 * MB};
 }
 // the per-row sizes are visible to the launchers only while this scope enqueues work (null: nothing is published)
@@ -578,9 +581,7 @@ int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, i
     if (!e) return 1;
     return guard(e, [&] {
         SE_CHECK(e->finalized, "engine not finalized");
-        e->strm.carve_B = -1;          // (any decode re-carves the arena: a stream running on this handle zero-fills its next windows)
-        stream_order_wait(e, static_cast<hipStream_t>(stream));
-        StreamMarkScope sms(e, static_cast<hipStream_t>(stream));
+        ArenaCall call(e, static_cast<hipStream_t>(stream));
         SE_CHECK(wav_in_dev && wav_out_dev && lengths, "null argument");
         SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
         SE_CHECK(e->model->ragged_supported(),
@@ -603,7 +604,7 @@ int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, i
 
 // frames [e->strm.t_done, t_end) of the stream through the network, then every output sample they complete (all of them up to
 // the end when `last`); the samples are appended to out row b at out_dev[b * out_pitch + *written ...].  The input rows are the
-// stream's own window (wav = S.wav, pitch = S.pitch, origin w0 = S.w0) or, for se_enhance_long, the caller's resident clip (origin 0)
+// stream's own window (S.wav, pitch S.pitch, origin S.w0) or, for se_enhance_long, the caller's resident clip (S.ext, origin 0)
 // `rows` (se_enhance_long_ragged; null otherwise): the rows' own sizes over their whole clips, absolute.  S.n_total / t_end are then
 // those of the LONGEST row.  The STFT and the iSTFT count frames and samples absolutely inside a window too, so a row's sample
 // counts (len, lpad, olen) mean in a window what they mean offline: its reflected edge and tail pad fall into whichever window holds
@@ -616,9 +617,12 @@ int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, i
 // without per-row sizes: past its end a row is fed zero frames.  That is exact for a look-ahead at the network's INPUT (FullSubNet,
 // cumulative norm: the zero frames `last` appends are the ones the STFT wrote); a model that looks ahead behind its input layer (the
 // `_vb` DCCRN's decoder) needs zeros behind every layer, which is not built yet: the caller refuses it.
-static void stream_process(se_engine* e, const float* wav, long pitch, int w0, int t_end, bool last, float* out_dev,
-                           int64_t out_pitch, int* written, hipStream_t st, const Ragged* rows = nullptr) {
+static void stream_process(se_engine* e, int t_end, bool last, float* out_dev, int64_t out_pitch, int* written, hipStream_t st,
+                           const Ragged* rows = nullptr) {
     se_engine::Stream& S = e->strm;
+    const float* wav = S.ext ? S.ext : S.wav.get();
+    const long pitch = S.ext ? S.ext_pitch : S.pitch;
+    const int w0 = S.w0;
     const StftGeom& g = e->ctx.geom;
     const int HC = e->model->stream_hc(), LAG = e->model->stream_lag(), B = S.batch;
     // a frame that is transformed before the end of the stream never touches the end reflection / the tail padding
@@ -626,10 +630,11 @@ static void stream_process(se_engine* e, const float* wav, long pitch, int w0, i
     const int Lpad = last ? e->model->padded_samples(S.n_total) : S.n_total;
     const int n_final = last ? (int)e->model->output_samples(S.n_total) : S.n_total;
     const int MB = e->ctx.max_batch;
-    if (rows && !e->rag_win) SE_HIP(hipMalloc(reinterpret_cast<void**>(&e->rag_win), sizeof(int) * 4 * MB));
+    if (rows && !e->rag_win) e->rag_win.alloc((size_t)4 * MB);
     // (one buffer: a view, the launch that reads it and the next view follow one another on `st`; rows->len is the base of the
     // uploaded [4][MB] block, upload_row_sizes)
-    const Ragged win{e->rag_win, e->rag_win + MB, e->rag_win + 2 * MB, e->rag_win + 3 * MB};
+    int* const rw = e->rag_win.get();
+    const Ragged win{rw, rw + MB, rw + 2 * MB, rw + 3 * MB};
     const Ragged* view = rows ? &win : nullptr;
     while (S.t_done < t_end) {
         const int t0 = S.t_done, n = std::min(S.max_chunk, t_end - t0), Tw = HC + n;
@@ -645,9 +650,9 @@ static void stream_process(se_engine* e, const float* wav, long pitch, int w0, i
             S.carve_n = n;
         }
         {
-            if (rows) launch_window_rows(rows->len, e->rag_win, MB, B, t0 + n, st);
+            if (rows) launch_window_rows(rows->len, rw, MB, B, t0 + n, st);
             RaggedScope rs(view);
-            launch_stft(g, wav, pitch, B, S.n_total, Lpad, S.c, e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, w0);
+            launch_stft(g, wav, pitch, B, S.n_total, Lpad, S.c.get(), e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, w0);
         }
         e->model->stream_chunk(B, t0, n, st, last && t0 + n == t_end);
         S.t_done = t0 + n;
@@ -657,23 +662,26 @@ static void stream_process(se_engine* e, const float* wav, long pitch, int w0, i
         const int t_fin = end ? S.t_done : S.t_done - LAG;
         const int o_hi = end ? n_final : std::min(S.n_total, t_fin * g.hop - g.n_fft / 2);
         if (o_hi > S.o_done) {
-            if (rows && t_fin != t0 + n) launch_window_rows(rows->len, e->rag_win, MB, B, t_fin, st);      // (else the STFT's view holds)
+            if (rows && t_fin != t0 + n) launch_window_rows(rows->len, rw, MB, B, t_fin, st);      // (else the STFT's view holds)
             RaggedScope rs(view);
-            launch_istft(g, est, B, t_fin, Tw, nullptr, S.running ? nullptr : S.c, out_dev + *written, out_pitch, o_hi, st, t0 - HC,
-                         std::max(0, t0 - HC), S.o_done, S.running ? S.frame_inv : nullptr, S.ring);
+            launch_istft(g, est, B, t_fin, Tw, nullptr, S.running ? nullptr : S.c.get(), out_dev + *written, out_pitch, o_hi, st, t0 - HC,
+                         std::max(0, t0 - HC), S.o_done, S.running ? S.frame_inv.get() : nullptr, S.ring);
             *written += o_hi - S.o_done;
             S.o_done = o_hi;
         }
     }
 }
 
-// the last thing a stream call does on its hipStream: record the ordering event the NEXT se_stream_begin (possibly on another
-// hipStream) waits for, while the handle is certainly alive
-static void stream_mark(se_engine::Stream& S, hipStream_t st) {
-    if (!S.ev_order) SE_HIP(hipEventCreateWithFlags(&S.ev_order, hipEventDisableTiming));
-    SE_HIP(hipEventRecord(S.ev_order, st));
-    S.has_last = true;
-    S.last_st = st;
+// what a frame-online stream and a windowed decode ask of the model's geometry, and how many frames one window launch takes
+static void check_stream_geometry(const se_engine* e) {
+    const StftGeom& g = e->ctx.geom;
+    SE_CHECK((g.n_fft + g.hop - 1) / g.hop - 1 + e->model->stream_lag() <= e->model->stream_hc(),
+             "front end overlap + look-ahead exceed the history the model keeps");
+}
+// (the workspace holds `room` frames behind the model's history columns; dflt: the chunk of a call that names none)
+static int window_frames(const se_engine* e, int requested, int dflt) {
+    const int room = std::max(1, e->plan_frames - e->model->stream_hc());
+    return std::min(requested > 0 ? requested : dflt, room);
 }
 
 static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_frames, const float* c_dev, bool running, void* stream) {
@@ -683,38 +691,34 @@ static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_fram
         e->strm.carve_B = -1;          // (any decode re-carves the arena: a stream running on this handle zero-fills its next windows)
         SE_CHECK(e->model->stream_supported(), "this model has no frame-online mode (CRN, LSTM, GCRN, DPCRN, DCCRN, FullSubNet with the cumulative norm and the cLN `_new` weights of CTSNet / TaylorSENet / G2Net have)");
         SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
+        check_stream_geometry(e);
         const StftGeom& g = e->ctx.geom;
-        SE_CHECK((g.n_fft + g.hop - 1) / g.hop - 1 + e->model->stream_lag() <= e->model->stream_hc(),
-                 "front end overlap + look-ahead exceed the history the model keeps");
         hipStream_t st = static_cast<hipStream_t>(stream);
         se_engine::Stream& S = e->strm;
         // work of the previous stream on another hipStream: wait for the event that stream_mark() recorded behind ITS last
         // call (the handle itself may have been destroyed since - it is never touched again)
-        if (S.has_last && S.last_st != st && S.ev_order) SE_HIP(hipStreamWaitEvent(st, S.ev_order, 0));
-        S.max_chunk = std::max(1, std::min(max_chunk_frames > 0 ? max_chunk_frames : 16, e->plan_frames - e->model->stream_hc()));
+        stream_order_wait(S, st);
+        S.max_chunk = window_frames(e, max_chunk_frames, 16);
         if (!S.wav) {
             const bool sliding = (e->cfg.flags & SE_CFG_STREAM_SLIDING) != 0;
             S.pitch = sliding ? stream_window_pitch(e->ctx.max_samples, g.n_fft, g.hop) : e->ctx.max_samples;
-            SE_HIP(hipMalloc(&S.wav, (size_t)e->ctx.max_batch * S.pitch * sizeof(float)));
-            if (sliding) SE_HIP(hipMalloc(&S.wav2, (size_t)e->ctx.max_batch * S.pitch * sizeof(float)));
+            S.wav.alloc((size_t)e->ctx.max_batch * S.pitch);
+            if (sliding) S.wav2.alloc((size_t)e->ctx.max_batch * S.pitch);
         }
-        if (!S.c) SE_HIP(hipMalloc(&S.c, (size_t)e->ctx.max_batch * sizeof(float)));      // (se_enhance_long may have made it already)
-        if (c_dev) SE_HIP(hipMemcpyAsync(S.c, c_dev, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, st));
-        else launch_fill(S.c, batch, 1.f, st);
-        S.running = running;
+        if (!S.c) S.c.alloc(e->ctx.max_batch);      // (se_enhance_long may have made it already)
+        if (c_dev) SE_HIP(hipMemcpyAsync(S.c.get(), c_dev, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, st));
+        else launch_fill(S.c.get(), batch, 1.f, st);
         if (running) {
             if (!S.sumsq) {
                 S.ring = 64;
                 while (S.ring < e->plan_frames + 64) S.ring <<= 1;
-                SE_HIP(hipMalloc(&S.sumsq, (size_t)e->ctx.max_batch * sizeof(double)));
-                SE_HIP(hipMalloc(&S.frame_inv, (size_t)e->ctx.max_batch * S.ring * sizeof(float)));
+                S.sumsq.alloc(e->ctx.max_batch);
+                S.frame_inv.alloc((size_t)e->ctx.max_batch * S.ring);
             }
-            SE_HIP(hipMemsetAsync(S.sumsq, 0, (size_t)batch * sizeof(double), st));
-            launch_fill(S.frame_inv, (long)batch * S.ring, 1.f, st);
+            SE_HIP(hipMemsetAsync(S.sumsq.get(), 0, (size_t)batch * sizeof(double), st));
+            launch_fill(S.frame_inv.get(), (long)batch * S.ring, 1.f, st);
         }
-        S.batch = batch;
-        S.n_total = S.t_done = S.o_done = S.w0 = 0;
-        S.carve_B = S.carve_n = -1;
+        S.start(batch, 0, running);
         e->model->stream_begin(batch, S.max_chunk, st);
         S.active = true;
         stream_mark(S, st);
@@ -753,16 +757,16 @@ int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_
             SE_CHECK(S.n_total + n_new <= e->ctx.max_samples, "stream longer than max_samples given at create");
         }
         hipStream_t st = static_cast<hipStream_t>(stream);
-        StreamMarkScope sms(e, st);
+        ArenaCall call(e, st, ArenaCall::MARK_ONLY);
         if (keep != S.w0) {
             // [keep, n_total) of every row to column 0 of the other buffer (whole float4s: up to three columns past the tail
             // travel along, inside the row - the append below overwrites them)
-            launch_stream_slide(S.wav, S.wav2, S.pitch, S.batch, keep - S.w0, (S.n_total - keep + 3) & ~3, st);
+            launch_stream_slide(S.wav.get(), S.wav2.get(), S.pitch, S.batch, keep - S.w0, (S.n_total - keep + 3) & ~3, st);
             std::swap(S.wav, S.wav2);
             S.w0 = keep;
         }
         if (n_new > 0)
-            SE_HIP(hipMemcpy2DAsync(S.wav + (S.n_total - S.w0), (size_t)S.pitch * sizeof(float), wav_dev,
+            SE_HIP(hipMemcpy2DAsync(S.wav.get() + (S.n_total - S.w0), (size_t)S.pitch * sizeof(float), wav_dev,
                                     (size_t)pitch * sizeof(float), (size_t)n_new * sizeof(float), S.batch,
                                     hipMemcpyDeviceToDevice, st));
         S.n_total += n_new;
@@ -770,13 +774,13 @@ int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_
         // left half needs sample n_fft / 2 as well)
         const int t_avail = S.n_total > g.n_fft / 2 ? (S.n_total - g.n_fft / 2 - 1) / g.hop + 1 : 0;
         if (S.running)      // c of the frames this push releases: sqrt(samples so far / their sum of squares)
-            launch_stream_rms(S.wav, S.pitch, S.batch, S.n_total, n_new, S.sumsq, S.c, S.frame_inv, S.ring, S.t_done,
+            launch_stream_rms(S.wav.get(), S.pitch, S.batch, S.n_total, n_new, S.sumsq.get(), S.c.get(), S.frame_inv.get(), S.ring, S.t_done,
                               std::max(t_avail, S.t_done), st, S.w0);
         int written = 0;
         const int will = std::max(0, std::min(S.n_total, (t_avail - e->model->stream_lag()) * g.hop - g.n_fft / 2) - S.o_done);
         SE_CHECK(out_pitch >= will, "output row pitch too small for the samples this push completes");
         e->ctx.prof_reset();
-        stream_process(e, S.wav, S.pitch, S.w0, std::max(t_avail, S.t_done), false, out_dev, out_pitch, &written, st);
+        stream_process(e, std::max(t_avail, S.t_done), false, out_dev, out_pitch, &written, st);
         *n_out = written;
     });
 }
@@ -790,13 +794,13 @@ int se_stream_flush(se_engine* e, float* out_dev, int64_t out_pitch, int32_t* n_
         SE_CHECK(S.n_total >= e->ctx.geom.n_fft, "stream shorter than one FFT frame");
         SE_CHECK(out_pitch >= e->model->output_samples(S.n_total) - S.o_done, "output row pitch too small for the rest of the stream");
         int written = 0;
-        StreamMarkScope sms(e, static_cast<hipStream_t>(stream));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        ArenaCall call(e, st, ArenaCall::MARK_ONLY);
         e->ctx.prof_reset();
         if (S.running)
-            launch_stream_rms(S.wav, S.pitch, S.batch, S.n_total, 0, S.sumsq, S.c, S.frame_inv, S.ring, S.t_done,
-                              e->model->num_frames(S.n_total), static_cast<hipStream_t>(stream), S.w0);
-        stream_process(e, S.wav, S.pitch, S.w0, e->model->num_frames(S.n_total), true, out_dev, out_pitch, &written,
-                       static_cast<hipStream_t>(stream));
+            launch_stream_rms(S.wav.get(), S.pitch, S.batch, S.n_total, 0, S.sumsq.get(), S.c.get(), S.frame_inv.get(), S.ring, S.t_done,
+                              e->model->num_frames(S.n_total), st, S.w0);
+        stream_process(e, e->model->num_frames(S.n_total), true, out_dev, out_pitch, &written, st);
         *n_out = written;
         S.active = false;
     });
@@ -820,49 +824,66 @@ static std::string why_not_causal(const se_engine* e) {
     }
 }
 
+// The windowed decode of whole clips behind se_enhance_long (lengths null: every row holds n_samples) and se_enhance_long_ragged
+// (rows of their own lengths): the rows' unit-RMS scales over their whole clips first, then the stream's begin step and one walk
+// over every frame of the longest row, the last window included (right-edge reflection, hop-multiple tail pad); the STFT reads the
+// caller's rows, nothing is copied.  `fn` names the entry point in the refusals
+static void enhance_long_impl(se_engine* e, const std::string& fn, const float* wav_in_dev, int64_t in_pitch, int32_t batch,
+                              int32_t n_samples, const int32_t* lengths /* null: equal rows */, int32_t max_chunk_frames,
+                              float* wav_out_dev, int64_t out_pitch, hipStream_t st) {
+    SE_CHECK(e->model->stream_supported(),
+             fn + " decodes in windows, which needs a network that is causal end to end: " + why_not_causal(e));
+    SE_CHECK(!(lengths && e->cfg.model == SE_MODEL_DCCRN && e->model->stream_lag() > 0),
+             fn + ": DCCRN's look-ahead decoder reads one frame ahead per layer into tensors that are not zero "
+                  "behind a row's own last frame; the per-layer zeroing that rows of different lengths need is not built yet: decode "
+                  "them one at a time with se_enhance_long (the causal decoder, SE_CFG_DCCRN_CAUSAL_DEC, is accepted)");
+    SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
+    const StftGeom& g = e->ctx.geom;
+    int Lmax = 0;
+    for (int b = 0; b < (lengths ? batch : 1); ++b) {
+        const int n = lengths ? lengths[b] : n_samples;
+        const std::string what = fn + (lengths ? ": lengths[" + std::to_string(b) + "]" : ": n_samples");
+        SE_CHECK(n >= g.n_fft, what + " shorter than one FFT frame (n_fft)");
+        // no push follows, so the headroom of the position counters is the kernels' own reach (stream_window.h), whatever max_samples
+        SE_CHECK(n <= stream_sample_limit(0, g.n_fft, g.hop), what + " above the position bound 2^31 - 1 - n_fft - 32 hop");
+        Lmax = std::max(Lmax, n);
+    }
+    SE_CHECK(batch == 1 || in_pitch >= Lmax, fn + ": input row pitch smaller than " + (lengths ? "the longest row" : "n_samples"));
+    SE_CHECK(out_pitch >= e->model->output_samples(Lmax),
+             fn + ": output row pitch smaller than se_output_samples(" + (lengths ? "longest row" : "n_samples") + ")");
+    SE_CHECK(max_chunk_frames >= 0, fn + ": negative max_chunk_frames");
+    check_stream_geometry(e);
+    // every refusal is above: a refused call leaves a stream running on this handle as it was.  From here the call takes over
+    // the stream state, so that stream ends
+    ArenaCall call(e, st, ArenaCall::TAKE_OVER);
+    se_engine::Stream& S = e->strm;
+    S.max_chunk = window_frames(e, max_chunk_frames, INT_MAX);
+    if (!S.c) S.c.alloc(e->ctx.max_batch);
+    e->ctx.prof_reset();
+    // rows of their own lengths: the sizes go up once, for the scales here and for every window of the walk
+    const Ragged rg = lengths ? upload_row_sizes(e, batch, lengths, st) : Ragged{};
+    const Ragged* rows = lengths ? &rg : nullptr;
+    {
+        RaggedScope rs(rows);
+        launch_rms_scale(wav_in_dev, batch, Lmax, in_pitch, S.c.get(), st);
+    }
+    S.start(batch, Lmax, false);
+    S.ext = wav_in_dev;
+    S.ext_pitch = in_pitch;
+    e->model->stream_begin(batch, S.max_chunk, st);
+    int written = 0;
+    stream_process(e, e->model->num_frames(Lmax), true, wav_out_dev, out_pitch, &written, st, rows);
+    S.carve_B = -1;
+}
+
 int se_enhance_long(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int32_t batch, int32_t n_samples,
                     int32_t max_chunk_frames, float* wav_out_dev, int64_t out_pitch, void* stream) {
     if (!e) return 1;
     return guard(e, [&] {
         SE_CHECK(e->finalized, "engine not finalized");
-        se_engine::Stream& S = e->strm;
-        hipStream_t st = static_cast<hipStream_t>(stream);
         SE_CHECK(wav_in_dev && wav_out_dev, "null argument");
-        SE_CHECK(e->model->stream_supported(),
-                 "se_enhance_long decodes in windows, which needs a network that is causal end to end: " + why_not_causal(e));
-        SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
-        const StftGeom& g = e->ctx.geom;
-        SE_CHECK(n_samples >= g.n_fft, "se_enhance_long: n_samples shorter than one FFT frame (n_fft)");
-        // no push follows, so the headroom of the position counters is the kernels' own reach (stream_window.h), whatever max_samples
-        SE_CHECK(n_samples <= stream_sample_limit(0, g.n_fft, g.hop),
-                 "se_enhance_long: n_samples above the position bound 2^31 - 1 - n_fft - 32 hop");
-        SE_CHECK(batch == 1 || in_pitch >= n_samples, "se_enhance_long: input row pitch smaller than n_samples");
-        SE_CHECK(out_pitch >= e->model->output_samples(n_samples), "se_enhance_long: output row pitch smaller than se_output_samples(n_samples)");
-        SE_CHECK(max_chunk_frames >= 0, "se_enhance_long: negative max_chunk_frames");
-        SE_CHECK((g.n_fft + g.hop - 1) / g.hop - 1 + e->model->stream_lag() <= e->model->stream_hc(),
-                 "front end overlap + look-ahead exceed the history the model keeps");
-        // every refusal is above: a refused call leaves a stream running on this handle as it was.  From here the call takes over
-        // the stream state, so that stream ends
-        S.active = false;
-        S.carve_B = -1;
-        stream_order_wait(e, st);
-        StreamMarkScope sms(e, st);
-        // the whole clip's unit-RMS scale first, then the stream's begin step and one walk over every frame, the last window
-        // included (right-edge reflection, hop-multiple tail pad); the STFT reads the caller's rows, nothing is copied
-        const int room = std::max(1, e->plan_frames - e->model->stream_hc());
-        S.max_chunk = max_chunk_frames > 0 ? std::min(max_chunk_frames, room) : room;
-        if (!S.c) SE_HIP(hipMalloc(&S.c, (size_t)e->ctx.max_batch * sizeof(float)));
-        e->ctx.prof_reset();
-        launch_rms_scale(wav_in_dev, batch, n_samples, in_pitch, S.c, st);
-        S.running = false;
-        S.batch = batch;
-        S.n_total = n_samples;
-        S.t_done = S.o_done = S.w0 = 0;
-        S.carve_n = -1;
-        e->model->stream_begin(batch, S.max_chunk, st);
-        int written = 0;
-        stream_process(e, wav_in_dev, in_pitch, 0, e->model->num_frames(n_samples), true, wav_out_dev, out_pitch, &written, st);
-        S.carve_B = -1;
+        enhance_long_impl(e, "se_enhance_long", wav_in_dev, in_pitch, batch, n_samples, nullptr, max_chunk_frames, wav_out_dev,
+                          out_pitch, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -871,54 +892,9 @@ int se_enhance_long_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pit
     if (!e) return 1;
     return guard(e, [&] {
         SE_CHECK(e->finalized, "engine not finalized");
-        se_engine::Stream& S = e->strm;
-        hipStream_t st = static_cast<hipStream_t>(stream);
         SE_CHECK(wav_in_dev && wav_out_dev && lengths, "null argument");
-        SE_CHECK(e->model->stream_supported(),
-                 "se_enhance_long_ragged decodes in windows, which needs a network that is causal end to end: " + why_not_causal(e));
-        SE_CHECK(!(e->cfg.model == SE_MODEL_DCCRN && e->model->stream_lag() > 0),
-                 "se_enhance_long_ragged: DCCRN's look-ahead decoder reads one frame ahead per layer into tensors that are not zero "
-                 "behind a row's own last frame; the per-layer zeroing that rows of different lengths need is not built yet: decode "
-                 "them one at a time with se_enhance_long (the causal decoder, SE_CFG_DCCRN_CAUSAL_DEC, is accepted)");
-        SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
-        const StftGeom& g = e->ctx.geom;
-        int Lmax = 0;
-        for (int b = 0; b < batch; ++b) {
-            SE_CHECK(lengths[b] >= g.n_fft, "se_enhance_long_ragged: lengths[" + std::to_string(b) + "] shorter than one FFT frame (n_fft)");
-            SE_CHECK(lengths[b] <= stream_sample_limit(0, g.n_fft, g.hop),
-                     "se_enhance_long_ragged: lengths[" + std::to_string(b) + "] above the position bound 2^31 - 1 - n_fft - 32 hop");
-            Lmax = std::max(Lmax, (int)lengths[b]);
-        }
-        SE_CHECK(batch == 1 || in_pitch >= Lmax, "se_enhance_long_ragged: input row pitch smaller than the longest row");
-        SE_CHECK(out_pitch >= e->model->output_samples(Lmax),
-                 "se_enhance_long_ragged: output row pitch smaller than se_output_samples(longest row)");
-        SE_CHECK(max_chunk_frames >= 0, "se_enhance_long_ragged: negative max_chunk_frames");
-        SE_CHECK((g.n_fft + g.hop - 1) / g.hop - 1 + e->model->stream_lag() <= e->model->stream_hc(),
-                 "front end overlap + look-ahead exceed the history the model keeps");
-        // every refusal is above (se_enhance_long): from here the call takes over the stream state, so a running stream ends
-        S.active = false;
-        S.carve_B = -1;
-        stream_order_wait(e, st);
-        StreamMarkScope sms(e, st);
-        const int room = std::max(1, e->plan_frames - e->model->stream_hc());
-        S.max_chunk = max_chunk_frames > 0 ? std::min(max_chunk_frames, room) : room;
-        if (!S.c) SE_HIP(hipMalloc(&S.c, (size_t)e->ctx.max_batch * sizeof(float)));
-        e->ctx.prof_reset();
-        // the rows' sizes go up once; every row's scale is that of its own whole clip; then one walk over the frames of the longest row
-        const Ragged rg = upload_row_sizes(e, batch, lengths, st);
-        {
-            RaggedScope rs(&rg);
-            launch_rms_scale(wav_in_dev, batch, Lmax, in_pitch, S.c, st);
-        }
-        S.running = false;
-        S.batch = batch;
-        S.n_total = Lmax;
-        S.t_done = S.o_done = S.w0 = 0;
-        S.carve_n = -1;
-        e->model->stream_begin(batch, S.max_chunk, st);
-        int written = 0;
-        stream_process(e, wav_in_dev, in_pitch, 0, e->model->num_frames(Lmax), true, wav_out_dev, out_pitch, &written, st, &rg);
-        S.carve_B = -1;
+        enhance_long_impl(e, "se_enhance_long_ragged", wav_in_dev, in_pitch, batch, 0, lengths, max_chunk_frames, wav_out_dev,
+                          out_pitch, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -979,16 +955,14 @@ int se_backend(se_engine* e, int32_t kind, const float* est_dev, const float* sp
         const size_t need = (size_t)batch * 2 * F * n_frames * sizeof(float);
         if (need > e->hook_cap) {
             SE_HIP(hipStreamSynchronize(st));       // (an earlier call on this stream may still read the old buffer)
-            if (e->hook_buf) SE_HIP(hipFree(e->hook_buf));
-            e->hook_buf = nullptr;
             e->hook_cap = 0;
-            SE_HIP(hipMalloc(&e->hook_buf, need));
+            e->hook_buf.alloc(need / sizeof(float));
             e->hook_cap = need;
         }
-        if (kind == SE_BACKEND_RI) launch_polar_pow(est_dev, e->hook_buf, batch, F, n_frames, e->ctx.p_out, st);
-        else if (kind == SE_BACKEND_MAG) launch_mag_phase(est_dev, spec_dev, e->hook_buf, batch, F, n_frames, e->ctx.p_out, st);
-        else launch_cmask_apply(est_dev, spec_dev, e->hook_buf, batch, F, n_frames, e->ctx.p_out, st);
-        launch_istft(e->ctx.geom, e->hook_buf, batch, n_frames, n_frames, nullptr, c_dev, wav_dev, pitch, n_out, st);
+        if (kind == SE_BACKEND_RI) launch_polar_pow(est_dev, e->hook_buf.get(), batch, F, n_frames, e->ctx.p_out, st);
+        else if (kind == SE_BACKEND_MAG) launch_mag_phase(est_dev, spec_dev, e->hook_buf.get(), batch, F, n_frames, e->ctx.p_out, st);
+        else launch_cmask_apply(est_dev, spec_dev, e->hook_buf.get(), batch, F, n_frames, e->ctx.p_out, st);
+        launch_istft(e->ctx.geom, e->hook_buf.get(), batch, n_frames, n_frames, nullptr, c_dev, wav_dev, pitch, n_out, st);
     });
 }
 

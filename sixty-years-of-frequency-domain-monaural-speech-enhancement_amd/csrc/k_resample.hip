@@ -27,6 +27,7 @@
 //              rate, so the outputs are spread over as many CUs as there are waves instead of filling one 256-thread block.
 #include "kernels.h"
 #include "common.h"
+#include "hip_owned.h"
 #include "resample_pos.h"
 #include "resampler.h"
 #include <climits>
@@ -298,14 +299,12 @@ struct DeviceScope {          // the object's device is current while a call run
 class StreamResampler {
   public:
     StreamResampler(int sr_in, int sr_out, int max_batch, int max_push);
-    ~StreamResampler() { release(); }
     void begin(int batch, hipStream_t s);
     int push(const float* in, long in_pitch, int n_new, float* out, long out_pitch, hipStream_t s);
     int flush(float* out, long out_pitch, hipStream_t s);
 
   private:
     static constexpr int RING = 8;
-    void release();
     void order_behind_last(hipStream_t s);
     const double* upload_positions(ResamplePos& pos, int64_t n_in, int64_t t_end, int64_t count, hipStream_t s);
     void launch(const float* in, long in_pitch, float* out, long out_pitch, int n_total, int w0_next, int t0, int n_calc,
@@ -315,14 +314,15 @@ class StreamResampler {
     ResamplePlan plan_{};
     bool pass_;                      // sr_in == sr_out: samples are copied through, nothing else is allocated
     long pitch_ = 0;                 // floats per row of a history buffer (2 * reach, rounded up to 4)
-    float* hist_[2] = {nullptr, nullptr};
-    double* win_ = nullptr;          // the table, scaled by the ratio when downsampling
-    double* ring_host_ = nullptr;    // pinned [RING][ring_cap_]
-    double* ring_dev_ = nullptr;     // device [RING][ring_cap_]
+    // (owners, hip_owned.h: released with the object, also when the constructor throws half way)
+    DevBuf<float> hist_[2];
+    DevBuf<double> win_;             // the table, scaled by the ratio when downsampling
+    PinnedBuf<double> ring_host_;    // pinned [RING][ring_cap_]
+    DevBuf<double> ring_dev_;        // device [RING][ring_cap_]
     long ring_cap_ = 0;              // the most outputs one push or the flush can release
-    hipEvent_t ring_ev_[RING] = {};
+    Event ring_ev_[RING];
     int ring_next_ = 0;
-    hipEvent_t ev_order_ = nullptr;
+    Event ev_order_;
     bool has_last_ = false;
     hipStream_t last_st_ = nullptr;
     // the stream: rows, which buffer holds the history, samples arrived, first sample of the history, next output
@@ -339,49 +339,25 @@ StreamResampler::StreamResampler(int sr_in, int sr_out, int max_batch, int max_p
     SE_CHECK(pass_ || plan_.index_step > 0, "se_resampler_create: sr_out / sr_in below the table's resolution");
     SE_HIP(hipGetDevice(&dev_));
     if (pass_) return;
-    try {
-        const long hist = 2L * plan_.reach;
-        pitch_ = (hist + 3) / 4 * 4;
-        SE_CHECK((double)max_batch * (double)pitch_ < 1e9, "se_resampler_create: max_batch too large");
-        for (auto& h : hist_) SE_HIP(hipMalloc(&h, sizeof(float) * (size_t)max_batch * pitch_));
-        std::vector<double> w = build_window();
-        if (plan_.ratio < 1.0)
-            for (auto& v : w) v *= plan_.ratio;                         // interp_win *= sample_ratio
-        SE_HIP(hipMalloc(&win_, RS_NWIN * sizeof(double)));
-        SE_HIP(hipMemcpy(win_, w.data(), RS_NWIN * sizeof(double), hipMemcpyHostToDevice));
-        ring_cap_ = (long)std::ceil((double)std::max(max_push, plan_.reach + 1) * plan_.ratio) + 2;
-        if (!plan_.exact) {
-            SE_HIP(hipHostMalloc(reinterpret_cast<void**>(&ring_host_), sizeof(double) * ring_cap_ * RING, hipHostMallocDefault));
-            SE_HIP(hipMalloc(&ring_dev_, sizeof(double) * ring_cap_ * RING));
-            for (auto& ev : ring_ev_) SE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        }
-        SE_HIP(hipEventCreateWithFlags(&ev_order_, hipEventDisableTiming));
-    } catch (...) {
-        release();
-        throw;
+    const long hist = 2L * plan_.reach;
+    pitch_ = (hist + 3) / 4 * 4;
+    SE_CHECK((double)max_batch * (double)pitch_ < 1e9, "se_resampler_create: max_batch too large");
+    for (auto& h : hist_) h.alloc((size_t)max_batch * pitch_);
+    std::vector<double> w = build_window();
+    if (plan_.ratio < 1.0)
+        for (auto& v : w) v *= plan_.ratio;                         // interp_win *= sample_ratio
+    win_.alloc(RS_NWIN);
+    SE_HIP(hipMemcpy(win_.get(), w.data(), RS_NWIN * sizeof(double), hipMemcpyHostToDevice));
+    ring_cap_ = (long)std::ceil((double)std::max(max_push, plan_.reach + 1) * plan_.ratio) + 2;
+    if (!plan_.exact) {
+        ring_host_.alloc((size_t)ring_cap_ * RING);
+        ring_dev_.alloc((size_t)ring_cap_ * RING);
     }
-}
-
-void StreamResampler::release() {
-    for (auto& h : hist_) {
-        if (h) (void)hipFree(h);
-        h = nullptr;
-    }
-    if (win_) (void)hipFree(win_);
-    if (ring_host_) (void)hipHostFree(ring_host_);
-    if (ring_dev_) (void)hipFree(ring_dev_);
-    for (auto& ev : ring_ev_) {
-        if (ev) (void)hipEventDestroy(ev);
-        ev = nullptr;
-    }
-    if (ev_order_) (void)hipEventDestroy(ev_order_);
-    win_ = ring_host_ = ring_dev_ = nullptr;
-    ev_order_ = nullptr;
 }
 
 // a call on ANOTHER hipStream than the last one re-uses the history buffers: it is ordered behind the work in flight there
 void StreamResampler::order_behind_last(hipStream_t s) {
-    if (has_last_ && last_st_ != s) SE_HIP(hipStreamWaitEvent(s, ev_order_, 0));
+    if (has_last_ && last_st_ != s) SE_HIP(hipStreamWaitEvent(s, ev_order_.get(), 0));
 }
 
 void StreamResampler::begin(int batch, hipStream_t s) {
@@ -402,22 +378,22 @@ void StreamResampler::begin(int batch, hipStream_t s) {
 const double* StreamResampler::upload_positions(ResamplePos& pos, int64_t n_in, int64_t t_end, int64_t count, hipStream_t s) {
     const int slot = ring_next_;
     ring_next_ = (slot + 1) % RING;
-    SE_HIP(hipEventSynchronize(ring_ev_[slot]));      // the copy that last used this slot has run (no-op when unused)
-    double* h = ring_host_ + (size_t)slot * ring_cap_;
-    double* d = ring_dev_ + (size_t)slot * ring_cap_;
+    SE_HIP(hipEventSynchronize(ring_ev_[slot].get()));      // the copy that last used this slot has run (no-op when unused)
+    double* h = ring_host_.get() + (size_t)slot * ring_cap_;
+    double* d = ring_dev_.get() + (size_t)slot * ring_cap_;
     const int64_t k = resample_advance(plan_, pos, n_in, t_end, h, count);
     SE_CHECK(k == count, "resampler: position count changed between two walks");
     SE_HIP(hipMemcpyAsync(d, h, sizeof(double) * count, hipMemcpyHostToDevice, s));
-    SE_HIP(hipEventRecord(ring_ev_[slot], s));
+    SE_HIP(hipEventRecord(ring_ev_[slot].get(), s));
     return d;
 }
 
 void StreamResampler::launch(const float* in, long in_pitch, float* out, long out_pitch, int n_total, int w0_next, int t0,
                              int n_calc, int n_emit, const double* treg, hipStream_t s) {
     ResampleStreamArgs a{};
-    a.hist = hist_[cur_]; a.hist_next = hist_[cur_ ^ 1]; a.hist_pitch = pitch_;
+    a.hist = hist_[cur_].get(); a.hist_next = hist_[cur_ ^ 1].get(); a.hist_pitch = pitch_;
     a.in = in; a.in_pitch = in_pitch; a.y = out; a.out_pitch = out_pitch;
-    a.win = win_; a.treg = treg; a.inc = plan_.inc; a.scale = plan_.scale; a.index_step = plan_.index_step;
+    a.win = win_.get(); a.treg = treg; a.inc = plan_.inc; a.scale = plan_.scale; a.index_step = plan_.index_step;
     a.w0 = w0_; a.split = (int)n_total_; a.n_total = n_total; a.w0_next = w0_next;
     a.t0 = t0; a.n_calc = n_calc; a.n_emit = n_emit;
     a.out_blocks = (n_emit + RS_STREAM_BLOCK - 1) / RS_STREAM_BLOCK;
@@ -464,7 +440,7 @@ int StreamResampler::push(const float* in, long in_pitch, int n_new, float* out,
     }
     const int w0_next = (int)std::max<int64_t>(0, n_after - 2L * plan_.reach);
     launch(in, in_pitch, out, out_pitch, (int)n_after, w0_next, (int)pos_.t, (int)count, (int)count, treg, s);
-    SE_HIP(hipEventRecord(ev_order_, s));
+    SE_HIP(hipEventRecord(ev_order_.get(), s));
     has_last_ = true;
     last_st_ = s;
     cur_ ^= 1;
@@ -500,7 +476,7 @@ int StreamResampler::flush(float* out, long out_pitch, hipStream_t s) {
     }
     // the right wing is clamped by n_total_, now the final length; no history is written (w0_next = n_total_)
     launch(nullptr, 0, out, out_pitch, (int)n_total_, (int)n_total_, (int)pos_.t, (int)n_calc, (int)n_emit, treg, s);
-    SE_HIP(hipEventRecord(ev_order_, s));
+    SE_HIP(hipEventRecord(ev_order_.get(), s));
     has_last_ = true;
     last_st_ = s;
     active_ = false;

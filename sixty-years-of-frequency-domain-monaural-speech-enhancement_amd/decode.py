@@ -176,6 +176,12 @@ def _rank_world(rank, world):
     return int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
 
 
+def _write_clip(path, samples_i16, fs):
+    """One clip's int16 samples as a PCM_16 WAV file, header and samples in a single unbuffered write."""
+    with open(path, 'wb', buffering=0) as f:
+        f.write(wavio.wav_header_pcm16(2 * len(samples_i16), fs) + samples_i16.tobytes())
+
+
 class _Slot:
     """One stage of the pipeline's ring: pinned host + device staging for a call's input and output.  The buffers are flat;
     a call of nb rows x n samples uses the first nb * n elements as a dense [nb, n] matrix, so every host <-> device
@@ -383,8 +389,7 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
                 t0 = time.perf_counter()
                 for r, i in enumerate(b):
                     n = eng.output_samples(lengths[i])
-                    with open(os.path.join(out_dir, files[i]), 'wb', buffering=0) as f:
-                        f.write(wavio.wav_header_pcm16(2 * n, args.fs) + sl.h_q_np[r * n_out:r * n_out + n].tobytes())
+                    _write_clip(os.path.join(out_dir, files[i]), sl.h_q_np[r * n_out:r * n_out + n], args.fs)
                     cnt[0] += 1
                     if verbose:
                         print(' The %d utterance has been decoded!' % cnt[0])
@@ -472,9 +477,7 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
         _check(lib.se_pcm16_encode(C.c_void_p(out.data_ptr()), n, nb, n, C.c_void_p(q.data_ptr()), n, st))
         q = q.cpu().numpy()
         for r, i in enumerate(grp):
-            ni = eng.output_samples(lengths[i])
-            with open(os.path.join(out_dir, files[i]), 'wb', buffering=0) as f:
-                f.write(wavio.wav_header_pcm16(2 * ni, args.fs) + q[r, :ni].tobytes())
+            _write_clip(os.path.join(out_dir, files[i]), q[r, :eng.output_samples(lengths[i])], args.fs)
             cnt[0] += 1
             if verbose:
                 print(' The %d utterance has been decoded!' % cnt[0])

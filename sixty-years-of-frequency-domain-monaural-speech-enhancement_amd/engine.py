@@ -123,75 +123,63 @@ class Engine:
     def num_bins(self):
         return int(self._lib.se_num_bins(self._h))
 
-    def enhance_batch(self, wav, out=None):
-        """wav [B, L] float32 cuda tensor -> [B, output_samples(L)]."""
+    def _rows_call(self, what, wav, lengths, out, window=None):
+        """The body of the four enhance_* wrappers: se_<what> on the rows of wav, all of wav.shape[1] samples (lengths None) or
+        of `lengths`.  window: max_chunk_frames of the two windowed decodes, which also refuse a row count outside the engine's
+        and rows that overlap before the library sees them."""
         import torch
-        self._check_tensor(wav, 'enhance_batch input', 2)
-        B, L = wav.shape
-        n_out = self.output_samples(L)
+        self._check_tensor(wav, f'{what} input', 2)
+        B, W = wav.shape
+        if window is not None and (B < 1 or B > self.max_batch):
+            raise EngineError(f"{what} input: {B} rows outside 1..max_batch ({self.max_batch})")
+        width = W
+        if lengths is not None:
+            lengths = [int(n) for n in lengths]
+            if window is None:
+                if len(lengths) != B or max(lengths) > W:
+                    raise EngineError(f"{what}: {len(lengths)} lengths (max {max(lengths)}) for a {tuple(wav.shape)} batch")
+            elif len(lengths) != B:
+                raise EngineError(f"{what}: {len(lengths)} lengths for a batch of {B} rows")
+            elif min(lengths) < 1 or max(lengths) > W:
+                raise EngineError(f"{what}: lengths {min(lengths)}..{max(lengths)} outside rows of {W} samples")
+            width = max(lengths)
+        if window is not None:
+            if B > 1 and wav.stride(0) < width:
+                raise EngineError(f"{what} input: rows of {width} samples overlap (strides {wav.stride()})")
+            window = int(window)
+            if window < 0:
+                raise EngineError(f"{what}: max_chunk_frames {window} is negative (0 = the largest window)")
+        n_out = self.output_samples(width)
         if out is None:
             out = torch.empty((B, n_out), dtype=torch.float32, device=wav.device)
         else:
-            self._check_tensor(out, 'enhance_batch output', 2)
+            self._check_tensor(out, f'{what} output', 2)
             if out.shape[0] != B or out.shape[1] < n_out:
-                raise EngineError(f"enhance_batch output: need [{B}, >= {n_out}], got {tuple(out.shape)}")
-        # the stride of a size-1 dimension is arbitrary in torch / numpy: a single row has pitch L
-        in_pitch = wav.stride(0) if B > 1 else L
-        out_pitch = out.stride(0) if B > 1 else n_out
-        self._check(self._lib.se_enhance_batch(self._h, C.c_void_p(wav.data_ptr()), in_pitch, B, L,
-                                               C.c_void_p(out.data_ptr()), out_pitch, self._stream()))
+                raise EngineError(f"{what} output: need [{B}, >= {n_out}], got {tuple(out.shape)}")
+        # the stride of a size-1 dimension is arbitrary in torch / numpy: a single row's pitch is its width (of equal rows: the
+        # samples decoded, of ragged rows: the tensor's)
+        in_pitch = wav.stride(0) if B > 1 else W
+        out_pitch = out.stride(0) if B > 1 else n_out if lengths is None else out.shape[1]
+        n = (width if lengths is None else (C.c_int32 * B)(*lengths),) + (() if window is None else (window,))
+        self._check(getattr(self._lib, 'se_' + what)(self._h, C.c_void_p(wav.data_ptr()), in_pitch, B, *n,
+                                                     C.c_void_p(out.data_ptr()), out_pitch, self._stream()))
         return out
+
+    def enhance_batch(self, wav, out=None):
+        """wav [B, L] float32 cuda tensor -> [B, output_samples(L)]."""
+        return self._rows_call('enhance_batch', wav, None, out)
 
     def enhance_ragged(self, wav, lengths, out=None):
         """wav [B, >= max(lengths)] float32 cuda tensor, lengths: B sample counts (host ints) ->
         [B, output_samples(max(lengths))]; row b holds output_samples(lengths[b]) samples, then zeros."""
-        import torch
-        self._check_tensor(wav, 'enhance_ragged input', 2)
-        B = wav.shape[0]
-        lengths = [int(n) for n in lengths]
-        if len(lengths) != B or max(lengths) > wav.shape[1]:
-            raise EngineError(f"enhance_ragged: {len(lengths)} lengths (max {max(lengths)}) for a {tuple(wav.shape)} batch")
-        n_out = self.output_samples(max(lengths))
-        if out is None:
-            out = torch.empty((B, n_out), dtype=torch.float32, device=wav.device)
-        else:
-            self._check_tensor(out, 'enhance_ragged output', 2)
-            if out.shape[0] != B or out.shape[1] < n_out:
-                raise EngineError(f"enhance_ragged output: need [{B}, >= {n_out}], got {tuple(out.shape)}")
-        in_pitch = wav.stride(0) if B > 1 else wav.shape[1]
-        out_pitch = out.stride(0) if B > 1 else out.shape[1]
-        arr = (C.c_int32 * B)(*lengths)
-        self._check(self._lib.se_enhance_ragged(self._h, C.c_void_p(wav.data_ptr()), in_pitch, B, arr,
-                                                C.c_void_p(out.data_ptr()), out_pitch, self._stream()))
-        return out
+        return self._rows_call('enhance_ragged', wav, lengths, out)
 
     def enhance_long(self, wav, out=None, max_chunk_frames=0):
         """wav [B, L] float32 cuda tensor, L of any length (max_samples does not bound it) -> [B, output_samples(L)]: the offline
         decode of the whole clips, run in windows of max_chunk_frames frames (0 = the largest the workspace holds) with the
         network state carried from window to window (se_enhance_long).  Models that stream only; ends a stream running on
         this engine."""
-        import torch
-        self._check_tensor(wav, 'enhance_long input', 2)
-        B, L = wav.shape
-        if B < 1 or B > self.max_batch:
-            raise EngineError(f"enhance_long input: {B} rows outside 1..max_batch ({self.max_batch})")
-        if B > 1 and wav.stride(0) < L:
-            raise EngineError(f"enhance_long input: rows of {L} samples overlap (strides {wav.stride()})")
-        max_chunk_frames = int(max_chunk_frames)
-        if max_chunk_frames < 0:
-            raise EngineError(f"enhance_long: max_chunk_frames {max_chunk_frames} is negative (0 = the largest window)")
-        n_out = self.output_samples(L)
-        if out is None:
-            out = torch.empty((B, n_out), dtype=torch.float32, device=wav.device)
-        else:
-            self._check_tensor(out, 'enhance_long output', 2)
-            if out.shape[0] != B or out.shape[1] < n_out:
-                raise EngineError(f"enhance_long output: need [{B}, >= {n_out}], got {tuple(out.shape)}")
-        in_pitch = wav.stride(0) if B > 1 else L
-        out_pitch = out.stride(0) if B > 1 else n_out
-        self._check(self._lib.se_enhance_long(self._h, C.c_void_p(wav.data_ptr()), in_pitch, B, L, max_chunk_frames,
-                                              C.c_void_p(out.data_ptr()), out_pitch, self._stream()))
-        return out
+        return self._rows_call('enhance_long', wav, None, out, max_chunk_frames)
 
     def enhance_long_ragged(self, wav, lengths, max_chunk_frames=0, out=None):
         """wav [B, >= max(lengths)] float32 cuda tensor, lengths: B sample counts (host ints, each of any length from n_fft on) ->
@@ -199,34 +187,7 @@ class Engine:
         scale, right edge and frame count - in ONE walk over the windows of the longest row (se_enhance_long_ragged).  Row b
         holds output_samples(lengths[b]) samples, then zeros; nothing past lengths[b] is read.  Models that stream only; ends a
         stream running on this engine."""
-        import torch
-        self._check_tensor(wav, 'enhance_long_ragged input', 2)
-        B, W = wav.shape
-        if B < 1 or B > self.max_batch:
-            raise EngineError(f"enhance_long_ragged input: {B} rows outside 1..max_batch ({self.max_batch})")
-        lengths = [int(n) for n in lengths]
-        if len(lengths) != B:
-            raise EngineError(f"enhance_long_ragged: {len(lengths)} lengths for a batch of {B} rows")
-        if min(lengths) < 1 or max(lengths) > W:
-            raise EngineError(f"enhance_long_ragged: lengths {min(lengths)}..{max(lengths)} outside rows of {W} samples")
-        if B > 1 and wav.stride(0) < max(lengths):
-            raise EngineError(f"enhance_long_ragged input: rows of {max(lengths)} samples overlap (strides {wav.stride()})")
-        max_chunk_frames = int(max_chunk_frames)
-        if max_chunk_frames < 0:
-            raise EngineError(f"enhance_long_ragged: max_chunk_frames {max_chunk_frames} is negative (0 = the largest window)")
-        n_out = self.output_samples(max(lengths))
-        if out is None:
-            out = torch.empty((B, n_out), dtype=torch.float32, device=wav.device)
-        else:
-            self._check_tensor(out, 'enhance_long_ragged output', 2)
-            if out.shape[0] != B or out.shape[1] < n_out:
-                raise EngineError(f"enhance_long_ragged output: need [{B}, >= {n_out}], got {tuple(out.shape)}")
-        in_pitch = wav.stride(0) if B > 1 else W
-        out_pitch = out.stride(0) if B > 1 else out.shape[1]
-        arr = (C.c_int32 * B)(*lengths)
-        self._check(self._lib.se_enhance_long_ragged(self._h, C.c_void_p(wav.data_ptr()), in_pitch, B, arr, max_chunk_frames,
-                                                     C.c_void_p(out.data_ptr()), out_pitch, self._stream()))
-        return out
+        return self._rows_call('enhance_long_ragged', wav, lengths, out, max_chunk_frames)
 
     # ------------------------------------------------------------------ frame-online decoding
     def stream_begin(self, batch, c=None, max_chunk_frames=16, running_rms=False):
