@@ -206,6 +206,56 @@ int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_
                    int32_t* n_out, void* stream);
 int se_stream_flush(se_engine* e, float* out_dev, int64_t out_pitch, int32_t* n_out, void* stream);
 
+/* Parking a frame-online stream and putting it back.  A handle carries ONE stream group; se_stream_begin for another group, and
+ * se_enhance_long / se_enhance_long_ragged, end it for good.  se_stream_save copies everything the next se_stream_push or
+ * se_stream_flush of the running stream reads into a library-owned object; se_stream_restore makes a saved stream the running
+ * stream of a handle again, replacing whatever ran there as se_stream_begin does.  One engine can so serve more callers than
+ * max_batch, or groups that began at different times, by turns: restore -> push -> save per group.
+ *   CONTRACT: take any stream and any point between two calls on it - before its first frame is complete, after its last push.
+ *   Save it.  Let anything else happen on the engine: other streams, offline decodes, se_enhance_long, nothing at all.  Restore
+ *   it there, or on another engine of the same configuration and weights.  The outputs of every later se_stream_push and of
+ *   se_stream_flush then equal those of the uninterrupted stream bit for bit, *n_out included.
+ * The object holds a host record (the manifest: the engine's identity, the stream's counters, the size of every carried buffer)
+ * and one device payload: the conv history, LSTM (h, c) and call-order state slots of the model, the scale(s) - under a running
+ * scale also the sum of squares and the per-frame ring -, and the input samples a later frame or the flush's right-edge
+ * reflection can still reach, rows back to back (less than n_fft + hop + 4 per row), so they find their place in an engine with
+ * another max_samples.  The workspace is not part of it: the first window after a restore is zero-filled as after any decode.
+ *   se_stream_state_create : an empty object; touches no device.  se_stream_state_destroy releases it (NULL: nothing).
+ *   se_stream_state_bytes  : device memory of the payload (its window part sized for the most a stream keeps live, so the
+ *                            figure does not move from save to save; of an imported image not restored yet: its payload); 0 = empty.
+ *   se_stream_save   : needs a running stream on e ("... without se_stream_begin" otherwise); does not end or alter it.  One
+ *                      kernel, enqueued on `stream`, ordered against the handle's last stream call as the entry points above.
+ *                      The first save of a layout (model, batch, chunk size, slot set) allocates; saving again into an object
+ *                      that holds the same layout allocates nothing and waits for nothing.
+ *   se_stream_restore: e must be finalized, on the device the payload lives on, and match the engine the stream was saved on in:
+ *                      model id; every se_config.flags bit except SE_CFG_GRAPHS and SE_CFG_STREAM_SLIDING; n_fft / hop / win;
+ *                      p_in / p_out.  Further: max_batch >= the snapshot's batch; a workspace planned for its max_chunk_frames;
+ *                      without SE_CFG_STREAM_SLIDING max_samples >= the samples the stream has received, with it a window that
+ *                      holds the saved live samples; for a running-scale stream a per-frame ring no longer than the snapshot's
+ *                      (an engine planned for a larger max_samples may need a longer one).  Each mismatch is refused with its own
+ *                      reason.  WEIGHTS ARE NOT COMPARED: the same weights on both engines are the caller's duty (weights of other
+ *                      SHAPES are noticed - the state buffers differ in size - but only after the handle's stream has ended).
+ *                      The same object may be restored any number of times and on more than one engine: that forks a stream.  An
+ *                      engine that has not streamed yet gets its state buffers made here, the cLN networks' slots in the recorded
+ *                      order and sizes; one that already holds the layout is copied into, one kernel and no allocation.
+ *   se_stream_state_export / _import: the object as one byte string in HOST memory, for another device or process.  Synchronous:
+ *                      the image is complete on return.  export with cap == 0 returns the size needed, else the size written
+ *                      (-1: error - an empty object, a buffer too small).  import parses and validates the manifest and keeps the
+ *                      bytes on the host - it runs, and refuses, without a GPU; the upload happens at the first restore, on that
+ *                      engine's device.  It refuses a wrong magic or version, an image cut short, a segment table whose sizes do
+ *                      not add up to the recorded payload, negative or overflowing sizes, and trailing bytes.
+ * Errors of the calls that take an engine are read through that engine's se_last_error, of the others through se_last_error(NULL).
+ * A refused call changes nothing: neither the object nor a stream running on the engine.  An object is not thread-safe, and like
+ * a handle it orders calls made on different hipStreams behind one another. */
+typedef struct se_stream_state se_stream_state;
+int se_stream_state_create(se_stream_state** out);
+int se_stream_state_destroy(se_stream_state* s);
+int64_t se_stream_state_bytes(const se_stream_state* s);
+int se_stream_save(se_engine* e, se_stream_state* s, void* stream);
+int se_stream_restore(se_engine* e, const se_stream_state* s, void* stream);
+int64_t se_stream_state_export(const se_stream_state* s, void* host_buf, int64_t cap);
+int se_stream_state_import(se_stream_state* s, const void* host_buf, int64_t bytes);
+
 /* se_enhance_batch for clips LONGER than max_samples (any length; shorter ones take the same path): `batch` equal-length clips
  * resident on the device, decoded in windows of max_chunk_frames frames through the frame-online machinery above - conv history,
  * TCM rings, LSTM (h, c) and the running norm sums carried from window to window - under the WHOLE clip's unit-RMS scale, so
@@ -352,7 +402,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise) */
 
 #ifdef __cplusplus
 }

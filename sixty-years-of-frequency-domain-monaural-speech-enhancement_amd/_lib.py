@@ -21,7 +21,8 @@ SYMBOLS = [
     'se_resample_samples', 'se_enhance_ragged', 'se_get_stage_profile', 'se_stream_begin', 'se_stream_begin_running', 'se_stream_push', 'se_stream_flush',
     'se_uformer_forward', 'se_pcm16_decode', 'se_pcm16_encode', 'se_frontend', 'se_backend', 'se_enhance_long',
     'se_enhance_long_ragged', 'se_resampler_create', 'se_resampler_destroy', 'se_resampler_begin', 'se_resampler_push',
-    'se_resampler_flush', 'se_resampler_ready_samples',
+    'se_resampler_flush', 'se_resampler_ready_samples', 'se_stream_state_create', 'se_stream_state_destroy',
+    'se_stream_state_bytes', 'se_stream_save', 'se_stream_restore', 'se_stream_state_export', 'se_stream_state_import',
 ]
 
 
@@ -96,5 +97,14 @@ def load():
     lib.se_resampler_flush.argtypes = [vp, vp, i64, C.POINTER(i32), vp]
     lib.se_resampler_ready_samples.restype = i64
     lib.se_resampler_ready_samples.argtypes = [i64, i32, i32]
+    lib.se_stream_state_create.argtypes = [C.POINTER(vp)]
+    lib.se_stream_state_destroy.argtypes = [vp]
+    lib.se_stream_state_bytes.restype = i64
+    lib.se_stream_state_bytes.argtypes = [vp]
+    lib.se_stream_save.argtypes = [vp, vp, vp]
+    lib.se_stream_restore.argtypes = [vp, vp, vp]
+    lib.se_stream_state_export.restype = i64
+    lib.se_stream_state_export.argtypes = [vp, vp, i64]
+    lib.se_stream_state_import.argtypes = [vp, vp, i64]
     _lib = lib
     return lib

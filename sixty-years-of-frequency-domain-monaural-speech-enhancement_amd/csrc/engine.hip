@@ -3,6 +3,8 @@
 #include "hip_owned.h"
 #include "model.h"
 #include "resampler.h"
+#include "rnn.h"
+#include "stream_manifest.h"
 #include "stream_window.h"
 #include "window_rows.h"
 #include <algorithm>
@@ -997,6 +999,481 @@ int se_get_stage_profile(se_engine* e, int32_t stage, double* ms, int64_t* launc
         if (ms) *ms = e->ctx.stage_prof.ms(stage);
         if (launches) *launches = e->ctx.stage_prof.slot[stage].launches;
         if (bytes) *bytes = e->ctx.stage_prof.slot[stage].bytes;
+    });
+}
+
+// ---- se_stream_save / se_stream_restore: a running stream parked in an object of its own and put back -----------------------
+// The object: the manifest (stream_manifest.h, host) + one device payload, every carried buffer at a 16 B aligned offset, the input
+// window last.  The payload is sized when a layout is first seen - its window part for the most a stream keeps live between two
+// calls - so saving again into the same object allocates nothing.  The two device tables (engine -> payload, payload -> engine) of
+// the copy kernel (k_stream_state.hip) are rebuilt on the host at every call, which is a few hundred assignments, and uploaded only
+// when they differ from the last upload: through a pinned buffer, so that the call waits for nothing either.
+}  // extern "C"
+
+struct se_stream_state {
+    SnapManifest man;
+    bool filled = false;
+    int device = -1;                      // the device the payload, the tables and the event live on
+    bool dev_valid = false;               // dev holds the payload of `man` (false after an import, until the first restore)
+    std::vector<SnapSeg> dev_layout;      // the segments in front of the window `dev` was laid out for
+    int64_t dev_fixed = 0, dev_win_cap = 0;
+    std::vector<uint8_t> host;            // payload of an imported image (kept: another device may restore it too)
+    struct Table {
+        DevBuf<StateSeg> dev;
+        PinnedBuf<StateSeg> pin;
+        size_t cap = 0;
+        std::vector<StateSeg> last;
+        Event ev;                         // behind the last upload: the pinned buffer is free again
+    };
+    struct Side {                         // what belongs to one device (an imported image may be restored on several, one after the other)
+        DevBuf<uint8_t> dev;
+        Table tab[2];                     // 0: save, 1: restore
+        Event ev_use;
+    };
+    std::unique_ptr<Side> side{new Side()};
+    // the hipStream the object was last used on: a call on another one is ordered behind it
+    bool has_use = false;
+    hipStream_t use_st = nullptr;
+};
+
+namespace {
+
+struct DeviceScope {      // a call on the object alone: its device is current while the call runs
+    int prev = -1;
+    explicit DeviceScope(int dev) {
+        if (dev < 0) return;
+        int cur = -1;
+        SE_HIP(hipGetDevice(&cur));
+        if (cur != dev) {
+            SE_HIP(hipSetDevice(dev));
+            prev = cur;
+        }
+    }
+    ~DeviceScope() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+struct EngSeg {
+    SnapSeg seg;
+    void* ptr;
+};
+
+// every buffer chunk k of the stream writes and chunk k + 1 reads, except the input window, in payload order
+std::vector<EngSeg> engine_segments(se_engine* e, int batch, bool running, int ring) {
+    se_engine::Stream& S = e->strm;
+    std::vector<EngSeg> v;
+    auto add = [&](int32_t kind, int32_t index, void* p, int64_t bytes) {
+        EngSeg s;
+        s.seg.kind = kind;
+        s.seg.index = index;
+        s.seg.bytes = bytes;
+        s.ptr = p;
+        v.push_back(s);
+    };
+    add(SNAP_C, 0, S.c.get(), (int64_t)batch * sizeof(float));
+    if (running) {
+        add(SNAP_SUMSQ, 0, S.sumsq.get(), (int64_t)batch * sizeof(double));
+        add(SNAP_FRAME_INV, 0, S.frame_inv.get(), (int64_t)batch * ring * sizeof(float));
+    }
+    if (StreamState* ss = e->model->stream_state()) {
+        for (size_t i = 0; i < ss->hist.size(); ++i) add(SNAP_HIST, (int32_t)i, ss->hist[i], (int64_t)ss->size_of.at(ss->hist[i]) * sizeof(float));
+        for (int l = 0; l < 4; ++l) {
+            if (ss->h[l]) add(SNAP_H, l, ss->h[l], (int64_t)ss->size_of.at(ss->h[l]) * sizeof(float));
+            if (ss->c[l]) add(SNAP_CELL, l, ss->c[l], (int64_t)ss->size_of.at(ss->c[l]) * sizeof(float));
+        }
+    }
+    if (StreamSlots* sl = e->model->stream_slots())
+        for (size_t i = 0; i < sl->v.size(); ++i) add(SNAP_SLOT, (int32_t)i, sl->v[i].first, (int64_t)sl->v[i].second);
+    return v;
+}
+
+bool same_segs(const std::vector<EngSeg>& a, const std::vector<SnapSeg>& b, size_t nb) {
+    if (a.size() != nb) return false;
+    for (size_t i = 0; i < nb; ++i)
+        if (a[i].seg.kind != b[i].kind || a[i].seg.index != b[i].index || a[i].seg.bytes != b[i].bytes) return false;
+    return true;
+}
+bool same_layout(const std::vector<SnapSeg>& a, const std::vector<SnapSeg>& b, size_t nb) {
+    if (a.size() != nb) return false;
+    for (size_t i = 0; i < nb; ++i)
+        if (a[i].kind != b[i].kind || a[i].index != b[i].index || a[i].bytes != b[i].bytes) return false;
+    return true;
+}
+
+// the most input samples a stream keeps live between two calls: every frame whose samples have all arrived is transformed before
+// a push returns, so what a later frame or the flush's reflection still reads is less than a window and a hop (stream_window.h)
+int snap_window_cap(const StftGeom& g) { return (g.n_fft + g.hop + 3 + 3) & ~3; }
+
+int64_t fixed_bytes_of(const SnapManifest& m) {
+    int64_t n = 0;
+    for (const SnapSeg& s : m.segs)
+        if (s.kind != SNAP_WINDOW) n += snap_align16(s.bytes);
+    return n;
+}
+size_t fixed_count_of(const SnapManifest& m) {
+    return m.segs.empty() || m.segs.back().kind != SNAP_WINDOW ? m.segs.size() : m.segs.size() - 1;
+}
+
+void obj_wait(se_stream_state* s, hipStream_t st) {
+    if (s->has_use && s->use_st != st) SE_HIP(hipStreamWaitEvent(st, s->side->ev_use.get(), 0));
+}
+void obj_mark(se_stream_state* s, hipStream_t st) {
+    SE_HIP(hipEventRecord(s->side->ev_use.get(), st));
+    s->has_use = true;
+    s->use_st = st;
+}
+
+// a payload buffer on the current device for the layout of m (window part: at least win_cap bytes); the old contents are dropped
+void payload_alloc(se_stream_state* s, const SnapManifest& m, int64_t win_cap, int device) {
+    const size_t nfix = fixed_count_of(m);
+    const int64_t fixed = fixed_bytes_of(m);
+    if (s->side->dev && s->device == device && same_layout(s->dev_layout, m.segs, nfix) && s->dev_win_cap >= win_cap) return;
+    if (s->side->dev && s->device != device) {          // (payload, tables and event of another device go with that device current)
+        DeviceScope ds(s->device);
+        s->side.reset();
+        s->has_use = false;
+    }
+    if (!s->side) s->side.reset(new se_stream_state::Side());
+    DevBuf<uint8_t> fresh;
+    fresh.alloc((size_t)(fixed + win_cap + 16));
+    s->side->dev = std::move(fresh);
+    s->device = device;
+    s->dev_layout.assign(m.segs.begin(), m.segs.begin() + (long)nfix);
+    s->dev_fixed = fixed;
+    s->dev_win_cap = win_cap;
+    s->dev_valid = false;
+}
+
+// engine-side segments against payload offsets -> the device table of direction dir (0: engine -> payload); uploaded when it changed
+const StateSeg* table_for(se_stream_state* s, int dir, const std::vector<EngSeg>& eng, float* wav, int batch, long* fix_tiles,
+                          hipStream_t st) {
+    std::vector<StateSeg> v(eng.size() + 1);
+    long tiles = 0;
+    int64_t off = 0;
+    for (size_t i = 0; i <= eng.size(); ++i) {
+        StateSeg sg{};
+        float* pay = reinterpret_cast<float*>(s->side->dev.get() + (i < eng.size() ? off : s->dev_fixed));
+        float* own = i < eng.size() ? static_cast<float*>(eng[i].ptr) : wav;
+        sg.src = dir == 0 ? own : pay;
+        sg.dst = dir == 0 ? pay : own;
+        if (i < eng.size()) {
+            SE_CHECK(eng[i].seg.bytes / 4 < INT_MAX, "stream state: segment too large");
+            sg.rows = 1;
+            sg.len = (int)(eng[i].seg.bytes / 4);
+            sg.tile0 = (int)tiles;
+            tiles += state_seg_tiles(1, sg.len);
+            SE_CHECK(tiles < INT_MAX, "stream state: too many tiles");
+            off += snap_align16(eng[i].seg.bytes);
+        } else {
+            sg.rows = batch;          // the window: extent from the call
+            sg.tile0 = (int)tiles;
+        }
+        v[i] = sg;
+    }
+    *fix_tiles = tiles;
+    auto& T = s->side->tab[dir];
+    if (T.dev && T.last.size() == v.size() && std::memcmp(T.last.data(), v.data(), v.size() * sizeof(StateSeg)) == 0) return T.dev.get();
+    SE_HIP(hipEventSynchronize(T.ev.get()));
+    if (v.size() > T.cap) {
+        // (room for the slots a stream of the cLN networks creates on its first chunk: the table of a group that has not produced a
+        // frame yet is a handful of rows, the next one well over a hundred)
+        const size_t cap = std::max<size_t>(v.size() + 64, 512);
+        T.last.clear();
+        T.dev.alloc(cap);
+        T.pin.alloc(cap);
+        T.cap = cap;
+    }
+    std::memcpy(T.pin.get(), v.data(), v.size() * sizeof(StateSeg));
+    SE_HIP(hipMemcpyAsync(T.dev.get(), T.pin.get(), v.size() * sizeof(StateSeg), hipMemcpyHostToDevice, st));
+    SE_HIP(hipEventRecord(T.ev.get(), st));
+    T.last = v;
+    return T.dev.get();
+}
+
+std::string hex(int v) {
+    char b[16];
+    snprintf(b, sizeof b, "0x%x", (unsigned)v);
+    return b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int se_stream_state_create(se_stream_state** out) {
+    return guard(nullptr, [&] {
+        SE_CHECK(out, "se_stream_state_create: null argument");
+        *out = new se_stream_state();
+    });
+}
+
+int se_stream_state_destroy(se_stream_state* s) {
+    if (!s) return 0;
+    return guard(nullptr, [&] {
+        std::unique_ptr<se_stream_state> own(s);
+        if (s->device >= 0) {
+            DeviceScope ds(s->device);
+            if (s->has_use) (void)hipEventSynchronize(s->side->ev_use.get());
+            own.reset();
+        }
+    });
+}
+
+int64_t se_stream_state_bytes(const se_stream_state* s) {
+    if (!s || !s->filled) return 0;
+    return s->side->dev ? s->dev_fixed + s->dev_win_cap : snap_payload_bytes(s->man);
+}
+
+int se_stream_save(se_engine* e, se_stream_state* s, void* stream) {
+    if (!e) return 1;
+    return guard(e, [&] {
+        SE_CHECK(s, "se_stream_save: null argument");
+        se_engine::Stream& S = e->strm;
+        SE_CHECK(S.active, "se_stream_save without se_stream_begin");
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const StftGeom& g = e->ctx.geom;
+        SnapManifest m;
+        m.model = e->cfg.model;
+        m.flags = e->cfg.flags;
+        m.n_fft = g.n_fft;
+        m.hop = g.hop;
+        m.win = g.win;
+        m.p_in = e->ctx.p_in;
+        m.p_out = e->ctx.p_out;
+        m.batch = S.batch;
+        m.max_chunk = S.max_chunk;
+        m.n_total = S.n_total;
+        m.t_done = S.t_done;
+        m.o_done = S.o_done;
+        // only what a later launch can still read (stream_window.h): rows stored back to back, not at this engine's pitch
+        m.keep = std::max(S.w0, stream_keep_from(g.n_fft, g.hop, S.t_done, S.n_total));
+        m.running = S.running ? 1 : 0;
+        m.ring = S.running ? S.ring : 0;
+        const StreamState* ss = e->model->stream_state();
+        const StreamSlots* sl = e->model->stream_slots();
+        m.first = ss ? (ss->first ? 1 : 0) : 1;
+        m.state_B = ss ? ss->B : sl ? sl->B : 0;
+        const int live = m.n_total - m.keep;
+        const int wcap = snap_window_cap(g);
+        SE_CHECK(live >= 0 && live <= wcap, "se_stream_save: " + std::to_string(live) + " live input samples, more than a window and a hop");
+        const std::vector<EngSeg> eng = engine_segments(e, S.batch, S.running, S.ring);
+        for (const EngSeg& sg : eng) {
+            SE_CHECK(sg.ptr && sg.seg.bytes >= 0 && (sg.seg.bytes & 3) == 0, "se_stream_save: a carried buffer is missing or of an odd size");
+            m.segs.push_back(sg.seg);
+        }
+        SnapSeg wseg;
+        wseg.kind = SNAP_WINDOW;
+        wseg.bytes = (int64_t)S.batch * live * sizeof(float);
+        m.segs.push_back(wseg);
+        // nothing of the object or the stream has changed up to here
+        payload_alloc(s, m, (int64_t)S.batch * wcap * sizeof(float), e->cfg.device);
+        stream_order_wait(S, st);
+        obj_wait(s, st);
+        long fix_tiles = 0;
+        const StateSeg* tab = table_for(s, 0, eng, S.wav.get(), S.batch, &fix_tiles, st);
+        StateWindow w;
+        w.src_off = m.keep - S.w0;
+        w.src_pitch = S.pitch;
+        w.dst_pitch = live;
+        w.rows = S.batch;
+        w.len = live;
+        launch_stream_state_copy(tab, (int)eng.size(), fix_tiles, (int)eng.size(), w, st);
+        s->man = std::move(m);
+        s->filled = true;
+        s->dev_valid = true;
+        s->host.clear();
+        s->host.shrink_to_fit();
+        stream_mark(S, st);
+        obj_mark(s, st);
+    });
+}
+
+int se_stream_restore(se_engine* e, const se_stream_state* cs, void* stream) {
+    if (!e) return 1;
+    return guard(e, [&] {
+        se_stream_state* s = const_cast<se_stream_state*>(cs);      // (the tables and the uploaded payload are caches of the object)
+        SE_CHECK(s, "se_stream_restore: null argument");
+        SE_CHECK(e->finalized, "engine not finalized");
+        SE_CHECK(s->filled, "se_stream_restore: the stream state object is empty");
+        const SnapManifest& m = s->man;
+        const StftGeom& g = e->ctx.geom;
+        const std::string fn = "se_stream_restore: ";
+        SE_CHECK(m.model == e->cfg.model, fn + "the snapshot was taken on model id " + std::to_string(m.model) + ", this engine runs model id " +
+                                              std::to_string(e->cfg.model));
+        const int free_bits = SE_CFG_GRAPHS | SE_CFG_STREAM_SLIDING;
+        SE_CHECK(((m.flags ^ e->cfg.flags) & ~free_bits) == 0,
+                 fn + "se_config.flags differ (snapshot " + hex(m.flags) + ", engine " + hex(e->cfg.flags) +
+                     "; every bit except SE_CFG_GRAPHS and SE_CFG_STREAM_SLIDING has to match)");
+        SE_CHECK(m.n_fft == g.n_fft && m.hop == g.hop && m.win == g.win,
+                 fn + "front end differs (snapshot n_fft / hop / win " + std::to_string(m.n_fft) + " / " + std::to_string(m.hop) + " / " +
+                     std::to_string(m.win) + ", engine " + std::to_string(g.n_fft) + " / " + std::to_string(g.hop) + " / " + std::to_string(g.win) + ")");
+        SE_CHECK(m.p_in == e->ctx.p_in && m.p_out == e->ctx.p_out, fn + "magnitude exponents p_in / p_out differ");
+        SE_CHECK(e->model->stream_supported(), fn + "this engine's model has no frame-online mode");
+        SE_CHECK(m.batch <= e->ctx.max_batch, fn + "snapshot of " + std::to_string(m.batch) + " rows exceeds max_batch " +
+                                                  std::to_string(e->ctx.max_batch) + " given at create");
+        check_stream_geometry(e);
+        SE_CHECK(window_frames(e, m.max_chunk, 16) == m.max_chunk,
+                 fn + "the workspace is not planned for the snapshot's max_chunk_frames (" + std::to_string(m.max_chunk) + ")");
+        const bool sliding = (e->cfg.flags & SE_CFG_STREAM_SLIDING) != 0;
+        const int live = m.n_total - m.keep;
+        const long pitch = sliding ? stream_window_pitch(e->ctx.max_samples, g.n_fft, g.hop) : e->ctx.max_samples;
+        if (sliding) SE_CHECK(live <= pitch, fn + "the stream window of this engine cannot hold the " + std::to_string(live) + " live samples of the snapshot");
+        else
+            SE_CHECK(m.n_total <= e->ctx.max_samples, fn + "the stream has received " + std::to_string(m.n_total) +
+                                                          " samples, more than max_samples given at create (and the engine has no SE_CFG_STREAM_SLIDING)");
+        SE_CHECK(live <= snap_window_cap(g), fn + "more live input samples than a window and a hop");
+        se_engine::Stream& S = e->strm;
+        int ring = 0;
+        if (m.running) {
+            int need = S.sumsq ? S.ring : 64;
+            if (!S.sumsq)
+                while (need < e->plan_frames + 64) need <<= 1;
+            SE_CHECK(m.ring >= need && (m.ring & (m.ring - 1)) == 0,
+                     fn + "the snapshot of a running-scale stream keeps 1 / c of " + std::to_string(m.ring) + " frames per row, this engine needs " +
+                         std::to_string(need) + " (planned for a larger max_samples)");
+            ring = m.ring;
+        }
+        const size_t nfix = fixed_count_of(m);
+        SE_CHECK(nfix + 1 == m.segs.size(), fn + "snapshot without an input window segment");
+        const bool has_ss = e->model->stream_state() != nullptr;
+        std::vector<std::pair<void*, size_t>> want_slots;
+        for (size_t i = 0; i < nfix; ++i) {
+            const SnapSeg& sg = m.segs[i];
+            const bool rec = sg.kind == SNAP_HIST || sg.kind == SNAP_H || sg.kind == SNAP_CELL;
+            SE_CHECK(!(rec && !has_ss) && !(sg.kind == SNAP_SLOT && has_ss), fn + "the snapshot's state is not of this model's kind");
+            if (sg.kind == SNAP_SLOT) {
+                SE_CHECK(sg.index == (int32_t)want_slots.size() && sg.bytes > 0, fn + "state slots out of order");
+                want_slots.emplace_back(nullptr, (size_t)sg.bytes);
+            }
+        }
+        if (!s->dev_valid || s->device != e->cfg.device)
+            SE_CHECK(!s->host.empty(), fn + "the payload lives on device " + std::to_string(s->device) + ", this engine on device " +
+                                           std::to_string(e->cfg.device) + " (export the state and import it to move it)");
+        // ---- every refusal is above: from here the call takes the handle's stream over, as se_stream_begin does
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        S.active = false;
+        if (!s->dev_valid || s->device != e->cfg.device) {
+            if (s->has_use) {
+                DeviceScope ds(s->device);
+                SE_HIP(hipEventSynchronize(s->side->ev_use.get()));
+                s->has_use = false;
+            }
+            payload_alloc(s, m, std::max<int64_t>(snap_align16(m.segs.back().bytes), (int64_t)m.batch * snap_window_cap(g) * sizeof(float)),
+                          e->cfg.device);
+            SE_CHECK((int64_t)s->host.size() == snap_payload_bytes(m), fn + "host image of the wrong size");
+            SE_HIP(hipMemcpy(s->side->dev.get(), s->host.data(), s->host.size(), hipMemcpyHostToDevice));
+            s->dev_valid = true;
+        }
+        stream_order_wait(S, st);
+        obj_wait(s, st);
+        S.max_chunk = m.max_chunk;
+        if (!S.wav) {
+            S.pitch = pitch;
+            S.wav.alloc((size_t)e->ctx.max_batch * S.pitch);
+            if (sliding) S.wav2.alloc((size_t)e->ctx.max_batch * S.pitch);
+        }
+        if (!S.c) S.c.alloc(e->ctx.max_batch);
+        if (m.running && (!S.sumsq || S.ring != ring)) {
+            if (!S.sumsq) S.sumsq.alloc(e->ctx.max_batch);
+            S.frame_inv.alloc((size_t)e->ctx.max_batch * ring);
+            S.ring = ring;
+        }
+        // the model's state buffers: left where they are when they already have the snapshot's layout (two groups that alternate
+        // on one engine), else made as a new stream makes them - the slots of the cLN networks in the recorded order and sizes,
+        // which a stream creates lazily on its first chunk and checks on every later one
+        if (StreamState* ss = e->model->stream_state()) {
+            if (ss->B != m.batch || !same_segs(engine_segments(e, m.batch, m.running != 0, ring), m.segs, nfix))
+                e->model->stream_begin(m.batch, m.max_chunk, st);
+            ss->first = m.first != 0;
+        } else if (StreamSlots* sl = e->model->stream_slots()) {
+            bool same = sl->B == m.batch && sl->v.size() == want_slots.size() && !want_slots.empty();
+            for (size_t i = 0; same && i < want_slots.size(); ++i) same = sl->v[i].second == want_slots[i].second;
+            if (want_slots.empty()) {
+                e->model->stream_begin(m.batch, m.max_chunk, st);
+                // (slots an earlier stream of the same batch left are zero now: what a snapshot from before the first chunk means)
+            } else if (!same) {
+                sl->clear();
+                for (auto& w : want_slots) {
+                    void* d = nullptr;
+                    SE_HIP(hipMalloc(&d, w.second));
+                    sl->v.emplace_back(d, w.second);
+                }
+                sl->B = m.batch;
+            }
+        }
+        const std::vector<EngSeg> eng = engine_segments(e, m.batch, m.running != 0, ring);
+        // (a snapshot from before the first chunk into an engine whose slots exist: they were zeroed above and stay out of the copy)
+        std::vector<EngSeg> dst;
+        for (const EngSeg& sg : eng)
+            if (!(sg.seg.kind == SNAP_SLOT && want_slots.empty())) dst.push_back(sg);
+        SE_CHECK(same_segs(dst, m.segs, nfix),
+                 fn + "the snapshot's state buffers do not have the sizes this engine's model keeps (weights of other shapes?); the handle's stream has ended");
+        S.start(m.batch, m.n_total, m.running != 0);
+        S.t_done = m.t_done;
+        S.o_done = m.o_done;
+        S.w0 = sliding ? m.keep : 0;
+        long fix_tiles = 0;
+        const StateSeg* tab = table_for(s, 1, dst, S.wav.get(), m.batch, &fix_tiles, st);
+        StateWindow w;
+        w.dst_off = m.keep - S.w0;
+        w.src_pitch = live;
+        w.dst_pitch = S.pitch;
+        w.rows = m.batch;
+        w.len = live;
+        launch_stream_state_copy(tab, (int)dst.size(), fix_tiles, (int)dst.size(), w, st);
+        S.active = true;
+        stream_mark(S, st);
+        obj_mark(s, st);
+    });
+}
+
+int64_t se_stream_state_export(const se_stream_state* s, void* host_buf, int64_t cap) {
+    int64_t ret = -1;
+    guard(nullptr, [&] {
+        SE_CHECK(s, "se_stream_state_export: null argument");
+        SE_CHECK(s->filled, "se_stream_state_export: the stream state object is empty");
+        const int64_t size = snap_image_bytes(s->man), table = snap_table_bytes(s->man), pay = snap_payload_bytes(s->man);
+        if (cap == 0) {
+            ret = size;
+            return;
+        }
+        SE_CHECK(host_buf && cap >= size, "se_stream_state_export: the buffer holds " + std::to_string(cap) + " bytes, the image needs " + std::to_string(size));
+        uint8_t* out = static_cast<uint8_t*>(host_buf);
+        snap_write_table(s->man, out);
+        if (!s->host.empty()) {
+            SE_CHECK((int64_t)s->host.size() == pay, "se_stream_state_export: host image of the wrong size");
+            std::memcpy(out + table, s->host.data(), (size_t)pay);
+        } else {
+            SE_CHECK(s->side->dev && s->dev_valid, "se_stream_state_export: no payload");
+            DeviceScope ds(s->device);
+            se_stream_state* ms = const_cast<se_stream_state*>(s);
+            if (s->has_use) SE_HIP(hipEventSynchronize(ms->side->ev_use.get()));
+            if (pay > 0) SE_HIP(hipMemcpy(out + table, s->side->dev.get(), (size_t)pay, hipMemcpyDeviceToHost));
+            int64_t off = 0;
+            for (const SnapSeg& sg : s->man.segs) {      // the bytes between two segments are nobody's: zeros in the image
+                std::memset(out + table + off + sg.bytes, 0, (size_t)(snap_align16(sg.bytes) - sg.bytes));
+                off += snap_align16(sg.bytes);
+            }
+        }
+        ret = size;
+    });
+    return ret;
+}
+
+int se_stream_state_import(se_stream_state* s, const void* host_buf, int64_t bytes) {
+    return guard(nullptr, [&] {
+        SE_CHECK(s && host_buf, "se_stream_state_import: null argument");
+        SnapManifest m;
+        int64_t off = 0;
+        const std::string why = snap_parse(host_buf, bytes, m, off);
+        SE_CHECK(why.empty(), "se_stream_state_import: " + why);
+        std::vector<uint8_t> pay(static_cast<const uint8_t*>(host_buf) + off, static_cast<const uint8_t*>(host_buf) + bytes);
+        // nothing of the object has changed up to here
+        s->man = std::move(m);
+        s->host = std::move(pay);
+        s->filled = true;
+        s->dev_valid = false;
     });
 }
 

@@ -1,0 +1,96 @@
+// Parking and resuming a frame-online stream (se_stream_save / se_stream_restore): every carried buffer of a stream - conv
+// history, LSTM (h, c), the cLN networks' call-order slots, the scales, the live input samples - moves between the engine and a
+// snapshot's payload in ONE launch, however many buffers the model has (DCCRN ~25, the cLN networks well over 100): a one-frame
+// push is bound by its launch count, and a server that time-slices one engine pays a save and a restore per push.
+//
+// The segments are rows of a table in device memory (kernels.h: StateSeg), built when a layout is first seen.  Each segment is
+// `rows` runs of `len` floats (a flat buffer: one run); run r goes from src + r * src_pitch to dst + r * dst_pitch.  The work is
+// cut into tiles of STATE_TILE floats, one workgroup per tile, and the table carries the first tile of every segment: the grid is
+// the total tile count - sized to the bytes, so a large segment spreads over as many workgroups as it has tiles - and a
+// workgroup finds its segment by bisection (<= 9 steps of wave-uniform 8 B loads for 300 segments).  The input window is the one
+// segment whose extent changes from call to call (the live samples [keep, n_total)): its offsets and run length are kernel
+// arguments, its tiles follow the table's.
+//
+// Access width (MI355X: 16 B per lane is the widest global access, 64 lanes x 16 B = 1 KiB per wave instruction): payload offsets
+// are 16 B aligned and so is every buffer hipMalloc returns, so flat segments move as float4.  A run whose two ends are 16 B
+// aligned relative to each other is copied as a scalar head up to the first aligned destination, float4 body, scalar tail; a run
+// whose ends are not (a window row whose pitch or origin is no multiple of 4 floats against the compact payload rows) moves as
+// scalars.  Nothing outside [0, len) of a run is read or written.
+#include "kernels.h"
+
+namespace se {
+
+// n floats from s to d by the 256 threads of a workgroup
+__device__ __forceinline__ void state_copy_run(const float* __restrict__ s, float* __restrict__ d, int n) {
+    const int tid = threadIdx.x;
+    const int head = min(n, (int)(((16u - (unsigned)((uintptr_t)d & 15u)) & 15u) >> 2));
+    if ((((uintptr_t)(s + head)) & 15u) != 0) {
+        for (int i = tid; i < n; i += 256) d[i] = s[i];
+        return;
+    }
+    if (tid < head) d[tid] = s[tid];
+    const int nv = (n - head) >> 2;
+    const float4* __restrict__ s4 = reinterpret_cast<const float4*>(s + head);
+    float4* __restrict__ d4 = reinterpret_cast<float4*>(d + head);
+    for (int i = tid; i < nv; i += 256) d4[i] = s4[i];
+    const int done = head + (nv << 2);
+    if (tid < n - done) d[done + tid] = s[done + tid];
+}
+
+__global__ __launch_bounds__(256) void stream_state_copy_kernel(const StateSeg* __restrict__ tab, int nfix, int fix_tiles,
+                                                                int win, long win_src_off, long win_dst_off, long win_src_pitch,
+                                                                long win_dst_pitch, int win_len, int win_tpr) {
+    const int b = blockIdx.x;
+    const float* src;
+    float* dst;
+    long sp, dp;
+    int rows, len, tpr, t;
+    if (b < fix_tiles) {
+        int lo = 0, hi = nfix - 1;          // the last segment whose first tile is <= b (empty segments share their successor's)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (tab[mid].tile0 <= b) lo = mid;
+            else hi = mid - 1;
+        }
+        const StateSeg sg = tab[lo];
+        src = sg.src;
+        dst = sg.dst;
+        sp = sg.src_pitch;
+        dp = sg.dst_pitch;
+        rows = sg.rows;
+        len = sg.len;
+        tpr = (len + STATE_TILE - 1) / STATE_TILE;
+        t = b - sg.tile0;
+    } else {
+        if (win < 0) return;
+        const StateSeg sg = tab[win];
+        src = sg.src + win_src_off;
+        dst = sg.dst + win_dst_off;
+        sp = win_src_pitch;
+        dp = win_dst_pitch;
+        rows = sg.rows;
+        len = win_len;
+        tpr = win_tpr;
+        t = b - fix_tiles;
+    }
+    if (tpr <= 0) return;
+    const int r = t / tpr;
+    const int c0 = (t - r * tpr) * STATE_TILE;
+    if (r >= rows || c0 >= len) return;
+    state_copy_run(src + (long)r * sp + c0, dst + (long)r * dp + c0, min(STATE_TILE, len - c0));
+}
+
+long state_seg_tiles(int rows, int len) { return (long)rows * ((len + STATE_TILE - 1) / STATE_TILE); }
+
+void launch_stream_state_copy(const StateSeg* tab_dev, int nfix, long fix_tiles, int win, const StateWindow& w, hipStream_t s) {
+    SE_CHECK(nfix >= 0 && fix_tiles >= 0 && w.len >= 0 && w.rows >= 0, "launch_stream_state_copy: bad table");
+    const int tpr = (w.len + STATE_TILE - 1) / STATE_TILE;
+    const long tiles = fix_tiles + (win >= 0 ? (long)w.rows * tpr : 0);
+    if (tiles == 0) return;
+    SE_CHECK(tiles < (1L << 31), "launch_stream_state_copy: too many tiles");
+    hipLaunchKernelGGL(stream_state_copy_kernel, dim3((unsigned)tiles), dim3(256), 0, s, tab_dev, nfix, (int)fix_tiles, win, w.src_off,
+                       w.dst_off, w.src_pitch, w.dst_pitch, w.len, tpr);
+    SE_HIP(hipGetLastError());
+}
+
+}  // namespace se

@@ -175,6 +175,26 @@ struct HistBatch {
 };
 void launch_hist_batch(const HistBatch& hb, int B, int Tw, int hc, bool save, hipStream_t s);
 
+// Every carried buffer of a stream between the engine and a snapshot's payload in one launch (k_stream_state.hip; se_stream_save /
+// se_stream_restore).  A row of the device table: `rows` runs of `len` floats, run r from src + r * src_pitch to dst + r * dst_pitch
+// (pitches in floats), cut into tiles of STATE_TILE floats; tile0 = the tiles of the segments before it (state_seg_tiles each).
+// Segments [0, nfix) are laid out by the table alone.  Segment `win` (-1: none; not below nfix) is the input window: the table
+// gives its bases and row count, the call its column offsets, pitches and run length - they change with every push.
+constexpr int STATE_TILE = 2048;
+struct StateSeg {
+    const float* src;
+    float* dst;
+    long src_pitch, dst_pitch;
+    int rows, len;
+    int tile0, pad;
+};
+struct StateWindow {
+    long src_off = 0, dst_off = 0, src_pitch = 0, dst_pitch = 0;
+    int rows = 0, len = 0;
+};
+long state_seg_tiles(int rows, int len);
+void launch_stream_state_copy(const StateSeg* tab_dev, int nfix, long fix_tiles, int win, const StateWindow& w, hipStream_t s);
+
 // DCCRN 'E' mask (DCCRN_cprs.py:201-225) + the decode script's mag/phase/decompress (dccrn_decode_vb.py:45-58):
 //   mask [B][2][F-1][Tp] (bins 1..F-1), spec [B][2][F][Tp] -> est [B][2][F][Tp], DC bin = 0.
 void launch_dccrn_mask(const float* mask, const float* spec, float* est, int B, int F, int T, int Tp, float p_out,

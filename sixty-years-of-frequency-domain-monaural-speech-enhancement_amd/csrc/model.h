@@ -8,6 +8,8 @@
 
 namespace se {
 
+struct StreamState;      // rnn.h
+
 struct EngineCtx {
     int max_batch = 1, max_samples = 64000;
     float p_in = 1.f, p_out = 1.f;
@@ -211,6 +213,10 @@ class Model {
     virtual void stream_bufs(int B, int n, float** spec, float** mag, float** est) { SE_CHECK(false, "no streaming mode"); }
     // (`last`: no frame follows this chunk - a model that looks ahead finalises its provisional frames)
     virtual void stream_chunk(int B, int t0, int n, hipStream_t st, bool last) { SE_CHECK(false, "no streaming mode"); }
+    // the state a stream carries from chunk to chunk, for se_stream_save / se_stream_restore: a model keeps it in one of the two
+    // owners (rnn.h StreamState: history columns + LSTM (h, c); kernels.h StreamSlots: the call-order slots of the cLN networks)
+    virtual StreamState* stream_state() { return nullptr; }
+    virtual StreamSlots* stream_slots() { return nullptr; }
     // false: enhance() forks onto auxiliary streams and is not replayed from a captured hipGraph (SE_CFG_GRAPHS)
     virtual bool graph_capturable() const { return true; }
 

@@ -153,6 +153,11 @@ class Crn final : public Model {
     DeconvPlan dec[5];
     LstmBig lstm[2];
     StreamState ss;
+
+  public:
+    StreamState* stream_state() override { return &ss; }
+
+  private:
     static std::vector<long> stream_rows() {      // rows (C * F) of spec, mag, E[0..4], D[0..5]
         return {2L * NBIN, NBIN, 16L * 80, 32L * 39, 64L * 19, 128L * 9, 256L * 4, 1024L, 128L * 9, 64L * 19, 32L * 39, 16L * 80,
                 1L * 161};
@@ -341,6 +346,11 @@ class LstmNet final : public Model {
     LstmBig lstm[3];
     GCPlan fc, fc_fm;
     StreamState ss;
+
+  public:
+    StreamState* stream_state() override { return &ss; }
+
+  private:
 
     Bufs& bufs(int B, int T) {
         if (cur.B == B && cur.T == T) return cur;

@@ -192,6 +192,11 @@ class CtsNet final : public Model {
 
   private:
     StreamSlots slots;
+
+  public:
+    StreamSlots* stream_slots() override { return &slots; }
+
+  private:
     bool cum = false;
     struct Bufs {
         int B = 0, T = 0;

@@ -319,6 +319,11 @@ class Dccrn final : public Model {
 
   private:
     StreamState ss;
+
+  public:
+    StreamState* stream_state() override { return &ss; }
+
+  private:
     std::vector<long> stream_rows() const {      // rows (C * F) of spec, E[0..5], D[0..5], est
         return {2L * NBIN, KN[1] * 128L, KN[2] * 64L, KN[3] * 32L, KN[4] * 16L, KN[5] * 8L, KN[6] * 4L, 1024L, KN[5] * 8L, KN[4] * 16L,
                 KN[3] * 32L, KN[2] * 64L, KN[1] * 128L, 2L * NBIN};

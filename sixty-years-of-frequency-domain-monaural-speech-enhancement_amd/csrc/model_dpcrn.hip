@@ -172,6 +172,11 @@ class Dpcrn final : public Model {
 
   private:
     StreamState ss;
+
+  public:
+    StreamState* stream_state() override { return &ss; }
+
+  private:
     static std::vector<long> stream_rows() {      // rows (C * F) of spec, E[0..4], P1, D[0..5]
         return {2L * NBIN, 32L * 80, 32L * 39, 32L * 19, 64L * 9, 128L * 4, (long)CH * NF, (long)CH * NF, 64L * 9, 32L * 19, 32L * 39,
                 32L * 80, 2L * 161};

@@ -320,6 +320,11 @@ class FullSubNet final : public Model {
 
   private:
     StreamState ss;
+
+  public:
+    StreamState* stream_state() override { return &ss; }
+
+  private:
     bool cum = false, is_gru = false;
     struct Bufs {
         int B = 0, T = 0;

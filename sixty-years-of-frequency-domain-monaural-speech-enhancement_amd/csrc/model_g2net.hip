@@ -152,6 +152,11 @@ class G2Net final : public Model {
 
   private:
     StreamSlots slots;
+
+  public:
+    StreamSlots* stream_slots() override { return &slots; }
+
+  private:
     bool cum = false;
     struct Bufs {
         int B = 0, T = 0;

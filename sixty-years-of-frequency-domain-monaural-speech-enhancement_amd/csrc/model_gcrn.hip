@@ -156,6 +156,11 @@ class Gcrn final : public Model {
         float *c, *spec, *est, *frames, *E[5], *EE[4], *D[2][5], *X, *Y, *Z, *G, *cell, *L0;
     } cur;
     StreamState ss;
+
+  public:
+    StreamState* stream_state() override { return &ss; }
+
+  private:
     GCPlan enc[5], fc[2];
     DeconvPlan dec[2][5];
     LstmBig l1[2], l2[2];

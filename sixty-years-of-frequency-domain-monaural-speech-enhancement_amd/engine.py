@@ -10,6 +10,75 @@ class EngineError(RuntimeError):
     pass
 
 
+class StreamSnapshot:
+    """A parked frame-online stream (se_stream_state of include/se_engine.h): what `Engine.stream_save()` fills and
+    `Engine.stream_restore()` puts back - on the same engine or on another of the same configuration and weights, any number of
+    times.  `to_bytes()` / `from_bytes()` move it through host memory (another device, another process)."""
+
+    def __init__(self):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.batch = 0             # rows of the saved stream (0 = empty)
+        if self._lib.se_stream_state_create(C.byref(self._h)):
+            self._h = C.c_void_p()
+            raise EngineError(self._lib.se_last_error(None).decode())
+
+    @property
+    def closed(self):
+        return getattr(self, '_h', None) is None or not self._h.value
+
+    def close(self):
+        if not self.closed:
+            self._lib.se_stream_state_destroy(self._h)
+            self._h = C.c_void_p()
+            self.batch = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @property
+    def nbytes(self):
+        """device memory of the payload (0 = empty)"""
+        if self.closed:
+            raise EngineError("StreamSnapshot.nbytes: the snapshot is closed")
+        return int(self._lib.se_stream_state_bytes(self._h))
+
+    def to_bytes(self):
+        """the snapshot as one byte string (manifest + payload); synchronises with the save that filled it"""
+        if self.closed:
+            raise EngineError("StreamSnapshot.to_bytes: the snapshot is closed")
+        n = int(self._lib.se_stream_state_export(self._h, None, 0))
+        if n < 0:
+            raise EngineError(self._lib.se_last_error(None).decode())
+        buf = C.create_string_buffer(n)
+        if self._lib.se_stream_state_export(self._h, C.cast(buf, C.c_void_p), n) != n:
+            raise EngineError(self._lib.se_last_error(None).decode())
+        return buf.raw
+
+    @classmethod
+    def from_bytes(cls, b):
+        """a snapshot from `to_bytes()` output: validated here, on the host; uploaded by the first stream_restore"""
+        if not isinstance(b, (bytes, bytearray, memoryview)):
+            raise EngineError(f"StreamSnapshot.from_bytes: expected bytes, got {type(b).__name__}")
+        b = bytes(b)
+        snap = cls()
+        if snap._lib.se_stream_state_import(snap._h, b, len(b)):
+            snap.close()
+            raise EngineError(snap._lib.se_last_error(None).decode())
+        snap.batch = int.from_bytes(b[28:32], 'little', signed=True)      # csrc/stream_manifest.h: the sixth int32 behind magic and version
+        return snap
+
+
 class Engine:
     """One engine handle = one model replica on one GPU (one per rank)."""
 
@@ -241,6 +310,44 @@ class Engine:
                                               self._stream()))
         self._stream_batch = 0
         return out[:, :n_out.value]
+
+    def _closed(self):
+        h = getattr(self, '_h', None)
+        return h is None or not getattr(h, 'value', h)
+
+    def _check_snapshot(self, what, snapshot):
+        if not isinstance(snapshot, StreamSnapshot):
+            raise EngineError(f"{what}: expected a StreamSnapshot, got {type(snapshot).__name__}")
+        if snapshot.closed:
+            raise EngineError(f"{what}: the snapshot is closed")
+        if self._closed():
+            raise EngineError(f"{what}: the engine is closed")
+
+    def stream_save(self, snapshot=None):
+        """Copy the running stream into `snapshot` (a new StreamSnapshot when None) without ending or altering it; returns the
+        snapshot.  Saving again into the same object allocates nothing."""
+        if snapshot is not None:
+            self._check_snapshot('stream_save', snapshot)
+        elif self._closed():
+            raise EngineError("stream_save: the engine is closed")
+        if not self._stream_batch:
+            raise EngineError("stream_save without stream_begin")
+        snap = snapshot if snapshot is not None else StreamSnapshot()
+        try:
+            self._check(self._lib.se_stream_save(self._h, snap._h, self._stream()))
+        except EngineError:
+            if snapshot is None:
+                snap.close()
+            raise
+        snap.batch = self._stream_batch
+        return snap
+
+    def stream_restore(self, snapshot):
+        """Make the saved stream the running stream of this engine (whatever ran here is replaced, as by stream_begin): the
+        outputs of every later stream_push / stream_flush equal those of the stream had it never been interrupted, bit for bit."""
+        self._check_snapshot('stream_restore', snapshot)
+        self._check(self._lib.se_stream_restore(self._h, snapshot._h, self._stream()))
+        self._stream_batch = snapshot.batch
 
     # ------------------------------------------------------------------ stage hooks
     def rms_scale(self, wav):

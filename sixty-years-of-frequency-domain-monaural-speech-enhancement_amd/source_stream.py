@@ -13,7 +13,9 @@ from .resample import StreamResampler
 class SourceRateStream:
     """`SourceRateStream(model.engine, 48000)`: `begin(batch, ...)`, `push(x)` with x [batch, n <= max_push] at sr_in ->
     enhanced 16 kHz samples [batch, n_out] (n_out may be 0), `flush()` -> the rest.  `begin` takes what `Engine.stream_begin`
-    takes: a per-stream scale `c` (of the 16 kHz signal, e.g. from a calibration run) or `running_rms=True`."""
+    takes: a per-stream scale `c` (of the 16 kHz signal, e.g. from a calibration run) or `running_rms=True`.
+    Not covered by `Engine.stream_save` / `stream_restore`: the resampler in front carries state of its own (filter history, read
+    position) that a StreamSnapshot does not hold, so a stream fed through this class cannot be parked and resumed."""
 
     def __init__(self, engine, sr_in, sr_out=16000, max_push=None):
         self.engine = engine

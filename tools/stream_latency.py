@@ -7,7 +7,11 @@ streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, 
   and `mean_ms` (the median of a run in which one push in ~26 slides does not see them).
 --source-rate SR: the pushes arrive at SR Hz (48000, 44100, 32000) through se_amd.source_stream.SourceRateStream - a StreamResampler
   in front of the engine's stream; a push then carries the source samples of `chunk` frames and its time includes the resampling.
-Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000]"""
+--swap: time-slicing - two stream groups alternate on ONE engine through two StreamSnapshot objects, every push is
+  restore -> push -> save (se_stream_restore / se_stream_save).  The line then carries, next to the plain `ms_per_push` of the same run,
+  `save_ms`, `restore_ms` (one call each, timed alone) and `swapped_push_ms` (the three together), medians over the same pushes, each
+  with its p95, and `snapshot_bytes`.
+Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000] [--swap]"""
 import argparse
 import json
 import os
@@ -85,6 +89,45 @@ def time_source_rate(a, name, B, L, hop, eng, c):
                           'x_realtime_all_streams': round(B * piece / sr / t, 1)}), flush=True)
 
 
+def time_swap(eng, x, c, B, chunk, piece, L):
+    """--swap: two groups by turns on one engine; returns the extra fields of the result line"""
+    import torch
+    from se_amd.engine import StreamSnapshot
+    xs = [x, torch.flip(x, dims=[1]).contiguous()]
+    snaps = [StreamSnapshot(), StreamSnapshot()]
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    for rep in range(2):                    # first pass warms up (payload and tables of the layout, lazy state slots)
+        for g in range(2):
+            eng.stream_begin(B, c=c, max_chunk_frames=chunk)
+            eng.stream_save(snaps[g])
+        sv, rs, sw = [], [], []
+        for p in range(0, L - piece + 1, piece):
+            for g in range(2):
+                seg = xs[g][:, p:p + piece]
+                if g == 0:                  # the parts alone
+                    rs.append(timed(lambda: eng.stream_restore(snaps[g])))
+                    eng.stream_push(seg)
+                    sv.append(timed(lambda: eng.stream_save(snaps[g])))
+                else:                       # one swapped push: restore -> push -> save
+                    sw.append(timed(lambda: (eng.stream_restore(snaps[g]), eng.stream_push(seg), eng.stream_save(snaps[g]))))
+        for g in range(2):
+            eng.stream_restore(snaps[g])
+            eng.stream_flush()
+    med = lambda v: round(float(np.median(v[4:])) * 1e3, 3)
+    p95 = lambda v: round(float(np.percentile(v[4:], 95)) * 1e3, 3)
+    out = {'save_ms': med(sv), 'save_p95_ms': p95(sv), 'restore_ms': med(rs), 'restore_p95_ms': p95(rs), 'swapped_push_ms': med(sw),
+           'swapped_push_p95_ms': p95(sw), 'snapshot_bytes': snaps[0].nbytes}
+    for sn in snaps:
+        sn.close()
+    return out
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -94,6 +137,7 @@ def main():
     ap.add_argument('--seconds', type=float, default=2.0)
     ap.add_argument('--sliding', type=int, default=0, help='max_samples of a sliding-stream engine (0: a bounded engine as long as the clip)')
     ap.add_argument('--source-rate', type=int, default=0, help='push at this sample rate through SourceRateStream (0: push 16 kHz samples)')
+    ap.add_argument('--swap', action='store_true', help='also time two groups alternating on the engine: restore -> push -> save per push')
     a = ap.parse_args()
     L = int(a.seconds * 16000)
     for name in a.models.split(','):
@@ -128,8 +172,11 @@ def main():
                     n_fft = 320 if hop == 160 else 512
                     extra = {'sliding_max_samples': a.sliding, 'slides': count_slides(L, piece, 4, a.sliding, n_fft, hop),
                              'pushes': len(times[4:]), 'mean_ms': round(float(np.mean(times[4:])) * 1e3, 3)}
+                if a.swap:
+                    extra.update(time_swap(eng, x, c, B, chunk, piece, L))
                 print(json.dumps({'model': name, 'streams': B, 'frames_per_push': chunk, 'ms_per_push': round(t * 1e3, 3), **extra,
                                   'p95_ms': round(float(np.percentile(times[4:], 95)) * 1e3, 3),
+                                  'p05_ms': round(float(np.percentile(times[4:], 5)) * 1e3, 3),
                                   'host_enqueue_ms': round(float(np.median(enq[4:])) * 1e3, 3),
                                   'x_realtime_per_stream': round(piece / 16000 / t, 2),
                                   'x_realtime_all_streams': round(B * piece / 16000 / t, 1)}), flush=True)
