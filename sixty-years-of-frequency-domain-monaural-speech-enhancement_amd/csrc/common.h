@@ -12,19 +12,10 @@
 #include <string>
 #include <vector>
 #include "fastmath.h"
+#include "se_check.h"
 
 namespace se {
 
-struct Error : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-
-#define SE_STR2(x) #x
-#define SE_STR(x) SE_STR2(x)
-#define SE_CHECK(cond, msg)                                                                 \
-    do {                                                                                    \
-        if (!(cond)) throw ::se::Error(std::string(__FILE__ ":" SE_STR(__LINE__) ": ") + (msg)); \
-    } while (0)
 #define SE_HIP(expr)                                                                         \
     do {                                                                                    \
         hipError_t e_ = (expr);                                                             \

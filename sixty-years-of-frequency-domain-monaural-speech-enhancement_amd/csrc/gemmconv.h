@@ -15,16 +15,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
+#include "gc_select.h"
 
 namespace se {
 
-constexpr int GC_MAX_TAPS = 16;
-constexpr int GC_MAX_ROWS = 8;
-constexpr int GC_MAX_KCP = 48;
-constexpr int GC_TAB_KOFF = GC_MAX_ROWS + 2 * GC_MAX_TAPS;   // start of the per-K-row patch offsets in GCParams::tab
-// K rows of one staged chunk and patch elements staged per thread, by output-channel tile
-constexpr int gc_kcp_max(int BM) { return 32; }
-constexpr int gc_bld_max(int BM) { return (BM >= 128 || BM <= 32) ? 9 : 13; }
 // resident blocks per CU the kernel is register-budgeted for: small-M tiles do little matrix work per staged K row and
 // hide the global-load latency with occupancy instead
 // (the 32-row tile keeps one accumulator tile per wave: with 9 patch slots it fits 78 VGPRs, i.e. 6 workgroups per CU - its
@@ -32,20 +26,6 @@ constexpr int gc_bld_max(int BM) { return (BM >= 128 || BM <= 32) ? 9 : 13; }
 constexpr int gc_blocks_per_cu(int BM) { return BM <= 32 ? 6 : 3; }
 
 enum Act : int { ACT_NONE = 0, ACT_PRELU = 1, ACT_ELU = 2, ACT_SOFTPLUS = 3, ACT_SIGMOID = 4, ACT_TANH = 5, ACT_RELU = 6 };
-enum Epi : int {
-    EPI_ACT = 0,     // dst = act(acc + bias)
-    EPI_LSTM = 1,    // rows are gate-interleaved (4j+{i,f,g,o}); dst = h_t, c updated in place (GCParams::gru: the GRU cell on the same 4-row layout)
-    EPI_GLU = 2,     // rows are pair-interleaved (2j, 2j+1): dst[j] = (a+bias) * sigmoid(g+bias)
-    EPI_ADD = 3,     // dst = act(acc + bias) + res   (res laid out like dst)
-    EPI_MUL = 4,     // dst = act(acc + bias) * aux   (gated TCM branches, CTSNet/Step1_network.py:184)
-    EPI_CMB = 5,     // dst = prelu((aux +- acc) * post_scale + post_shift): the last two of Gauss' three products finish the complex
-                     // layer in their own store (aux = k1; GCParams::cmb_neg bit z: minus; per-z rows of post_scale / post_shift /
-                     // slope at stride ps_z) - gauss.h
-};
-
-// launches that produce at most this many frames per row go to the thin kernel (frame-online chunks)
-constexpr int GC_THIN_NT = 8;
-
 struct GCParams {
     const float* A;          // packed weights [nchunks][KCp][Mp]
     const float* Ws;         // direct small-M path (M <= 4): plain weights [z][ci][tap][MM]; nullptr -> MFMA path
@@ -132,18 +112,13 @@ struct GCParams {
     int flat_upr;            // units per row (0: off)
     int flat_units;          // B * flat_upr
 };
-constexpr int GC_NRM_MAXC = 128;
-// batch rows whose InstanceNorm parameters a flattened tile with NRM holds in LDS (gc_kernel: nrmC / nrmK); gc_launch only
-// sends a normalising launch to the flattened tiles when no tile spans more rows than this
-constexpr int GC_FLAT_NRM_ROWS = 2;
-
 // Device tables of one patch geometry (owned by the plan)
 struct GCGeom {
     int* tab = nullptr;
     unsigned* desc = nullptr;
     unsigned* desc4 = nullptr;
 };
-// Narrow geometry for the last time tile of a row (BN = 0: unused)
+// One patch geometry of a plan (BN = 0: the plan does not have it)
 struct GCTail {
     int BN = 0, Wp = 0;
     GCGeom g;
@@ -162,28 +137,17 @@ struct GCPlan {
     double flop_scale = 1.0; // algorithmic / executed multiply-adds (fused parity pairs carry zero-weight taps)
     float* dA = nullptr;     // device copies owned by the plan
     float* dWs = nullptr;
-    unsigned* dDesc = nullptr;
-    unsigned* dDesc4 = nullptr;
     GCSmallGeom small;       // direct path only
-    bool tail_split = false; // tail[0] may be used as a separate launch for the last time tile
-    GCTail tail[3];          // [0]: 32-column geometry for a mostly empty last time tile; [1]: 64-column geometry of the whole layer for small launches; [2]: 256-column geometry of a 64-row layer for big launches
-    GCTail qt2;              // two-row geometry: 2 output rows x 64 frames per tile (BN = 0: unused)
-    GCTail flat[2];          // unit-flattened geometries (GCParams::flat_upr): [0] 128 columns = 4 units, [1] 256 columns = 8 units of a
-                             // 64-row layer; Wp = units x flat_uw (BN = 0: unused)
+    bool tail_split = false; // geom[GC_G_N32] may be used as a separate launch for the last time tile
+    GCTail geom[GC_G_COUNT]; // every patch geometry of the layer with its device tables, by GCGeomId (gc_select.h); geom[GC_G_MAIN]'s
+                             // tables are the ones p.tab / p.desc / p.desc4 name
     int flat_uw = 0;         // LDS columns per unit and patch row: 32 (pointwise) or 36 (causal taps, <= 4 frames of look-back)
     int qt2_nrows = 0, qt2_qoff = 0;
     float* dBias = nullptr;
     float* dSlope = nullptr;
-    int* dTab = nullptr;
     float* dBiasPad = nullptr;
     float* dPostScale = nullptr;
     float* dPostShift = nullptr;
-};
-
-struct TapSpec {
-    int ntaps = 0;
-    int df[GC_MAX_TAPS];
-    int dt[GC_MAX_TAPS];
 };
 
 // Build a plan.  w_logical[m][ci][j] (row-major, M x Cin x ntaps) are the effective real weights
@@ -207,23 +171,10 @@ void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream);
 // false: nothing was launched
 bool gc_launch_thin_pair(const GCParams& p0, const GCParams& p1, hipStream_t stream);
 
-// Geometry of one dispatch, for tests that must know which kernel form a launch reached (csrc/tests/gc_probe.hip).  Host-side
-// only: nothing the kernels compute depends on it.
-enum GCFamily : int { GC_FAM_TILE = 0, GC_FAM_THIN = 1, GC_FAM_THIN_PAIR = 2, GC_FAM_DIRECT = 3, GC_FAM_DIRECT_LDS = 4 };
-struct GCLaunchRec {
-    int family = GC_FAM_TILE;
-    int BM = 0, BN = 0;          // tile (GC_FAM_TILE)
-    int flat_upr = 0, upt = 0;   // flattened column tiles: units per batch row, units per tile (0: plain tiles)
-    int flat_rows = 0;           // flattened: most batch rows one tile spans
-    int qt2 = 0, nrm = 0, res = 0, trim = 0, stats = 0, ragged = 0;
-    int flat_nrm_refused = 0;    // the flattened tiles were considered and refused because a normalising tile would span
-                                 // more than GC_FLAT_NRM_ROWS rows (value: rows spanned)
-    long nblk = 0;               // workgroups
-    int epi = 0, gru = 0;        // the launch's epilogue (EPI_LSTM: one recurrent step; gru: its GRU cell)
-};
+// Launch log (GCLaunchRec: gc_select.h), for tests that must know which kernel form a launch reached.
 // nullptr (the default): nothing is recorded.  Otherwise every dispatch of this thread appends its record.
 void gc_set_launch_log(std::vector<GCLaunchRec>* log);
-// most batch rows that one flattened tile of `upt` units touches when B rows of `upr` units each are laid end to end
-int gc_flat_rows_spanned(int B, int upr, int upt);
+// nullptr (the default): nothing is recorded.  Otherwise every gc_launch call of this thread appends what it gave gc_select.
+void gc_set_select_log(std::vector<GCSelIn>* log);
 
 }  // namespace se

@@ -1461,6 +1461,96 @@ __global__ __launch_bounds__(256) void gc_thin_pair_kernel(const GCThinPair a) {
     const int cls = (int)blockIdx.x >= a.nblk0 ? 1 : 0;
     gc_thin_body<EPI, NT>(a.p[cls], (int)blockIdx.x - (cls ? a.nblk0 : 0));
 }
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+// Three layers: what a layer's plan is (gc_select.h: gc_plan_shape -> gc_make_plan), which kernel form a launch takes
+// (gc_select.h: gc_select, pure) and the launch itself (gc_launch_k / gc_dispatch below).
+static_assert(GC_SMALL_QB == SQB && GC_SMALL_WT == SWT, "gc_select.h: the direct kernel's tile constants");
+
+// gc_set_launch_log / gc_set_select_log: per-thread records of the dispatches and of what gc_select was given (tests only; off
+// unless a log is set)
+static thread_local std::vector<GCLaunchRec>* g_launch_log = nullptr;
+static thread_local std::vector<GCSelIn>* g_select_log = nullptr;
+void gc_set_launch_log(std::vector<GCLaunchRec>* log) { g_launch_log = log; }
+void gc_set_select_log(std::vector<GCSelIn>* log) { g_select_log = log; }
+static void gc_log_launch(const GCSelIn& in, const GCDispatch& d, int gru) {
+    if (g_launch_log) g_launch_log->push_back(gc_launch_rec(in, d, gru));
+}
+
+// Device ranges whose tensors may be over-read by up to 12 B past their last element (the engine arenas: every
+// allocation is followed by more arena or by the arena's tail slack).  Pointwise layers stage their patch in 16 B groups;
+// a group that straddles the end of a row only feeds output columns that are never stored, so the only requirement on
+// the over-read is that it stays inside mapped memory.
+static std::vector<std::pair<const char*, const char*>>& gc_safe_ranges() {
+    static std::vector<std::pair<const char*, const char*>> r;
+    return r;
+}
+static std::mutex& gc_safe_mutex() {       // engines may be created / destroyed from different host threads
+    static std::mutex m;
+    return m;
+}
+void gc_register_overread_range(const void* lo, size_t bytes) {
+    std::lock_guard<std::mutex> lk(gc_safe_mutex());
+    gc_safe_ranges().emplace_back(static_cast<const char*>(lo), static_cast<const char*>(lo) + bytes);
+}
+void gc_unregister_overread_range(const void* lo) {
+    std::lock_guard<std::mutex> lk(gc_safe_mutex());
+    auto& r = gc_safe_ranges();
+    for (size_t i = 0; i < r.size(); ++i)
+        if (r[i].first == lo) {
+            r.erase(r.begin() + i);
+            return;
+        }
+}
+static bool gc_overread_ok(const void* ptr) {
+    if (!ptr) return true;
+    std::lock_guard<std::mutex> lk(gc_safe_mutex());
+    for (const auto& r : gc_safe_ranges())
+        if (ptr >= r.first && static_cast<const char*>(ptr) + 16 <= r.second) return true;
+    return false;
+}
+
+// What gc_select reads of a launch (pl == nullptr: the launch's own fields only - all the thin rule needs)
+static GCSelIn gc_sel_in(const GCPlan* pl, const GCParams& p) {
+    GCSelIn s{};
+    if (pl) {
+        s.BM = pl->BM;
+        s.BN = pl->BN;
+        for (int g = 0; g < GC_G_COUNT; ++g) {
+            s.g_BN[g] = pl->geom[g].BN;
+            s.g_Wp[g] = pl->geom[g].Wp;
+        }
+        s.flat_uw = pl->flat_uw;
+        s.tail_split = pl->tail_split;
+        s.qt2_nrows = pl->qt2_nrows;
+        s.qt2_qoff = pl->qt2_qoff;
+        s.sm_dfmin = pl->small.dfmin;
+        s.sm_dfmax = pl->small.dfmax;
+        s.sm_dtmin = pl->small.dtmin;
+        s.sm_dtmax = pl->small.dtmax;
+        s.pl_C0 = pl->p.C0;
+        s.pl_C1 = pl->p.C1;
+        s.pl_epi = pl->p.epi;
+        s.pl_Ws = pl->p.Ws != nullptr;
+        // (the registry is only asked where the ladder can need the answer: 16 B groups that straddle the end of a row)
+        const bool straddle = p.desc4 && p.Tin % 4 != 0;
+        s.overread0 = straddle && gc_overread_ok(p.src0);
+        s.overread1 = straddle && gc_overread_ok(p.src1);
+        s.tun = gc_tuning_env();
+    }
+    s.CI_C = p.CI_C; s.nrows = p.nrows; s.KCp = p.KCp; s.causal = p.causal;
+    s.epi = p.epi; s.Z = p.Z; s.B = p.B; s.Q = p.Q; s.M = p.M; s.n_mtiles = p.n_mtiles;
+    s.Tout = p.Tout; s.Tin = p.Tin; s.Fin = p.Fin; s.t_base = p.t_base; s.tb_soft = p.tb_soft;
+    s.C0 = p.C0; s.C1 = p.C1; s.pad_lo = p.pad_lo; s.first_step = p.first_step; s.pair = p.pair; s.si = p.si;
+    s.s0_b = p.s0_b; s.s0_c = p.s0_c; s.s0_f = p.s0_f; s.s1_b = p.s1_b; s.s1_c = p.s1_c; s.s1_f = p.s1_f;
+    s.Ws = p.Ws != nullptr; s.desc4 = p.desc4 != nullptr; s.stats = p.stats != nullptr; s.cstats = p.cstats != nullptr;
+    s.nrm0 = p.nrm0 != nullptr; s.nrm1 = p.nrm1 != nullptr; s.fz = p.fz != nullptr; s.dst_elu = p.dst_elu != nullptr;
+    s.tlen = p.tlen != nullptr;
+    return s;
+}
+
+// ---- thin path
 template <int EPI>
 static void gc_thin_launch_n(const GCParams& p, dim3 grid, int n, hipStream_t stream) {
     if (n <= 1) hipLaunchKernelGGL((gc_thin_kernel<EPI, 1>), grid, dim3(256), 0, stream, p);
@@ -1468,86 +1558,17 @@ static void gc_thin_launch_n(const GCParams& p, dim3 grid, int n, hipStream_t st
     else if (n <= 4) hipLaunchKernelGGL((gc_thin_kernel<EPI, 4>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((gc_thin_kernel<EPI, 8>), grid, dim3(256), 0, stream, p);
 }
-// gc_set_launch_log: per-thread record of the dispatches (tests only; off unless a log is set)
-static thread_local std::vector<GCLaunchRec>* g_launch_log = nullptr;
-static thread_local int g_flat_nrm_refused = 0;      // gc_launch -> the record of its dispatch
-void gc_set_launch_log(std::vector<GCLaunchRec>* log) { g_launch_log = log; }
-static void gc_log_launch(int family, const GCParams& p, long nblk, int BM = 0, int BN = 0, bool res = false) {
-    if (!g_launch_log) return;
-    GCLaunchRec r;
-    r.family = family;
-    r.BM = BM;
-    r.BN = BN;
-    r.flat_upr = p.flat_upr;
-    r.upt = p.flat_upr ? BN / 32 : 0;
-    r.flat_rows = p.flat_upr ? gc_flat_rows_spanned(p.B, p.flat_upr, BN / 32) : 0;
-    r.qt2 = p.qt2;
-    r.nrm = (p.nrm0 || p.nrm1) ? 1 : 0;
-    r.res = res ? 1 : 0;
-    r.trim = p.trim;
-    r.stats = (p.stats || p.cstats) ? 1 : 0;
-    r.ragged = p.tlen ? 1 : 0;
-    r.flat_nrm_refused = g_flat_nrm_refused;
-    r.nblk = nblk;
-    r.epi = p.epi;
-    r.gru = p.gru;
-    g_launch_log->push_back(r);
-}
-int gc_flat_rows_spanned(int B, int upr, int upt) {
-    // tile k covers units [k upt, (k + 1) upt); tile k + upr starts exactly upt rows further on, so the first upr tiles show
-    // every pattern (a shortened last tile spans no more rows than the full one of its pattern)
-    const long units = (long)B * upr, tiles = (units + upt - 1) / upt;
-    int most = 0;
-    for (long k = 0; k < std::min<long>(tiles, upr); ++k) {
-        const long u0 = k * upt, u1 = std::min(u0 + upt, units) - 1;
-        most = std::max(most, (int)(u1 / upr - u0 / upr + 1));
-    }
-    return most;
-}
-
-// most workgroups a launch may have on the thin path
-constexpr long GC_THIN_MAX_BLOCKS = 8192;
-// number of workgroups of the launch on the thin path, 0: not a thin launch
-static long gc_thin_blocks(const GCParams& p) {
-    const int n = p.Tout - p.t_base;
-    // (layers with <= 4 output channels have the packed matrix too: a one-frame launch of the direct kernel walks its whole K
-    // in one thread per output - 20-40 us; the fused parity pair of a transposed conv only exists there)
-    if ((p.Ws && p.pair) || n > GC_THIN_NT || p.Z > 1 || p.stats || p.cstats || p.nrm0 || p.nrm1) return 0;
-    if (p.epi != EPI_ACT && p.epi != EPI_ADD && p.epi != EPI_MUL && p.epi != EPI_GLU && p.epi != EPI_LSTM) return 0;
-    if (p.epi == EPI_LSTM && (p.M & 3)) return 0;
-    const long nblk = (long)((p.M + 7) >> 3) * p.Q * p.B;
-    // (a few frames per row is not yet a small launch: the LSTM input projections of a batch-1 decode are 1 "frame" wide
-    // and 401 rows high with K = 1024 - matrix work)
-    if (nblk > GC_THIN_MAX_BLOCKS) return 0;
-    // Both paths are latency-bound at these sizes: a thin block walks K / 32 rows with 1 + NT loads each (~0.08 us per row
-    // and load, ~2 048 blocks in flight) and re-reads its 8 weight rows from L2 (32 B x K per block: 16 streams x one frame of
-    // DCCRN's 256-channel layers = 4 096 blocks x 80 KB - 110 us against 80 us of the MFMA tiles); an MFMA workgroup makes K / 16
-    // staged steps of ~0.5 us (~512 in flight).  Measured on the frame-online chunks of CRN / GCRN / DPCRN / DCCRN with 1 and 16
-    // streams x 1 and 8 frames: up to 64 columns in all go to the thin kernel unless its weight traffic or its waves say no.
-    if (!p.Ws) {
-        const int nt = n <= 1 ? 1 : (n <= 2 ? 2 : (n <= 4 ? 4 : 8));
-        const double waves_thin = std::ceil((double)nblk / 2048.0);
-        const double waves_mfma = std::ceil((double)std::max(p.Z, 1) * p.B * p.Q * std::max(p.n_mtiles, 1) / 512.0);
-        if ((long)p.B * n > 64 || nblk > 2800 * waves_mfma || waves_thin * (1 + nt) > 12 * waves_mfma) return 0;
-    }
-    return nblk;
-}
-static bool gc_thin_launch(const GCParams& p, hipStream_t stream) {
-    const long nblk = (p.fz || p.dst_elu) ? 0 : gc_thin_blocks(p);          // (GCParams::fz / dst_elu: MFMA kernel only)
-    if (nblk <= 0) return false;
-    const int n = p.Tout - p.t_base;
-    dim3 grid((unsigned)nblk);
+static void gc_launch_thin(const GCParams& p, const GCDispatch& d, hipStream_t stream) {
+    dim3 grid((unsigned)d.nblk);
     switch (p.epi) {
-        case EPI_ACT: gc_thin_launch_n<EPI_ACT>(p, grid, n, stream); break;
-        case EPI_ADD: gc_thin_launch_n<EPI_ADD>(p, grid, n, stream); break;
-        case EPI_MUL: gc_thin_launch_n<EPI_MUL>(p, grid, n, stream); break;
-        case EPI_GLU: gc_thin_launch_n<EPI_GLU>(p, grid, n, stream); break;
-        case EPI_LSTM: gc_thin_launch_n<EPI_LSTM>(p, grid, n, stream); break;
-        default: return false;
+        case EPI_ACT: gc_thin_launch_n<EPI_ACT>(p, grid, d.thin_n, stream); break;
+        case EPI_ADD: gc_thin_launch_n<EPI_ADD>(p, grid, d.thin_n, stream); break;
+        case EPI_MUL: gc_thin_launch_n<EPI_MUL>(p, grid, d.thin_n, stream); break;
+        case EPI_GLU: gc_thin_launch_n<EPI_GLU>(p, grid, d.thin_n, stream); break;
+        case EPI_LSTM: gc_thin_launch_n<EPI_LSTM>(p, grid, d.thin_n, stream); break;
+        default: SE_CHECK(false, "thin path: unsupported epilogue");
     }
     SE_HIP(hipGetLastError());
-    gc_log_launch(GC_FAM_THIN, p, nblk);
-    return true;
 }
 
 template <int EPI>
@@ -1558,7 +1579,7 @@ static void gc_thin_pair_launch_n(const GCThinPair& a, dim3 grid, int n, hipStre
     else hipLaunchKernelGGL((gc_thin_pair_kernel<EPI, 8>), grid, dim3(256), 0, stream, a);
 }
 bool gc_launch_thin_pair(const GCParams& p0, const GCParams& p1, hipStream_t stream) {
-    const long n0 = gc_thin_blocks(p0), n1 = gc_thin_blocks(p1);
+    const long n0 = gc_thin_blocks(gc_sel_in(nullptr, p0), p0.t_base), n1 = gc_thin_blocks(gc_sel_in(nullptr, p1), p1.t_base);
     if (n0 <= 0 || n1 <= 0 || p0.epi != p1.epi || p0.Tout - p0.t_base != p1.Tout - p1.t_base) return false;
     GCThinPair a;
     a.p[0] = p0;
@@ -1574,79 +1595,173 @@ bool gc_launch_thin_pair(const GCParams& p0, const GCParams& p1, hipStream_t str
         default: return false;
     }
     SE_HIP(hipGetLastError());
-    gc_log_launch(GC_FAM_THIN_PAIR, p0, n0 + n1);
+    GCDispatch d;
+    d.family = GC_FAM_THIN_PAIR;
+    d.nblk = n0 + n1;
+    d.qt2 = p0.qt2;
+    d.trim = p0.trim;
+    gc_log_launch(gc_sel_in(nullptr, p0), d, p0.gru);
     return true;
 }
 
+// ---- direct (<= 4 output channels) path
 template <int MM, int EPI>
-static void gc_small_lds_launch(const GCParams& p, dim3 grid, size_t shm, int CC, int NR, const GCSmallGeom& sg, hipStream_t stream) {
-    if (p.si == 1) hipLaunchKernelGGL((gc_small_lds_kernel<MM, EPI, 1>), grid, dim3(256), shm, stream, p, CC, NR, sg.dfmin, sg.dtmin);
-    else hipLaunchKernelGGL((gc_small_lds_kernel<MM, EPI, 2>), grid, dim3(256), shm, stream, p, CC, NR, sg.dfmin, sg.dtmin);
+static void gc_launch_direct_e(const GCParams& p, const GCSmallGeom& sg, const GCDispatch& d, hipStream_t stream) {
+    const dim3 grid((unsigned)d.nblk);
+    if (d.family == GC_FAM_DIRECT) hipLaunchKernelGGL((gc_small_kernel<MM, EPI>), grid, dim3(256), 0, stream, p);
+    else if (p.si == 1) hipLaunchKernelGGL((gc_small_lds_kernel<MM, EPI, 1>), grid, dim3(256), d.lds, stream, p, d.CC, d.NR, sg.dfmin, sg.dtmin);
+    else hipLaunchKernelGGL((gc_small_lds_kernel<MM, EPI, 2>), grid, dim3(256), d.lds, stream, p, d.CC, d.NR, sg.dfmin, sg.dtmin);
 }
-
 template <int MM>
-static void gc_small_launch(const GCParams& p, const GCSmallGeom& sg, hipStream_t stream) {
-    // LDS-tiled form when the launch still fills the chip with 8-row workgroups and the patch of at least 2 channels fits
-    const int NR = (SQB - 1) * p.si + (sg.dfmax - sg.dfmin) + 1;
-    constexpr int small_kb = 24;       // LDS budget of the staged patch (KB): 2-channel chunks, 6-7 workgroups per CU (40 KB: DCCRN -0.4 %, CTSNet -1.7 %)
-    // <= 8: s_w holds 8 channels; <= 24 patch rows per chunk: a wave carries 6 rows of the next chunk in registers (gc_small_lds_kernel)
-    const int CC = std::min(std::min(8, 24 / std::max(NR, 1)), (int)((size_t)small_kb * 1024 / ((size_t)NR * SWT * sizeof(float))));
-    const long nblk8 = (long)((p.Tout + 255) / 256) * ((p.Q + SQB - 1) / SQB) * p.B * p.Z;
-    // (worth it from three frequency rows per output row on: with one or two the plain kernel's caches do as well - CRN /
-    // DPCRN last layers measured 1-3 % slower here, DCCRN's 5-tap deconv 1 % faster with a third of the fetches)
-    if (CC >= 2 && p.Q >= SQB && (p.si == 1 || p.si == 2) && sg.dtmax - sg.dtmin <= SWT - 256 && nblk8 >= 4 * 256 &&
-        (sg.dfmax - sg.dfmin >= 2 || (sg.dfmax - sg.dfmin >= 1 && MM >= 2 && p.C0 + p.C1 >= 64))) {
-        SE_CHECK(nblk8 < (1L << 31), "grid size");
-        const size_t shm = (size_t)CC * NR * SWT * sizeof(float);
-        dim3 grid((unsigned)nblk8);
-        switch (p.epi) {
-            case EPI_ACT: gc_small_lds_launch<MM, EPI_ACT>(p, grid, shm, CC, NR, sg, stream); break;
-            case EPI_ADD: gc_small_lds_launch<MM, EPI_ADD>(p, grid, shm, CC, NR, sg, stream); break;
-            case EPI_MUL: gc_small_lds_launch<MM, EPI_MUL>(p, grid, shm, CC, NR, sg, stream); break;
-            case EPI_GLU:
-                if constexpr (MM >= 2) gc_small_lds_launch<MM, EPI_GLU>(p, grid, shm, CC, NR, sg, stream);
-                break;
-            default: SE_CHECK(false, "direct small-M path: unsupported epilogue");
-        }
-        SE_HIP(hipGetLastError());
-        gc_log_launch(GC_FAM_DIRECT_LDS, p, nblk8);
-        return;
-    }
-    const long nblk = (long)((p.Tout + 255) / 256) * p.Q * p.B * p.Z;
-    SE_CHECK(nblk > 0 && nblk < (1L << 31), "grid size");
-    dim3 grid((unsigned)nblk);
+static void gc_launch_direct(const GCParams& p, const GCSmallGeom& sg, const GCDispatch& d, hipStream_t stream) {
     switch (p.epi) {
-        case EPI_ACT: hipLaunchKernelGGL((gc_small_kernel<MM, EPI_ACT>), grid, dim3(256), 0, stream, p); break;
-        case EPI_ADD: hipLaunchKernelGGL((gc_small_kernel<MM, EPI_ADD>), grid, dim3(256), 0, stream, p); break;
-        case EPI_MUL: hipLaunchKernelGGL((gc_small_kernel<MM, EPI_MUL>), grid, dim3(256), 0, stream, p); break;
+        case EPI_ACT: gc_launch_direct_e<MM, EPI_ACT>(p, sg, d, stream); break;
+        case EPI_ADD: gc_launch_direct_e<MM, EPI_ADD>(p, sg, d, stream); break;
+        case EPI_MUL: gc_launch_direct_e<MM, EPI_MUL>(p, sg, d, stream); break;
         case EPI_GLU:
-            if constexpr (MM >= 2) hipLaunchKernelGGL((gc_small_kernel<MM, EPI_GLU>), grid, dim3(256), 0, stream, p);
+            if constexpr (MM >= 2) gc_launch_direct_e<MM, EPI_GLU>(p, sg, d, stream);
             break;
         default: SE_CHECK(false, "direct small-M path: unsupported epilogue");
     }
     SE_HIP(hipGetLastError());
-    gc_log_launch(GC_FAM_DIRECT, p, nblk);
 }
 
-// ------------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------------
-static size_t gc_lds_bytes(const GCParams& p, int BM, size_t epi_bytes, int nbuf = 2) {
-    const size_t as = (size_t)((p.KCp * (BM / 4) + 255) / 256) * 1024, bs = (size_t)((p.CI_C * p.nrows * p.Wp + 255) / 256) * 256;
-    const size_t nrb = p.flat_upr ? GC_FLAT_NRM_ROWS : 1;      // FLAT: parameters of two batch rows
-    const size_t nrm = ((p.nrm0 || p.nrm1) ? (size_t)(nrb * GC_NRM_MAXC + 2 * nrb * gc_kcp_max(BM) + 2) * 16 : 0) + (p.flat_upr ? 128 : 0);      // gc_kernel NRM: nrmC + nrmK; FLAT: utab
-    const size_t cst = p.cstats ? (size_t)4 * 256 * 2 * 4 : 0;      // GCParams::cstats: cpart [WM][4][BN][2] <= 8 KB, behind the strips inside the staging area
-    return std::max((size_t)nbuf * (as + bs) * 4, epi_bytes + cst) + (GC_TAB_KOFF + GC_MAX_KCP + 8) * 4 + (size_t)4 * BM * 4 + 64 + nrm;
+// ---- tile path
+// The instantiated variants of gc_kernel: by tile, epilogue and form
+constexpr bool gc_has_variant(int BM, int BN, int EPI, bool RES, bool TRIM, bool FZ, bool NRM, int FLATW) {
+    const bool act = EPI == EPI_ACT, other = TRIM || FZ || NRM || FLATW;
+    if (BM == 128 && BN == 256) return EPI == EPI_LSTM && !RES && !other;       // the per-step LSTM GEMM's wide tile
+    if (EPI == EPI_CMB && BM < 64) return false;
+    if (RES) return ((BM == 128 && BN == 32) || (BM == 64 && BN == 64)) && EPI != EPI_CMB && EPI != EPI_LSTM && !other;
+    if (FLATW) return !TRIM && !FZ && gc_flat_inst(BM, BN, EPI, FLATW) && (!NRM || (act && BM == 64));
+    if (FZ) return (act || EPI == EPI_ADD) && !TRIM && !NRM;
+    if (NRM) return act && BM == 64 && !TRIM;
+    if (TRIM) return act;
+    return true;
 }
 
+// One launch of gc_kernel: the LDS attribute on first use per device, the launch and its check (gc_dispatch records it)
+template <int BM, int BN, int WM, int WN, int EPI, bool RES, bool TRIM, bool FZ, bool NRM, int FLATW>
+static void gc_launch_k(const GCParams& p, const GCDispatch& d, hipStream_t stream) {
+    if constexpr (gc_has_variant(BM, BN, EPI, RES, TRIM, FZ, NRM, FLATW)) {
+        static bool attr_set[64] = {};
+        if (first_on_device(attr_set)) {
+            SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gc_kernel<BM, BN, WM, WN, EPI, RES, TRIM, FZ, NRM, FLATW>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        }
+        hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, RES, TRIM, FZ, NRM, FLATW>), dim3((unsigned)d.nblk), dim3(256), d.lds, stream, p);
+        SE_HIP(hipGetLastError());
+    } else {
+        SE_CHECK(false, "gc_launch: the selected kernel variant is not instantiated");
+    }
+}
+// A GCDispatch of the tile family -> its instantiation
+template <int BM, int BN, int WM, int WN, int EPI>
+static void gc_dispatch_form(const GCParams& p, const GCDispatch& d, hipStream_t s) {
+    switch (d.form) {
+        case GC_FORM_PLAIN: gc_launch_k<BM, BN, WM, WN, EPI, false, false, false, false, 0>(p, d, s); break;
+        case GC_FORM_RES: gc_launch_k<BM, BN, WM, WN, EPI, true, false, false, false, 0>(p, d, s); break;
+        case GC_FORM_TRIM: gc_launch_k<BM, BN, WM, WN, EPI, false, true, false, false, 0>(p, d, s); break;
+        case GC_FORM_FZ: gc_launch_k<BM, BN, WM, WN, EPI, false, false, true, false, 0>(p, d, s); break;
+        case GC_FORM_NRM: gc_launch_k<BM, BN, WM, WN, EPI, false, false, false, true, 0>(p, d, s); break;
+        case GC_FORM_FLAT32: gc_launch_k<BM, BN, WM, WN, EPI, false, false, false, false, 32>(p, d, s); break;
+        case GC_FORM_FLAT36: gc_launch_k<BM, BN, WM, WN, EPI, false, false, false, false, 36>(p, d, s); break;
+        case GC_FORM_FLAT32_NRM: gc_launch_k<BM, BN, WM, WN, EPI, false, false, false, true, 32>(p, d, s); break;
+        case GC_FORM_FLAT36_NRM: gc_launch_k<BM, BN, WM, WN, EPI, false, false, false, true, 36>(p, d, s); break;
+        default: SE_CHECK(false, "gc_launch: unknown kernel form");
+    }
+}
+template <int BM, int BN, int WM, int WN>
+static void gc_dispatch_epi(const GCParams& p, const GCDispatch& d, hipStream_t s) {
+    switch (p.epi) {
+        case EPI_ACT: gc_dispatch_form<BM, BN, WM, WN, EPI_ACT>(p, d, s); break;
+        case EPI_ADD: gc_dispatch_form<BM, BN, WM, WN, EPI_ADD>(p, d, s); break;
+        case EPI_MUL: gc_dispatch_form<BM, BN, WM, WN, EPI_MUL>(p, d, s); break;
+        case EPI_GLU: gc_dispatch_form<BM, BN, WM, WN, EPI_GLU>(p, d, s); break;
+        case EPI_CMB: gc_dispatch_form<BM, BN, WM, WN, EPI_CMB>(p, d, s); break;
+        case EPI_LSTM: gc_dispatch_form<BM, BN, WM, WN, EPI_LSTM>(p, d, s); break;
+        default: SE_CHECK(false, "unknown epilogue");
+    }
+}
+static void gc_dispatch_tile(const GCParams& p, const GCDispatch& d, hipStream_t s) {
+    if (d.BM == 128 && d.BN == 128) gc_dispatch_epi<128, 128, 2, 2>(p, d, s);
+    else if (d.BM == 64 && d.BN == 128) gc_dispatch_epi<64, 128, 2, 2>(p, d, s);
+    else if (d.BM == 32 && d.BN == 128) gc_dispatch_epi<32, 128, 1, 4>(p, d, s);
+    else if (d.BM == 128 && d.BN == 64) gc_dispatch_epi<128, 64, 4, 1>(p, d, s);
+    else if (d.BM == 64 && d.BN == 64) gc_dispatch_epi<64, 64, 2, 2>(p, d, s);
+    else if (d.BM == 128 && d.BN == 32) gc_dispatch_epi<128, 32, 4, 1>(p, d, s);
+    else if (d.BM == 64 && d.BN == 256) gc_dispatch_epi<64, 256, 1, 4>(p, d, s);
+    else if (d.BM == 128 && d.BN == 256) gc_dispatch_epi<128, 256, 2, 2>(p, d, s);
+    else SE_CHECK(false, "no gemmconv tile config");
+}
+
+// The per-launch values of a dispatch into the kernel's arguments; a geometry other than the plan's own is swapped in
+static void gc_apply(const GCPlan& pl, const GCDispatch& d, GCParams& p) {
+    p.C0 = d.C0;
+    if (d.early) return;
+    if (d.geom != GC_G_MAIN) {
+        const GCTail& g = pl.geom[d.geom];
+        p.Wp = g.Wp;
+        p.tab = g.g.tab;
+        p.desc = g.g.desc;
+        p.desc4 = g.g.desc4;
+    }
+    p.t_base = d.t_base;
+    p.n_ttiles = d.n_ttiles;
+    p.Qt = d.Qt;
+    p.qt2 = d.qt2;
+    p.qq_off = d.qq_off;
+    p.nrows = d.nrows;
+    p.dbg = d.dbg;
+    p.pw4 = d.pw4;
+    p.trim = d.trim;
+    if (d.nbuf) p.nbuf = d.nbuf;
+    if (d.flat_upr) {
+        p.flat_upr = d.flat_upr;
+        p.flat_units = d.flat_units;
+    }
+}
+static void gc_dispatch(const GCPlan& pl, const GCSelIn& in, const GCDispatch& d, GCParams p, hipStream_t stream) {
+    gc_apply(pl, d, p);
+    switch (d.family) {
+        case GC_FAM_THIN: gc_launch_thin(p, d, stream); break;
+        case GC_FAM_DIRECT:
+        case GC_FAM_DIRECT_LDS:
+            if (p.M <= 1) gc_launch_direct<1>(p, pl.small, d, stream);
+            else if (p.M <= 2) gc_launch_direct<2>(p, pl.small, d, stream);
+            else gc_launch_direct<4>(p, pl.small, d, stream);
+            break;
+        default: gc_dispatch_tile(p, d, stream);
+    }
+    gc_log_launch(in, d, p.gru);
+}
+
+void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
+    const GCSelIn in = gc_sel_in(&pl, p);
+    if (g_select_log) g_select_log->push_back(in);
+    const GCChoice ch = gc_select(in);
+    if (ch.has_tail) gc_dispatch(pl, in, ch.tail, p, stream);       // (the tail first)
+    gc_dispatch(pl, in, ch.main, p, stream);
+}
+
+bool gc_nrm_supported(const GCPlan& pl) {
+    static const bool on = !(getenv("SE_IN_FOLD") && atoi(getenv("SE_IN_FOLD")) == 0);
+    return on && !pl.p.Ws && pl.p.epi == EPI_ACT && pl.BM == 64 && pl.p.causal && pl.p.Z == 1 && pl.p.C0 + pl.p.C1 <= GC_NRM_MAXC;
+}
+
+bool gc_stats_supported(const GCPlan& pl) { return gc_stats_tile(pl.p.Ws != nullptr, pl.p.epi, pl.BM); }
+
+// ---- plans
 // Device tables of one patch geometry (row stride Wp): frequency rows / tap table / K-row patch offsets, and the
 // per-(thread, slot) descriptors of the patch seen as single frames and as 16 B groups of 4 frames.
-GCGeom gc_build_geom(const TapSpec& taps, const std::vector<int>& rows, int dtmin, int nrows, int Wp, int cic, int KC, int NB) {
+static GCGeom gc_build_geom(const TapSpec& taps, const GCGeomShape& gs, int dtmin, int cic, int KC, int NB) {
     GCGeom g;
+    const int nrows = gs.nrows, Wp = gs.Wp;
+    const int* rows = gs.rows;
     std::vector<int> tab(GC_TAB_KOFF + GC_MAX_KCP + 8, 0);
     for (int r = 0; r < nrows; ++r) tab[r] = rows[r];
     for (int j = 0; j < taps.ntaps; ++j) {
-        tab[GC_MAX_ROWS + j] = (int)(std::find(rows.begin(), rows.end(), taps.df[j]) - rows.begin());
+        tab[GC_MAX_ROWS + j] = (int)(std::find(rows, rows + nrows, taps.df[j]) - rows);
         tab[GC_MAX_ROWS + GC_MAX_TAPS + j] = taps.dt[j];
     }
     for (int k = 0; k < KC; ++k) {       // k = cil * ntaps + j
@@ -1681,156 +1796,40 @@ GCGeom gc_build_geom(const TapSpec& taps, const std::vector<int>& rows, int dtmi
 GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float>& w, const std::vector<float>& bias,
                     const std::vector<float>& slope, int act, int epi, int si, int so, int po, int tout_hint, int Z,
                     int C0split) {
-    const int C0 = (C0split < 0 || C0split > Cin) ? Cin : C0split;
-    SE_CHECK(taps.ntaps >= 1 && taps.ntaps <= GC_MAX_TAPS, "tap count");
+    const GCPlanShape sh = gc_plan_shape(M, Cin, taps, epi, si, tout_hint, Z, C0split);
     SE_CHECK((long)w.size() == (long)Z * M * Cin * taps.ntaps, "weight size mismatch in gc_make_plan");
     GCPlan pl;
     GCParams& p = pl.p;
-    pl.BM = M >= 96 ? 128 : (M >= 48 ? 64 : 32);
-    {   // memory-bound pointwise layers (<= 128 input channels, <= 384 rows: Uformer's conformer, the TCM blocks' 64 -> 256 layers) on
-        // 64-row tiles: twice the workgroups in flight, each small enough to spread its DMAs over the matrix loop
-        // (SE_GC_PW_BM64=k: input-channel limit, 0 = 128-row tiles; Uformer + 1.1 %, the others unchanged)
-        static const int pw64 = getenv("SE_GC_PW_BM64") ? atoi(getenv("SE_GC_PW_BM64")) : 128;
-        if (pw64 > 0 && taps.ntaps == 1 && Cin <= pw64 && M >= 96 && M <= 384 && epi != EPI_LSTM) pl.BM = 64;
-    }
-    pl.BN = (tout_hint >= 96 || pl.BM == 32) ? 128 : 64;
-    // distinct rows / dt span
-    int dtmin = taps.dt[0], dtmax = taps.dt[0];
-    std::vector<int> rows;
-    for (int j = 0; j < taps.ntaps; ++j) {
-        dtmin = std::min(dtmin, taps.dt[j]);
-        dtmax = std::max(dtmax, taps.dt[j]);
-        if (std::find(rows.begin(), rows.end(), taps.df[j]) == rows.end()) rows.push_back(taps.df[j]);
-    }
-    std::sort(rows.begin(), rows.end());
-    SE_CHECK((int)rows.size() <= GC_MAX_ROWS, "too many distinct frequency rows");
+    pl.BM = sh.BM;
+    pl.BN = sh.BN;
+    pl.lookback = sh.lookback;
+    pl.tail_split = sh.tail_split;
+    pl.flat_uw = sh.flat_uw;
+    pl.qt2_nrows = sh.qt2_nrows;
+    pl.qt2_qoff = sh.qt2_qoff;
+    const int C0 = sh.C0, cic = sh.CI_C;
     p.ntaps = taps.ntaps;
-    p.nrows = (int)rows.size();
+    p.nrows = sh.nrows;
     for (int j = 0; j < taps.ntaps; ++j) {       // the thin kernel reads the taps from its arguments
-        SE_CHECK(taps.df[j] >= -32768 && taps.df[j] <= 32767 && taps.dt[j] >= -32768 && taps.dt[j] <= 32767, "tap offset range");
         p.tdf[j] = (short)taps.df[j];
         p.tdt[j] = (short)taps.dt[j];
     }
-    // patch geometry: the staged time window starts a multiple of 4 frames before the tile (origin t0 - pad4) so that it
-    // decomposes into 16 B groups that never straddle frame 0 (t0 is a multiple of BN): LDS column w <-> frame t0 + dtmin + w
-    p.causal = dtmax <= 0;
-    pl.lookback = std::max(-dtmin, 0);                      // frames of history the taps reach back (frame-online mode)
-    dtmin = -((std::max(-dtmin, 0) + 3) & ~3);
-    dtmax = (std::max(dtmax, 0) + 3) & ~3;
-    p.dtmin = dtmin;
-    p.Wp = pl.BN + (dtmax - dtmin);                         // LDS row stride of the patch (multiple of 4)
-    SE_CHECK(p.nrows * p.Wp <= gc_bld_max(pl.BM) * 256, "tap span too wide for one staged patch");
-    // chunking: largest CI_C within the staging budgets
-    // chunk = CI_C input channels x all taps.  Among the sizes that fit the staging budgets take the one that wastes the
-    // fewest K rows on padding to a multiple of 4 (rows of zeros cost full MFMAs), then the largest: measured on the DCCRN
-    // bench, 20 exact rows per barrier beat 30 rows padded to 32 (taps = 10), 24 beat 30 / 32 (taps = 6)
-    int cic = 1;
-    double best = -1.0;
-    for (int c = 1; c <= std::max(std::max(C0, Cin - C0), 1); ++c) {
-        const int kc = c * taps.ntaps, kcp = (kc + 3) & ~3;
-        // pointwise layers stage 16 B groups (4x the slots) and size the chunk by the LDS budget of 3 blocks per CU
-        const bool pw = taps.ntaps == 1;
-        const int kmax = pw ? (pl.BM >= 128 ? 24 : 32) : gc_kcp_max(pl.BM);
-        const int cap = gc_bld_max(pl.BM) * 256 * (pw ? 4 : 1);
-        if (kcp > kmax || c * p.nrows * p.Wp > cap) continue;
-        // 64-row layers: keep the chunk small enough for the 64 x 256 tile's patch (3 workgroups per CU) when that still
-        // leaves >= 12 K rows per barrier - G2Net's 3-tap convs would stage 8 channels x 3 rows and fall back to 64 x 128
-        // tiles (measured: + 4 % for the whole model at batch 256 with 4-channel chunks)
-        if (pl.BM == 64 && pl.BN == 128 && taps.ntaps > 1 && epi != EPI_LSTM && kc > 12 &&
-            (long)c * p.nrows * (256 + (dtmax - dtmin)) > 4608)
-            continue;
-        const double score = (double)kc / kcp + 1e-4 * kc;       // padding efficiency first, size second
-        if (score > best) {
-            best = score;
-            cic = c;
-        }
-    }
+    p.causal = sh.causal;
+    p.dtmin = sh.dtmin;
+    p.Wp = sh.geom[GC_G_MAIN].Wp;
     p.CI_C = cic;
-    p.KC = cic * taps.ntaps;
-    p.KCp = (p.KC + 3) & ~3;
-    SE_CHECK(p.KCp <= gc_kcp_max(pl.BM), "single-channel chunk exceeds K budget");
-    {
-        GCGeom g = gc_build_geom(taps, rows, dtmin, p.nrows, p.Wp, cic, p.KC, gc_bld_max(pl.BM));
-        pl.dTab = g.tab;
-        pl.dDesc = g.desc;
-        pl.dDesc4 = g.desc4;
-        p.tab = g.tab;
-        p.desc = g.desc;
-        p.desc4 = g.desc4;
-        // narrower geometries for the last, mostly empty time tile of a row (T = 401 fills 17 of 128 columns of its 4th
-        // tile): same weights and chunking, own patch tables; gc_launch sends that tile to a 32- / 64-column kernel
-        // (only where the narrow kernel keeps all four waves busy: 128 rows x 32 columns; a 64-row layer would leave half
-        // its waves on padding again - measured slower than the skip logic of the full-width tile)
-        // (pointwise layers get the geometry for tiny launches only: as a separate tail launch it doubled the launch count
-        // of FullSubNet's per-step LSTM GEMMs)
-        pl.tail_split = taps.ntaps != 1;
-        if (pl.BN == 128 && pl.BM == 128) {
-            pl.tail[0].BN = 32;
-            pl.tail[0].Wp = 32 + (dtmax - dtmin);
-            pl.tail[0].g = gc_build_geom(taps, rows, dtmin, p.nrows, pl.tail[0].Wp, cic, p.KC, gc_bld_max(pl.BM));
+    p.KC = sh.KC;
+    p.KCp = sh.KCp;
+    // same weights and chunking for every geometry, own patch tables
+    for (int g = 0; g < GC_G_COUNT; ++g)
+        if (sh.geom[g].BN) {
+            pl.geom[g].BN = sh.geom[g].BN;
+            pl.geom[g].Wp = sh.geom[g].Wp;
+            pl.geom[g].g = gc_build_geom(taps, sh.geom[g], sh.dtmin, cic, sh.KC, gc_bld_max(sh.BM));
         }
-        // 64-column geometry of the whole layer (tail[1]) for launches that would not fill the chip with 128-column
-        // tiles: the batch is only known at launch time, gc_launch picks
-        // two-row geometry (gc_kernel: qt2): rows of the patch = union of the input rows of two neighbouring output rows,
-        // when that union is an interval and smaller than twice the single-row set
-        if (pl.BN == 128 && epi != EPI_LSTM && taps.ntaps > 1) {
-            std::vector<int> r2 = rows;
-            for (int r : rows)
-                if (std::find(r2.begin(), r2.end(), r + si) == r2.end()) r2.push_back(r + si);
-            std::sort(r2.begin(), r2.end());
-            const bool interval = r2.back() - r2.front() + 1 == (int)r2.size();
-            const int wp2 = 64 + (dtmax - dtmin);
-            if (interval && (int)r2.size() <= GC_MAX_ROWS && (int)r2.size() < 2 * p.nrows &&
-                cic * (int)r2.size() * wp2 <= gc_bld_max(pl.BM) * 256) {
-                pl.qt2.BN = 64;
-                pl.qt2.Wp = wp2;
-                pl.qt2.g = gc_build_geom(taps, r2, dtmin, (int)r2.size(), wp2, cic, p.KC, gc_bld_max(pl.BM));
-                pl.qt2_nrows = (int)r2.size();
-                pl.qt2_qoff = si * wp2;
-            }
-        }
-        // 256-column geometry of a 64-row layer (tail[2]): 1 x 4 waves of 64 x 64 do the 128 x 128 tile's matrix work per
-        // staged K row (the 64 x 128 tile does half of it), for big launches whose rows fill the wide tiles (T = 501: 98 %)
-        if (pl.BN == 128 && pl.BM == 64 && epi != EPI_LSTM && taps.ntaps > 1) {
-            pl.tail[2].BN = 256;
-            pl.tail[2].Wp = 256 + (dtmax - dtmin);
-            pl.tail[2].g = gc_build_geom(taps, rows, dtmin, p.nrows, pl.tail[2].Wp, cic, p.KC, gc_bld_max(pl.BM));
-        }
-        // 256-column geometry of the per-step LSTM GEMM (tail[2] as well; FullSubNet's sub-band layers): 2 x 2 waves of 64 x 128 -
-        // a staged K row feeds twice the matrix work of the 128 x 128 tile and a weight chunk is fetched once per 256 columns.
-        // Measured in round 4 on every 128-row pointwise layer: + 1.7 % on FullSubNet (two streams of step launches fill each
-        // other's tails), 1 - 8 % SLOWER on the LSTM input projections, DPCRN's and the conformer's pointwise layers (two
-        // workgroups per CU instead of three, coarser tails; with loads and epilogue ablated both tiles run the same
-        // 132 - 134 TFLOP/s, so the K loop itself gains nothing) - hence only here
-        static const int wide128_env = getenv("SE_GC_WIDE128") ? atoi(getenv("SE_GC_WIDE128")) : 1;
-        if (wide128_env && pl.BN == 128 && pl.BM == 128 && taps.ntaps == 1 && epi == EPI_LSTM && cic * 256 <= 6 * 1024) {
-            pl.tail[2].BN = 256;
-            pl.tail[2].Wp = 256;
-            pl.tail[2].g = gc_build_geom(taps, rows, dtmin, p.nrows, 256, cic, p.KC, gc_bld_max(pl.BM));
-        }
-        // unit-flattened geometries (GCParams::flat_upr): every 32-frame unit of the tile with its own halo
-        static const int flat_env = getenv("SE_GC_FLAT") ? atoi(getenv("SE_GC_FLAT")) : 1;
-        if (flat_env && pl.BM == 64 && pl.BN == 128 && epi != EPI_LSTM && p.causal && dtmin >= -4 && Z == 1) {
-            const int uw = 32 - dtmin;      // 32 or 36
-            pl.flat_uw = uw;
-            const int nbk = gc_bld_max(pl.BM);
-            if ((long)cic * p.nrows * 4 * uw <= (long)nbk * 256 * 4) {
-                pl.flat[0].BN = 128;
-                pl.flat[0].Wp = 4 * uw;
-                pl.flat[0].g = gc_build_geom(taps, rows, dtmin, p.nrows, 4 * uw, cic, p.KC, nbk);
-            }
-            if (pl.BM == 64 && (long)cic * p.nrows * 8 * uw <= 4608) {      // (5 x 256 groups, 3 workgroups' LDS - as the plain 64 x 256 tile)
-                pl.flat[1].BN = 256;
-                pl.flat[1].Wp = 8 * uw;
-                pl.flat[1].g = gc_build_geom(taps, rows, dtmin, p.nrows, 8 * uw, cic, p.KC, nbk);
-            }
-        }
-        if (pl.BN == 128 && (pl.BM == 64 || pl.BM == 128) && epi != EPI_LSTM) {
-            pl.tail[1].BN = 64;
-            pl.tail[1].Wp = 64 + (dtmax - dtmin);
-            pl.tail[1].g = gc_build_geom(taps, rows, dtmin, p.nrows, pl.tail[1].Wp, cic, p.KC, gc_bld_max(pl.BM));
-        }
-    }
+    p.tab = pl.geom[GC_G_MAIN].g.tab;
+    p.desc = pl.geom[GC_G_MAIN].g.desc;
+    p.desc4 = pl.geom[GC_G_MAIN].g.desc4;
     const int nch0 = (C0 + cic - 1) / cic, nch1 = (Cin - C0 + cic - 1) / cic;
     p.nchunks = nch0 + nch1;
     p.M = M;
@@ -1871,14 +1870,10 @@ GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float
         pl.dWs = to_device(ws);
         p.Ws = pl.dWs;
         // exact tap extents for the LDS-tiled form of the direct kernel
-        pl.small.dfmin = pl.small.dfmax = taps.df[0];
-        pl.small.dtmin = pl.small.dtmax = taps.dt[0];
-        for (int j = 1; j < taps.ntaps; ++j) {
-            pl.small.dfmin = std::min(pl.small.dfmin, taps.df[j]);
-            pl.small.dfmax = std::max(pl.small.dfmax, taps.df[j]);
-            pl.small.dtmin = std::min(pl.small.dtmin, taps.dt[j]);
-            pl.small.dtmax = std::max(pl.small.dtmax, taps.dt[j]);
-        }
+        pl.small.dfmin = *std::min_element(taps.df, taps.df + taps.ntaps);
+        pl.small.dfmax = *std::max_element(taps.df, taps.df + taps.ntaps);
+        pl.small.dtmin = *std::min_element(taps.dt, taps.dt + taps.ntaps);
+        pl.small.dtmax = *std::max_element(taps.dt, taps.dt + taps.ntaps);
     }
     if (!bias.empty()) {
         SE_CHECK((long)bias.size() == (long)Z * M, "bias size");
@@ -1894,465 +1889,16 @@ GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float
     return pl;
 }
 
-// Device ranges whose tensors may be over-read by up to 12 B past their last element (the engine arenas: every
-// allocation is followed by more arena or by the arena's tail slack).  Pointwise layers stage their patch in 16 B groups;
-// a group that straddles the end of a row only feeds output columns that are never stored, so the only requirement on
-// the over-read is that it stays inside mapped memory.
-static std::vector<std::pair<const char*, const char*>>& gc_safe_ranges() {
-    static std::vector<std::pair<const char*, const char*>> r;
-    return r;
-}
-static std::mutex& gc_safe_mutex() {       // engines may be created / destroyed from different host threads
-    static std::mutex m;
-    return m;
-}
-void gc_register_overread_range(const void* lo, size_t bytes) {
-    std::lock_guard<std::mutex> lk(gc_safe_mutex());
-    gc_safe_ranges().emplace_back(static_cast<const char*>(lo), static_cast<const char*>(lo) + bytes);
-}
-void gc_unregister_overread_range(const void* lo) {
-    std::lock_guard<std::mutex> lk(gc_safe_mutex());
-    auto& r = gc_safe_ranges();
-    for (size_t i = 0; i < r.size(); ++i)
-        if (r[i].first == lo) {
-            r.erase(r.begin() + i);
-            return;
-        }
-}
-static bool gc_overread_ok(const void* ptr) {
-    if (!ptr) return true;
-    std::lock_guard<std::mutex> lk(gc_safe_mutex());
-    for (const auto& r : gc_safe_ranges())
-        if (ptr >= r.first && static_cast<const char*>(ptr) + 16 <= r.second) return true;
-    return false;
-}
-
 void gc_free_plan(GCPlan& pl) {
-    if (pl.dA) (void)hipFree(pl.dA);
-    if (pl.dWs) (void)hipFree(pl.dWs);
-    if (pl.dDesc) (void)hipFree(pl.dDesc);
-    if (pl.dDesc4) (void)hipFree(pl.dDesc4);
-    pl.dDesc4 = nullptr;
-    if (pl.qt2.g.tab) (void)hipFree(pl.qt2.g.tab);
-    if (pl.qt2.g.desc) (void)hipFree(pl.qt2.g.desc);
-    if (pl.qt2.g.desc4) (void)hipFree(pl.qt2.g.desc4);
-    pl.qt2 = GCTail{};
-    for (auto& t : pl.tail) {
-        if (t.g.tab) (void)hipFree(t.g.tab);
-        if (t.g.desc) (void)hipFree(t.g.desc);
-        if (t.g.desc4) (void)hipFree(t.g.desc4);
+    for (GCTail& t : pl.geom) {
+        for (void* d : {(void*)t.g.tab, (void*)t.g.desc, (void*)t.g.desc4})
+            if (d) (void)hipFree(d);
         t = GCTail{};
     }
-    for (auto& t : pl.flat) {
-        if (t.g.tab) (void)hipFree(t.g.tab);
-        if (t.g.desc) (void)hipFree(t.g.desc);
-        if (t.g.desc4) (void)hipFree(t.g.desc4);
-        t = GCTail{};
+    for (float** d : {&pl.dA, &pl.dWs, &pl.dBias, &pl.dSlope, &pl.dBiasPad, &pl.dPostScale, &pl.dPostShift}) {
+        if (*d) (void)hipFree(*d);
+        *d = nullptr;
     }
-    pl.dWs = nullptr;
-    pl.dDesc = nullptr;
-    if (pl.dBias) (void)hipFree(pl.dBias);
-    if (pl.dSlope) (void)hipFree(pl.dSlope);
-    if (pl.dTab) (void)hipFree(pl.dTab);
-    if (pl.dBiasPad) (void)hipFree(pl.dBiasPad);
-    if (pl.dPostScale) (void)hipFree(pl.dPostScale);
-    if (pl.dPostShift) (void)hipFree(pl.dPostShift);
-    pl.dPostScale = pl.dPostShift = nullptr;
-    pl.dTab = nullptr;
-    pl.dBiasPad = nullptr;
-    pl.dA = pl.dBias = pl.dSlope = nullptr;
-}
-
-// kernel variants with unit-flattened column tiles (GCParams::flat_upr) that are instantiated: the tiles whose last time tile
-// of a T = 401 row is mostly padding, for the epilogues the zoo uses on them
-// (64-row tiles only.  Measured in round 6 on one box, batch 256, T = 401, flattened against plain tiles with identical output
-// hashes: 64 -> 64 channels at F = 79 on the 64 x 256 tile 3.43 -> 3.17 ms; 32 -> 32 channels on the 32 x 128 tile 1.13 -> 1.26 ms -
-// that tile is bound by its staging, not by matrix slots, and a unit's own halo is 9 % more bytes; 64 -> 128 channels on the
-// 128 x 128 tile 5.61 -> 5.63 ms against three full tiles + the 32-column tail launch, CTSNet as a whole 3 138 -> 3 017 utt/s)
-constexpr bool gc_flat_inst(int BM, int BN, int EPI, int UWv) {
-    const bool tile = BM == 64 && (BN == 256 || BN == 128);
-    if (!tile) return false;
-    if (UWv == 36) return EPI == EPI_ACT || EPI == EPI_GLU || (EPI == EPI_CMB && BN == 256);
-    if (UWv == 32) return EPI == EPI_ACT || (EPI == EPI_ADD && BN == 128);
-    return false;
-}
-static bool gc_flat_supported(int BM, int BN, int epi, int uw) {
-    switch (epi) {
-        case EPI_ACT: return gc_flat_inst(BM, BN, EPI_ACT, uw);
-        case EPI_ADD: return gc_flat_inst(BM, BN, EPI_ADD, uw);
-        case EPI_GLU: return gc_flat_inst(BM, BN, EPI_GLU, uw);
-        case EPI_CMB: return gc_flat_inst(BM, BN, EPI_CMB, uw);
-        default: return false;
-    }
-}
-template <int BM, int BN, int WM, int WN, int EPI, bool NRMv, int UWv>
-static void gc_launch_flat_k(const GCParams& p, long nblk, size_t lds, hipStream_t stream) {
-    static bool attr_fl[64] = {};
-    if (first_on_device(attr_fl)) {
-        SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gc_kernel<BM, BN, WM, WN, EPI, false, false, false, NRMv, UWv>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, false, false, false, NRMv, UWv>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
-    SE_HIP(hipGetLastError());
-    gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN);
-}
-
-template <int BM, int BN, int WM, int WN, int EPI, bool RES = false>
-static void gc_launch_e(const GCParams& p_in, hipStream_t stream) {
-    // epilogue: 4*BM row parameters + one transposition strip per wave (rows x (cols + 4))
-    const size_t epi = (size_t)(4 * (BM / WM) * 36) * sizeof(float);
-    const size_t lds = gc_lds_bytes(p_in, BM, epi, RES ? p_in.nbuf : 2);
-    static bool attr_set[64] = {};
-    if (first_on_device(attr_set)) {
-        SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gc_kernel<BM, BN, WM, WN, EPI, RES>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    const long nblk = (long)p_in.Z * (p_in.flat_upr ? 1 : p_in.B) * p_in.Qt * p_in.n_ttiles * p_in.n_mtiles;
-    SE_CHECK(nblk > 0 && nblk < (1L << 31), "grid size");
-    const GCParams& p = p_in;
-    if (p.flat_upr) {        // unit-flattened column tiles (gc_launch decided; only the instantiated variants get here)
-        const int uw = p.Wp / (BN / 32);
-        SE_CHECK(!RES && !p.fz && !p.trim && !p.qt2 && p.pw4 && p.t_base == 0, "gc_launch: flattened tiles on a launch they do not cover");
-        const bool nrm = p.nrm0 || p.nrm1;
-        if constexpr (!RES && gc_flat_inst(BM, BN, EPI, 36)) {
-            if (uw == 36) {
-                if constexpr (EPI == EPI_ACT && BM == 64) {
-                    if (nrm) {
-                        SE_CHECK(p.causal && p.Z == 1 && p.C0 + p.C1 <= GC_NRM_MAXC, "gc_launch: on-the-fly InstanceNorm needs causal taps and <= 128 input channels");
-                        SE_CHECK(gc_flat_rows_spanned(p.B, p.flat_upr, BN / 32) <= GC_FLAT_NRM_ROWS,
-                                 "gc_launch: a flattened tile with on-the-fly InstanceNorm would span more batch rows than it holds parameters for");
-                        gc_launch_flat_k<BM, BN, WM, WN, EPI, true, 36>(p, nblk, lds, stream);
-                        return;
-                    }
-                }
-                SE_CHECK(!nrm, "gc_launch: this flattened variant cannot normalise its sources on the fly");
-                gc_launch_flat_k<BM, BN, WM, WN, EPI, false, 36>(p, nblk, lds, stream);
-                return;
-            }
-        }
-        if constexpr (!RES && gc_flat_inst(BM, BN, EPI, 32)) {
-            if (uw == 32) {
-                if constexpr (EPI == EPI_ACT && BM == 64) {
-                    if (nrm) {
-                        SE_CHECK(p.causal && p.Z == 1 && p.C0 + p.C1 <= GC_NRM_MAXC, "gc_launch: on-the-fly InstanceNorm needs causal taps and <= 128 input channels");
-                        SE_CHECK(gc_flat_rows_spanned(p.B, p.flat_upr, BN / 32) <= GC_FLAT_NRM_ROWS,
-                                 "gc_launch: a flattened tile with on-the-fly InstanceNorm would span more batch rows than it holds parameters for");
-                        gc_launch_flat_k<BM, BN, WM, WN, EPI, true, 32>(p, nblk, lds, stream);
-                        return;
-                    }
-                }
-                SE_CHECK(!nrm, "gc_launch: this flattened variant cannot normalise its sources on the fly");
-                gc_launch_flat_k<BM, BN, WM, WN, EPI, false, 32>(p, nblk, lds, stream);
-                return;
-            }
-        }
-        SE_CHECK(false, "gc_launch: no flattened variant of this kernel");
-    }
-    if constexpr ((EPI == EPI_ACT || EPI == EPI_ADD) && !RES) {
-        if (p.fz) {          // branch interaction folded into the store (GCParams::fz)
-            SE_CHECK(!p.trim && !p.stats, "gc_launch: no trimming / statistics variant of the kernel with the folded interaction");
-            static bool attr_fz[64] = {};
-            if (first_on_device(attr_fz)) {
-                SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gc_kernel<BM, BN, WM, WN, EPI, false, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
-            hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, false, false, true>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
-            SE_HIP(hipGetLastError());
-            gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN);
-            return;
-        }
-    }
-    SE_CHECK(!p.fz, "gc_launch: this kernel variant cannot fold the branch interaction into its store");
-    if constexpr (EPI == EPI_ACT && BM == 64 && !RES) {
-        if (p.nrm0 || p.nrm1) {      // sources normalised on the fly (GCParams::nrm0 / nrm1)
-            SE_CHECK(!p.trim && p.causal && !p.qt2 && p.Z == 1 && p.C0 + p.C1 <= GC_NRM_MAXC,
-                     "gc_launch: on-the-fly InstanceNorm needs causal taps, one-row tiles and <= 128 input channels");
-            static bool attr_nrm[64] = {};
-            if (first_on_device(attr_nrm)) {
-                SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gc_kernel<BM, BN, WM, WN, EPI, false, false, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
-            hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, false, false, false, true>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
-            SE_HIP(hipGetLastError());
-            gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN);
-            return;
-        }
-    }
-    SE_CHECK(!p.nrm0 && !p.nrm1, "gc_launch: this kernel variant cannot normalise its sources on the fly");
-    if constexpr (EPI == EPI_ACT && !RES) {
-        if (p.trim) {
-            static bool attr_trim[64] = {};
-            if (first_on_device(attr_trim)) {
-                SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gc_kernel<BM, BN, WM, WN, EPI, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
-            hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, false, true>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
-            SE_HIP(hipGetLastError());
-            gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN);
-            return;
-        }
-    }
-    SE_CHECK(!p.trim, "gc_launch: no trimming variant of this kernel");
-    hipLaunchKernelGGL((gc_kernel<BM, BN, WM, WN, EPI, RES>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
-    SE_HIP(hipGetLastError());
-    gc_log_launch(GC_FAM_TILE, p, nblk, BM, BN, RES);
-}
-
-template <int BM, int BN, int WM, int WN, bool RES = false>
-static void gc_launch_t(const GCParams& p, hipStream_t stream) {
-    switch (p.epi) {
-        case EPI_ACT: gc_launch_e<BM, BN, WM, WN, EPI_ACT, RES>(p, stream); break;
-        case EPI_ADD: gc_launch_e<BM, BN, WM, WN, EPI_ADD, RES>(p, stream); break;
-        case EPI_MUL: gc_launch_e<BM, BN, WM, WN, EPI_MUL, RES>(p, stream); break;
-        case EPI_GLU: gc_launch_e<BM, BN, WM, WN, EPI_GLU, RES>(p, stream); break;
-        case EPI_CMB:
-            if constexpr (!RES && BM >= 64) gc_launch_e<BM, BN, WM, WN, EPI_CMB>(p, stream);
-            else SE_CHECK(false, "no resident-K / 32-row form of the combine epilogue");
-            break;
-        case EPI_LSTM:
-            if constexpr (!RES) gc_launch_e<BM, BN, WM, WN, EPI_LSTM>(p, stream);
-            else SE_CHECK(false, "no resident-K form of the LSTM step");
-            break;
-        default: SE_CHECK(false, "unknown epilogue");
-    }
-}
-// all chunks of a source resident in LDS at once (gc_kernel RES): launches of at most one workgroup per CU whose staging fits
-static bool gc_resident_fits(GCParams& p, int BM, int BM_div_WM) {
-    if (p.trim || p.epi == EPI_LSTM || p.epi == EPI_CMB || p.fz || p.nrm0 || p.nrm1 || p.cstats) return false;
-    const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;
-    const int nch0 = p.C0 > 0 ? (p.C0 + p.CI_C - 1) / p.CI_C : 0, nch1 = p.C1 > 0 ? (p.C1 + p.CI_C - 1) / p.CI_C : 0;
-    int nb = std::max(std::max(nch0, nch1), 1);
-    // (few frames per row: the chunks of the frame-online mode.  A batch-1 offline decode has as few workgroups, but 64
-    // frames of matrix work per chunk to hide the next load under - the double-buffered loop is 1-3 % faster there)
-    if (nblk > 256 || nb <= 2 || p.Tout - p.t_base > 64) return false;
-    // as many chunks per round trip as the LDS holds (a longer source goes in groups)
-    const size_t epi = (size_t)(4 * BM_div_WM * 36) * sizeof(float);
-    while (nb > 2 && gc_lds_bytes(p, BM, epi, nb) > 158 * 1024) --nb;
-    if (nb <= 2) return false;
-    p.nbuf = nb;
-    return true;
-}
-
-bool gc_nrm_supported(const GCPlan& pl) {
-    static const bool on = !(getenv("SE_IN_FOLD") && atoi(getenv("SE_IN_FOLD")) == 0);
-    return on && !pl.p.Ws && pl.p.epi == EPI_ACT && pl.BM == 64 && pl.p.causal && pl.p.Z == 1 && pl.p.C0 + pl.p.C1 <= GC_NRM_MAXC;
-}
-
-bool gc_stats_supported(const GCPlan& pl) {
-    return !pl.p.Ws && (pl.p.epi == EPI_GLU || (pl.p.epi == EPI_ACT && pl.BM == 64));
-}
-
-void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
-    // p.t_base (default 0): first output frame of the launch - frame-online chunks only produce the frames behind their
-    // history columns.  A multiple of 4, so that the 16 B staging groups keep their alignment to frame 0.
-    SE_CHECK(p.C0 == pl.p.C0 && p.C1 == pl.p.C1, "gc_launch: source channel split differs from the plan");
-    SE_CHECK(!p.dst_elu || (p.epi == EPI_GLU && p.Z == 1), "gc_launch: the second (ELU) store belongs to the gated epilogue");
-    if (p.epi == EPI_LSTM && p.first_step && p.C1 == 0) p.C0 = 0;       // h_{-1} = 0: no matrix work (a step that also projects its input keeps both)
-    g_flat_nrm_refused = 0;
-    if (p.t_base > 0 && gc_thin_launch(p, stream)) return;       // (any first frame)
-    if (p.tb_soft) p.t_base &= ~3;
-    const int tb = p.t_base, Tspan = p.Tout - tb;
-    SE_CHECK(tb >= 0 && (tb & 3) == 0 && Tspan > 0, "gc_launch: first output frame must be a multiple of 4 below Tout");
-    SE_CHECK(tb == 0 || (!p.stats && !p.cstats), "gc_launch: the statistics epilogue needs whole rows");
-    p.n_ttiles = (Tspan + pl.BN - 1) / pl.BN;
-    p.Qt = p.Q;
-    p.qt2 = 0;
-    p.qq_off = 0;
-    static const int dbg_env = getenv("SE_GC_DBG") ? atoi(getenv("SE_GC_DBG")) : 0;
-    p.dbg = dbg_env;
-    // patch offsets inside one staged chunk are 32-bit (the 64-bit part of an address is the per-block / per-chunk base)
-    SE_CHECK((double)p.CI_C * (double)std::max(p.s0_c, p.s1_c) + (double)p.Fin * (double)std::max(p.s0_f, p.s1_f) + p.Tin < 1.0e9,
-             "gc_launch: source plane too large for 32-bit patch byte offsets");
-    // 16 B staging groups: exact when no group straddles the end of a row (Tin % 4 == 0); for causal tap sets a straddling
-    // group only feeds output frames >= Tin, which are never stored - then it merely has to stay inside mapped memory
-    // (a tap set that looks ahead would read the straddling group's foreign frames into stored outputs: the kernel trims
-    // them in LDS, GC_TRIM_TAIL)
-    // the trimming variant exists for the plain epilogue (DCCRN's decoder); it pays from a few thousand workgroups on - small
-    // launches are latency-bound and the extra LDS stores per chunk cost them 3 % (batch 1)
-    constexpr long trim_min = 8192;
-    const bool trim_ok = p.epi == EPI_ACT && (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles >= trim_min;
-    p.pw4 = (p.desc4 && (p.Tin % 4 == 0 || ((p.causal || trim_ok) && gc_overread_ok(p.src0) && gc_overread_ok(p.src1)))) ? 1 : 0;
-    p.trim = (p.pw4 && !p.causal && p.Tin % 4 != 0) ? 1 : 0;
-    SE_CHECK(!p.stats || gc_stats_supported(pl), "gc_launch: this tile configuration has no statistics epilogue");
-    SE_CHECK(!p.cstats || (gc_stats_supported(pl) && p.n_mtiles == 1 && p.Z == 1),
-             "gc_launch: column statistics need a statistics tile configuration and one m-tile (M " + std::to_string(p.M) + ", BM " +
-                 std::to_string(pl.BM) + ", m-tiles " + std::to_string(p.n_mtiles) + ", epilogue " + std::to_string(p.epi) + ", direct " +
-                 std::to_string(p.Ws != nullptr) + ")");
-    SE_CHECK(p.pw4 || p.CI_C * p.nrows * p.Wp <= gc_bld_max(pl.BM) * 256,
-             "pointwise layer with a row length that is not a multiple of 4 needs its sources inside the engine arena");
-    if (gc_thin_launch(p, stream)) return;
-    if (p.Ws) {
-        SE_CHECK(!p.fz, "gc_launch: the direct (<= 4 channel) path cannot fold the branch interaction into its store");
-        SE_CHECK(!p.dst_elu, "gc_launch: the direct (<= 4 channel) path has no second (ELU) store");
-        SE_CHECK(!p.nrm0 && !p.nrm1, "gc_launch: the direct (<= 4 channel) path cannot normalise its sources on the fly");
-        if (p.M <= 1) gc_small_launch<1>(p, pl.small, stream);
-        else if (p.M <= 2) gc_small_launch<2>(p, pl.small, stream);
-        else gc_small_launch<4>(p, pl.small, stream);
-        return;
-    }
-    // small launches: 64-column tiles double the workgroup count (and waste less of the last time tile: T = 401 is
-    // 6.3 x 64).  Measured on the TCM models: 64-row layers gain up to ~1 500 workgroups of 128 columns (G2Net + 7 % at
-    // B = 64, + 4 % at B = 256, + 16 % at B = 8; DCCRN's big grids lose 1 %), 128-row layers only below one workgroup
-    // per CU (B = 8: + 15 %; B = 64: - 3 %)
-    {
-        const GCTail& alt = pl.tail[1];
-        const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;
-        static const int alt_n64 = getenv("SE_GC_ALT_N64") ? atoi(getenv("SE_GC_ALT_N64")) : 4096;
-        if (alt.BN == 64 && nblk < (pl.BM == 64 ? alt_n64 : 256)) {
-            GCParams pa = p;
-            pa.n_ttiles = (Tspan + 63) / 64;
-            pa.Wp = alt.Wp;
-            pa.tab = alt.g.tab;
-            pa.desc = alt.g.desc;
-            pa.desc4 = alt.g.desc4;
-            constexpr long alt32_max = 512;      // 64-column workgroup count below which a 128-row layer uses 32-column tiles
-            const long nblk64 = (long)p.Z * p.B * p.Q * pa.n_ttiles * p.n_mtiles;
-            if (pl.BM == 128 && pl.tail[0].BN == 32 && nblk64 < alt32_max) {       // tiny launches: 32 columns
-                pa.n_ttiles = (Tspan + 31) / 32;
-                pa.Wp = pl.tail[0].Wp;
-                pa.tab = pl.tail[0].g.tab;
-                pa.desc = pl.tail[0].g.desc;
-                pa.desc4 = pl.tail[0].g.desc4;
-                if (gc_resident_fits(pa, 128, 32)) gc_launch_t<128, 32, 4, 1, true>(pa, stream);
-                else gc_launch_t<128, 32, 4, 1>(pa, stream);
-                return;
-            }
-            if (pl.BM == 64) {
-                if (gc_resident_fits(pa, 64, 32)) gc_launch_t<64, 64, 2, 2, true>(pa, stream);
-                else gc_launch_t<64, 64, 2, 2>(pa, stream);
-            } else {
-                gc_launch_t<128, 64, 4, 1>(pa, stream);
-            }
-            return;
-        }
-    }
-    // unit-flattened column tiles (GCParams::flat_upr): equal-length offline batches whose rows do not fill their last time tile.
-    // T = 401 is 13 units of 32 frames: 2 tiles of 256 / 4 tiles of 128 columns per row hold 16, the flattened batch needs
-    // 13 B / 8 (or / 4) tiles - 19 % fewer workgroups for the same stored values
-    {
-        static const int flat_env = getenv("SE_GC_FLAT") ? atoi(getenv("SE_GC_FLAT")) : 1;
-        constexpr long flat_min = 1024;
-        static const long wide_min = getenv("SE_GC_WIDE_MIN") ? atol(getenv("SE_GC_WIDE_MIN")) : 6144;
-        const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;      // (128-column tiles)
-        const int upr = (Tspan + 31) / 32;
-        const double sbmax = 4.0 * (double)std::max(p.s0_b, p.s1_b);
-        // (flattened tiles take precedence over the two-row tiles where both apply)
-        if (flat_env && pl.BM == 64 && pl.flat_uw && tb == 0 && p.pw4 && !p.trim && !p.fz && p.Z == 1 && nblk >= flat_min && p.B > 1) {
-            // tile width as the plain path would choose it
-            const bool wide = pl.BM == 64 && pl.flat[1].BN == 256 && nblk >= wide_min && gc_flat_supported(64, 256, p.epi, pl.flat_uw);
-            const GCTail& fg = wide ? pl.flat[1] : pl.flat[0];
-            const int upt = wide ? 8 : 4;
-            const long tiles_plain = (long)p.B * ((Tspan + 32 * upt - 1) / (32 * upt));
-            const long tiles_flat = ((long)p.B * upr + upt - 1) / upt;
-            // (a unit of a later batch row adds (rows ahead) x batch stride to a 32-bit byte offset)
-            const double span = ((double)(upt + upr - 1) / upr + 1.0) * sbmax;
-            // a normalising tile holds the InstanceNorm parameters of GC_FLAT_NRM_ROWS batch rows: rows shorter than a tile
-            // (wide: upr 1, 2, 3, 5; narrow: upr 1) would put three or more rows into some tiles - those launches keep the plain tiles
-            const int nrm_rows = (p.nrm0 || p.nrm1) ? gc_flat_rows_spanned(p.B, upr, upt) : 0;
-            const bool nrm_ok = nrm_rows <= GC_FLAT_NRM_ROWS;
-            const bool flat_ok = fg.BN && gc_flat_supported(pl.BM, fg.BN, p.epi, pl.flat_uw) && tiles_flat * 100 <= tiles_plain * 94 &&
-                                 span < 3.0e9;
-            if (flat_ok && !nrm_ok) g_flat_nrm_refused = nrm_rows;
-            if (flat_ok && nrm_ok) {
-                GCParams pa = p;
-                pa.flat_upr = upr;
-                pa.flat_units = p.B * upr;
-                pa.n_ttiles = (int)tiles_flat;
-                pa.Wp = fg.Wp;
-                pa.tab = fg.g.tab;
-                pa.desc = fg.g.desc;
-                pa.desc4 = fg.g.desc4;
-                if (wide) gc_launch_t<64, 256, 1, 4>(pa, stream);
-                else gc_launch_t<64, 128, 2, 2>(pa, stream);
-                return;
-            }
-        }
-    }
-    // big launches of a 64-row layer: 64 x 256 tiles when the patch goes in 16 B groups (4 x fewer slots), the rows fill the
-    // wide tiles and the staging buffers leave room for 3 workgroups per CU
-    {
-        const GCTail& wd = pl.tail[2];
-        static const long wide_min = getenv("SE_GC_WIDE_MIN") ? atol(getenv("SE_GC_WIDE_MIN")) : 6144;
-        const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;
-        const int nt = (Tspan + 255) / 256;
-        static const int wide_fill = getenv("SE_GC_WIDE_FILL") ? atoi(getenv("SE_GC_WIDE_FILL")) : 75;
-        if (wd.BN == 256 && pl.BM == 64 && p.pw4 && nblk >= wide_min && Tspan * 100 >= nt * 256 * wide_fill &&
-            (long)p.CI_C * p.nrows * wd.Wp <= 4608 /* 5 x 256 groups, 3 workgroups' LDS */) {
-            GCParams pa = p;
-            pa.n_ttiles = nt;
-            pa.Wp = wd.Wp;
-            pa.tab = wd.g.tab;
-            pa.desc = wd.g.desc;
-            pa.desc4 = wd.g.desc4;
-            gc_launch_t<64, 256, 1, 4>(pa, stream);
-            return;
-        }
-    }
-    // big launches of the per-step LSTM GEMM: 128 x 256 tiles (two workgroups per CU)
-    {
-        const GCTail& wd = pl.tail[2];
-        constexpr long wide128_min = 1536;      // 128-column workgroup count from which the 128 x 256 tile is used
-        constexpr int wide128_fill = 75;        // least fill of the wide tiles in percent
-        const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;
-        const int nt = (Tspan + 255) / 256;
-        if (wd.BN == 256 && pl.BM == 128 && p.epi == EPI_LSTM && p.pw4 && !p.trim && !p.stats && nblk >= wide128_min &&
-            Tspan * 100L >= (long)nt * 256 * wide128_fill) {
-            GCParams pa = p;
-            pa.n_ttiles = nt;
-            pa.Wp = wd.Wp;
-            pa.tab = wd.g.tab;
-            pa.desc = wd.g.desc;
-            pa.desc4 = wd.g.desc4;
-            gc_launch_e<128, 256, 2, 2, EPI_LSTM>(pa, stream);
-            return;
-        }
-    }
-    // big launches of layers whose neighbouring output rows share input rows: two-row tiles (2 x 64 frames)
-    {
-        static const long qt2_min = getenv("SE_GC_QT2_MIN") ? atol(getenv("SE_GC_QT2_MIN")) : 4096;
-        const long nblk = (long)p.Z * p.B * p.Q * p.n_ttiles * p.n_mtiles;
-        if (pl.qt2.BN == 64 && pl.BN == 128 && p.Q >= 2 && !p.stats && !p.cstats && p.pad_lo == 0 && p.epi != EPI_LSTM &&
-            !p.nrm0 && !p.nrm1 && nblk >= qt2_min) {
-            GCParams pa = p;
-            pa.qt2 = 1;
-            pa.qq_off = pl.qt2_qoff;
-            pa.nrows = pl.qt2_nrows;
-            pa.Qt = (p.Q + 1) / 2;
-            pa.n_ttiles = (Tspan + 63) / 64;
-            pa.Wp = pl.qt2.Wp;
-            pa.tab = pl.qt2.g.tab;
-            pa.desc = pl.qt2.g.desc;
-            pa.desc4 = pl.qt2.g.desc4;
-            if (pl.BM == 128) gc_launch_t<128, 128, 2, 2>(pa, stream);
-            else if (pl.BM == 64) gc_launch_t<64, 128, 2, 2>(pa, stream);
-            else gc_launch_t<32, 128, 1, 4>(pa, stream);
-            return;
-        }
-    }
-    // the last time tile of a row, when it is at most half full, goes to a narrower kernel (own launch, same weights)
-    const int full = Tspan / pl.BN, rem = Tspan - full * pl.BN;
-    const GCTail* tl = nullptr;
-    if (pl.tail_split && full >= 1 && rem > 0 && pl.tail[0].BN && rem <= pl.tail[0].BN) tl = &pl.tail[0];
-    if (tl) {
-        GCParams pt = p;
-        pt.t_base = tb + full * pl.BN;
-        pt.n_ttiles = 1;
-        pt.Wp = tl->Wp;
-        pt.tab = tl->g.tab;
-        pt.desc = tl->g.desc;
-        pt.desc4 = tl->g.desc4;
-        p.n_ttiles = full;
-        if (pl.BM == 128 && tl->BN == 32) gc_launch_t<128, 32, 4, 1>(pt, stream);
-        else if (pl.BM == 128 && tl->BN == 64) gc_launch_t<128, 64, 4, 1>(pt, stream);
-        else if (pl.BM == 64 && tl->BN == 64) gc_launch_t<64, 64, 2, 2>(pt, stream);
-        else SE_CHECK(false, "no gemmconv tail tile config");
-    }
-    if (pl.BM == 128 && pl.BN == 128) gc_launch_t<128, 128, 2, 2>(p, stream);
-    else if (pl.BM == 64 && pl.BN == 128) gc_launch_t<64, 128, 2, 2>(p, stream);
-    else if (pl.BM == 32 && pl.BN == 128) gc_launch_t<32, 128, 1, 4>(p, stream);
-    else if (pl.BM == 128 && pl.BN == 64) gc_launch_t<128, 64, 4, 1>(p, stream);
-    else if (pl.BM == 64 && pl.BN == 64) gc_launch_t<64, 64, 2, 2>(p, stream);
-    else SE_CHECK(false, "no gemmconv tile config");
 }
 
 }  // namespace se

@@ -4,6 +4,7 @@
 // tests/test_gpu_gemmconv_geometry.py compares the launches with a float64 reference.  Not linked into libse_engine.so.
 #include "../layers.h"
 #include "../kernels.h"
+#include "gc_selin_flat.h"
 #include <string>
 #include <vector>
 
@@ -12,6 +13,7 @@ using namespace se;
 namespace {
 thread_local std::string g_err;
 thread_local std::vector<GCLaunchRec> g_log;
+thread_local std::vector<GCSelIn> g_sel;
 
 struct Probe {
     bool deconv = false;
@@ -116,15 +118,15 @@ int gcp_info(void* h, int cls, int* out, int n) {
                        p->deconv ? (int)deconv_stats_supported(p->dec) : (int)conv_stats_supported(p->conv),
                        g.flat_uw,
                        g.p.Ws != nullptr,
-                       g.flat[0].BN,
-                       g.flat[1].BN,
-                       g.tail[2].BN,
-                       g.qt2.BN,
-                       g.tail[1].BN,
-                       g.tail[0].BN,
+                       g.geom[GC_G_FLAT128].BN,
+                       g.geom[GC_G_FLAT256].BN,
+                       g.geom[GC_G_N256].BN,
+                       g.geom[GC_G_QT2].BN,
+                       g.geom[GC_G_N64].BN,
+                       g.geom[GC_G_N32].BN,
                        g.p.CI_C,
                        g.p.nrows,
-                       g.tail[2].Wp,
+                       g.geom[GC_G_N256].Wp,
                        (int)g.tail_split,
                        g.p.po,
                        g.p.so};
@@ -147,7 +149,9 @@ int gcp_run(void* h, const float* x0, const float* nrm0, const float* x1, const 
         rg.tlen = tlen;
         SE_HIP(hipDeviceSynchronize());
         g_log.clear();
+        g_sel.clear();
         gc_set_launch_log(&g_log);
+        gc_set_select_log(&g_sel);
         if (tlen) set_ragged_ctx(&rg);
         try {
             if (p->deconv) run_deconv(p->dec, a0, s1, dst, dstC, Fout, B, T, Tp, 0, nullptr, stats);
@@ -155,10 +159,12 @@ int gcp_run(void* h, const float* x0, const float* nrm0, const float* x1, const 
         } catch (...) {
             set_ragged_ctx(nullptr);
             gc_set_launch_log(nullptr);
+            gc_set_select_log(nullptr);
             throw;
         }
         set_ragged_ctx(nullptr);
         gc_set_launch_log(nullptr);
+        gc_set_select_log(nullptr);
         SE_HIP(hipDeviceSynchronize());
     });
 }
@@ -173,6 +179,15 @@ int gcp_launch_get(int i, long long* out, int n) {
                              r.nrm,    r.res,   r.trim,   r.stats,    r.ragged, r.flat_nrm_refused, r.nblk};
     for (int k = 0; k < n && k < 14; ++k) out[k] = v[k];
     return 14;
+}
+
+// gc_launch calls of the last gcp_run, and what call i gave gc_select: GCSelIn as GC_SELIN_FIELDS integers in the order of the
+// struct's declaration (gc_selin_flat.h; tests/test_gc_select_host.py SELIN names them)
+int gcp_select_count() { return (int)g_sel.size(); }
+int gcp_select_get(int i, long long* out, int n) {
+    if (i < 0 || i >= (int)g_sel.size() || n < GC_SELIN_FIELDS) return -1;
+    gc_selin_flatten(g_sel[i], out);
+    return GC_SELIN_FIELDS;
 }
 
 int gcp_flat_rows_spanned(int B, int upr, int upt) { return gc_flat_rows_spanned(B, upr, upt); }
