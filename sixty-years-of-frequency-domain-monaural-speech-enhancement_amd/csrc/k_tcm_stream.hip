@@ -18,6 +18,7 @@
 // chunk size.
 #include "kernels.h"
 #include "common.h"
+#include "online_log.h"
 
 namespace se {
 
@@ -326,6 +327,10 @@ void tcm_stream_free(TcmStreamW& f) {
     }
 }
 
+// launch record of launch_tcm_chain (online_log.h); null outside tests
+static thread_local std::vector<NormLaunchRec>* g_online_log = nullptr;
+void online_set_launch_log(std::vector<NormLaunchRec>* log) { g_online_log = log; }
+
 void launch_tcm_chain(const TcmStreamW* const* f, const TcmFusedHeads* hd, const int* dil, const int* K, int nblk, const float* x,
                       float* y, hipStream_t s) {
     StreamCtx* cx = stream_ctx();
@@ -359,6 +364,11 @@ void launch_tcm_chain(const TcmStreamW* const* f, const TcmFusedHeads* hd, const
     else if (ks == 5) hipLaunchKernelGGL(tcm_chain_kernel<5>, dim3(cx->B), dim3(256), lds, s, a);
     else SE_CHECK(false, "tcm_stream: dilated conv with 3 or 5 taps expected");
     SE_HIP(hipGetLastError());
+    if (g_online_log) {
+        NormLaunchRec r;
+        r.kernel = "tcm_chain"; r.grid = cx->B; r.block = 256; r.shmem = (long)lds; r.KS = ks;
+        g_online_log->push_back(r);
+    }
 }
 
 }  // namespace se
