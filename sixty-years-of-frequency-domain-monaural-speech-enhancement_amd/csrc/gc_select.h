@@ -296,6 +296,8 @@ struct GCLaunchRec {
                                  // more than GC_FLAT_NRM_ROWS rows (value: rows spanned)
     long nblk = 0;               // workgroups
     int epi = 0, gru = 0;        // the launch's epilogue (EPI_LSTM: one recurrent step; gru: its GRU cell)
+    int form = GC_FORM_PLAIN;    // GCForm of a GC_FAM_TILE dispatch
+    int Z = 1;                   // grouped launches: products per dispatch (blockIdx.z)
 };
 inline GCLaunchRec gc_launch_rec(const GCSelIn& in, const GCDispatch& d, int gru) {
     GCLaunchRec r;
@@ -315,6 +317,8 @@ inline GCLaunchRec gc_launch_rec(const GCSelIn& in, const GCDispatch& d, int gru
     r.nblk = d.nblk;
     r.epi = in.epi;
     r.gru = gru;
+    r.form = d.form;
+    r.Z = in.Z;
     return r;
 }
 
