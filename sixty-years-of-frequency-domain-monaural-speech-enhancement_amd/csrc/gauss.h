@@ -160,12 +160,15 @@ inline TapSpec deconv52_taps(int par, int toff, std::vector<int>& sel) {
 }
 // grouped plans of a (5, 2) conv, stride 2 along frequency (encoder) / of both parity classes of its transposed form (decoder;
 // wr / wi: [co][ci][10] real matrices, ci = all complex input channels, the first c0split of them from the first source)
-inline void make_conv_plans(GaussLayer& g, const DenseW& wr, const DenseW& wi, int tout) {
+// edge_Fin > 0 (opt-in, the deep layers of DCCRN): the input plane's rows - output rows whose frequency taps partly lie outside it
+// run on the live K rows only (gc_make_plan: edge classes)
+inline void make_conv_plans(GaussLayer& g, const DenseW& wr, const DenseW& wi, int tout, int edge_Fin = 0) {
     g.co = wr.M;
-    g.pl.push_back(gc_make_plan(wr.M, wr.Cin, conv52_taps(), three_products(wr.w, wi.w), {}, {}, ACT_NONE, EPI_ACT, 2, 1, 0, tout, 3));
+    g.pl.push_back(gc_make_plan(wr.M, wr.Cin, conv52_taps(), three_products(wr.w, wi.w), {}, {}, ACT_NONE, EPI_ACT, 2, 1, 0, tout, 3, -1,
+                                edge_Fin, edge_Fin / 2));
     g.pl.back().flop_scale = 4.0 / 3.0;          // the profiler books the reference's four products
 }
-inline void make_deconv_plans(GaussLayer& g, const DenseW& wr, const DenseW& wi, int toff, int c0split, int tout) {
+inline void make_deconv_plans(GaussLayer& g, const DenseW& wr, const DenseW& wi, int toff, int c0split, int tout, int edge_Fin = 0) {
     const int co = wr.M, ci = wr.Cin;
     g.co = co;
     for (int par = 0; par < 2; ++par) {
@@ -178,7 +181,8 @@ inline void make_deconv_plans(GaussLayer& g, const DenseW& wr, const DenseW& wi,
                     r[((size_t)m * ci + c) * ts.ntaps + j] = wr.w[((size_t)m * ci + c) * 10 + sel[j]];
                     i[((size_t)m * ci + c) * ts.ntaps + j] = wi.w[((size_t)m * ci + c) * 10 + sel[j]];
                 }
-        g.pl.push_back(gc_make_plan(co, ci, ts, three_products(r, i), {}, {}, ACT_NONE, EPI_ACT, 1, 2, par, tout, 3, c0split));
+        g.pl.push_back(gc_make_plan(co, ci, ts, three_products(r, i), {}, {}, ACT_NONE, EPI_ACT, 1, 2, par, tout, 3, c0split, edge_Fin,
+                                    edge_Fin));      // (each parity class makes Fin of the 2 Fin output rows)
         g.pl.back().flop_scale = 4.0 / 3.0;
     }
 }

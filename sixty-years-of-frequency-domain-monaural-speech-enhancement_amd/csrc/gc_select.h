@@ -222,6 +222,68 @@ inline GCPlanShape gc_plan_shape(int M, int Cin, const TapSpec& taps, int epi, i
     return s;
 }
 
+// ------------------------------------------------------------------------------------------------ edge-row classes
+// Output rows whose frequency taps partly lie outside the input plane multiply those taps against the zeros of the padding.  A
+// plan that opts in (gc_make_plan: edge_Fin / edge_Q) gives such rows K tables and packed weights of their own that list the
+// live K rows only.  Rows with the same dead taps form a class; class 0 has nothing dead.  The kernel's row-to-class rule is
+// "row 0, row Q - 1, everything else", so classes are built only when every other row is whole, and at most GC_EDGE_MAX of them.
+constexpr int GC_EDGE_MAX = 2;
+struct GCEdgeShape {
+    int nclass = 0;                           // further classes built (0: the plan behaves as one without)
+    int cls_lo = 0, cls_hi = 0;               // class of output row 0 / of row Q - 1
+    int Fin = 0, Q = 0;                       // the plane the classes hold for
+    unsigned dead[GC_EDGE_MAX] = {};          // bit j: tap j of the class lies outside the plane
+    int KC[GC_EDGE_MAX] = {};                 // live K rows of a full chunk
+    int KCp[GC_EDGE_MAX] = {};                // ... padded to the K loop's group of two k-pairs
+    int live[GC_EDGE_MAX][GC_MAX_KCP] = {};   // class-0 K row (cil * ntaps + j) of surviving row i, ascending
+};
+// cic: input channels per staged chunk; si: input rows per output row; output row q reads input rows q si + df[j]
+inline GCEdgeShape gc_edge_classes(const TapSpec& taps, int cic, int si, int Fin, int Q) {
+    GCEdgeShape e;
+    if (Fin <= 0 || Q < 2 || taps.ntaps > 31 || cic * taps.ntaps > GC_MAX_KCP) return e;      // (a one-row plane: its row is both edges)
+    auto dead_of = [&](int q) {
+        unsigned d = 0;
+        for (int j = 0; j < taps.ntaps; ++j) {
+            const int f = q * si + taps.df[j];
+            if (f < 0 || f >= Fin) d |= 1u << j;
+        }
+        return d;
+    };
+    for (int q = 1; q + 1 < Q; ++q)
+        if (dead_of(q)) return e;              // an inner row with dead taps would need a class the row rule cannot name
+    const unsigned all = (1u << taps.ntaps) - 1u, dl = dead_of(0), dh = dead_of(Q - 1);
+    if (dl == all || dh == all) return e;
+    int n = 0, lo = 0, hi = 0;
+    unsigned dd[GC_EDGE_MAX] = {};
+    if (dl) {
+        dd[n] = dl;
+        lo = ++n;
+    }
+    if (dh) {
+        if (dh == dl) hi = lo;
+        else {
+            dd[n] = dh;
+            hi = ++n;
+        }
+    }
+    if (n == 0) return e;
+    e.nclass = n;
+    e.cls_lo = lo;
+    e.cls_hi = hi;
+    e.Fin = Fin;
+    e.Q = Q;
+    for (int c = 0; c < n; ++c) {
+        e.dead[c] = dd[c];
+        int k = 0;
+        for (int cil = 0; cil < cic; ++cil)
+            for (int j = 0; j < taps.ntaps; ++j)
+                if (!((dd[c] >> j) & 1u)) e.live[c][k++] = cil * taps.ntaps + j;
+        e.KC[c] = k;
+        e.KCp[c] = (k + 3) & ~3;
+    }
+    return e;
+}
+
 // ------------------------------------------------------------------------------------------------ launch selection
 // Everything the ladder reads of a plan and of one launch.  No addresses: a pointer of GCParams is its presence flag here, so
 // the same launch gives the same bytes on every run (tests/golden/gc_select_parent.jsonl.gz; as integers: tests/gc_selin_flat.h).
@@ -239,6 +301,9 @@ struct GCSelIn {
     int Ws, desc4, stats, cstats, nrm0, nrm1, fz, dst_elu, tlen;
     int overread0, overread1;    // gc_overread_ok(src0), gc_overread_ok(src1)
     GCTuning tun;
+    // the plan has edge-row classes this launch can use (GCEdgeShape; gc_launch).  Behind `tun` and outside the flat form of
+    // tests/gc_selin_flat.h: a recorded launch has none
+    int edge;
 };
 // kernel variant of a tile launch (template arguments RES / TRIM / FZ / NRM / FLATW of gc_kernel)
 enum GCForm : int {
@@ -620,7 +685,8 @@ inline GCChoice gc_select(const GCSelIn& in) {
         return ch;
     }
     // big launches of layers whose neighbouring output rows share input rows: two-row tiles (2 x 64 frames)
-    if (in.g_BN[GC_G_QT2] == 64 && in.BN == 128 && in.Q >= 2 && !in.stats && !in.cstats && in.pad_lo == 0 && in.epi != EPI_LSTM &&
+    // (not with edge-row classes: a two-row tile pairs an edge row with a whole one, and both would run the full K)
+    if (!in.edge && in.g_BN[GC_G_QT2] == 64 && in.BN == 128 && in.Q >= 2 && !in.stats && !in.cstats && in.pad_lo == 0 && in.epi != EPI_LSTM &&
         !in.nrm0 && !in.nrm1 && nblk >= in.tun.qt2_min) {
         d.qt2 = 1;
         d.qq_off = in.qt2_qoff;

@@ -25,6 +25,13 @@ namespace se {
 // chunks are short, 10 MFMAs per wave and barrier, and more resident workgroups fill the gaps: DPCRN / Uformer + 1.5 %)
 constexpr int gc_blocks_per_cu(int BM) { return BM <= 32 ? 6 : 3; }
 
+// One edge-row class of a plan (GCEdgeShape, gc_select.h) as the kernel reads it
+struct GCEdgeClass {
+    const int* tab;          // the class's device table: as GCParams::tab, koff lists the live K rows only
+    const float* A;          // its packed weights [z][nchunks][KCp][Mp] (gc_launch: moved along z with GCParams::A)
+    int KCp;                 // live K rows of a chunk, padded to a multiple of 4
+    int cstride;             // floats of one packed chunk: KCp * Mp
+};
 enum Act : int { ACT_NONE = 0, ACT_PRELU = 1, ACT_ELU = 2, ACT_SOFTPLUS = 3, ACT_SIGMOID = 4, ACT_TANH = 5, ACT_RELU = 6 };
 struct GCParams {
     const float* A;          // packed weights [nchunks][KCp][Mp]
@@ -111,6 +118,11 @@ struct GCParams {
     // A unit is staged with its own halo (32 + 4 columns of LDS per patch row), its own batch row and first frame.
     int flat_upr;            // units per row (0: off)
     int flat_units;          // B * flat_upr
+    // optional (plans built with edge classes; the plain form of gc_kernel on the plan's own one-row tiles, else gc_launch
+    // zeroes the rule): output row 0 runs class ec_lo, row Q - 1 class ec_hi, every other row class 0 = the fields above;
+    // class c > 0 is ec[c - 1].  Zero everywhere else
+    int ec_lo, ec_hi;
+    GCEdgeClass ec[GC_EDGE_MAX];
 };
 // Device tables of one patch geometry (owned by the plan)
 struct GCGeom {
@@ -148,13 +160,19 @@ struct GCPlan {
     float* dBiasPad = nullptr;
     float* dPostScale = nullptr;
     float* dPostShift = nullptr;
+    GCEdgeShape edge;        // edge-row classes (nclass = 0: none) with their device weights and tables, owned by the plan
+    float* dAe[GC_EDGE_MAX] = {};
+    int* dTabE[GC_EDGE_MAX] = {};
 };
 
 // Build a plan.  w_logical[m][ci][j] (row-major, M x Cin x ntaps) are the effective real weights
 // (BatchNorm folded, complex structure expanded) for this tap set.  bias/slope may be empty.
+// edge_Fin / edge_Q > 0 (opt-in; SE_GC_EDGE=0, read at every call, turns it off): the layer runs on a plane of edge_Fin input and
+// edge_Q output rows (of this plan: one parity class) - output rows whose taps partly lie outside it get K tables and weights
+// of the live K rows only (gc_edge_classes).  A launch on another plane runs as a plan without.
 GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float>& w_logical,
                     const std::vector<float>& bias, const std::vector<float>& slope, int act, int epi,
-                    int si, int so, int po, int tout_hint, int z = 1, int C0split = -1);
+                    int si, int so, int po, int tout_hint, int z = 1, int C0split = -1, int edge_Fin = 0, int edge_Q = 0);
 void gc_free_plan(GCPlan& pl);
 
 // Device ranges (the engine arenas) whose tensors may be over-read by <= 12 B past their end (pointwise 16 B staging).

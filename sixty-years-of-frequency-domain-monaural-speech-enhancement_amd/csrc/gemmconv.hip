@@ -206,8 +206,7 @@ __global__ __launch_bounds__(256, RES ? 1 : (FZ || (BM >= 128 && BN >= 256)) ? (
     // 16 B groups under taps that look ahead in time, rows that are not whole groups: see GC_TRIM_TAIL (block-uniform)
     constexpr bool fixt = TRIM;
     const int bit4 = (npatch / 4 + 255) >> 8;
-    const int nA4 = p.KCp * (BM / 4);
-    const int ait = (nA4 + 255) >> 8;                // float4 groups of the weight chunk per thread (uniform)
+    const int ait = (p.KCp * (BM / 4) + 255) >> 8;   // float4 groups of the weight chunk per thread (uniform; every edge class issues class 0's count)
     const int As_sz = ait * 1024;                    // padded so that every thread stores unconditionally
     const int Bs_sz = bit * 256;                     // padded: every thread stores unconditionally
     const int nbuf = RES ? p.nbuf : 2;               // double-buffered staging (RES: one buffer per chunk of a source)
@@ -251,7 +250,26 @@ __global__ __launch_bounds__(256, RES ? 1 : (FZ || (BM >= 128 && BN >= 256)) ? (
     const int t0 = FLAT ? p.t_base + (u0 - b * p.flat_upr) * 32 : p.t_base + ttile * (qt2 ? BN / 2 : BN);
     const int m0 = mt * BM;
 
+    // edge-row classes (GCParams::ec; plain form on one-row tiles only - every other form runs the full table, which is always
+    // correct): the workgroup's output row picks the K table, the packed weights, their chunk stride and the K rows per chunk.
+    // Block-uniform scalars; the staging of the patch, the LDS layout and the number of DMAs per chunk are class 0's
+    // (only where the layers that opt in run - tiles of at most 128 columns with the plain or the combine epilogue: every other
+    // variant keeps its code as it was)
+    constexpr bool EDGE = !RES && !TRIM && !FZ && !NRM && !FLAT && BN <= 128 && (EPI == EPI_ACT || EPI == EPI_CMB);
+    const int* __restrict__ tabg = p.tab;
     const float* __restrict__ Ag = p.A + (long)z * p.A_z + m0;
+    int kcp = p.KCp, cstride = p.KCp * p.Mp;
+    if constexpr (EDGE) {
+        const int ecls = (p.ec_lo | p.ec_hi) == 0 || qt2 ? 0 : __builtin_amdgcn_readfirstlane(q == 0 ? p.ec_lo : (q == p.Q - 1 ? p.ec_hi : 0));
+        if (ecls) {
+            const GCEdgeClass ec = ecls == 1 ? p.ec[0] : p.ec[1];
+            tabg = ec.tab;
+            kcp = ec.KCp;
+            cstride = ec.cstride;
+            Ag = ec.A + (long)z * p.nchunks * ec.cstride + m0;
+        }
+    }
+    const int nA4 = kcp * (BM / 4);                  // (rows beyond the class's K rows: the clamped DMAs land in the padding of As)
 
     // patch offsets of the K rows of one chunk (identical for every chunk): lane half `hi` serves row 2*kp + hi of
     // k-pair kp.  They live in registers indexed at compile time (the MFMA loop is fully unrolled over k-pairs), so no
@@ -283,7 +301,7 @@ __global__ __launch_bounds__(256, RES ? 1 : (FZ || (BM >= 128 && BN >= 256)) ? (
     GC_T(7);      /* kernel entry .. index decode */
     // one barrier for both block-wide LDS initialisations: the tap table (its global load is in flight while the patch
     // buffers are cleared) and the zeros of the padding (masked DMA lanes never touch their LDS words again)
-    const int tabv = (tid < GC_TAB_KOFF + KCP_MAX + 8) ? p.tab[tid] : 0;
+    const int tabv = (tid < GC_TAB_KOFF + KCP_MAX + 8) ? tabg[tid] : 0;
     // per-row epilogue parameters (bias, PReLU slope, GLU post scale / shift) are fetched here, under the rest of the
     // prologue, and parked in LDS: the epilogue then has no global load and no block barrier in front of its stores
     const int fo = q * p.so + p.po;
@@ -509,7 +527,7 @@ __global__ __launch_bounds__(256, RES ? 1 : (FZ || (BM >= 128 && BN >= 256)) ? (
                 if (e < bit) gc_dma4_masked_s(Bc, boff[e], bl + 1024u * e, vbits, 1u << e);         \
             });                                                                                    \
         }                                                                                          \
-        const float* __restrict__ Ac = Ag + (long)(gchunk + (CH)) * p.KCp * p.Mp;                  \
+        const float* __restrict__ Ac = Ag + (long)(gchunk + (CH)) * cstride;                       \
         /* wave-uniform LDS base of this wave's 1 KB slice */                                      \
         const unsigned Adw = __builtin_amdgcn_readfirstlane(lds_addr(As + (BUF) * As_sz)) + 1024u * wave_u; \
         static_for<A_IT>([&](auto I) {                                                             \
@@ -583,7 +601,7 @@ __global__ __launch_bounds__(256, RES ? 1 : (FZ || (BM >= 128 && BN >= 256)) ? (
 #pragma unroll
                 for (int j = 0; j < TN; ++j) nkd[j] = utab[4 * min(wn * TN + j, UPT - 1)] * KCP_MAX;
             }
-            const int npair = p.KCp >> 1;
+            const int npair = kcp >> 1;
             // software pipeline, depth 1: the operands of k-pair kp+1 are fetched (ds_read2_b32) before the MFMAs of
             // k-pair kp issue; sched_group_barrier pins "2 DS reads, then 4 MFMAs" so the LDS latency sits under
             // 256 cycles of matrix work.  Reads one pair past the chunk (valid LDS, result unused).
@@ -1538,6 +1556,7 @@ static GCSelIn gc_sel_in(const GCPlan* pl, const GCParams& p) {
         s.overread0 = straddle && gc_overread_ok(p.src0);
         s.overread1 = straddle && gc_overread_ok(p.src1);
         s.tun = gc_tuning_env();
+        s.edge = pl->edge.nclass > 0 && p.Fin == pl->edge.Fin && p.Q == pl->edge.Q;
     }
     s.CI_C = p.CI_C; s.nrows = p.nrows; s.KCp = p.KCp; s.causal = p.causal;
     s.epi = p.epi; s.Z = p.Z; s.B = p.B; s.Q = p.Q; s.M = p.M; s.n_mtiles = p.n_mtiles;
@@ -1698,6 +1717,8 @@ static void gc_dispatch_tile(const GCParams& p, const GCDispatch& d, hipStream_t
 // The per-launch values of a dispatch into the kernel's arguments; a geometry other than the plan's own is swapped in
 static void gc_apply(const GCPlan& pl, const GCDispatch& d, GCParams& p) {
     p.C0 = d.C0;
+    // edge-row classes hold for the plan's own tables on one-row tiles of the plain form (gc_kernel: EDGE)
+    if (d.early || d.family != GC_FAM_TILE || d.geom != GC_G_MAIN || d.form != GC_FORM_PLAIN || d.qt2) p.ec_lo = p.ec_hi = 0;
     if (d.early) return;
     if (d.geom != GC_G_MAIN) {
         const GCTail& g = pl.geom[d.geom];
@@ -1738,6 +1759,13 @@ static void gc_dispatch(const GCPlan& pl, const GCSelIn& in, const GCDispatch& d
 
 void gc_launch(const GCPlan& pl, GCParams p, hipStream_t stream) {
     const GCSelIn in = gc_sel_in(&pl, p);
+    if (!in.edge) {
+        p.ec_lo = p.ec_hi = 0;      // no classes, or a plane other than the one they were built for
+    } else if (p.A != pl.p.A) {     // a launch of some of the plan's z (gauss.h): the classes' weights move along z with A
+        const long zoff = (p.A - pl.p.A) / pl.p.A_z;
+        SE_CHECK(pl.p.A + zoff * pl.p.A_z == p.A && zoff >= 0 && zoff + p.Z <= pl.p.Z, "gc_launch: weights of a plan with edge classes moved by other than whole z");
+        for (int c = 0; c < pl.edge.nclass; ++c) p.ec[c].A = pl.p.ec[c].A + zoff * pl.p.nchunks * pl.p.ec[c].cstride;
+    }
     if (g_select_log) g_select_log->push_back(in);
     const GCChoice ch = gc_select(in);
     if (ch.has_tail) gc_dispatch(pl, in, ch.tail, p, stream);       // (the tail first)
@@ -1795,7 +1823,7 @@ static GCGeom gc_build_geom(const TapSpec& taps, const GCGeomShape& gs, int dtmi
 
 GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float>& w, const std::vector<float>& bias,
                     const std::vector<float>& slope, int act, int epi, int si, int so, int po, int tout_hint, int Z,
-                    int C0split) {
+                    int C0split, int edge_Fin, int edge_Q) {
     const GCPlanShape sh = gc_plan_shape(M, Cin, taps, epi, si, tout_hint, Z, C0split);
     SE_CHECK((long)w.size() == (long)Z * M * Cin * taps.ntaps, "weight size mismatch in gc_make_plan");
     GCPlan pl;
@@ -1858,6 +1886,33 @@ GCPlan gc_make_plan(int M, int Cin, const TapSpec& taps, const std::vector<float
     p.A_z = (long)per_z;
     pl.dA = to_device(packed);
     p.A = pl.dA;
+    // edge-row classes (opt-in): per class the live K rows of every chunk in class 0's order, padded with zero-weight rows, and
+    // the main geometry's table with koff of those rows.  SE_GC_EDGE=0 (read here, at every call): none
+    const char* edge_env = getenv("SE_GC_EDGE");
+    if (edge_Fin > 0 && edge_Q > 0 && !(edge_env && atoi(edge_env) == 0) && p.nchunks > 0) {
+        pl.edge = gc_edge_classes(taps, cic, si, edge_Fin, edge_Q);
+        std::vector<int> tab0(GC_TAB_KOFF + GC_MAX_KCP + 8);
+        if (pl.edge.nclass) SE_HIP(hipMemcpy(tab0.data(), p.tab, tab0.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int c = 0; c < pl.edge.nclass; ++c) {
+            const int kcp = pl.edge.KCp[c], kc = pl.edge.KC[c];
+            const size_t per_zc = (size_t)p.nchunks * kcp * p.Mp;
+            std::vector<float> pk(per_zc * Z, 0.f);
+            for (int z = 0; z < Z; ++z)
+                for (int ch = 0; ch < p.nchunks; ++ch)
+                    for (int i = 0; i < kc; ++i)
+                        std::copy_n(packed.begin() + z * per_z + ((size_t)ch * p.KCp + pl.edge.live[c][i]) * p.Mp, p.Mp,
+                                    pk.begin() + z * per_zc + ((size_t)ch * kcp + i) * p.Mp);
+            std::vector<int> tab = tab0;
+            std::fill(tab.begin() + GC_TAB_KOFF, tab.end(), 0);
+            for (int i = 0; i < kc; ++i) tab[GC_TAB_KOFF + i] = tab0[GC_TAB_KOFF + pl.edge.live[c][i]];
+            pl.dAe[c] = to_device(pk);
+            SE_HIP(hipMalloc(&pl.dTabE[c], tab.size() * sizeof(int)));
+            SE_HIP(hipMemcpy(pl.dTabE[c], tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+            p.ec[c] = GCEdgeClass{pl.dTabE[c], pl.dAe[c], kcp, kcp * p.Mp};
+        }
+        p.ec_lo = pl.edge.cls_lo;
+        p.ec_hi = pl.edge.cls_hi;
+    }
     // direct path (gc_small_kernel): plain weights [z][ci][tap][MM] for layers with <= 4 output channels
     if (M <= 4 && (epi == EPI_ACT || epi == EPI_ADD || epi == EPI_MUL || (epi == EPI_GLU && M % 2 == 0))) {
         const int MM = M <= 1 ? 1 : (M <= 2 ? 2 : 4);
@@ -1895,6 +1950,13 @@ void gc_free_plan(GCPlan& pl) {
             if (d) (void)hipFree(d);
         t = GCTail{};
     }
+    for (int c = 0; c < GC_EDGE_MAX; ++c) {
+        if (pl.dAe[c]) (void)hipFree(pl.dAe[c]);
+        if (pl.dTabE[c]) (void)hipFree(pl.dTabE[c]);
+        pl.dAe[c] = nullptr;
+        pl.dTabE[c] = nullptr;
+    }
+    pl.edge = GCEdgeShape{};
     for (float** d : {&pl.dA, &pl.dWs, &pl.dBias, &pl.dSlope, &pl.dBiasPad, &pl.dPostScale, &pl.dPostShift}) {
         if (*d) (void)hipFree(*d);
         *d = nullptr;

@@ -134,7 +134,9 @@ class Dccrn final : public Model {
                              &mu = sd.get(p + "1.running_mean", {2 * co}), &va = sd.get(p + "1.running_var", {2 * co});
             const std::vector<float> slope = prelu_slopes(sd.get(p + "2.weight"), 2 * co);
             if (gauss_on && k >= GENC) {
-                gauss::make_conv_plans(genc[k], wr, wi, tout);
+                // (encoder 4 - 5 and decoder 0 - 1, planes of 16 rows and fewer: 3 of every 5 F_out row-taps of a layer multiply zero
+                // padding - their edge rows run on the live taps only)
+                gauss::make_conv_plans(genc[k], wr, wi, tout, k >= 4 ? 256 >> k : 0);
                 gauss::fold_tail(genc[k], w.bias, ga, be, mu, va, slope);
             }
             fold_bn(w, ga, be, mu, va);
@@ -162,7 +164,7 @@ class Dccrn final : public Model {
                                  &mu = sd.get(p + "1.running_mean", {2 * co}), &va = sd.get(p + "1.running_var", {2 * co});
                 slope = prelu_slopes(sd.get(p + "2.weight"), 2 * co);
                 if (gauss_on && k < GDEC) {      // complex input channels: [previous (ci / 2) | skip (ci / 2)] (:197)
-                    gauss::make_deconv_plans(gdec[k], wr, wi, toff, /*c0split*/ ci / 2, tout);
+                    gauss::make_deconv_plans(gdec[k], wr, wi, toff, /*c0split*/ ci / 2, tout, k <= 1 ? 4 << k : 0);
                     gauss::fold_tail(gdec[k], w.bias, ga, be, mu, va, slope);
                 }
                 fold_bn(w, ga, be, mu, va);

@@ -213,8 +213,8 @@ void epp_unregister_overread(const void* p) { gc_unregister_overread_range(p); }
 
 // ---- three-product layers.  wr / wi [co][ci][5][2]; bias, bn = {gamma, beta, mean, var}, slope: [2 co] rows [real; imag]
 // deconv = 0: the (5, 2) conv, frequency stride 2, pad 2, one frame of look-back; else its transposed form with toff / c0split
-void* epp_gauss_create(const float* wr, const float* wi, const float* bias, const float* bn, const float* slope, int co, int ci, int deconv,
-                       int toff, int c0split) {
+static void* gauss_create(const float* wr, const float* wi, const float* bias, const float* bn, const float* slope, int co, int ci, int deconv,
+                          int toff, int c0split, int tout, int edge_Fin) {
     Gauss* out = nullptr;
     guarded([&] {
         auto* p = new Gauss();
@@ -222,8 +222,8 @@ void* epp_gauss_create(const float* wr, const float* wi, const float* bias, cons
         p->C0 = c0split < 0 ? ci : c0split;
         try {
             const DenseW dr = dense(wr, nullptr, co, ci, 5, 2), di = dense(wi, nullptr, co, ci, 5, 2);
-            if (deconv) gauss::make_deconv_plans(p->g, dr, di, toff, c0split, 401);
-            else gauss::make_conv_plans(p->g, dr, di, 401);
+            if (deconv) gauss::make_deconv_plans(p->g, dr, di, toff, c0split, tout, edge_Fin);
+            else gauss::make_conv_plans(p->g, dr, di, tout, edge_Fin);
             const int n = 2 * co;
             gauss::fold_tail(p->g, std::vector<float>(bias, bias + n), host(bn, n), host(bn + n, n), host(bn + 2 * n, n), host(bn + 3 * n, n),
                              std::vector<float>(slope, slope + n));
@@ -234,6 +234,23 @@ void* epp_gauss_create(const float* wr, const float* wi, const float* bias, cons
         out = p;
     });
     return out;
+}
+void* epp_gauss_create(const float* wr, const float* wi, const float* bias, const float* bn, const float* slope, int co, int ci, int deconv,
+                       int toff, int c0split) {
+    return gauss_create(wr, wi, bias, bn, slope, co, ci, deconv, toff, c0split, 401, 0);
+}
+// the same layer planned for rows of `tout` frames, with edge-row classes for a plane of edge_Fin input rows (0: none)
+void* epp_gauss_create_edge(const float* wr, const float* wi, const float* bias, const float* bn, const float* slope, int co, int ci,
+                            int deconv, int toff, int c0split, int tout, int edge_Fin) {
+    return gauss_create(wr, wi, bias, bn, slope, co, ci, deconv, toff, c0split, tout, edge_Fin);
+}
+// edge-row classes of the layer's plan `cls`: [0] classes built, [1] class of row 0, [2] class of row Q - 1
+int epp_gauss_edge_info(void* h, int cls, int* out) {
+    const Gauss* p = static_cast<const Gauss*>(h);
+    if (cls < 0 || cls >= (int)p->g.pl.size()) return -1;
+    const GCEdgeShape& e = p->g.pl[cls].edge;
+    out[0] = e.nclass; out[1] = e.cls_lo; out[2] = e.cls_hi;
+    return 3;
 }
 void epp_gauss_destroy(void* h) { delete static_cast<Gauss*>(h); }
 

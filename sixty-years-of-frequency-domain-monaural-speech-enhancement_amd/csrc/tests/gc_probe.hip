@@ -4,6 +4,7 @@
 // tests/test_gpu_gemmconv_geometry.py compares the launches with a float64 reference.  Not linked into libse_engine.so.
 #include "../layers.h"
 #include "../kernels.h"
+#include "../gauss.h"
 #include "gc_selin_flat.h"
 #include <string>
 #include <vector>
@@ -96,6 +97,56 @@ void* gcp_deconv_create(const float* w, const float* bias, const float* slope, i
         pr = p;
     });
     return pr;
+}
+
+// DCCRN's (5, 2) layer with edge-row classes (gc_make_plan: edge_Fin / edge_Q), planned for rows of `tout` frames on a plane of
+// edge_Fin input rows: deconv = 0 the conv (frequency stride 2, pad 2, one frame of look-back, as make_conv_plan(w, 2, 2, 1, 1, 1, ..)),
+// else both parity classes of its transposed form (make_deconv_plan(w, 2, 2, toff, ..)).  w [M][Cin][5][2].  Run with gcp_run.
+// edge_Fin = 0: the same plans without classes
+void* gcp_edge_create(const float* w, const float* bias, const float* slope, int M, int Cin, int deconv, int toff, int act, int c0split,
+                      int tout, int edge_Fin) {
+    Probe* pr = nullptr;
+    guarded([&] {
+        auto* p = new Probe();
+        p->M = M;
+        p->Cin = Cin;
+        p->C0 = c0split < 0 ? Cin : c0split;
+        p->deconv = deconv != 0;
+        const DenseW d = dense(w, bias, M, Cin, 5, 2);
+        const std::vector<float> sl = slope ? std::vector<float>(slope, slope + M) : std::vector<float>();
+        try {
+            if (!deconv) {
+                p->conv = gc_make_plan(M, Cin, gauss::conv52_taps(), d.w, d.bias, sl, act, EPI_ACT, 2, 1, 0, tout, 1, c0split, edge_Fin, edge_Fin / 2);
+            } else {
+                p->dec.sf = 2;
+                for (int par = 0; par < 2; ++par) {
+                    std::vector<int> sel;
+                    const TapSpec ts = gauss::deconv52_taps(par, toff, sel);
+                    std::vector<float> wc((size_t)M * Cin * ts.ntaps);
+                    for (int m = 0; m < M; ++m)
+                        for (int c = 0; c < Cin; ++c)
+                            for (int j = 0; j < ts.ntaps; ++j) wc[((size_t)m * Cin + c) * ts.ntaps + j] = d.w[((size_t)m * Cin + c) * 10 + sel[j]];
+                    p->dec.par.push_back(gc_make_plan(M, Cin, ts, wc, d.bias, sl, act, EPI_ACT, 1, 2, par, tout, 1, c0split, edge_Fin, edge_Fin));
+                }
+            }
+        } catch (...) {
+            delete p;
+            throw;
+        }
+        pr = p;
+    });
+    return pr;
+}
+// edge-row classes of plan `cls`: [0] classes built, [1] class of row 0, [2] class of row Q - 1, [3] Fin, [4] Q, [5] K rows per
+// chunk of class 0, [6] / [7] of classes 1 / 2
+int gcp_edge_info(void* h, int cls, int* out, int n) {
+    const Probe* p = static_cast<const Probe*>(h);
+    const int np = p->deconv ? (int)p->dec.par.size() : 1;
+    if (cls < 0 || cls >= np) return -1;
+    const GCPlan& g = p->deconv ? p->dec.par[cls] : p->conv;
+    const int v[8] = {g.edge.nclass, g.edge.cls_lo, g.edge.cls_hi, g.edge.Fin, g.edge.Q, g.p.KCp, g.edge.KCp[0], g.edge.KCp[1]};
+    for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
+    return 8;
 }
 
 void gcp_destroy(void* h) { delete static_cast<Probe*>(h); }

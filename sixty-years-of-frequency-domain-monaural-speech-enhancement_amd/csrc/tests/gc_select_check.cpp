@@ -88,6 +88,13 @@ int main() {
         EXPECT(b.lookback == 1 && b.dtmin == -4 && b.geom[GC_G_MAIN].Wp == 132 && b.KCp % 4 == 0);
         EXPECT(b.geom[GC_G_QT2].BN == 64 && b.qt2_nrows == 7 && b.qt2_qoff == 2 * b.geom[GC_G_QT2].Wp);
     }
+    {   // edge-row classes of the (5, 2) conv, stride 2, pad 2: two one-row classes from 4 output rows on, none for one row
+        const GCEdgeShape e = gc_edge_classes(t52, 2, 2, 8, 4);
+        EXPECT(e.nclass == 2 && e.cls_lo == 1 && e.cls_hi == 2 && e.dead[0] == 0x00fu && e.dead[1] == 0x300u);
+        EXPECT(e.KC[0] == 12 && e.KCp[0] == 12 && e.KC[1] == 16 && e.KCp[1] == 16 && e.live[0][0] == 4 && e.live[0][6] == 14 && e.live[1][8] == 10);
+        EXPECT(gc_edge_classes(t52, 2, 2, 2, 1).nclass == 0 && gc_edge_classes(t52, 2, 2, 4, 2).nclass == 2);
+        EXPECT(gc_edge_classes(pw, 8, 1, 4, 4).nclass == 0);
+    }
     {   // thin: one frame of a stream, before the preamble (t_base > 0) and after it
         GCSelIn in = launch_of(64, 64, t32, EPI_ACT, 2, 1, 39, 9);
         in.t_base = 8;
@@ -155,6 +162,11 @@ int main() {
         in.overread0 = in.overread1 = 1;
         c = gc_select(in);
         EXPECT(c.main.geom == GC_G_QT2 && c.main.qt2 == 1 && c.main.Qt == 16 && c.main.nrows == in.qt2_nrows && c.main.n_ttiles == 7);
+        in.edge = 1;    // a plan with edge-row classes declines the two-row rung: its own one-row tiles (and the tail split)
+        c = gc_select(in);
+        EXPECT(c.main.geom == GC_G_MAIN && c.main.qt2 == 0 && c.main.Qt == 32 && c.main.BN == 128 && c.main.form == GC_FORM_PLAIN);
+        EXPECT(c.main.n_ttiles == 3 && c.has_tail && c.tail.geom == GC_G_N32 && c.tail.qt2 == 0);
+        in.edge = 0;
         in.B = 8;       // 1 024 workgroups: below qt2_min -> three full tiles and the 17-frame tail on 32 columns
         c = gc_select(in);
         EXPECT(c.has_tail && c.tail.geom == GC_G_N32 && c.tail.t_base == 384 && c.tail.n_ttiles == 1 && c.tail.nblk == 8L * 32);

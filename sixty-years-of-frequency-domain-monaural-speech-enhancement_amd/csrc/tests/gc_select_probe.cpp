@@ -72,4 +72,24 @@ int gcs_plan_shape(int M, int Cin, int ntaps, const int* df, const int* dt, int 
     }
 }
 
+// edge-row classes of a tap set on a plane (gc_edge_classes): out = nclass, cls_lo, cls_hi, then per class (GC_EDGE_MAX of them)
+// dead-tap mask, live K rows of a chunk, the same padded, and GC_MAX_KCP entries of the surviving class-0 K rows
+int gcs_edge_classes(int ntaps, const int* df, int cic, int si, int Fin, int Q, int* out) {
+    TapSpec t;
+    if (ntaps < 0 || ntaps > GC_MAX_TAPS) return -1;
+    t.ntaps = ntaps;
+    for (int j = 0; j < ntaps; ++j) {
+        t.df[j] = df[j];
+        t.dt[j] = 0;
+    }
+    const GCEdgeShape e = gc_edge_classes(t, cic, si, Fin, Q);
+    int k = 0;
+    out[k++] = e.nclass; out[k++] = e.cls_lo; out[k++] = e.cls_hi;
+    for (int c = 0; c < GC_EDGE_MAX; ++c) {
+        out[k++] = (int)e.dead[c]; out[k++] = e.KC[c]; out[k++] = e.KCp[c];
+        for (int i = 0; i < GC_MAX_KCP; ++i) out[k++] = e.live[c][i];
+    }
+    return k;
+}
+
 }  // extern "C"
