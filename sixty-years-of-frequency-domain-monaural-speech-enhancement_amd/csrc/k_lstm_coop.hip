@@ -1053,53 +1053,133 @@ __global__ __launch_bounds__(256, 1) void lstm_coop16_kernel(const LstmCoopArgs 
 
 char* coop_scratch(size_t need, hipStream_t s) { return device_scratch(0, need, s); }
 
-// the launch-log record of one cooperative dispatch (lstm_set_launch_log)
-void log_coop(const char* kernel, const LstmCoopArgs& a, int H, int NS, int TAG, int LEAD, int NW, long grid, size_t shmem) {
-    LstmLaunchRec r;
-    r.kernel = kernel;
-    r.H = H; r.NS = NS; r.TAG = TAG; r.LEAD = LEAD; r.NW = NW;
-    r.Z = a.Z; r.SS = a.SS;
-    r.chunk = a.pz;
-    for (int z = 0; a.pz && z < a.Z && z < 4; ++z) {
-        r.lz[z] = a.lz[z];
-        r.t0[z] = a.t0[z];
-        r.Tz[z] = a.Tz[z];
-    }
-    r.grid = grid;
-    r.shmem = (long)shmem;
-    lstm_log_launch(r);
+// CUs of the current device (the one copy of the query; cached by device)
+int coop_n_cu() {
+    static int n_cu[64] = {};
+    int dev = 0;
+    SE_HIP(hipGetDevice(&dev));
+    SE_CHECK(dev >= 0 && dev < 64, "device ordinal");
+    if (!n_cu[dev]) SE_HIP(hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev));
+    return n_cu[dev];
 }
 
-template <int H>
-void launch_t(LstmCoopArgs a, int n_cu, hipStream_t s) {
-    constexpr int US = H / 16;
-    const int NT = (a.S + 15) / 16;
-    SE_CHECK(US * a.Z <= n_cu, "cooperative LSTM: more unit slices than CUs");
-    a.SS = std::max(1, std::min(NT, n_cu / (US * a.Z)));
-    static const int dbg = getenv("SE_COOP_DBG") ? atoi(getenv("SE_COOP_DBG")) : 0;
-    a.dbg = dbg;
-    // 64 arrival flags per (z, sequence slice) + exchange tensor hx [Z][2][S][H]
-    constexpr size_t NFLAG = 256 * 64;        // (z, sequence slice) groups x 64 unit-slice words
-    const size_t slab = (size_t)a.S * H, hx_bytes = (size_t)a.Z * 2 * slab * sizeof(float);
-    char* sc = coop_scratch(NFLAG * sizeof(unsigned) + hx_bytes, s);
-    a.bar = reinterpret_cast<unsigned*>(sc);
-    a.hx = reinterpret_cast<float*>(sc + NFLAG * sizeof(unsigned));
+// A cooperative kernel with its once-per-device flag: the LDS limit is set on the function at its first launch on a device
+struct CoopFn {
+    const void* fn = nullptr;
+    bool (*attr_set)[64] = nullptr;
+};
+template <auto K>
+CoopFn coop_fn() {
+    static bool attr_set[64] = {};
+    return {reinterpret_cast<const void*>(K), &attr_set};
+}
+// From choice to instantiation: every kernel this file builds.  `v`: the form's own template value (NS, LEAD or L)
+constexpr int coop_key(int form, int H, int v) { return (form * 2048 + H) * 32 + v; }
+CoopFn coop_fn_of(const LstmChoice& c) {
+    const int v = c.form == LSTM_FORM_KS ? c.NS : c.form == LSTM_FORM_COOP8 ? c.LEAD : c.form == LSTM_FORM_STACK ? c.L : 0;
+#define SE_COOP_CASE(form, H, v, ...) \
+    case coop_key(form, H, v): return coop_fn<&__VA_ARGS__>();
+    switch (coop_key(c.form, c.H, v)) {
+        SE_COOP_CASE(LSTM_FORM_COOP, 512, 0, lstm_coop_kernel<512>)
+        SE_COOP_CASE(LSTM_FORM_COOP, 1024, 0, lstm_coop_kernel<1024>)
+        SE_COOP_CASE(LSTM_FORM_KS, 512, 1, lstm_coop_ks_kernel<512, 1, true>)
+        SE_COOP_CASE(LSTM_FORM_KS, 512, 4, lstm_coop_ks_kernel<512, 4, true>)
+        SE_COOP_CASE(LSTM_FORM_KS, 512, 16, lstm_coop_ks_kernel<512, 16, false>)
+        SE_COOP_CASE(LSTM_FORM_KS, 1024, 1, lstm_coop_ks_kernel<1024, 1, true>)
+        SE_COOP_CASE(LSTM_FORM_KS, 1024, 4, lstm_coop_ks_kernel<1024, 4, true>)
+        SE_COOP_CASE(LSTM_FORM_KS, 1024, 16, lstm_coop_ks_kernel<1024, 16, false>)
+        SE_COOP_CASE(LSTM_FORM_COOP8, 512, 1, lstm_coop8_kernel<512, 1, 4>)
+        SE_COOP_CASE(LSTM_FORM_COOP8, 512, 2, lstm_coop8_kernel<512, 2, 4>)
+        SE_COOP_CASE(LSTM_FORM_COOP8, 512, 3, lstm_coop8_kernel<512, 3, 4>)
+        SE_COOP_CASE(LSTM_FORM_COOP8, 1024, 1, lstm_coop8_kernel<1024, 1, 4>)
+        SE_COOP_CASE(LSTM_FORM_COOP8, 1024, 2, lstm_coop8_kernel<1024, 2, 4>)
+        SE_COOP_CASE(LSTM_FORM_COOP8, 1024, 3, lstm_coop8_kernel<1024, 3, 4>)
+        SE_COOP_CASE(LSTM_FORM_COOP16, 256, 0, lstm_coop16_kernel<256>)
+        SE_COOP_CASE(LSTM_FORM_COOP16, 512, 0, lstm_coop16_kernel<512>)
+        SE_COOP_CASE(LSTM_FORM_COOP16, 1024, 0, lstm_coop16_kernel<1024>)
+        SE_COOP_CASE(LSTM_FORM_STACK, 512, 2, lstm_stack_kernel<512, 2>)
+        SE_COOP_CASE(LSTM_FORM_STACK, 512, 3, lstm_stack_kernel<512, 3>)
+        SE_COOP_CASE(LSTM_FORM_STACK, 1024, 2, lstm_stack_kernel<1024, 2>)
+        SE_COOP_CASE(LSTM_FORM_STACK, 1024, 3, lstm_stack_kernel<1024, 3>)
+    }
+#undef SE_COOP_CASE
+    SE_CHECK(false, "cooperative LSTM: the selection names a kernel that is not built");
+    return {};
+}
+
+// Flags and exchange slabs of one launch carved out of the scratch, and the preparation its choice names enqueued on s.
+// chunk: the arguments of a chunk-pipeline launch, whose layers keep their slabs from launch to launch
+struct CoopScratch {
+    unsigned* bar;
+    float* hx;       // [c.slabs][2][S][c.H]
+};
+CoopScratch coop_prepare(const LstmChoice& c, int S, const LstmCoopArgs* chunk, hipStream_t s) {
+    constexpr size_t NFLAG = 256 * 64;       // (z, sequence slice) groups x 64 unit-slice words
+    const long slab = (long)S * c.H;
+    char* sc = coop_scratch(NFLAG * sizeof(unsigned) + (size_t)c.slabs * 2 * slab * sizeof(float), s);
+    const CoopScratch m{reinterpret_cast<unsigned*>(sc), reinterpret_cast<float*>(sc + NFLAG * sizeof(unsigned))};
+    const unsigned one = 1u;
+    float stale;
+    memcpy(&stale, &one, sizeof(float));
     // zeroed by a kernel, not a memset node: under hipGraph replay the memset was observed not to be ordered before the
     // cooperative kernel (stale arrival counts let every barrier fall through)
-    launch_fill(reinterpret_cast<float*>(a.bar), (long)a.Z * a.SS * 64, 0.f, s);
-    // h_{-1} = 0 and c_{-1} = 0 are data, not branches in the kernel
-    launch_fill(a.hx, (long)a.Z * 2 * slab, 0.f, s);
-    launch_fill(a.cell, (long)a.Z * H * a.S, 0.f, s);
-    const size_t shmem = (size_t)2 * 16 * (H + 4) * sizeof(float);
-    static bool attr_set[64] = {};
-    if (first_on_device(attr_set)) {
-        SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop_kernel<H>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    if (c.nflag) launch_fill(reinterpret_cast<float*>(m.bar), c.nflag, 0.f, s);
+    if (chunk) {
+        for (int z = 0; z < chunk->Z; ++z)
+            if (chunk->t0[z] == 0) {      // a layer's first range: h_{-1} = 0 (tag 0), and slab 1 must not look like h_0
+                launch_fill(m.hx + (long)chunk->lz[z] * 2 * slab, slab, 0.f, s);
+                launch_fill(m.hx + ((long)chunk->lz[z] * 2 + 1) * slab, slab, stale, s);
+            }
+        return m;
     }
-    log_coop("coop", a, H, 0, 0, 0, 0, (long)US * a.SS * a.Z, shmem);
+    launch_fill(m.hx, c.slabs * 2 * slab, 0.f, s);          // h_{-1} = 0 (tag 0) ...
+    for (int p = 0; c.stale && p < c.slabs; ++p) launch_fill(m.hx + ((long)p * 2 + 1) * slab, slab, stale, s);   // ... slab 1 must not look like h_0
+    return m;
+}
+
+// the once-per-device LDS limit, the launch-log record (lstm_set_launch_log) and the cooperative launch
+template <typename Args>
+void coop_dispatch(const LstmChoice& c, Args& a, int chunk, hipStream_t s) {
+    const CoopFn k = coop_fn_of(c);
+    if (first_on_device(*k.attr_set)) SE_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, c.lds_attr));
+    LstmLaunchRec r;
+    r.kernel = lstm_form_name(c.form);
+    r.H = c.H; r.NS = c.NS; r.TAG = c.TAG; r.LEAD = c.LEAD; r.NW = c.NW; r.L = c.L;
+    r.Z = c.Z; r.SS = c.SS;
+    r.chunk = chunk;
+    if constexpr (std::is_same_v<Args, LstmCoopArgs>)
+        for (int z = 0; chunk && z < a.Z && z < 4; ++z) {
+            r.lz[z] = a.lz[z];
+            r.t0[z] = a.t0[z];
+            r.Tz[z] = a.Tz[z];
+        }
+    r.grid = c.grid;
+    r.shmem = (long)c.lds;
+    lstm_log_launch(r);
     void* params[] = {&a};
-    SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop_kernel<H>), dim3(US * a.SS * a.Z), dim3(256),
-                                      params, (unsigned)shmem, s));
+    SE_HIP(hipLaunchCooperativeKernel(k.fn, dim3((unsigned)c.grid), dim3(c.block), params, (unsigned)c.lds, s));
+}
+
+// The one launcher of launch_lstm_coop and launch_lstm_coop_chunk
+void launch_form(LstmCoopArgs a, const LstmChoice& c, hipStream_t s) {
+    SE_CHECK(c.form != LSTM_FORM_REFUSED, c.refusal);
+    const CoopScratch m = coop_prepare(c, a.S, c.chunk ? &a : nullptr, s);
+    a.bar = m.bar;
+    a.hx = m.hx;
+    if (c.zero_cell) launch_fill(a.cell, (long)a.Z * a.H * a.S, 0.f, s);
+    a.SS = c.SS;
+    a.dbg = lstm_tuning_env().dbg;
+    if (c.chunk) a.pz = 1;
+    coop_dispatch(c, a, a.pz, s);
+}
+
+LstmSelIn sel_in(const LstmCoopArgs& a, int chunk, int n_layers) {
+    LstmSelIn in;
+    in.H = a.H; in.S = a.S; in.Z = a.Z;
+    in.gx_row = a.gx_row; in.out_row = a.out_row;
+    in.n_cu = coop_n_cu();
+    in.chunk = chunk; in.n_layers = n_layers;
+    return in;
 }
 
 }  // namespace
@@ -1111,280 +1191,24 @@ void lstm_log_launch(const LstmLaunchRec& r) {
     if (g_lstm_log) g_lstm_log->push_back(r);
 }
 
-bool lstm_coop_supported(int H, int S, int Z) { return (H == 512 || H == 1024) && (H / 16) * Z <= 256 && S <= 4096; }
+// the support queries: lstm_select.h's pure forms on this device's CU count and the process's switches
+bool lstm_coop_supported(int H, int S, int Z) { return lstm_coop_ok(H, S, Z); }
+bool lstm_coop256_supported(int S) { return lstm_coop256_ok(S, coop_n_cu(), lstm_tuning_env()); }
+bool lstm_coop_chunk_supported(int H, int S, int n_layers) { return lstm_coop_chunk_ok(H, S, n_layers, coop_n_cu(), lstm_tuning_env()); }
+int lstm_stack_chunk_steps(int H, int S, int n_layers, int T) { return lstm_chunk_steps(H, S, n_layers, T, coop_n_cu(), lstm_tuning_env()); }
+bool lstm_stack_supported(int H, int L) { return lstm_stack_ok(H, L, coop_n_cu()); }
 
-// sub-tile pipelined form: sequence slices by 4-sequence sub-tiles, LEAD = slots a fetch runs ahead (at most the sub-tiles a
-// workgroup owns: the padding slots at the end of the launch are sub-tiles of step T)
-template <int H, int LEAD, int NW>
-static void launch_c8(LstmCoopArgs a, hipStream_t s) {
-    constexpr int US = H / 16;
-    static const int dbg = getenv("SE_COOP_DBG") ? atoi(getenv("SE_COOP_DBG")) : 0;
-    a.dbg = dbg;
-    constexpr size_t NFLAG = 256 * 64;
-    const size_t slab = (size_t)a.S * H, hx_bytes = (size_t)a.Z * 2 * slab * sizeof(float);
-    char* sc = coop_scratch(NFLAG * sizeof(unsigned) + hx_bytes, s);
-    a.bar = reinterpret_cast<unsigned*>(sc);
-    a.hx = reinterpret_cast<float*>(sc + NFLAG * sizeof(unsigned));
-    launch_fill(a.hx, (long)a.Z * 2 * slab, 0.f, s);          // h_{-1} = 0 (tag 0) ...
-    const unsigned one = 1u;
-    float stale;
-    memcpy(&stale, &one, sizeof(float));
-    for (int z = 0; z < a.Z; ++z) launch_fill(a.hx + ((long)z * 2 + 1) * slab, (long)slab, stale, s);   // ... slab 1 must not look like h_0
-    const int nsub_max = ((a.S + 3) / 4 + a.SS - 1) / a.SS;
-    const size_t wl_floats = (NW == 4 && H == 1024) ? (size_t)NW * (H / 64) * 256 : 0;      // one unit's weights per wave (kernel: UL)
-    const size_t shmem = ((size_t)(LEAD + 1) * 4 * (H + 16) + (size_t)(LEAD + 1) * NW * 64 + wl_floats + (size_t)64 * nsub_max) * sizeof(float);
-    SE_CHECK(shmem <= 160 * 1024, "cooperative LSTM (sub-tile form): too many sequences per workgroup for the LDS-resident cell state");
-    static bool attr_set[64] = {};
-    if (first_on_device(attr_set)) {
-        SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop8_kernel<H, LEAD, NW>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    log_coop("coop8", a, H, 0, 0, LEAD, NW, (long)US * a.SS * a.Z, shmem);
-    void* params[] = {&a};
-    SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop8_kernel<H, LEAD, NW>), dim3(US * a.SS * a.Z),
-                                      dim3(64 * NW), params, (unsigned)shmem, s));
-}
-template <int H>
-static bool launch_c16(LstmCoopArgs a, int n_cu, hipStream_t s) {
-    static const int on = getenv("SE_COOP16") ? atoi(getenv("SE_COOP16")) : 1;
-    constexpr int US = H / 16;
-    if (!on || a.S < 17 || US * a.Z > n_cu || (long)a.S * H * 8 >= (1L << 31) || (double)a.gx_row * 4 * H * 4 >= 4.0e9 ||
-        (double)a.out_row * H >= 4.0e9)
-        return false;
-    const int NT = (a.S + 15) / 16;
-    a.SS = std::max(1, std::min(NT, n_cu / (US * a.Z)));
-    const int ntl_max = (NT + a.SS - 1) / a.SS;
-    const size_t shmem = ((size_t)2 * 16 * (H + 4) + (size_t)2 * 4 * 256 + (size_t)4 * ntl_max * 64) * sizeof(float);
-    if (shmem > 160 * 1024) return false;
-    static const int dbg = getenv("SE_COOP_DBG") ? atoi(getenv("SE_COOP_DBG")) : 0;
-    a.dbg = dbg;
-    constexpr size_t NFLAG = 256 * 64;
-    const size_t slab = (size_t)a.S * H, hx_bytes = (size_t)a.Z * 2 * slab * sizeof(float);
-    char* sc = coop_scratch(NFLAG * sizeof(unsigned) + hx_bytes, s);
-    a.bar = reinterpret_cast<unsigned*>(sc);
-    a.hx = reinterpret_cast<float*>(sc + NFLAG * sizeof(unsigned));
-    launch_fill(a.hx, (long)a.Z * 2 * slab, 0.f, s);          // h_{-1} = 0 (tag 0) ...
-    const unsigned one = 1u;
-    float stale;
-    memcpy(&stale, &one, sizeof(float));
-    for (int z = 0; z < a.Z; ++z) launch_fill(a.hx + ((long)z * 2 + 1) * slab, (long)slab, stale, s);   // ... slab 1 must not look like h_0
-    static bool attr_set[64] = {};
-    if (first_on_device(attr_set)) {
-        SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop16_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-    }
-    log_coop("coop16", a, H, 0, 0, 0, 0, (long)US * a.SS * a.Z, shmem);
-    void* params[] = {&a};
-    SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop16_kernel<H>), dim3(US * a.SS * a.Z), dim3(256), params,
-                                      (unsigned)shmem, s));
-    return true;
-}
-static int coop_n_cu() {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        SE_HIP(hipGetDevice(&dev));
-        SE_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    return n_cu;
-}
-bool lstm_coop256_supported(int S) {
-    // SE_LSTM_COOP256=0: the per-step GEMM launches of LstmBig instead (the A/B of tests/test_gpu_dccrn_real_lstm.py)
-    static const int on = getenv("SE_LSTM_COOP256") ? atoi(getenv("SE_LSTM_COOP256")) : 1;
-    static const int on16 = getenv("SE_COOP16") ? atoi(getenv("SE_COOP16")) : 1;
-    constexpr int H = 256, US = H / 16;
-    if (!on || !on16 || S < 17 || S > 4096) return false;
-    // the conditions launch_c16<256> checks for a time-major Z = 1 layer (gx_row = out_row = S): one workgroup per CU
-    // (__launch_bounds__(256, 1), grid US x SS <= CUs), 32-bit lane offsets, the tiles' cell states in LDS
-    const int n_cu = coop_n_cu(), NT = (S + 15) / 16;
-    if (US > n_cu || (long)S * H * 8 >= (1L << 31) || (double)S * 4 * H * 4 >= 4.0e9) return false;
-    const int SS = std::max(1, std::min(NT, n_cu / US)), ntl_max = (NT + SS - 1) / SS;
-    return ((size_t)2 * 16 * (H + 4) + (size_t)2 * 4 * 256 + (size_t)4 * ntl_max * 64) * sizeof(float) <= 160 * 1024;
-}
-bool lstm_coop_chunk_supported(int H, int S, int n_layers) {
-    static const int on = getenv("SE_LSTM_CHUNK") ? atoi(getenv("SE_LSTM_CHUNK")) : 1;
-    if (!on || (H != 512 && H != 1024) || n_layers < 2 || n_layers > 4 || S < 17) return false;
-    const int n_cu = coop_n_cu(), US = H / 16, NT = (S + 15) / 16;
-    // worth it where one layer alone leaves a workgroup a single tile per step (its exchange is then exposed) and the layers
-    // together still fit the chip
-    return US * n_layers <= n_cu && NT <= n_cu / US && (long)S * H * 8 < (1L << 31);
-}
-template <int H>
-static void launch_chunk_t(LstmCoopArgs a, int n_layers, hipStream_t s) {
-    constexpr int US = H / 16;
-    const int n_cu = coop_n_cu(), NT = (a.S + 15) / 16;
-    a.SS = std::max(1, std::min(NT, n_cu / (US * a.Z)));
-    const int ntl_max = (NT + a.SS - 1) / a.SS;
-    const size_t shmem = ((size_t)2 * 16 * (H + 4) + (size_t)2 * 4 * 256 + (size_t)4 * ntl_max * 64) * sizeof(float);
-    SE_CHECK(shmem <= 160 * 1024, "chunked cooperative LSTM: too many tiles per workgroup");
-    static const int dbg = getenv("SE_COOP_DBG") ? atoi(getenv("SE_COOP_DBG")) : 0;
-    a.dbg = dbg;
-    a.pz = 1;
-    constexpr size_t NFLAG = 256 * 64;
-    const size_t slab = (size_t)a.S * H, hx_bytes = (size_t)n_layers * 2 * slab * sizeof(float);
-    char* sc = coop_scratch(NFLAG * sizeof(unsigned) + hx_bytes, s);
-    a.bar = reinterpret_cast<unsigned*>(sc);
-    a.hx = reinterpret_cast<float*>(sc + NFLAG * sizeof(unsigned));
-    const unsigned one = 1u;
-    float stale;
-    memcpy(&stale, &one, sizeof(float));
-    for (int z = 0; z < a.Z; ++z)
-        if (a.t0[z] == 0) {      // a layer's first range: h_{-1} = 0 (tag 0), and slab 1 must not look like h_0
-            launch_fill(a.hx + (long)a.lz[z] * 2 * slab, (long)slab, 0.f, s);
-            launch_fill(a.hx + ((long)a.lz[z] * 2 + 1) * slab, (long)slab, stale, s);
-        }
-    static bool attr_set[64] = {};
-    if (first_on_device(attr_set)) {
-        SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop16_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-    }
-    log_coop("coop16", a, H, 0, 0, 0, 0, (long)US * a.SS * a.Z, shmem);
-    void* params[] = {&a};
-    SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop16_kernel<H>), dim3(US * a.SS * a.Z), dim3(256), params,
-                                      (unsigned)shmem, s));
-}
+void launch_lstm_coop(const LstmCoopArgs& a, hipStream_t s) { launch_form(a, lstm_coop_select(sel_in(a, 0, 0), lstm_tuning_env()), s); }
 void launch_lstm_coop_chunk(const LstmCoopArgs& a, int n_layers, hipStream_t s) {
-    SE_CHECK(a.Z >= 1 && a.Z <= 4 && n_layers <= 4 && (a.H == 512 || a.H == 1024), "launch_lstm_coop_chunk: 1 - 4 layers of 512 / 1024 units");
-    SE_CHECK((double)a.gx_row * 4 * a.H * 4 < 4.0e9 && (double)a.out_row * a.H < 4.0e9, "launch_lstm_coop_chunk: tensor too large for 32-bit lane offsets");
-    if (a.H == 1024) launch_chunk_t<1024>(a, n_layers, s);
-    else launch_chunk_t<512>(a, n_layers, s);
+    launch_form(a, lstm_coop_select(sel_in(a, 1, n_layers), lstm_tuning_env()), s);
 }
-template <int H>
-static bool launch_c4_n(LstmCoopArgs a, int n_cu, hipStream_t s) {
-    static const int on = getenv("SE_COOP4") ? atoi(getenv("SE_COOP4")) : 1;
-    constexpr int US = H / 16;
-    // (the per-lane parts of the gate / output addresses are 32-bit offsets inside one LSTM's tensors)
-    if (!on || a.S < 17 || US * a.Z > n_cu || (long)a.S * H * 8 >= (1L << 31) || (double)a.gx_row * 4 * H * 4 >= 4.0e9 ||
-        (double)a.out_row * H >= 4.0e9)
-        return false;
-    const int NS4 = (a.S + 3) / 4;
-    a.SS = std::max(1, std::min(NS4, n_cu / (US * a.Z)));
-    if ((size_t)((NS4 + a.SS - 1) / a.SS) * 256 > 24 * 1024) return false;        // cell state of the slice must fit LDS
-    const int nsub_min = NS4 / a.SS;                           // the fewest sub-tiles a workgroup owns (>= 1)
-    int lead = std::min(3, nsub_min);
-    if (nsub_min >= 3 && nsub_min < 6) lead = 2;             // a fetch issued 3 slots ahead of a 4-slot cycle would read before h_{t-1} is out
-    if (lead <= 1) launch_c8<H, 1, 4>(a, s);
-    else if (lead == 2) launch_c8<H, 2, 4>(a, s);
-    else launch_c8<H, 3, 4>(a, s);
-    return true;
-}
-
-template <int H, int NS, bool TAG>
-static void launch_ks(LstmCoopArgs a, hipStream_t s) {
-    constexpr int NWG = H / 4;
-    static const int dbg = getenv("SE_COOP_DBG") ? atoi(getenv("SE_COOP_DBG")) : 0;
-    a.dbg = dbg;
-    a.SS = 1;
-    constexpr size_t NFLAG = 256 * 64;
-    const size_t slab = (size_t)a.S * H, hx_bytes = (size_t)a.Z * 2 * slab * sizeof(float);
-    char* sc = coop_scratch(NFLAG * sizeof(unsigned) + hx_bytes, s);
-    a.bar = reinterpret_cast<unsigned*>(sc);
-    a.hx = reinterpret_cast<float*>(sc + NFLAG * sizeof(unsigned));
-    launch_fill(reinterpret_cast<float*>(a.bar), (long)a.Z * 256, 0.f, s);
-    launch_fill(a.hx, (long)a.Z * 2 * slab, 0.f, s);
-    if (TAG) {      // slab 1 must not look like h_0 (tag 0) before h_0 has been written
-        const unsigned one = 1u;
-        float stale;
-        memcpy(&stale, &one, sizeof(float));
-        for (int z = 0; z < a.Z; ++z) launch_fill(a.hx + ((long)z * 2 + 1) * slab, (long)slab, stale, s);
-    }
-    const size_t shmem = (size_t)4 * 16 * (H / 4 + 4) * sizeof(float) + (size_t)4 * 64 * 16;
-    static bool attr_set[64] = {};
-    if (first_on_device(attr_set)) {
-        SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_coop_ks_kernel<H, NS, TAG>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    }
-    log_coop("ks", a, H, NS, TAG ? 1 : 0, 0, 0, (long)NWG * a.Z, shmem);
-    void* params[] = {&a};
-    SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_coop_ks_kernel<H, NS, TAG>), dim3(NWG * a.Z), dim3(256),
-                                      params, (unsigned)shmem, s));
-}
-template <int H>
-static void launch_ks_n(const LstmCoopArgs& a, hipStream_t s) {
-    // (the tagged exchange pays while a wave's share of h is one or two loads per lane: 4.9 -> 3.1 us per step at one sequence,
-    // 5.4 -> 4.2 at four, nothing at sixteen)
-    if (a.S <= 1) launch_ks<H, 1, true>(a, s);
-    else if (a.S <= 4) launch_ks<H, 4, true>(a, s);
-    else launch_ks<H, 16, false>(a, s);
-}
-
-template <int H, int L>
-static void launch_stack_t(LstmStackArgs a, hipStream_t s) {
-    constexpr int NWG = H / 4, NV = 2 * L - 1;
-    const size_t hx_bytes = (size_t)L * 2 * H * sizeof(float);
-    char* sc = coop_scratch(256 * 64 * sizeof(unsigned) + hx_bytes, s);
-    a.hx = reinterpret_cast<float*>(sc + 256 * 64 * sizeof(unsigned));
-    launch_fill(a.hx, (long)L * 2 * H, 0.f, s);
-    const unsigned one = 1u;
-    float stale;
-    memcpy(&stale, &one, sizeof(float));
-    for (int l = 0; l < L; ++l) launch_fill(a.hx + ((long)l * 2 + 1) * H, H, stale, s);     // slab 1 must not look like h_0
-    const size_t shmem = ((size_t)4 * NV * (H / 4) + (size_t)L * 64) * sizeof(float) + (size_t)(L - 1) * 16 * H * sizeof(float);
-    static bool attr_set[64] = {};
-    if (first_on_device(attr_set)) {
-        SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_stack_kernel<H, L>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)shmem));
-    }
-    LstmLaunchRec r;
-    r.kernel = "stack";
-    r.H = H; r.L = L; r.Z = 1; r.SS = 1;
-    r.grid = NWG;
-    r.shmem = (long)shmem;
-    lstm_log_launch(r);
-    void* params[] = {&a};
-    SE_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lstm_stack_kernel<H, L>), dim3(NWG), dim3(256), params,
-                                      (unsigned)shmem, s));
-}
-bool lstm_stack_supported(int H, int L) {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        SE_HIP(hipGetDevice(&dev));
-        SE_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    return (H == 1024 || H == 512) && (L == 2 || L == 3) && H / 4 <= n_cu;
-}
-void launch_lstm_stack(const LstmStackArgs& a, hipStream_t s) {
-    SE_CHECK(lstm_stack_supported(a.H, a.L), "launch_lstm_stack: 2 or 3 layers of 512 / 1024 units on one sequence");
-    if (a.H == 1024) a.L == 2 ? launch_stack_t<1024, 2>(a, s) : launch_stack_t<1024, 3>(a, s);
-    else a.L == 2 ? launch_stack_t<512, 2>(a, s) : launch_stack_t<512, 3>(a, s);
-}
-
-void launch_lstm_coop(const LstmCoopArgs& a, hipStream_t s) {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        SE_HIP(hipGetDevice(&dev));
-        SE_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    SE_CHECK(a.Z * std::max(1, std::min((a.S + 15) / 16, n_cu / ((a.H / 16) * a.Z))) <= 256, "cooperative LSTM: too many slices");
-    // one tile: every CU on the K-split form (H = 1024: 7.5 -> 5.1 ... 5.9 us per step for 1 ... 16 sequences; H = 512: 4.4 -> 3.8 at
-    // one sequence, nothing from 8 on or with two LSTMs per launch - tools/coopbench.cpp)
-    if (a.H == 256) {            // opt-in width (lstm_coop256_supported): 16-sequence tiles only
-        SE_CHECK(a.Z == 1 && lstm_coop256_supported(a.S) && launch_c16<256>(a, n_cu, s),
-                 "cooperative LSTM at H = 256: one LSTM of 17 - 4096 sequences (lstm_coop256_supported)");
-        return;
-    }
-    constexpr int ks_z = 2;      // most LSTMs per launch on the K-split form (two, GCRN: 4.4 -> 2.5 ... 3.0 us)
-    if (a.S <= (a.H == 1024 ? 16 : 4) && (a.H == 1024 || a.Z <= ks_z) && (a.H / 4) * a.Z <= n_cu && (a.H / 4) * a.Z <= 256) {
-        if (a.H == 1024) launch_ks_n<1024>(a, s);
-        else if (a.H == 512) launch_ks_n<512>(a, s);
-        else SE_CHECK(false, "cooperative LSTM kernel is built for H = 512 / 1024");
-        return;
-    }
-    // 16-sequence tiles (lstm_coop16_kernel) unless a workgroup would own a single tile per step AND fewer than 16 sequences per
-    // unit slice's share of the chip are left to split: there the 4-sequence sub-tiles overlap their own exchange (batch 32,
-    // H = 1024: 5.1 us per step against 7.4; batch 64: 8.1 against 7.8)
-    const int us_z = (a.H / 16) * a.Z, nt16 = (a.S + 15) / 16;
-    const bool sub4 = a.H == 1024 && us_z <= n_cu && nt16 <= n_cu / us_z && a.S * us_z < 60 * n_cu / 4;
-    if (sub4 && launch_c4_n<1024>(a, n_cu, s)) return;
-    if (a.H == 1024 && launch_c16<1024>(a, n_cu, s)) return;
-    if (a.H == 512 && launch_c16<512>(a, n_cu, s)) return;
-    if (a.H == 1024 && launch_c4_n<1024>(a, n_cu, s)) return;
-    if (a.H == 512 && launch_c4_n<512>(a, n_cu, s)) return;
-    if (a.H == 1024) launch_t<1024>(a, n_cu, s);
-    else if (a.H == 512) launch_t<512>(a, n_cu, s);
-    else SE_CHECK(false, "cooperative LSTM kernel is built for H = 512 / 1024");
+// (its own argument struct: one sequence, a slab pair per layer)
+void launch_lstm_stack(const LstmStackArgs& a0, hipStream_t s) {
+    const LstmChoice c = lstm_stack_select(a0.H, a0.L, coop_n_cu());
+    SE_CHECK(c.form != LSTM_FORM_REFUSED, c.refusal);
+    LstmStackArgs a = a0;
+    a.hx = coop_prepare(c, 1, nullptr, s).hx;
+    coop_dispatch(c, a, 0, s);
 }
 
 }  // namespace se

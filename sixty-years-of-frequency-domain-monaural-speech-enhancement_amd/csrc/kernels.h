@@ -5,6 +5,7 @@
 #include <utility>
 #include <vector>
 #include "common.h"
+#include "lstm_select.h"
 
 namespace se {
 
@@ -363,6 +364,9 @@ bool lstm_coop256_supported(int S);
 // layers of a stack on consecutive chunks of steps in one cooperative launch (k_lstm_coop.hip: lstm_coop16_kernel); false: the
 // shape has no such kernel.  n_layers = layers of the whole stack (sizes the exchange slabs / `cell` = [n_layers][H][S])
 bool lstm_coop_chunk_supported(int H, int S, int n_layers);
+// steps per chunk when a feature-major stack of n_layers layers over T steps runs as that pipeline (lstm_select.h
+// lstm_chunk_steps on this device), 0: it does not
+int lstm_stack_chunk_steps(int H, int S, int n_layers, int T);
 void launch_lstm_coop_chunk(const LstmCoopArgs& a, int n_layers, hipStream_t s);
 // A stack of L LSTM layers (equal width) on ONE sequence as one cooperative launch (k_lstm_coop.hip: lstm_stack_kernel):
 // layer l runs l frames behind layer l - 1, one exchange latency per frame serves all layers.  gx0: the first layer's gate

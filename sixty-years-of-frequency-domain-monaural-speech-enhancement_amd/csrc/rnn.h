@@ -160,6 +160,50 @@ inline void run_pointwise(const GCPlan& pl, const float* src, long s_o, long s_c
     gc_launch_prof(pl, p, st, prof);
 }
 
+// GCParams of one recurrent step (the EPI_LSTM GEMM of plan pl) on Sn sequence columns of tensors whose rows hold S: h_{t-1} from
+// `h` (row pitch h_c), x: optional second source projected inside the step (row pitch S), aux: the step's gate pre-activations
+// (row pitch S) or nullptr, h_t to dst (row pitch d_c), the cell state updated in place
+inline GCParams lstm_step_params(const GCPlan& pl, const float* h, long h_c, const float* x, const float* aux, float* dst, long d_c,
+                                 float* cell, int S, int Sn, bool first_step) {
+    GCParams p = pl.p;
+    p.first_step = first_step;
+    p.src0 = h;
+    p.s0_b = 0;
+    p.s0_c = h_c;
+    p.s0_f = 0;
+    p.src1 = x;
+    if (x) {
+        p.s1_b = 0;
+        p.s1_c = S;
+        p.s1_f = 0;
+    }
+    p.Fin = 1;
+    p.Tin = Sn;
+    p.B = 1;
+    p.Q = 1;
+    p.Tout = Sn;
+    p.aux = aux;
+    if (aux) {
+        p.x_b = 0;
+        p.x_c = S;
+        p.x_f = 0;
+    }
+    p.dst = dst;
+    p.d_b = 0;
+    p.d_c = d_c;
+    p.d_f = 0;
+    p.cell = cell;
+    return p;
+}
+
+// launch_lstm_coop under the profiler, booked with the recurrent matrix work of its Z LSTMs
+inline void launch_lstm_coop_timed(const LstmCoopArgs& a, hipStream_t st, Profiler* prof) {
+    const bool timed = prof && prof->on;
+    if (timed) prof->begin(st);
+    launch_lstm_coop(a, st);
+    if (timed) prof->end(st, 2.0 * a.Z * 4 * a.H * (double)a.H * a.S * (a.T - 1));
+}
+
 // LSTM layer with a hidden size too large for register-resident weights (H = 1024 in LSTM/CRN): input projection
 // as one GEMM over all steps, then one fused GEMM + LSTM-cell launch per step (weights stream from L2 / Infinity Cache).
 struct LstmBig {
@@ -224,10 +268,7 @@ struct LstmBig {
         a.whh_z = 0;
         a.out_z = 0; a.out_t = S; a.out_row = N;
         a.H = H; a.T = T; a.S = S; a.Z = 1; a.reverse = 0;
-        const bool timed = prof && prof->on;
-        if (timed) prof->begin(st);
-        launch_lstm_coop(a, st);
-        if (timed) prof->end(st, 2.0 * 4 * H * (double)H * S * (T - 1));
+        launch_lstm_coop_timed(a, st, prof);
     }
     void free() {
         gc_free_plan(gin);
@@ -264,27 +305,8 @@ struct LstmBig {
                             int T, int S, bool first, hipStream_t st, Profiler* prof) const {
         run_pointwise(gin, x, x_t, S, G, 4L * H * S, S, T, S, st, prof);
         for (int t = 0; t < T; ++t) {
-            GCParams p = step.p;
-            p.first_step = (first && t == 0);
-            p.src0 = t > 0 ? out + (size_t)(t - 1) * out_t : h_state;
-            p.s0_b = 0;
-            p.s0_c = t > 0 ? (long)out_rs * S : S;
-            p.s0_f = 0;
-            p.src1 = nullptr;
-            p.Fin = 1;
-            p.Tin = S;
-            p.B = 1;
-            p.Q = 1;
-            p.Tout = S;
-            p.aux = G + (size_t)t * 4 * H * S;
-            p.x_b = 0;
-            p.x_c = S;
-            p.x_f = 0;
-            p.dst = out + (size_t)t * out_t;
-            p.d_b = 0;
-            p.d_c = (long)out_rs * S;
-            p.d_f = 0;
-            p.cell = cell;
+            const GCParams p = lstm_step_params(step, t > 0 ? out + (size_t)(t - 1) * out_t : h_state, t > 0 ? (long)out_rs * S : S, nullptr,
+                                                G + (size_t)t * 4 * H * S, out + (size_t)t * out_t, (long)out_rs * S, cell, S, S, first && t == 0);
             gc_launch_prof(step, p, st, prof);
         }
         SE_HIP(hipMemcpy2DAsync(h_state, (size_t)S * sizeof(float), out + (size_t)(T - 1) * out_t,
@@ -302,34 +324,13 @@ struct LstmBig {
             a.whh_z = 0;
             a.out_z = 0; a.out_t = out_t; a.out_row = (long)out_rs * S;
             a.H = H; a.T = T; a.S = S; a.Z = 1; a.reverse = 0;
-            const bool timed = prof && prof->on;
-            if (timed) prof->begin(st);
-            launch_lstm_coop(a, st);
-            if (timed) prof->end(st, 2.0 * 4 * H * (double)H * S * (T - 1));
+            launch_lstm_coop_timed(a, st, prof);
             return;
         }
         for (int t = 0; t < T; ++t) {
-            GCParams p = step.p;
-            p.first_step = (t == 0);
-            p.src0 = (t > 0 ? out + (size_t)(t - 1) * out_t : out) + c0;
-            p.s0_b = 0;
-            p.s0_c = (long)out_rs * S;
-            p.s0_f = 0;
-            p.src1 = nullptr;
-            p.Fin = 1;
-            p.Tin = Sn;
-            p.B = 1;
-            p.Q = 1;
-            p.Tout = Sn;
-            p.aux = G + (size_t)t * 4 * H * S + c0;
-            p.x_b = 0;
-            p.x_c = S;
-            p.x_f = 0;
-            p.dst = out + (size_t)t * out_t + c0;
-            p.d_b = 0;
-            p.d_c = (long)out_rs * S;
-            p.d_f = 0;
-            p.cell = cell + c0;
+            const GCParams p = lstm_step_params(step, (t > 0 ? out + (size_t)(t - 1) * out_t : out) + c0, (long)out_rs * S, nullptr,
+                                                G + (size_t)t * 4 * H * S + c0, out + (size_t)t * out_t + c0, (long)out_rs * S, cell + c0, S, Sn,
+                                                t == 0);
             gc_launch_prof(step, p, st, prof);
         }
     }
@@ -338,27 +339,9 @@ struct LstmBig {
                     int Sn, hipStream_t st, Profiler* prof) const {
         SE_CHECK(has_x, "run_cols_x: layer was not built with a fused input projection");
         for (int t = 0; t < T; ++t) {
-            GCParams p = step_x.p;
-            p.first_step = (t == 0);
-            p.src0 = (t > 0 ? out + (size_t)(t - 1) * out_t : hz) + c0;
-            p.s0_b = 0;
-            p.s0_c = t > 0 ? (long)out_rs * S : S;
-            p.s0_f = 0;
-            p.src1 = x + (size_t)t * x_t + c0;
-            p.s1_b = 0;
-            p.s1_c = S;
-            p.s1_f = 0;
-            p.Fin = 1;
-            p.Tin = Sn;
-            p.B = 1;
-            p.Q = 1;
-            p.Tout = Sn;
-            p.aux = nullptr;
-            p.dst = out + (size_t)t * out_t + c0;
-            p.d_b = 0;
-            p.d_c = (long)out_rs * S;
-            p.d_f = 0;
-            p.cell = cell + c0;
+            const GCParams p = lstm_step_params(step_x, (t > 0 ? out + (size_t)(t - 1) * out_t : hz) + c0, t > 0 ? (long)out_rs * S : S,
+                                                x + (size_t)t * x_t + c0, nullptr, out + (size_t)t * out_t + c0, (long)out_rs * S, cell + c0, S,
+                                                Sn, t == 0);
             gc_launch_prof(step_x, p, st, prof);
         }
     }
@@ -404,28 +387,19 @@ inline bool lstm_stack_chunked_fm(const LstmBig* const* ly, int L, const float* 
     const int H = ly[0]->H;
     for (int l = 0; l < L; ++l)
         if (!ly[l]->has_fm || !ly[l]->whh_dev || ly[l]->H != H || (l > 0 && ly[l]->I != H)) return false;
-    if (!lstm_coop_chunk_supported(H, S, L)) return false;
-    // the chunk kernel addresses G / out with 32-bit lane offsets over rows of T * S elements (launch_lstm_coop_chunk checks the same
-    // bound): batches of long clips (H = 1024: T * S >= ~244 k, e.g. 64 clips of 3 800 frames) go back to the per-layer path, whose
-    // launchers fall back by themselves
-    if ((double)T * S * 4 * H * 4 >= 4.0e9 || (double)T * S * H >= 4.0e9) return false;
-    // chunk length: the pipeline runs (L - 1) chunks longer than the sequence, every launch costs ~3 steps' worth of launch + fill
-    int Tc = 48;                                             // (measured at batch 64, T = 401: 24 / 36 / 48 / 64 -> CRN 4 907 / 5 022 / 5 281 / 5 204 utt/s)
-    Tc = std::max(2, std::min(Tc, T)) & ~1;                  // even: a chunk keeps the parity of the exchange slabs
-    if (T < 2 * Tc) return false;
+    const int Tc = lstm_stack_chunk_steps(H, S, L, T);       // whether and how to chunk: lstm_select.h
+    if (!Tc) return false;
     const long N = (long)T * S;
-    const int nc = (T + Tc - 1) / Tc;
     run_pointwise(ly[0]->gin_fm, x, 0, N, G, 0, N, 1, (int)N, st, prof);
-    for (int s = 0; s < nc + L - 1; ++s) {
+    for (int s = 0; s < lstm_chunk_launches(T, Tc, L); ++s) {
         LstmCoopArgs a{};
         a.cell = cells;
         a.gx_t = S; a.gx_row = N; a.out_t = S; a.out_row = N;
         a.H = H; a.S = S; a.reverse = 0;
         double flops = 0;
-        for (int l = 0; l < L; ++l) {
-            const int c = s - l;
-            if (c < 0 || c >= nc) continue;
-            const int t0 = c * Tc, len = std::min(Tc, T - t0);
+        LstmChunkRange rg[4];
+        for (int i = 0, n = lstm_chunk_launch(T, Tc, L, s, rg); i < n; ++i) {
+            const int l = rg[i].layer, t0 = rg[i].t0, len = rg[i].len;
             if (l > 0) {       // gates of layer l on this chunk, over the chunk of G layer l - 1 consumed one launch ago
                 const long off = (long)t0 * S;
                 run_pointwise(ly[l]->gin_fm, outs[l - 1] + off, 0, N, G + off, 0, N, 1, len * S, st, prof);
@@ -469,10 +443,7 @@ inline void run_lstm_pair(const LstmBig& l0, const LstmBig& l1, const float* whh
     a.whh_z = 4L * H * H;
     a.out_z = out_z; a.out_t = out_t; a.out_row = (long)out_rs * S;
     a.H = H; a.T = T; a.S = S; a.Z = 2; a.reverse = 0;
-    const bool timed = prof && prof->on;
-    if (timed) prof->begin(st);
-    launch_lstm_coop(a, st);
-    if (timed) prof->end(st, 2.0 * 2 * 4 * H * (double)H * S * (T - 1));
+    launch_lstm_coop_timed(a, st, prof);
 }
 
 }  // namespace se

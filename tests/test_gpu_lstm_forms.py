@@ -1,7 +1,8 @@
 """One recurrent layer (or stack) at a time against a float64 LSTM / GRU.  The recurrent kernels pick among a dozen forms by hidden
-size, sequence count, LSTMs per launch, CU count, an LDS budget and 32-bit offset bounds (k_lstm_coop.hip launch_lstm_coop and its
-helpers, the chunk pipeline, the one-sequence stack kernel, k_lstm.hip's persistent kernels, k_lstm_short.hip, and the per-step
-EPI_LSTM epilogue of gemmconv.hip); they exchange h_t across workgroups through tagged or flagged slabs.  The whole-model suites
+size, sequence count, LSTMs per launch, CU count, an LDS budget and 32-bit offset bounds (csrc/lstm_select.h: lstm_coop_select, the
+support queries and the chunk pipeline's plan, which `expected_coop` ... `chunk_plan` below mirror; the one-sequence stack kernel,
+k_lstm.hip's persistent kernels, k_lstm_short.hip, and the per-step EPI_LSTM epilogue of gemmconv.hip); they exchange h_t across
+workgroups through tagged or flagged slabs.  The whole-model suites
 reach a few of those forms at a few (S, T).  Here every case is one layer of torch.nn tensors, turned into an engine layer by the
 engine's own loaders and run through the entry points the models call (csrc/tests/lstm_probe.hip -> libse_lstmprobe.so); every
 stored h_t is checked against float64, every element the layer does not own must still hold its NaN sentinel, and the form the

@@ -1,6 +1,7 @@
 #!/bin/bash
-# The device code of gemmconv.o, two builds: bash tools/gc_devcode_compare.sh <gemmconv.o of build A> <gemmconv.o of build B>
-# Unbundles the gfx950 code object of each, and compares per kernel the disassembly (llvm-objdump -d) and the metadata (llvm-readelf
+# The device code of one object file, two builds: bash tools/gc_devcode_compare.sh <X.o of build A> <X.o of build B>
+# Written for gemmconv.o (hence the name) but not specific to it: any object of csrc/ with gfx950 kernels compares the same way
+# (k_lstm_coop.o: profiles/lstm_select.md).  Unbundles the gfx950 code object of each, and compares per kernel the disassembly (llvm-objdump -d) and the metadata (llvm-readelf
 # --notes: register counts, LDS, scratch, workgroup size).  Kernels may be emitted in another order; padding after a section's last
 # kernel is ignored.  Prints the number of kernels and `identical`, or the kernels that differ (exit status 1).
 set -e
