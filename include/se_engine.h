@@ -392,6 +392,52 @@ int se_resampler_push(se_resampler* r, const float* in_dev, int64_t in_pitch, in
 int se_resampler_flush(se_resampler* r, float* out_dev, int64_t out_pitch, int32_t* n_out, void* stream);
 int64_t se_resampler_ready_samples(int64_t n_in, int32_t sr_in, int32_t sr_out);
 
+/* Parking a source-rate signal and putting it back: what se_stream_save / se_stream_restore are to a handle's stream, for a
+ * se_resampler.  Together they park a stream that is fed at the source's rate (a resampler in front of se_stream_push): save both,
+ * restore both.  One object can so serve more signals than max_batch by turns: restore -> push -> save per signal.
+ *   CONTRACT: take any signal on a se_resampler and any point between two calls on it - before its first push, after a push that
+ *   released nothing, after its last push.  Save it.  Let anything else happen on the object: other signals, including ones that
+ *   overwrite both history buffers, nothing at all.  Restore it there, or on another object created with the same sr_in / sr_out.
+ *   The outputs of every later se_resampler_push and of se_resampler_flush then equal those of the uninterrupted signal bit for
+ *   bit, *n_out included - so the concatenation still equals se_resample of the whole signal, sample for sample.
+ * The object holds a host record (sr_in, sr_out, batch, the samples arrived, the first sample of the history, the next output and
+ * the running float64 read position as its 8 bytes) and one device payload: the live history of every row, rows back to back, at
+ * most 2 * reach floats per row.  Which of the two history buffers was current, the pinned position ring and the filter table are
+ * not part of it: a push's read positions are re-derived from the record.  A pass-through object (sr_in == sr_out) saves counters
+ * only: a payload of 0 bytes.
+ *   se_resampler_state_create : an empty object; touches no device.  se_resampler_state_destroy releases it (NULL: nothing).
+ *   se_resampler_state_bytes  : device memory of the payload (sized for the most a signal of that batch keeps, so the figure does
+ *                               not move from save to save; of an imported image not restored yet: its payload); 0 = empty.
+ *   se_resampler_state_counts : the host record - rates, rows, input samples arrived (n_in), output samples released (n_out); any
+ *                               out-pointer may be NULL.  An empty object is an error.
+ *   se_resampler_save   : needs an open signal on r ("... without se_resampler_begin" / "... after se_resampler_flush" otherwise);
+ *                         does not end or alter it.  One kernel, enqueued on `stream`, ordered against the object's last call like
+ *                         push and flush.  The first save into an object allocates its payload; saving again into an object that
+ *                         holds the same (sr_in, sr_out, batch) allocates nothing, and no save waits for the device.
+ *   se_resampler_restore: r must convert the same sr_in -> sr_out, have max_batch >= the snapshot's batch and live on the device the
+ *                         payload lives on (an imported image goes anywhere); max_push may differ.  Each mismatch, and an empty
+ *                         object, is refused with its own reason.  It replaces whatever signal is open on r, as se_resampler_begin
+ *                         does.  One kernel into the current history buffer; the first restore of an imported image uploads its
+ *                         payload once (synchronously).  The same object may be restored any number of times and on more than one
+ *                         se_resampler: that forks a signal.
+ *   se_resampler_state_export / _import: the object as one byte string in HOST memory, as se_stream_state_export / _import:
+ *                         synchronous; export with cap == 0 returns the size needed, else the size written (-1: error).  import
+ *                         parses and validates on the host - it runs, and refuses, without a GPU: a wrong magic or version, an
+ *                         image cut short, a payload size that is not batch * (n_total - w0) * 4, negative or overflowing
+ *                         counters, w0 > n_total, more history than 2 * reach of the recorded rates, and trailing bytes.
+ * Errors are read through se_last_error(NULL).  A refused call changes nothing: neither the object nor the signal running on r.  An
+ * object is not thread-safe, and like a se_resampler it orders calls made on different hipStreams behind one another. */
+typedef struct se_resampler_state se_resampler_state;
+int se_resampler_state_create(se_resampler_state** out);
+int se_resampler_state_destroy(se_resampler_state* s);
+int64_t se_resampler_state_bytes(const se_resampler_state* s);
+int se_resampler_state_counts(const se_resampler_state* s, int32_t* sr_in, int32_t* sr_out, int32_t* batch, int64_t* n_in,
+                              int64_t* n_out);
+int se_resampler_save(se_resampler* r, se_resampler_state* s, void* stream);
+int se_resampler_restore(se_resampler* r, const se_resampler_state* s, void* stream);
+int64_t se_resampler_state_export(const se_resampler_state* s, void* host_buf, int64_t cap);
+int se_resampler_state_import(se_resampler_state* s, const void* host_buf, int64_t bytes);
+
 /* The two ends of `enhance(args)`: `feat_wav, orig_fs = sf.read(path)` hands out int16 / 32768 as floats, and
  * `sf.write(path, y, fs)` stores PCM_16 (soundfile's default subtype for .wav: round to nearest, clipped) - e.g.
  * DCCRN/dccrn_decode_vb.py:25,64.  Both conversions are exact in fp32, so they run on the device and the host moves raw
@@ -402,7 +448,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise) */
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,8 @@ SYMBOLS = [
     'se_enhance_long_ragged', 'se_resampler_create', 'se_resampler_destroy', 'se_resampler_begin', 'se_resampler_push',
     'se_resampler_flush', 'se_resampler_ready_samples', 'se_stream_state_create', 'se_stream_state_destroy',
     'se_stream_state_bytes', 'se_stream_save', 'se_stream_restore', 'se_stream_state_export', 'se_stream_state_import',
+    'se_resampler_state_create', 'se_resampler_state_destroy', 'se_resampler_state_bytes', 'se_resampler_state_counts',
+    'se_resampler_save', 'se_resampler_restore', 'se_resampler_state_export', 'se_resampler_state_import',
 ]
 
 
@@ -106,5 +108,15 @@ def load():
     lib.se_stream_state_export.restype = i64
     lib.se_stream_state_export.argtypes = [vp, vp, i64]
     lib.se_stream_state_import.argtypes = [vp, vp, i64]
+    lib.se_resampler_state_create.argtypes = [C.POINTER(vp)]
+    lib.se_resampler_state_destroy.argtypes = [vp]
+    lib.se_resampler_state_bytes.restype = i64
+    lib.se_resampler_state_bytes.argtypes = [vp]
+    lib.se_resampler_state_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
+    lib.se_resampler_save.argtypes = [vp, vp, vp]
+    lib.se_resampler_restore.argtypes = [vp, vp, vp]
+    lib.se_resampler_state_export.restype = i64
+    lib.se_resampler_state_export.argtypes = [vp, vp, i64]
+    lib.se_resampler_state_import.argtypes = [vp, vp, i64]
     _lib = lib
     return lib

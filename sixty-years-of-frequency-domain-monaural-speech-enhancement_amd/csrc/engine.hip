@@ -174,6 +174,45 @@ int64_t se_resampler_ready_samples(int64_t n_in, int32_t sr_in, int32_t sr_out) 
     return se::resample_ready_samples(n_in, sr_in, sr_out);
 }
 
+// a parked signal of the stateful resampler (k_resample.hip, resampler_manifest.h)
+static se::ResamplerState* rst_of(const se_resampler_state* s) {
+    return reinterpret_cast<se::ResamplerState*>(const_cast<se_resampler_state*>(s));      // (the uploaded payload is a cache of the object)
+}
+
+int se_resampler_state_create(se_resampler_state** out) {
+    return guard(nullptr, [&] {
+        SE_CHECK(out, "se_resampler_state_create: null argument");
+        *out = reinterpret_cast<se_resampler_state*>(se::resampler_state_create());
+    });
+}
+int se_resampler_state_destroy(se_resampler_state* s) {
+    return guard(nullptr, [&] { se::resampler_state_destroy(rst_of(s)); });
+}
+int64_t se_resampler_state_bytes(const se_resampler_state* s) { return se::resampler_state_bytes(rst_of(s)); }
+int se_resampler_state_counts(const se_resampler_state* s, int32_t* sr_in, int32_t* sr_out, int32_t* batch, int64_t* n_in, int64_t* n_out) {
+    return guard(nullptr, [&] { se::resampler_state_counts(rst_of(s), sr_in, sr_out, batch, n_in, n_out); });
+}
+int se_resampler_save(se_resampler* r, se_resampler_state* s, void* stream) {
+    return guard(nullptr, [&] {
+        SE_CHECK(r && s, "se_resampler_save: null argument");
+        se::stream_resampler_save(rs_of(r), rst_of(s), static_cast<hipStream_t>(stream));
+    });
+}
+int se_resampler_restore(se_resampler* r, const se_resampler_state* s, void* stream) {
+    return guard(nullptr, [&] {
+        SE_CHECK(r && s, "se_resampler_restore: null argument");
+        se::stream_resampler_restore(rs_of(r), rst_of(s), static_cast<hipStream_t>(stream));
+    });
+}
+int64_t se_resampler_state_export(const se_resampler_state* s, void* host_buf, int64_t cap) {
+    int64_t ret = -1;
+    guard(nullptr, [&] { ret = se::resampler_state_export(rst_of(s), host_buf, cap); });
+    return ret;
+}
+int se_resampler_state_import(se_resampler_state* s, const void* host_buf, int64_t bytes) {
+    return guard(nullptr, [&] { se::resampler_state_import(rst_of(s), host_buf, bytes); });
+}
+
 int se_pcm16_decode(const int16_t* in_dev, int64_t in_pitch, int32_t batch, int32_t n, float* out_dev, int64_t out_pitch,
                     void* stream) {
     return guard(nullptr, [&] {

@@ -22,6 +22,9 @@
 //              few positions of a push travel through a ring of 8 pinned slots (hipMemcpyAsync, one event per slot).  The one
 //              wait left on that path: hipEventSynchronize on a slot's event before the host rewrites the slot, i.e. on the
 //              copy enqueued 8 pushes earlier - it blocks only a caller that runs 8 pushes ahead of the device.
+//   parking  : save / restore (se_resampler_save / _restore) copy the live history [w0, n_total) of every row to and from the packed
+//              rows of a ResamplerState, one launch of resampler_state_copy_kernel; the counters travel in the host record
+//              (resampler_manifest.h).  Which buffer is current, the ring and the table are not saved: nothing later reads them.
 //   launch   : one output per thread, 64-thread blocks.  A 10 ms push at 48 kHz makes 160 outputs per row: three waves of
 //              ~384 dependent float64 steps each.  The launch is bound by that chain's latency, not by occupancy or f64
 //              rate, so the outputs are spread over as many CUs as there are waves instead of filling one 256-thread block.
@@ -30,9 +33,13 @@
 #include "hip_owned.h"
 #include "resample_pos.h"
 #include "resampler.h"
+#include "resampler_manifest.h"
 #include <climits>
 #include <cmath>
+#include <cstring>
+#include <memory>
 #include <mutex>
+#include <string>
 #include <vector>
 
 namespace se {
@@ -172,6 +179,15 @@ __global__ __launch_bounds__(RS_STREAM_BLOCK) void resample_stream_kernel(const 
     yp[j] = (float)resample_taps(x, a.win, n, tr - n, a.n_total, a.scale, a.index_step);
 }
 
+// se_resampler_save / se_resampler_restore: `keep` live history samples of every row, from rows of src_pitch to rows of dst_pitch
+// (save: the current history buffer -> the packed rows of a snapshot's payload; restore: the other way).  Rows are a few hundred
+// floats at most, so the launch is the cost: one coalesced load and store per thread.
+__global__ __launch_bounds__(256) void resampler_state_copy_kernel(const float* __restrict__ src, long src_pitch, float* __restrict__ dst,
+                                                                   long dst_pitch, int keep) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < keep) dst[(long)blockIdx.y * dst_pitch + j] = src[(long)blockIdx.y * src_pitch + j];
+}
+
 struct Tables {
     std::mutex mu;
     std::vector<double> host;
@@ -296,16 +312,69 @@ struct DeviceScope {          // the object's device is current while a call run
 };
 }  // namespace
 
+// A parked signal: the host record (resampler_manifest.h) + one device payload, the rows' live history back to back.  The payload
+// is sized by the first save for the most a signal of that batch keeps (batch x pitch_ floats), so saving again allocates nothing.
+struct ResamplerState {
+    ResamplerManifest man;
+    bool filled = false;
+    int device = -1;                      // the device the payload and the event live on
+    bool dev_valid = false;               // dev holds the payload of `man` (false after an import, until the first restore)
+    int64_t dev_cap = 0;                  // floats
+    std::vector<uint8_t> host;            // payload of an imported image (kept: another device may restore it too)
+    struct Side {                         // what belongs to one device
+        DevBuf<float> dev;
+        Event ev_use;
+    };
+    std::unique_ptr<Side> side;
+    // the hipStream the object was last used on: a call on another one is ordered behind it
+    bool has_use = false;
+    hipStream_t use_st = nullptr;
+
+    void wait(hipStream_t st) {
+        if (has_use && use_st != st) SE_HIP(hipStreamWaitEvent(st, side->ev_use.get(), 0));
+    }
+    void mark(hipStream_t st) {
+        SE_HIP(hipEventRecord(side->ev_use.get(), st));
+        has_use = true;
+        use_st = st;
+    }
+    // what lives on the payload's device is released with that device current, behind the last work that used it
+    void drop_side() {
+        if (side && device >= 0) {
+            DeviceScope ds(device);
+            if (has_use) (void)hipEventSynchronize(side->ev_use.get());
+            side.reset();
+        }
+        side.reset();
+        has_use = false;
+        dev_valid = false;
+        dev_cap = 0;
+    }
+    // a payload of at least `floats` on `dev` (current); the old contents are dropped when a new buffer is made
+    void payload_alloc(int64_t floats, int dev) {
+        if (side && side->dev && device == dev && dev_cap >= floats) return;
+        drop_side();
+        std::unique_ptr<Side> fresh(new Side());
+        fresh->dev.alloc((size_t)floats);
+        side = std::move(fresh);
+        device = dev;
+        dev_cap = floats;
+    }
+};
+
 class StreamResampler {
   public:
     StreamResampler(int sr_in, int sr_out, int max_batch, int max_push);
     void begin(int batch, hipStream_t s);
     int push(const float* in, long in_pitch, int n_new, float* out, long out_pitch, hipStream_t s);
     int flush(float* out, long out_pitch, hipStream_t s);
+    void save(ResamplerState& s, hipStream_t st);
+    void restore(ResamplerState& s, hipStream_t st);
 
   private:
     static constexpr int RING = 8;
     void order_behind_last(hipStream_t s);
+    void copy_state(const float* src, long src_pitch, float* dst, long dst_pitch, int64_t n_total, int64_t w0, int batch, hipStream_t st);
     const double* upload_positions(ResamplePos& pos, int64_t n_in, int64_t t_end, int64_t count, hipStream_t s);
     void launch(const float* in, long in_pitch, float* out, long out_pitch, int n_total, int w0_next, int t0, int n_calc,
                 int n_emit, const double* treg, hipStream_t s);
@@ -327,6 +396,7 @@ class StreamResampler {
     hipStream_t last_st_ = nullptr;
     // the stream: rows, which buffer holds the history, samples arrived, first sample of the history, next output
     bool active_ = false;
+    bool ended_ = false;             // the last signal was flushed and none has begun since (what a refused save says)
     int batch_ = 0, cur_ = 0, w0_ = 0;
     int64_t n_total_ = 0;
     ResamplePos pos_;
@@ -368,6 +438,7 @@ void StreamResampler::begin(int batch, hipStream_t s) {
         order_behind_last(s);
     }
     active_ = true;
+    ended_ = false;
     batch_ = batch;
     cur_ = w0_ = 0;
     n_total_ = 0;
@@ -454,6 +525,7 @@ int StreamResampler::flush(float* out, long out_pitch, hipStream_t s) {
     SE_CHECK(active_, "se_resampler_flush without se_resampler_begin");
     if (pass_ || n_total_ == 0) {
         active_ = false;
+        ended_ = true;
         return 0;
     }
     const int64_t n_calc = resample_calc_samples(plan_, n_total_) - pos_.t;                    // still to compute
@@ -480,7 +552,159 @@ int StreamResampler::flush(float* out, long out_pitch, hipStream_t s) {
     has_last_ = true;
     last_st_ = s;
     active_ = false;
+    ended_ = true;
     return (int)n_emit;
+}
+
+// ---- se_resampler_save / se_resampler_restore.  What a later output depends on: the history, read by absolute position
+// (hist[p - w0]); the read positions, resample_advance from (t, acc); the wings, clamped by absolute position (n + 1 and n_total).
+// So a snapshot is (w0, n_total, t, acc) + samples [w0, n_total) of every row, and it does not matter which of the two buffers
+// they come back into: restore writes the current one, column 0 = sample w0 as a push leaves it.
+void StreamResampler::copy_state(const float* src, long src_pitch, float* dst, long dst_pitch, int64_t n_total, int64_t w0, int batch,
+                                 hipStream_t st) {
+    const int64_t keep = n_total - w0;
+    // what the kernel indexes, checked where the sizes are known: rows of the history buffer, rows of the payload
+    SE_CHECK(keep >= 0 && keep <= pitch_ && keep == n_total_ - w0_ && batch >= 1 && batch <= max_batch_ && batch == batch_ &&
+                 keep <= std::min(src_pitch, dst_pitch),
+             "resampler state: history out of range");
+    if (keep == 0) return;
+    hipLaunchKernelGGL(resampler_state_copy_kernel, dim3((unsigned)((keep + 255) / 256), batch), dim3(256), 0, st, src, src_pitch, dst,
+                       dst_pitch, (int)keep);
+    SE_HIP(hipGetLastError());
+}
+
+void StreamResampler::save(ResamplerState& s, hipStream_t st) {
+    SE_CHECK(!ended_ || active_, "se_resampler_save after se_resampler_flush: the signal has ended");
+    SE_CHECK(active_, "se_resampler_save without se_resampler_begin");
+    ResamplerManifest m;
+    m.sr_in = sr_in_;
+    m.sr_out = sr_out_;
+    m.batch = batch_;
+    m.n_total = n_total_;
+    // (a pass-through signal keeps no history and releases what it receives)
+    m.w0 = pass_ ? n_total_ : w0_;
+    m.t = pass_ ? n_total_ : pos_.t;
+    m.acc_bits = rsnap_bits_of(pass_ ? 0.0 : pos_.acc);
+    const std::string why = rsnap_check(m);
+    SE_CHECK(why.empty(), "se_resampler_save: " + why);
+    if (!pass_) {
+        SE_CHECK(rsnap_keep(m) <= pitch_, "se_resampler_save: more live history than a buffer row");
+        DeviceScope ds(dev_);
+        s.payload_alloc((int64_t)batch_ * pitch_, dev_);
+        // nothing of the object or the signal has changed up to here (a payload made anew held nothing valid for this signal)
+        order_behind_last(st);
+        s.wait(st);
+        const long keep = (long)rsnap_keep(m);
+        copy_state(hist_[cur_].get(), pitch_, s.side->dev.get(), keep, n_total_, w0_, batch_, st);
+        SE_HIP(hipEventRecord(ev_order_.get(), st));
+        has_last_ = true;
+        last_st_ = st;
+        s.mark(st);
+    }
+    s.man = m;
+    s.filled = true;
+    s.dev_valid = !pass_;
+    s.host.clear();
+    s.host.shrink_to_fit();
+}
+
+void StreamResampler::restore(ResamplerState& s, hipStream_t st) {
+    const std::string fn = "se_resampler_restore: ";
+    SE_CHECK(s.filled, fn + "the resampler state object is empty");
+    const ResamplerManifest& m = s.man;
+    SE_CHECK(m.sr_in == sr_in_ && m.sr_out == sr_out_, fn + "the snapshot was taken at " + std::to_string(m.sr_in) + " -> " + std::to_string(m.sr_out) +
+                                                           " Hz, this object converts " + std::to_string(sr_in_) + " -> " + std::to_string(sr_out_) + " Hz");
+    SE_CHECK(m.batch >= 1 && m.batch <= max_batch_, fn + "snapshot of " + std::to_string(m.batch) + " rows exceeds max_batch " +
+                                                        std::to_string(max_batch_) + " given at create");
+    const int64_t keep = rsnap_keep(m);
+    SE_CHECK(keep >= 0 && keep <= pitch_ && m.n_total <= INT_MAX && m.t <= INT_MAX, fn + "history or counters out of range");
+    const bool upload = keep > 0 && (!s.dev_valid || s.device != dev_);
+    if (upload)
+        SE_CHECK((int64_t)s.host.size() == rsnap_payload_bytes(m),
+                 fn + "the payload lives on device " + std::to_string(s.device) + ", this object on device " + std::to_string(dev_) +
+                     " (export the state and import it to move it)");
+    // ---- every refusal is above: from here the call replaces whatever signal is open, as se_resampler_begin does
+    if (upload) {             // an imported image, or one that moves to this device: once, until the object is saved into again
+        DeviceScope ds(dev_);
+        s.payload_alloc((int64_t)m.batch * pitch_, dev_);
+        if (s.has_use) SE_HIP(hipEventSynchronize(s.side->ev_use.get()));
+        SE_HIP(hipMemcpy(s.side->dev.get(), s.host.data(), s.host.size(), hipMemcpyHostToDevice));
+        s.dev_valid = true;
+    }
+    active_ = true;
+    ended_ = false;
+    batch_ = m.batch;
+    w0_ = (int)m.w0;
+    n_total_ = m.n_total;
+    pos_.t = m.t;
+    pos_.acc = rsnap_double_of(m.acc_bits);
+    if (keep > 0) {
+        DeviceScope ds(dev_);
+        order_behind_last(st);
+        s.wait(st);
+        copy_state(s.side->dev.get(), (long)keep, hist_[cur_].get(), pitch_, n_total_, w0_, batch_, st);
+        SE_HIP(hipEventRecord(ev_order_.get(), st));
+        has_last_ = true;
+        last_st_ = st;
+        s.mark(st);
+    }
+}
+
+ResamplerState* resampler_state_create() { return new ResamplerState(); }
+void resampler_state_destroy(ResamplerState* s) {
+    if (!s) return;
+    std::unique_ptr<ResamplerState> own(s);
+    s->drop_side();
+}
+int64_t resampler_state_bytes(const ResamplerState* s) {
+    if (!s || !s->filled || s->man.sr_in == s->man.sr_out) return 0;
+    return s->side && s->side->dev ? s->dev_cap * (int64_t)sizeof(float) : rsnap_payload_bytes(s->man);
+}
+void resampler_state_counts(const ResamplerState* s, int32_t* sr_in, int32_t* sr_out, int32_t* batch, int64_t* n_in, int64_t* n_out) {
+    SE_CHECK(s, "se_resampler_state_counts: null argument");
+    SE_CHECK(s->filled, "se_resampler_state_counts: the resampler state object is empty");
+    if (sr_in) *sr_in = s->man.sr_in;
+    if (sr_out) *sr_out = s->man.sr_out;
+    if (batch) *batch = s->man.batch;
+    if (n_in) *n_in = s->man.n_total;
+    if (n_out) *n_out = s->man.t;
+}
+void stream_resampler_save(StreamResampler* r, ResamplerState* s, hipStream_t st) { r->save(*s, st); }
+void stream_resampler_restore(StreamResampler* r, ResamplerState* s, hipStream_t st) { r->restore(*s, st); }
+
+int64_t resampler_state_export(const ResamplerState* s, void* host_buf, int64_t cap) {
+    SE_CHECK(s, "se_resampler_state_export: null argument");
+    SE_CHECK(s->filled, "se_resampler_state_export: the resampler state object is empty");
+    const int64_t size = rsnap_image_bytes(s->man), pay = rsnap_payload_bytes(s->man);
+    if (cap == 0) return size;
+    SE_CHECK(host_buf && cap >= size, "se_resampler_state_export: the buffer holds " + std::to_string(cap) + " bytes, the image needs " + std::to_string(size));
+    uint8_t* out = static_cast<uint8_t*>(host_buf);
+    rsnap_write_head(s->man, out);
+    if (pay == 0) return size;
+    if (!s->host.empty()) {
+        SE_CHECK((int64_t)s->host.size() == pay, "se_resampler_state_export: host image of the wrong size");
+        std::memcpy(out + RSNAP_HEAD_BYTES, s->host.data(), (size_t)pay);
+    } else {
+        SE_CHECK(s->side && s->side->dev && s->dev_valid && pay <= s->dev_cap * (int64_t)sizeof(float), "se_resampler_state_export: no payload");
+        DeviceScope ds(s->device);
+        if (s->has_use) SE_HIP(hipEventSynchronize(s->side->ev_use.get()));
+        SE_HIP(hipMemcpy(out + RSNAP_HEAD_BYTES, s->side->dev.get(), (size_t)pay, hipMemcpyDeviceToHost));
+    }
+    return size;
+}
+
+void resampler_state_import(ResamplerState* s, const void* host_buf, int64_t bytes) {
+    SE_CHECK(s && host_buf, "se_resampler_state_import: null argument");
+    ResamplerManifest m;
+    int64_t off = 0;
+    const std::string why = rsnap_parse(host_buf, bytes, m, off);
+    SE_CHECK(why.empty(), "se_resampler_state_import: " + why);
+    std::vector<uint8_t> pay(static_cast<const uint8_t*>(host_buf) + off, static_cast<const uint8_t*>(host_buf) + bytes);
+    // nothing of the object has changed up to here
+    s->man = m;
+    s->host = std::move(pay);
+    s->filled = true;
+    s->dev_valid = false;
 }
 
 StreamResampler* stream_resampler_create(int sr_in, int sr_out, int max_batch, int max_push) {

@@ -2,6 +2,7 @@
 // return how many samples per row they wrote to the start of `out`; errors are thrown like everywhere else.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
 
 namespace se {
 
@@ -13,5 +14,17 @@ int stream_resampler_push(StreamResampler* r, const float* in, long in_pitch, in
 int stream_resampler_flush(StreamResampler* r, float* out, long out_pitch, hipStream_t s);
 // outputs that are final once n_in samples of a signal that has not ended have arrived (host arithmetic, resample_pos.h)
 long resample_ready_samples(long n_in, int sr_in, int sr_out);
+
+// A parked signal (se_resampler_state of include/se_engine.h): the host record of resampler_manifest.h + one device payload.
+// save / restore enqueue one copy kernel; export is the one call that waits for the device; import touches none.
+struct ResamplerState;
+ResamplerState* resampler_state_create();
+void resampler_state_destroy(ResamplerState* s);
+int64_t resampler_state_bytes(const ResamplerState* s);
+void resampler_state_counts(const ResamplerState* s, int32_t* sr_in, int32_t* sr_out, int32_t* batch, int64_t* n_in, int64_t* n_out);
+void stream_resampler_save(StreamResampler* r, ResamplerState* s, hipStream_t st);
+void stream_resampler_restore(StreamResampler* r, ResamplerState* s, hipStream_t st);
+int64_t resampler_state_export(const ResamplerState* s, void* host_buf, int64_t cap);
+void resampler_state_import(ResamplerState* s, const void* host_buf, int64_t bytes);
 
 }  // namespace se

@@ -10,6 +10,7 @@ import math
 import ctypes as C
 
 from . import _lib
+from .engine import EngineError
 
 
 def resample_samples(n_in, sr_in, sr_out):
@@ -39,6 +40,82 @@ def resample(wav, sr_in, sr_out=16000):
 def ready_samples(n_in, sr_in, sr_out):
     """Output samples that are final once n_in input samples of a signal that has not ended have arrived (host arithmetic)."""
     return int(_lib.load().se_resampler_ready_samples(int(n_in), int(sr_in), int(sr_out)))
+
+
+class ResamplerSnapshot:
+    """A parked `StreamResampler` signal (se_resampler_state of include/se_engine.h): what `StreamResampler.save()` fills and
+    `StreamResampler.restore()` puts back - on the same object or on another of the same sr_in / sr_out, any number of times.
+    `to_bytes()` / `from_bytes()` move it through host memory (another device, another process)."""
+
+    def __init__(self):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.device = None         # where a save put the payload (None: empty, or an imported image, which goes anywhere)
+        if self._lib.se_resampler_state_create(C.byref(self._h)):
+            self._h = C.c_void_p()
+            raise EngineError(self._lib.se_last_error(None).decode())
+
+    @property
+    def closed(self):
+        return getattr(self, '_h', None) is None or not self._h.value
+
+    def close(self):
+        if not self.closed:
+            self._lib.se_resampler_state_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @property
+    def nbytes(self):
+        """device memory of the payload (0 = empty, or a pass-through signal)"""
+        if self.closed:
+            raise EngineError("ResamplerSnapshot.nbytes: the snapshot is closed")
+        return int(self._lib.se_resampler_state_bytes(self._h))
+
+    def counts(self):
+        """(sr_in, sr_out, batch, n_in, n_out) of the saved signal: the host record; an empty snapshot is an error"""
+        if self.closed:
+            raise EngineError("ResamplerSnapshot.counts: the snapshot is closed")
+        sr_in, sr_out, batch, n_in, n_out = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        if self._lib.se_resampler_state_counts(self._h, C.byref(sr_in), C.byref(sr_out), C.byref(batch), C.byref(n_in), C.byref(n_out)):
+            raise EngineError(self._lib.se_last_error(None).decode())
+        return sr_in.value, sr_out.value, batch.value, n_in.value, n_out.value
+
+    def to_bytes(self):
+        """the snapshot as one byte string (header + payload); synchronises with the save that filled it"""
+        if self.closed:
+            raise EngineError("ResamplerSnapshot.to_bytes: the snapshot is closed")
+        n = int(self._lib.se_resampler_state_export(self._h, None, 0))
+        if n < 0:
+            raise EngineError(self._lib.se_last_error(None).decode())
+        buf = C.create_string_buffer(n)
+        if self._lib.se_resampler_state_export(self._h, C.cast(buf, C.c_void_p), n) != n:
+            raise EngineError(self._lib.se_last_error(None).decode())
+        return buf.raw
+
+    @classmethod
+    def from_bytes(cls, b):
+        """a snapshot from `to_bytes()` output: validated here, on the host; uploaded by the first restore"""
+        if not isinstance(b, (bytes, bytearray, memoryview)):
+            raise EngineError(f"ResamplerSnapshot.from_bytes: expected bytes, got {type(b).__name__}")
+        b = bytes(b)
+        snap = cls()
+        if snap._lib.se_resampler_state_import(snap._h, b, len(b)):
+            snap.close()
+            raise EngineError(snap._lib.se_last_error(None).decode())
+        return snap
 
 
 class StreamResampler:
@@ -128,3 +205,53 @@ class StreamResampler:
         self._check(self._lib.se_resampler_flush(self._h, C.c_void_p(y.data_ptr()), y.stride(0), C.byref(n_out), self._stream()))
         self._batch = 0
         return y[:, :n_out.value]
+
+    def _closed(self):
+        h = getattr(self, '_h', None)
+        return h is None or not getattr(h, 'value', h)
+
+    def _check_snapshot(self, what, snapshot):
+        if not isinstance(snapshot, ResamplerSnapshot):
+            raise EngineError(f"{what}: expected a ResamplerSnapshot, got {type(snapshot).__name__}")
+        if snapshot.closed:
+            raise EngineError(f"{what}: the snapshot is closed")
+        if self._closed():
+            raise EngineError(f"{what}: the resampler is closed")
+
+    def save(self, snapshot=None):
+        """Copy the open signal into `snapshot` (a new ResamplerSnapshot when None) without ending or altering it; returns the
+        snapshot.  Saving again into the same object allocates nothing."""
+        if snapshot is not None:
+            self._check_snapshot('save', snapshot)
+        elif self._closed():
+            raise EngineError("save: the resampler is closed")
+        snap = snapshot if snapshot is not None else ResamplerSnapshot()
+        if self._lib.se_resampler_save(self._h, snap._h, self._stream()):
+            if snapshot is None:
+                snap.close()
+            raise EngineError(self._lib.se_last_error(None).decode())
+        snap.device = self.device
+        return snap
+
+    def check_restore(self, snapshot, what='restore'):
+        """Everything `restore(snapshot)` can refuse, checked on the host without touching this object or the snapshot; returns
+        the snapshot's (sr_in, sr_out, batch, n_in, n_out)."""
+        self._check_snapshot(what, snapshot)
+        counts = snapshot.counts()
+        sr_in, sr_out, batch = counts[:3]
+        if (sr_in, sr_out) != (self.sr_in, self.sr_out):
+            raise EngineError(f"{what}: the snapshot was taken at {sr_in} -> {sr_out} Hz, this object converts {self.sr_in} -> {self.sr_out} Hz")
+        if batch > self.max_batch:
+            raise EngineError(f"{what}: snapshot of {batch} rows exceeds max_batch {self.max_batch} given at create")
+        if snapshot.device not in (None, self.device) and snapshot.nbytes:
+            raise EngineError(f"{what}: the payload lives on device {snapshot.device}, this object on device {self.device} "
+                              f"(move it with to_bytes / from_bytes)")
+        return counts
+
+    def restore(self, snapshot):
+        """Make the saved signal the open signal of this object (whatever ran here is replaced, as by begin): the outputs of every
+        later push / flush equal those of the signal had it never been interrupted, bit for bit."""
+        self._check_snapshot('restore', snapshot)
+        if self._lib.se_resampler_restore(self._h, snapshot._h, self._stream()):
+            raise EngineError(self._lib.se_last_error(None).decode())
+        _, _, self._batch, self._n_in, self._n_out = snapshot.counts()      # flush() sizes its output from them

@@ -7,15 +7,78 @@ into the engine's stream; what comes back is the engine's 16 kHz output (the ref
 converted back to `sr_in`).  The engine and its stream state are used as they are; on top of the engine's own latency the
 resampler looks 192 input samples (4 ms) ahead at 48 -> 16 kHz.
 """
-from .resample import StreamResampler
+import struct
+
+from .engine import EngineError, StreamSnapshot
+from .resample import ResamplerSnapshot, StreamResampler
+
+
+class SourceStreamSnapshot:
+    """A parked `SourceRateStream`: the pair (`engine`: StreamSnapshot, `resampler`: ResamplerSnapshot) that
+    `SourceRateStream.save()` fills and `SourceRateStream.restore()` puts back.  `to_bytes()` is the two images, each behind its
+    length (u64, little endian)."""
+
+    def __init__(self, engine=None, resampler=None):
+        self.engine = engine if engine is not None else StreamSnapshot()
+        self.resampler = resampler if resampler is not None else ResamplerSnapshot()
+
+    @property
+    def closed(self):
+        return self.engine.closed or self.resampler.closed
+
+    def close(self):
+        self.engine.close()
+        self.resampler.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @property
+    def nbytes(self):
+        """device memory of the two payloads"""
+        return self.engine.nbytes + self.resampler.nbytes
+
+    def to_bytes(self):
+        e, r = self.engine.to_bytes(), self.resampler.to_bytes()
+        return struct.pack('<Q', len(e)) + e + struct.pack('<Q', len(r)) + r
+
+    @classmethod
+    def from_bytes(cls, b):
+        if not isinstance(b, (bytes, bytearray, memoryview)):
+            raise EngineError(f"SourceStreamSnapshot.from_bytes: expected bytes, got {type(b).__name__}")
+        b = bytes(b)
+        parts, at = [], 0
+        for name in ('engine', 'resampler'):
+            if len(b) < at + 8:
+                raise EngineError(f"SourceStreamSnapshot.from_bytes: truncated (no length in front of the {name} image)")
+            n, = struct.unpack_from('<Q', b, at)
+            at += 8
+            if len(b) < at + n:
+                raise EngineError(f"SourceStreamSnapshot.from_bytes: truncated ({name} image cut short)")
+            parts.append(b[at:at + n])
+            at += n
+        if at != len(b):
+            raise EngineError(f"SourceStreamSnapshot.from_bytes: {len(b) - at} trailing bytes behind the resampler image")
+        eng = StreamSnapshot.from_bytes(parts[0])
+        try:
+            res = ResamplerSnapshot.from_bytes(parts[1])
+        except EngineError:
+            eng.close()
+            raise
+        return cls(eng, res)
 
 
 class SourceRateStream:
     """`SourceRateStream(model.engine, 48000)`: `begin(batch, ...)`, `push(x)` with x [batch, n <= max_push] at sr_in ->
     enhanced 16 kHz samples [batch, n_out] (n_out may be 0), `flush()` -> the rest.  `begin` takes what `Engine.stream_begin`
     takes: a per-stream scale `c` (of the 16 kHz signal, e.g. from a calibration run) or `running_rms=True`.
-    Not covered by `Engine.stream_save` / `stream_restore`: the resampler in front carries state of its own (filter history, read
-    position) that a StreamSnapshot does not hold, so a stream fed through this class cannot be parked and resumed."""
+    `save()` / `restore()` park and resume the stream as `Engine.stream_save` / `stream_restore` do for a 16 kHz one: a
+    `SourceStreamSnapshot` holds the engine's stream and the resampler's filter history and read position, so groups fed at the
+    source's rate can share one engine and one `SourceRateStream` by turns (restore -> push -> save per group)."""
 
     def __init__(self, engine, sr_in, sr_out=16000, max_push=None):
         self.engine = engine
@@ -44,6 +107,42 @@ class SourceRateStream:
         outs.append(self.engine.stream_flush())
         self._batch = 0
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+
+    @staticmethod
+    def _check_pair(what, snapshot):
+        if not isinstance(snapshot, SourceStreamSnapshot):
+            raise EngineError(f"{what}: expected a SourceStreamSnapshot, got {type(snapshot).__name__}")
+        if snapshot.closed:
+            raise EngineError(f"{what}: the snapshot is closed")
+
+    def save(self, snapshot=None):
+        """Copy the running stream - the engine's and the resampler's half - into `snapshot` (a new SourceStreamSnapshot when
+        None) without ending or altering it; returns the snapshot."""
+        if snapshot is not None:
+            self._check_pair('save', snapshot)
+        if not self._batch:
+            raise EngineError("save without begin")
+        snap = snapshot if snapshot is not None else SourceStreamSnapshot()
+        try:
+            self.engine.stream_save(snap.engine)
+            self.resampler.save(snap.resampler)
+        except EngineError:
+            if snapshot is None:
+                snap.close()
+            raise
+        return snap
+
+    def restore(self, snapshot):
+        """Make the saved stream the running one (whatever ran here is replaced, as by begin): every later push / flush gives the
+        outputs of the stream had it never been interrupted, bit for bit.  A refused restore leaves both halves as they were:
+        what the resampler can refuse is checked on the host before the engine's half is put back."""
+        self._check_pair('restore', snapshot)
+        _, _, batch, _, _ = self.resampler.check_restore(snapshot.resampler)
+        if batch != snapshot.engine.batch:
+            raise EngineError(f"restore: the engine's half holds {snapshot.engine.batch} rows, the resampler's {batch}")
+        self.engine.stream_restore(snapshot.engine)
+        self.resampler.restore(snapshot.resampler)
+        self._batch = batch
 
     def close(self):
         self.resampler.close()

@@ -10,7 +10,10 @@ streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, 
 --swap: time-slicing - two stream groups alternate on ONE engine through two StreamSnapshot objects, every push is
   restore -> push -> save (se_stream_restore / se_stream_save).  The line then carries, next to the plain `ms_per_push` of the same run,
   `save_ms`, `restore_ms` (one call each, timed alone) and `swapped_push_ms` (the three together), medians over the same pushes, each
-  with its p95, and `snapshot_bytes`.
+  with its p95, and `snapshot_bytes`.  With --source-rate each group swaps through a SourceStreamSnapshot (the engine's stream and the
+  resampler's signal); `save_ms` / `restore_ms` are then the engine's half, `resampler_save_ms` / `resampler_restore_ms` the
+  resampler's (se_resampler_save / se_resampler_restore), `swapped_push_ms` a whole restore -> push -> save at the source rate, and
+  `resampler_snapshot_bytes` stands beside `snapshot_bytes`.
 Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000] [--swap]"""
 import argparse
 import json
@@ -80,10 +83,11 @@ def time_source_rate(a, name, B, L, hop, eng, c):
                 times.append(time.perf_counter() - t0)
                 enq.append(t1 - t0)
             src.flush()
+        extra = time_swap_source(src, xs, c, B, chunk, piece, Ls) if a.swap else {}
         src.close()
         t = float(np.median(times[4:]))
         print(json.dumps({'model': name, 'streams': B, 'frames_per_push': chunk, 'source_rate': sr, 'samples_per_push': piece,
-                          'ms_per_push': round(t * 1e3, 3), 'p95_ms': round(float(np.percentile(times[4:], 95)) * 1e3, 3),
+                          'ms_per_push': round(t * 1e3, 3), **extra, 'p95_ms': round(float(np.percentile(times[4:], 95)) * 1e3, 3),
                           'host_enqueue_ms': round(float(np.median(enq[4:])) * 1e3, 3),
                           'x_realtime_per_stream': round(piece / sr / t, 2),
                           'x_realtime_all_streams': round(B * piece / sr / t, 1)}), flush=True)
@@ -123,6 +127,50 @@ def time_swap(eng, x, c, B, chunk, piece, L):
     p95 = lambda v: round(float(np.percentile(v[4:], 95)) * 1e3, 3)
     out = {'save_ms': med(sv), 'save_p95_ms': p95(sv), 'restore_ms': med(rs), 'restore_p95_ms': p95(rs), 'swapped_push_ms': med(sw),
            'swapped_push_p95_ms': p95(sw), 'snapshot_bytes': snaps[0].nbytes}
+    for sn in snaps:
+        sn.close()
+    return out
+
+
+def time_swap_source(src, x, c, B, chunk, piece, L):
+    """--swap with --source-rate: two groups by turns on one engine and one SourceRateStream, each through a SourceStreamSnapshot"""
+    import torch
+    from se_amd.source_stream import SourceStreamSnapshot
+    eng, res = src.engine, src.resampler
+    xs = [x, torch.flip(x, dims=[1]).contiguous()]
+    snaps = [SourceStreamSnapshot(), SourceStreamSnapshot()]
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    for rep in range(2):                    # first pass warms up (payloads and tables of the layout, lazy state slots)
+        for g in range(2):
+            src.begin(B, c=c, max_chunk_frames=chunk)
+            src.save(snaps[g])
+        sv, rs, rsv, rrs, sw = [], [], [], [], []
+        for p in range(0, L - piece + 1, piece):
+            for g in range(2):
+                seg = xs[g][:, p:p + piece]
+                if g == 0:                  # the parts alone: the engine's half, then the resampler's
+                    rs.append(timed(lambda: eng.stream_restore(snaps[g].engine)))
+                    rrs.append(timed(lambda: res.restore(snaps[g].resampler)))
+                    src.push(seg)
+                    sv.append(timed(lambda: eng.stream_save(snaps[g].engine)))
+                    rsv.append(timed(lambda: res.save(snaps[g].resampler)))
+                else:                       # one swapped push: restore -> push -> save
+                    sw.append(timed(lambda: (src.restore(snaps[g]), src.push(seg), src.save(snaps[g]))))
+        for g in range(2):
+            src.restore(snaps[g])
+            src.flush()
+    med = lambda v: round(float(np.median(v[4:])) * 1e3, 3)
+    p95 = lambda v: round(float(np.percentile(v[4:], 95)) * 1e3, 3)
+    out = {'save_ms': med(sv), 'save_p95_ms': p95(sv), 'restore_ms': med(rs), 'restore_p95_ms': p95(rs),
+           'resampler_save_ms': med(rsv), 'resampler_save_p95_ms': p95(rsv), 'resampler_restore_ms': med(rrs),
+           'resampler_restore_p95_ms': p95(rrs), 'swapped_push_ms': med(sw), 'swapped_push_p95_ms': p95(sw),
+           'snapshot_bytes': snaps[0].engine.nbytes, 'resampler_snapshot_bytes': snaps[0].resampler.nbytes}
     for sn in snaps:
         sn.close()
     return out
