@@ -256,6 +256,27 @@ int se_stream_restore(se_engine* e, const se_stream_state* s, void* stream);
 int64_t se_stream_state_export(const se_stream_state* s, void* host_buf, int64_t cap);
 int se_stream_state_import(se_stream_state* s, const void* host_buf, int64_t bytes);
 
+/* Rows of parked groups (additions: the ABI number stays).  A snapshot holds `batch` rows that have advanced in lockstep; these two
+ * make a new snapshot out of some rows of one, or out of all rows of several - to drop the callers that hung up, move some rows to
+ * another device, fork a caller, or put two groups back into one.  The carried buffers keep the batch index in different places
+ * (conv history [B][rows][HC], LSTM state [H][B], ...), so an engine supplies the layouts: `e` must be finalized and of the
+ * snapshots' kind - the identity checks of se_stream_restore (model id, flags except SE_CFG_GRAPHS / SE_CFG_STREAM_SLIDING,
+ * n_fft / hop / win, p_in / p_out), with its reasons.  The capacity checks (max_batch, max_samples, window, ring) are left to the
+ * restore of the result.  Neither call touches the stream running on `e` or its workspace; both order themselves on `stream` as
+ * se_stream_save does, run one kernel launch, and leave the result on e's device, where it exports like a saved snapshot.  An
+ * imported image that has not been restored yet is uploaded to e's device first.  A `dst` that already holds the resulting layout
+ * is reused without allocating.  A refused call changes nothing; the reason is read through se_last_error(e).
+ *   select: dst = n_rows >= 1 rows of src, row j = row rows[j] (a host array; an index may repeat, which forks a caller; one outside
+ *           0 .. batch - 1 is refused).  Every counter and mode is copied; batch becomes n_rows.  dst == src is refused.
+ *   concat: dst = the rows of parts[0], then parts[1], ...  (n_parts >= 1; dst must be none of them).  The parts must agree in every
+ *           manifest field except the batch - each differing field is refused with a reason that names it ("n_total 4160 vs 4000"):
+ *           snapshots whose counters differ cannot be joined.
+ * A snapshot taken before the model's state exists (before the first frame) holds the engine-level segments only and is handled.
+ * A continued row decodes as it would have in its old group up to the fp32 rounding of kernels selected by batch size. */
+int se_stream_state_select(se_engine* e, se_stream_state* dst, const se_stream_state* src, const int32_t* rows, int32_t n_rows,
+                           void* stream);
+int se_stream_state_concat(se_engine* e, se_stream_state* dst, const se_stream_state* const* parts, int32_t n_parts, void* stream);
+
 /* se_enhance_batch for clips LONGER than max_samples (any length; shorter ones take the same path): `batch` equal-length clips
  * resident on the device, decoded in windows of max_chunk_frames frames through the frame-online machinery above - conv history,
  * TCM rings, LSTM (h, c) and the running norm sums carried from window to window - under the WHOLE clip's unit-RMS scale, so
@@ -437,6 +458,13 @@ int se_resampler_save(se_resampler* r, se_resampler_state* s, void* stream);
 int se_resampler_restore(se_resampler* r, const se_resampler_state* s, void* stream);
 int64_t se_resampler_state_export(const se_resampler_state* s, void* host_buf, int64_t cap);
 int se_resampler_state_import(se_resampler_state* s, const void* host_buf, int64_t bytes);
+/* The same row operations on the resampler's half of a parked group: the payload is [batch][n_total - w0] floats, so no engine is
+ * needed.  select: rows[j] of src (repeats allowed, dst != src, n_rows >= 1); concat: the parts' rows in order - sr_in / sr_out, the
+ * samples in and out, the history origin and the 8 bytes of the read position must agree, each difference is refused by name.
+ * Pass-through states hold counters only.  The result lives where the sources do: on their device, or on the host when every
+ * source is an imported image that has not been restored yet.  Errors through se_last_error(NULL). */
+int se_resampler_state_select(se_resampler_state* dst, const se_resampler_state* src, const int32_t* rows, int32_t n_rows, void* stream);
+int se_resampler_state_concat(se_resampler_state* dst, const se_resampler_state* const* parts, int32_t n_parts, void* stream);
 
 /* The two ends of `enhance(args)`: `feat_wav, orig_fs = sf.read(path)` hands out int16 / 32768 as floats, and
  * `sf.write(path, y, fs)` stores PCM_16 (soundfile's default subtype for .wav: round to nearest, clipped) - e.g.

@@ -5,6 +5,7 @@
 #include "resampler.h"
 #include "rnn.h"
 #include "stream_manifest.h"
+#include "stream_rows.h"
 #include "stream_window.h"
 #include "window_rows.h"
 #include <algorithm>
@@ -211,6 +212,16 @@ int64_t se_resampler_state_export(const se_resampler_state* s, void* host_buf, i
 }
 int se_resampler_state_import(se_resampler_state* s, const void* host_buf, int64_t bytes) {
     return guard(nullptr, [&] { se::resampler_state_import(rst_of(s), host_buf, bytes); });
+}
+
+int se_resampler_state_select(se_resampler_state* dst, const se_resampler_state* src, const int32_t* rows, int32_t n_rows, void* stream) {
+    return guard(nullptr, [&] { se::resampler_state_select(rst_of(dst), rst_of(src), rows, n_rows, static_cast<hipStream_t>(stream)); });
+}
+int se_resampler_state_concat(se_resampler_state* dst, const se_resampler_state* const* parts, int32_t n_parts, void* stream) {
+    return guard(nullptr, [&] {
+        se::resampler_state_concat(rst_of(dst), reinterpret_cast<se::ResamplerState* const*>(const_cast<se_resampler_state* const*>(parts)), n_parts,
+                                   static_cast<hipStream_t>(stream));
+    });
 }
 
 int se_pcm16_decode(const int16_t* in_dev, int64_t in_pitch, int32_t batch, int32_t n, float* out_dev, int64_t out_pitch,
@@ -1068,6 +1079,12 @@ struct se_stream_state {
         DevBuf<uint8_t> dev;
         Table tab[2];                     // 0: save, 1: restore
         Event ev_use;
+        // se_stream_state_select / _concat into this object: the gather kernel's tables (segments, source offsets, part bases, row
+        // map) in one block, through a pinned copy of it
+        DevBuf<uint8_t> gat_dev;
+        PinnedBuf<uint8_t> gat_pin;
+        size_t gat_cap = 0;
+        Event gat_ev;                     // behind the last upload: the pinned block is free again
     };
     std::unique_ptr<Side> side{new Side()};
     // the hipStream the object was last used on: a call on another one is ordered behind it
@@ -1236,6 +1253,44 @@ std::string hex(int v) {
     return b;
 }
 
+// the payload of s is on e's device, or s holds an imported image that can be put there
+void check_payload_reachable(const se_engine* e, const se_stream_state* s, const std::string& fn) {
+    if (!s->dev_valid || s->device != e->cfg.device)
+        SE_CHECK(!s->host.empty(), fn + "the payload lives on device " + std::to_string(s->device) + ", this engine on device " +
+                                       std::to_string(e->cfg.device) + " (export the state and import it to move it)");
+}
+// ... and puts it there (e's device is current): once, until the object is saved into again
+void payload_to_device(const se_engine* e, se_stream_state* s, const std::string& fn) {
+    if (s->dev_valid && s->device == e->cfg.device) return;
+    const SnapManifest& m = s->man;
+    if (s->has_use) {
+        DeviceScope ds(s->device);
+        SE_HIP(hipEventSynchronize(s->side->ev_use.get()));
+        s->has_use = false;
+    }
+    const int64_t win = m.segs.empty() ? 0 : snap_align16(m.segs.back().bytes);
+    payload_alloc(s, m, std::max<int64_t>(win, (int64_t)m.batch * snap_window_cap(e->ctx.geom) * sizeof(float)), e->cfg.device);
+    SE_CHECK((int64_t)s->host.size() == snap_payload_bytes(m), fn + "host image of the wrong size");
+    SE_HIP(hipMemcpy(s->side->dev.get(), s->host.data(), s->host.size(), hipMemcpyHostToDevice));
+    s->dev_valid = true;
+}
+
+// a snapshot is of this engine's kind: model, flags, front end, exponents (what se_stream_restore and the row operations compare)
+void check_snapshot_identity(const se_engine* e, const SnapManifest& m, const std::string& fn) {
+    const StftGeom& g = e->ctx.geom;
+    SE_CHECK(m.model == e->cfg.model, fn + "the snapshot was taken on model id " + std::to_string(m.model) + ", this engine runs model id " +
+                                          std::to_string(e->cfg.model));
+    const int free_bits = SE_CFG_GRAPHS | SE_CFG_STREAM_SLIDING;
+    SE_CHECK(((m.flags ^ e->cfg.flags) & ~free_bits) == 0,
+             fn + "se_config.flags differ (snapshot " + hex(m.flags) + ", engine " + hex(e->cfg.flags) +
+                 "; every bit except SE_CFG_GRAPHS and SE_CFG_STREAM_SLIDING has to match)");
+    SE_CHECK(m.n_fft == g.n_fft && m.hop == g.hop && m.win == g.win,
+             fn + "front end differs (snapshot n_fft / hop / win " + std::to_string(m.n_fft) + " / " + std::to_string(m.hop) + " / " +
+                 std::to_string(m.win) + ", engine " + std::to_string(g.n_fft) + " / " + std::to_string(g.hop) + " / " + std::to_string(g.win) + ")");
+    SE_CHECK(m.p_in == e->ctx.p_in && m.p_out == e->ctx.p_out, fn + "magnitude exponents p_in / p_out differ");
+    SE_CHECK(e->model->stream_supported(), fn + "this engine's model has no frame-online mode");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1338,17 +1393,7 @@ int se_stream_restore(se_engine* e, const se_stream_state* cs, void* stream) {
         const SnapManifest& m = s->man;
         const StftGeom& g = e->ctx.geom;
         const std::string fn = "se_stream_restore: ";
-        SE_CHECK(m.model == e->cfg.model, fn + "the snapshot was taken on model id " + std::to_string(m.model) + ", this engine runs model id " +
-                                              std::to_string(e->cfg.model));
-        const int free_bits = SE_CFG_GRAPHS | SE_CFG_STREAM_SLIDING;
-        SE_CHECK(((m.flags ^ e->cfg.flags) & ~free_bits) == 0,
-                 fn + "se_config.flags differ (snapshot " + hex(m.flags) + ", engine " + hex(e->cfg.flags) +
-                     "; every bit except SE_CFG_GRAPHS and SE_CFG_STREAM_SLIDING has to match)");
-        SE_CHECK(m.n_fft == g.n_fft && m.hop == g.hop && m.win == g.win,
-                 fn + "front end differs (snapshot n_fft / hop / win " + std::to_string(m.n_fft) + " / " + std::to_string(m.hop) + " / " +
-                     std::to_string(m.win) + ", engine " + std::to_string(g.n_fft) + " / " + std::to_string(g.hop) + " / " + std::to_string(g.win) + ")");
-        SE_CHECK(m.p_in == e->ctx.p_in && m.p_out == e->ctx.p_out, fn + "magnitude exponents p_in / p_out differ");
-        SE_CHECK(e->model->stream_supported(), fn + "this engine's model has no frame-online mode");
+        check_snapshot_identity(e, m, fn);
         SE_CHECK(m.batch <= e->ctx.max_batch, fn + "snapshot of " + std::to_string(m.batch) + " rows exceeds max_batch " +
                                                   std::to_string(e->ctx.max_batch) + " given at create");
         check_stream_geometry(e);
@@ -1386,24 +1431,11 @@ int se_stream_restore(se_engine* e, const se_stream_state* cs, void* stream) {
                 want_slots.emplace_back(nullptr, (size_t)sg.bytes);
             }
         }
-        if (!s->dev_valid || s->device != e->cfg.device)
-            SE_CHECK(!s->host.empty(), fn + "the payload lives on device " + std::to_string(s->device) + ", this engine on device " +
-                                           std::to_string(e->cfg.device) + " (export the state and import it to move it)");
+        check_payload_reachable(e, s, fn);
         // ---- every refusal is above: from here the call takes the handle's stream over, as se_stream_begin does
         hipStream_t st = static_cast<hipStream_t>(stream);
         S.active = false;
-        if (!s->dev_valid || s->device != e->cfg.device) {
-            if (s->has_use) {
-                DeviceScope ds(s->device);
-                SE_HIP(hipEventSynchronize(s->side->ev_use.get()));
-                s->has_use = false;
-            }
-            payload_alloc(s, m, std::max<int64_t>(snap_align16(m.segs.back().bytes), (int64_t)m.batch * snap_window_cap(g) * sizeof(float)),
-                          e->cfg.device);
-            SE_CHECK((int64_t)s->host.size() == snap_payload_bytes(m), fn + "host image of the wrong size");
-            SE_HIP(hipMemcpy(s->side->dev.get(), s->host.data(), s->host.size(), hipMemcpyHostToDevice));
-            s->dev_valid = true;
-        }
+        payload_to_device(e, s, fn);
         stream_order_wait(S, st);
         obj_wait(s, st);
         S.max_chunk = m.max_chunk;
@@ -1464,6 +1496,190 @@ int se_stream_restore(se_engine* e, const se_stream_state* cs, void* stream) {
         S.active = true;
         stream_mark(S, st);
         obj_mark(s, st);
+    });
+}
+
+}  // extern "C"
+
+// ---- se_stream_state_select / se_stream_state_concat: a snapshot made of rows of others ---------------------------------------
+// Only the model knows where the batch index sits in its carried buffers, so an engine of the snapshots' kind supplies the layouts
+// (stream_rows.h): the engine's own segments follow from the manifest, the recurrent models declare theirs (Model::stream_layout,
+// the declaration their buffers are allocated from), a call-order slot is [B][row bytes] by construction (StreamCtx::slot).  The
+// manifest arithmetic is host code (stream_rows.h); the rows move in one launch (k_stream_state.hip, stream_state_gather_kernel).
+// Neither call touches the stream running on the engine or its workspace.
+namespace {
+
+std::vector<RowLayout> snapshot_layouts(se_engine* e, const SnapManifest& m, const std::string& fn) {
+    std::vector<RowLayout> lay(m.segs.size());
+    StateLayout sl;
+    const bool rec = e->model->stream_state() != nullptr;
+    if (rec) sl = e->model->stream_layout();
+    for (size_t k = 0; k < m.segs.size(); ++k) {
+        const SnapSeg& sg = m.segs[k];
+        if (snap_engine_layout(m, sg, lay[k])) continue;
+        const std::string name = snap_seg_name(sg);
+        SE_CHECK(m.state_B >= 1, fn + "segment " + name + " of a snapshot without model state");
+        if (sg.kind == SNAP_SLOT) {
+            SE_CHECK(!rec && e->model->stream_slots(), fn + "the snapshot's state is not of this model's kind");
+            SE_CHECK(sg.bytes > 0 && sg.bytes % ((int64_t)m.state_B * 4) == 0,
+                     fn + "state slot " + name + " of " + std::to_string(sg.bytes) + " bytes is not " + std::to_string(m.state_B) + " rows of whole floats");
+            lay[k] = {1, sg.bytes / ((int64_t)m.state_B * 4)};
+            continue;
+        }
+        SE_CHECK(rec, fn + "the snapshot's state is not of this model's kind");
+        RowLayout l;
+        if (sg.kind == SNAP_HIST && (size_t)sg.index < sl.hist.size()) l = sl.hist[(size_t)sg.index];
+        else if (sg.kind == SNAP_H && sg.index < 4) l = sl.h[sg.index];
+        else if (sg.kind == SNAP_CELL && sg.index < 4) l = sl.c[sg.index];
+        SE_CHECK(l.outer >= 1, fn + "this engine's model keeps no state buffer " + name);
+        lay[k] = l;
+    }
+    const std::string why = snap_layout_check(m, lay);
+    SE_CHECK(why.empty(), fn + why + " (weights of other shapes?)");
+    return lay;
+}
+
+struct RowSource {
+    se_stream_state* part;
+    int32_t row;
+};
+
+// dst <- the rows `src` names, in order; parts: the distinct source objects, every one checked against e and of one layout `lay`
+void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream_state*>& parts, const std::vector<int2>& rowmap,
+                 const std::vector<RowLayout>& lay, const std::string& fn, hipStream_t st) {
+    const int Bd = (int)rowmap.size(), np = (int)parts.size();
+    const SnapManifest m = snap_rows_manifest(parts[0]->man, lay, Bd);
+    const int nseg = (int)m.segs.size();
+    SE_CHECK(nseg >= 1, fn + "snapshot without segments");
+    long tiles = 0;
+    std::vector<GatherSeg> tab((size_t)nseg);
+    for (int k = 0; k < nseg; ++k) {
+        SE_CHECK(m.segs[(size_t)k].bytes / 4 < INT_MAX && lay[(size_t)k].outer < INT_MAX && lay[(size_t)k].inner < INT_MAX, fn + "segment too large");
+        tab[(size_t)k].outer = (int)lay[(size_t)k].outer;
+        tab[(size_t)k].inner = (int)lay[(size_t)k].inner;
+        tab[(size_t)k].n = (int)(m.segs[(size_t)k].bytes / 4);
+        tab[(size_t)k].tile0 = (int)tiles;
+        tiles += state_gather_tiles(tab[(size_t)k].n);
+        SE_CHECK(tiles < INT_MAX, fn + "too many tiles");
+    }
+    for (se_stream_state* p : parts) check_payload_reachable(e, p, fn);
+    // ---- every refusal is above
+    for (se_stream_state* p : parts) payload_to_device(e, p, fn);
+    const StftGeom& g = e->ctx.geom;
+    const int64_t win = m.segs.back().kind == SNAP_WINDOW ? snap_align16(m.segs.back().bytes) : 0;
+    if (dst->has_use && dst->device != e->cfg.device) {
+        DeviceScope ds(dst->device);
+        SE_HIP(hipEventSynchronize(dst->side->ev_use.get()));
+        dst->has_use = false;
+    }
+    payload_alloc(dst, m, std::max<int64_t>(win, (int64_t)Bd * snap_window_cap(g) * sizeof(float)), e->cfg.device);
+    SE_CHECK(snap_payload_bytes(m) <= dst->dev_fixed + dst->dev_win_cap, fn + "payload smaller than its manifest");
+    for (se_stream_state* p : parts) obj_wait(p, st);
+    obj_wait(dst, st);
+    // one block: GatherSeg[nseg] | long src_off[np][nseg] | const float* base[np] | int2 rowmap[Bd] | int part_B[np]
+    const size_t o_off = (size_t)nseg * sizeof(GatherSeg), o_base = o_off + (size_t)np * nseg * sizeof(long),
+                 o_map = o_base + (size_t)np * sizeof(float*), o_pb = o_map + (size_t)Bd * sizeof(int2), total = o_pb + (size_t)np * sizeof(int);
+    auto& sd = *dst->side;
+    SE_HIP(hipEventSynchronize(sd.gat_ev.get()));
+    if (total > sd.gat_cap) {
+        const size_t cap = std::max<size_t>(total + 4096, 32768);
+        sd.gat_cap = 0;
+        sd.gat_dev.alloc(cap);
+        sd.gat_pin.alloc(cap);
+        sd.gat_cap = cap;
+    }
+    uint8_t* pin = sd.gat_pin.get();
+    const std::vector<int64_t> doff = snap_offsets(m);
+    for (int k = 0; k < nseg; ++k) tab[(size_t)k].dst = reinterpret_cast<float*>(dst->side->dev.get() + doff[(size_t)k]);
+    std::memcpy(pin, tab.data(), o_off);
+    long* soff = reinterpret_cast<long*>(pin + o_off);
+    const float** base = reinterpret_cast<const float**>(pin + o_base);
+    int* pb = reinterpret_cast<int*>(pin + o_pb);
+    for (int p = 0; p < np; ++p) {
+        const std::vector<int64_t> off = snap_offsets(parts[(size_t)p]->man);
+        for (int k = 0; k < nseg; ++k) soff[(size_t)p * nseg + k] = (long)(off[(size_t)k] / 4);
+        base[p] = reinterpret_cast<const float*>(parts[(size_t)p]->side->dev.get());
+        pb[p] = parts[(size_t)p]->man.batch;
+    }
+    std::memcpy(pin + o_map, rowmap.data(), (size_t)Bd * sizeof(int2));
+    uint8_t* dev = sd.gat_dev.get();
+    SE_HIP(hipMemcpyAsync(dev, pin, total, hipMemcpyHostToDevice, st));
+    SE_HIP(hipEventRecord(sd.gat_ev.get(), st));
+    GatherArgs a{};
+    a.tab = reinterpret_cast<const GatherSeg*>(dev);
+    a.src_off = reinterpret_cast<const long*>(dev + o_off);
+    a.part_base = reinterpret_cast<const float* const*>(dev + o_base);
+    a.rowmap = reinterpret_cast<const int2*>(dev + o_map);
+    a.part_B = reinterpret_cast<const int*>(dev + o_pb);
+    a.nseg = nseg;
+    a.Bd = Bd;
+    launch_stream_state_gather(a, tiles, st);
+    dst->man = m;
+    dst->filled = true;
+    dst->dev_valid = true;
+    dst->host.clear();
+    dst->host.shrink_to_fit();
+    obj_mark(dst, st);
+    for (se_stream_state* p : parts) obj_mark(p, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int se_stream_state_select(se_engine* e, se_stream_state* dst, const se_stream_state* csrc, const int32_t* rows, int32_t n_rows,
+                           void* stream) {
+    if (!e) return 1;
+    return guard(e, [&] {
+        const std::string fn = "se_stream_state_select: ";
+        se_stream_state* src = const_cast<se_stream_state*>(csrc);      // (the uploaded payload is a cache of the object)
+        SE_CHECK(dst && src, fn + "null argument");
+        SE_CHECK(e->finalized, "engine not finalized");
+        SE_CHECK(dst != src, fn + "dst == src: the rows are read while they are written");
+        SE_CHECK(src->filled, fn + "the stream state object is empty");
+        check_snapshot_identity(e, src->man, fn);
+        const std::string bad = snap_rows_check(rows, n_rows, src->man.batch);
+        SE_CHECK(bad.empty(), fn + bad);
+        const std::vector<RowLayout> lay = snapshot_layouts(e, src->man, fn);
+        std::vector<int2> map((size_t)n_rows);
+        for (int32_t j = 0; j < n_rows; ++j) map[(size_t)j] = make_int2(0, rows[j]);
+        gather_rows(e, dst, {src}, map, lay, fn, static_cast<hipStream_t>(stream));
+    });
+}
+
+int se_stream_state_concat(se_engine* e, se_stream_state* dst, const se_stream_state* const* cparts, int32_t n_parts, void* stream) {
+    if (!e) return 1;
+    return guard(e, [&] {
+        const std::string fn = "se_stream_state_concat: ";
+        SE_CHECK(dst && cparts, fn + "null argument");
+        SE_CHECK(e->finalized, "engine not finalized");
+        SE_CHECK(n_parts >= 1, fn + "n_parts " + std::to_string(n_parts) + ": at least one part has to be given");
+        std::vector<se_stream_state*> parts;
+        std::vector<int2> map;
+        int64_t total = 0;
+        for (int32_t p = 0; p < n_parts; ++p) {
+            se_stream_state* s = const_cast<se_stream_state*>(cparts[p]);
+            SE_CHECK(s, fn + "parts[" + std::to_string(p) + "] is null");
+            SE_CHECK(s != dst, fn + "dst == parts[" + std::to_string(p) + "]: the rows are read while they are written");
+            SE_CHECK(s->filled, fn + "parts[" + std::to_string(p) + "]: the stream state object is empty");
+            if (p > 0) {
+                const std::string why = snap_concat_differs(cparts[0]->man, s->man);
+                SE_CHECK(why.empty(), fn + "parts[0] and parts[" + std::to_string(p) + "] differ: " + why);
+            }
+            total += s->man.batch;
+            SE_CHECK(total < (1 << 24), fn + "too many rows");
+            parts.push_back(s);
+        }
+        check_snapshot_identity(e, parts[0]->man, fn);
+        const std::vector<RowLayout> lay = snapshot_layouts(e, parts[0]->man, fn);
+        for (int32_t p = 0; p < n_parts; ++p) {
+            if (p > 0) {      // the same layouts hold part p's sizes (a slot's row size is read off part 0)
+                const std::string why = snap_layout_check(parts[(size_t)p]->man, lay);
+                SE_CHECK(why.empty(), fn + "parts[" + std::to_string(p) + "]: " + why);
+            }
+            for (int32_t r = 0; r < parts[(size_t)p]->man.batch; ++r) map.push_back(make_int2(p, r));
+        }
+        gather_rows(e, dst, parts, map, lay, fn, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -1146,7 +1146,7 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
         SE_CHECK(back <= cx->H, "cLN FIR longer than the window's history");
         if (back > 0) stream_exchange(const_cast<float*>(x), (long)R * T, (long)F * T, T, B, C, F, back, s);
         cx->memo_src = nullptr;
-        double* carry = static_cast<double*>(cx->slot((size_t)B * 2 * sizeof(double), s));
+        double* carry = static_cast<double*>(cx->slot(SlotRow{2 * sizeof(double)}, s));
         const long tg0 = cx->t0 - cx->H;
         if (K <= 0 && !pre_slope && cx->n <= 2 && (long)R * cx->n <= 256L * 41 * cx->n && R <= 256 * 41 && C <= 256) {
             // (every frame of the chunk is live: tg0 + c0 = the stream index of the first new frame >= 0)
@@ -1361,8 +1361,10 @@ void launch_hist_batch(const HistBatch& hb, int B, int Tw, int hc, bool save, hi
 static thread_local StreamCtx* g_stream_ctx = nullptr;
 StreamCtx* stream_ctx() { return g_stream_ctx; }
 void set_stream_ctx(StreamCtx* c) { g_stream_ctx = c; }
-void* StreamCtx::slot(size_t bytes, hipStream_t st) {
+void* StreamCtx::slot(SlotRow row, hipStream_t st) {
     SE_CHECK(slots, "stream context without state");
+    SE_CHECK(B >= 1 && row.row_bytes % 4 == 0, "frame-online state: a slot is B rows of whole floats");
+    const size_t bytes = (size_t)B * row.row_bytes;
     if (cursor == slots->size()) {
         void* d = nullptr;
         SE_HIP(hipMalloc(&d, bytes));
@@ -1402,8 +1404,9 @@ __global__ __launch_bounds__(256) void stream_hist_kernel(float* __restrict__ x,
 void stream_exchange(float* x, long sb, long sc, long sf, int B, int C, int F, int need, hipStream_t st) {
     StreamCtx* cx = stream_ctx();
     SE_CHECK(cx && need > 0 && need <= cx->H, "stream_exchange: history deeper than the window keeps");
+    SE_CHECK(B == cx->B, "stream_exchange: tensor is not of the current chunk's batch");
     const long rows = (long)B * C * F;
-    float* state = static_cast<float*>(cx->slot((size_t)rows * need * sizeof(float), st));
+    float* state = static_cast<float*>(cx->slot(SlotRow{(size_t)C * F * need * sizeof(float)}, st));
     SE_CHECK(need <= 256, "stream_exchange: more than 256 history columns");
     int KP = 1;
     while (KP < need) KP <<= 1;
@@ -1454,11 +1457,12 @@ void stream_exchange_pair(float* x0, long sb0, long sc0, long sf0, int C0, int F
     }
     StreamCtx* cx = stream_ctx();
     SE_CHECK(cx && need > 0 && need <= cx->H && need <= 256, "stream_exchange: history deeper than the window keeps");
+    SE_CHECK(B == cx->B, "stream_exchange: tensor is not of the current chunk's batch");
     HistPair a;
     a.x[0] = x0; a.sb[0] = sb0; a.sc[0] = sc0; a.sf[0] = sf0; a.C[0] = C0; a.F[0] = F0; a.rows[0] = (long)B * C0 * F0;
     a.x[1] = x1; a.sb[1] = sb1; a.sc[1] = sc1; a.sf[1] = sf1; a.C[1] = C1; a.F[1] = F1; a.rows[1] = (long)B * C1 * F1;
-    a.state[0] = static_cast<float*>(cx->slot((size_t)a.rows[0] * need * sizeof(float), st));
-    a.state[1] = static_cast<float*>(cx->slot((size_t)a.rows[1] * need * sizeof(float), st));
+    a.state[0] = static_cast<float*>(cx->slot(SlotRow{(size_t)C0 * F0 * need * sizeof(float)}, st));
+    a.state[1] = static_cast<float*>(cx->slot(SlotRow{(size_t)C1 * F1 * need * sizeof(float)}, st));
     int KP = 1;
     while (KP < need) KP <<= 1;
     const int rpb = 256 / KP;

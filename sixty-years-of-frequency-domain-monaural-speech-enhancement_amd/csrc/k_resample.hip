@@ -188,6 +188,16 @@ __global__ __launch_bounds__(256) void resampler_state_copy_kernel(const float* 
     if (j < keep) dst[(long)blockIdx.y * dst_pitch + j] = src[(long)blockIdx.y * src_pitch + j];
 }
 
+// se_resampler_state_select / _concat: row y of the destination <- the packed row src[y], `keep` floats each; up to 64 rows a launch,
+// their sources as a kernel argument (a group is a few dozen rows, and the rows a few hundred floats)
+struct RowPtrs {
+    const float* src[64];
+};
+__global__ __launch_bounds__(256) void resampler_state_gather_kernel(const RowPtrs rp, float* __restrict__ dst, int keep) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < keep) dst[(long)blockIdx.y * keep + j] = rp.src[blockIdx.y][j];
+}
+
 struct Tables {
     std::mutex mu;
     std::vector<double> host;
@@ -705,6 +715,108 @@ void resampler_state_import(ResamplerState* s, const void* host_buf, int64_t byt
     s->host = std::move(pay);
     s->filled = true;
     s->dev_valid = false;
+}
+
+// ---- se_resampler_state_select / se_resampler_state_concat.  The rows of the result, in order, as (part, row); every refusal is
+// made by the callers and here before the destination changes.  Sources that are all imported images (host payloads, nothing
+// uploaded yet) are cut on the host and the result is such an image; otherwise the rows move on the device the sources live on - a
+// host-only part is uploaded there first, as its first restore would do it.
+namespace {
+void resampler_rows(ResamplerState* dst, const std::vector<ResamplerState*>& parts, const std::vector<std::pair<int, int32_t>>& map,
+                    const std::string& fn, hipStream_t st) {
+    ResamplerManifest m = parts[0]->man;
+    m.batch = (int32_t)map.size();
+    const int64_t keep = rsnap_keep(m);
+    auto finish = [&](bool on_dev) {
+        dst->man = m;
+        dst->filled = true;
+        dst->dev_valid = on_dev;
+    };
+    if (keep == 0) {      // pass-through, or nothing live: counters only
+        dst->host.clear();
+        finish(false);
+        return;
+    }
+    SE_CHECK(keep <= INT_MAX / 4, fn + "history out of range");
+    int dev = -1;
+    for (ResamplerState* p : parts)
+        if (p->dev_valid && p->side && p->side->dev) {
+            SE_CHECK(dev < 0 || dev == p->device, fn + "the parts' payloads live on devices " + std::to_string(dev) + " and " + std::to_string(p->device) +
+                                                      " (export and import a state to move it)");
+            dev = p->device;
+        }
+    for (ResamplerState* p : parts)
+        if (!(p->dev_valid && p->side && p->side->dev))
+            SE_CHECK((int64_t)p->host.size() == rsnap_payload_bytes(p->man), fn + "a part has no payload");
+    // ---- every refusal is above
+    if (dev < 0) {
+        std::vector<uint8_t> out((size_t)(m.batch * keep * 4));
+        for (size_t j = 0; j < map.size(); ++j)
+            std::memcpy(out.data() + j * (size_t)keep * 4, parts[(size_t)map[j].first]->host.data() + (size_t)map[j].second * (size_t)keep * 4, (size_t)keep * 4);
+        dst->drop_side();
+        dst->host = std::move(out);
+        finish(false);
+        return;
+    }
+    DeviceScope ds(dev);
+    for (ResamplerState* p : parts)
+        if (!p->dev_valid) {
+            p->payload_alloc((int64_t)p->man.batch * keep, dev);
+            SE_HIP(hipMemcpy(p->side->dev.get(), p->host.data(), p->host.size(), hipMemcpyHostToDevice));
+            p->dev_valid = true;
+        }
+    dst->payload_alloc((int64_t)m.batch * keep, dev);
+    for (ResamplerState* p : parts) p->wait(st);
+    dst->wait(st);
+    for (size_t y0 = 0; y0 < map.size(); y0 += 64) {
+        const int ny = (int)std::min<size_t>(64, map.size() - y0);
+        RowPtrs rp{};
+        for (int y = 0; y < ny; ++y)
+            rp.src[y] = parts[(size_t)map[y0 + y].first]->side->dev.get() + (size_t)map[y0 + y].second * (size_t)keep;
+        hipLaunchKernelGGL(resampler_state_gather_kernel, dim3((unsigned)((keep + 255) / 256), (unsigned)ny), dim3(256), 0, st, rp,
+                           dst->side->dev.get() + y0 * (size_t)keep, (int)keep);
+        SE_HIP(hipGetLastError());
+    }
+    dst->host.clear();
+    dst->host.shrink_to_fit();
+    finish(true);
+    dst->mark(st);
+    for (ResamplerState* p : parts) p->mark(st);
+}
+}  // namespace
+
+void resampler_state_select(ResamplerState* dst, ResamplerState* src, const int32_t* rows, int32_t n_rows, hipStream_t st) {
+    const std::string fn = "se_resampler_state_select: ";
+    SE_CHECK(dst && src, fn + "null argument");
+    SE_CHECK(dst != src, fn + "dst == src: the rows are read while they are written");
+    SE_CHECK(src->filled, fn + "the resampler state object is empty");
+    const std::string bad = rsnap_rows_check(rows, n_rows, src->man.batch);
+    SE_CHECK(bad.empty(), fn + bad);
+    std::vector<std::pair<int, int32_t>> map;
+    for (int32_t j = 0; j < n_rows; ++j) map.emplace_back(0, rows[j]);
+    resampler_rows(dst, {src}, map, fn, st);
+}
+
+void resampler_state_concat(ResamplerState* dst, ResamplerState* const* cparts, int32_t n_parts, hipStream_t st) {
+    const std::string fn = "se_resampler_state_concat: ";
+    SE_CHECK(dst && cparts, fn + "null argument");
+    SE_CHECK(n_parts >= 1, fn + "n_parts " + std::to_string(n_parts) + ": at least one part has to be given");
+    std::vector<ResamplerState*> parts;
+    std::vector<std::pair<int, int32_t>> map;
+    for (int32_t p = 0; p < n_parts; ++p) {
+        ResamplerState* s = cparts[p];
+        SE_CHECK(s, fn + "parts[" + std::to_string(p) + "] is null");
+        SE_CHECK(s != dst, fn + "dst == parts[" + std::to_string(p) + "]: the rows are read while they are written");
+        SE_CHECK(s->filled, fn + "parts[" + std::to_string(p) + "]: the resampler state object is empty");
+        if (p > 0) {
+            const std::string why = rsnap_concat_differs(cparts[0]->man, s->man);
+            SE_CHECK(why.empty(), fn + "parts[0] and parts[" + std::to_string(p) + "] differ: " + why);
+        }
+        SE_CHECK(map.size() + (size_t)s->man.batch < ((size_t)1 << 24), fn + "too many rows");
+        for (int32_t r = 0; r < s->man.batch; ++r) map.emplace_back(p, r);
+        parts.push_back(s);
+    }
+    resampler_rows(dst, parts, map, fn, st);
 }
 
 StreamResampler* stream_resampler_create(int sr_in, int sr_out, int max_batch, int max_push) {

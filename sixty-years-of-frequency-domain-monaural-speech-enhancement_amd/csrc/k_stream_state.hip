@@ -93,4 +93,55 @@ void launch_stream_state_copy(const StateSeg* tab_dev, int nfix, long fix_tiles,
     SE_HIP(hipGetLastError());
 }
 
+// ---- se_stream_state_select / se_stream_state_concat: rows of parked groups into a new payload ---------------------------------
+// The same walk - one workgroup per tile of STATE_TILE destination floats, its segment found by bisection - over a table that
+// carries the row layout of every segment (kernels.h GatherSeg): the destination is [outer][Bd][inner], a thread's flat index j
+// there is (o, bd, i), and it reads (o, row, i) of the part the row map names for bd.  Consecutive threads write consecutive
+// addresses; they read consecutive addresses within a run of `inner` floats, and for the inner == 1 layouts (LSTM state: the batch is
+// the fastest axis) the lanes of a wave read rows of ONE o - a gather inside a few cache lines.  A layout whose runs are whole
+// float4s (inner a multiple of 4: every run then starts 16 B aligned in both payloads, whose segments start 16 B aligned) moves 16 B
+// per lane; the others move floats and also write the zeros between the segment's end and the next 16 B boundary.
+__global__ __launch_bounds__(256) void stream_state_gather_kernel(const GatherArgs a) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = a.nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.tab[mid].tile0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const GatherSeg sg = a.tab[lo];
+    const unsigned n = (unsigned)sg.n, inner = (unsigned)sg.inner, run = (unsigned)a.Bd * inner;
+    const unsigned j0 = (unsigned)(b - sg.tile0) * STATE_TILE;
+    if (inner == 0 || j0 >= ((n + 3u) & ~3u)) return;
+    const long* __restrict__ off = a.src_off + lo;
+    auto source = [&](unsigned j) -> const float* {
+        const unsigned o = j / run, rem = j - o * run, bd = rem / inner, i = rem - bd * inner;
+        const int2 pr = a.rowmap[bd];
+        return a.part_base[pr.x] + off[(long)pr.x * a.nseg] + ((long)o * a.part_B[pr.x] + pr.y) * inner + i;
+    };
+    if ((inner & 3u) == 0) {
+        for (unsigned q = threadIdx.x; q < STATE_TILE / 4; q += 256) {
+            const unsigned j = j0 + 4 * q;
+            if (j >= n) break;
+            *reinterpret_cast<float4*>(sg.dst + j) = *reinterpret_cast<const float4*>(source(j));
+        }
+    } else {
+        const unsigned npad = (n + 3u) & ~3u;
+        for (unsigned q = threadIdx.x; q < STATE_TILE; q += 256) {
+            const unsigned j = j0 + q;
+            if (j >= npad) break;
+            sg.dst[j] = j < n ? *source(j) : 0.f;
+        }
+    }
+}
+
+long state_gather_tiles(long n) { return (n + STATE_TILE - 1) / STATE_TILE; }
+
+void launch_stream_state_gather(const GatherArgs& a, long tiles, hipStream_t s) {
+    SE_CHECK(a.nseg >= 1 && a.Bd >= 1 && tiles >= 0 && tiles < (1L << 31), "launch_stream_state_gather: bad table");
+    if (tiles == 0) return;
+    hipLaunchKernelGGL(stream_state_gather_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a);
+    SE_HIP(hipGetLastError());
+}
+
 }  // namespace se

@@ -346,7 +346,7 @@ void launch_tcm_chain(const TcmStreamW* const* f, const TcmFusedHeads* hd, const
         const int KH = K[i] > 0 ? K[i] - 1 : 0, CH = (ks - 1) * dil[i], nb = gated ? 2 : 1;
         const int RF = ring_host(KH), RC = ring_host(CH);
         const long stride = 64 + (long)nb * 64 * ((KH > 0 ? RF : 0) + RC) * sizeof(float);
-        char* state = static_cast<char*>(cx->slot((size_t)cx->B * stride, s));       // same slot layout as launch_tcm_stream
+        char* state = static_cast<char*>(cx->slot(SlotRow{(size_t)stride}, s));       // same slot layout as launch_tcm_stream
         a.blk[i] = TcmStreamBlk{f[i]->w_in, f[i]->w_l, f[i]->w_r, f[i]->w_out, hd[i], K[i], dil[i], state, stride};
         fp = std::max(fp, KH + NS);
     }

@@ -6,6 +6,7 @@
 #include <vector>
 #include "common.h"
 #include "lstm_select.h"
+#include "stream_rows.h"
 
 namespace se {
 
@@ -110,6 +111,9 @@ void launch_istft2(const StftGeom& g, const float* spec_ri, int B, int T, int Tp
 //     last columns of the window there for the next chunk,
 //   * carry the cumulative LayerNorm sums across chunks.
 // Zero-initialised slots are the zero padding of the causal convs; frames before the start of the stream never count.
+struct SlotRow {
+    size_t row_bytes;      // of one stream's part of the slot (a multiple of 4)
+};
 struct StreamCtx {
     int H = 0, n = 0;        // window = H history columns + n new frames
     long t0 = 0;             // index of the first new frame in the stream
@@ -118,7 +122,9 @@ struct StreamCtx {
     size_t cursor = 0;
     const void* memo_src = nullptr;     // source whose history the previous launch restored (parity classes of one deconv)
     int memo_need = 0;
-    void* slot(size_t bytes, hipStream_t st);      // next state slot (allocated zeroed on the first chunk)
+    // next state slot (allocated zeroed on the first chunk): B rows of row_bytes each, row b at b * row_bytes.  A slot has no other
+    // form - se_stream_state_select / _concat cut every slot by rows as [B][row_bytes / 4] floats (stream_rows.h)
+    void* slot(SlotRow row, hipStream_t st);
 };
 StreamCtx* stream_ctx();                 // nullptr outside frame-online chunks
 void set_stream_ctx(StreamCtx* c);
@@ -195,6 +201,27 @@ struct StateWindow {
 };
 long state_seg_tiles(int rows, int len);
 void launch_stream_state_copy(const StateSeg* tab_dev, int nfix, long fix_tiles, int win, const StateWindow& w, hipStream_t s);
+
+// Rows of parked groups into a new payload in one launch (se_stream_state_select / _concat): every segment of the destination is
+// [outer][Bd][inner] floats, its row bd is row rowmap[bd].y of part rowmap[bd].x, whose copy of segment k - [outer][part_B][inner] -
+// starts src_off[part * nseg + k] floats into part_base[part].  Tiles of STATE_TILE destination floats as above (tile0; a segment
+// has state_gather_tiles(n) of them); the floats between the end of a segment and the next 16 B boundary are written as zeros.
+struct GatherSeg {
+    float* dst;
+    int outer, inner;
+    int n;          // outer * Bd * inner
+    int tile0;
+};
+struct GatherArgs {
+    const GatherSeg* tab;
+    const long* src_off;
+    const float* const* part_base;
+    const int* part_B;
+    const int2* rowmap;
+    int nseg, Bd;
+};
+long state_gather_tiles(long n);
+void launch_stream_state_gather(const GatherArgs& a, long tiles, hipStream_t s);
 
 // DCCRN 'E' mask (DCCRN_cprs.py:201-225) + the decode script's mag/phase/decompress (dccrn_decode_vb.py:45-58):
 //   mask [B][2][F-1][Tp] (bins 1..F-1), spec [B][2][F][Tp] -> est [B][2][F][Tp], DC bin = 0.

@@ -217,6 +217,12 @@ class Model {
     // owners (rnn.h StreamState: history columns + LSTM (h, c); kernels.h StreamSlots: the call-order slots of the cLN networks)
     virtual StreamState* stream_state() { return nullptr; }
     virtual StreamSlots* stream_slots() { return nullptr; }
+    // where the batch index sits in every buffer of stream_state() (stream_rows.h), for se_stream_state_select / _concat: the
+    // declaration stream_begin() allocates from (StreamState::begin), so a buffer cannot exist without one.  The same for every batch
+    virtual StateLayout stream_layout() const {
+        SE_CHECK(false, "this model declares no row layout of its stream state");
+        return StateLayout();
+    }
     // false: enhance() forks onto auxiliary streams and is not replayed from a captured hipGraph (SE_CFG_GRAPHS)
     virtual bool graph_capturable() const { return true; }
 

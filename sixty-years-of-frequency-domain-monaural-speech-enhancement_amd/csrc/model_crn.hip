@@ -102,15 +102,14 @@ class Crn final : public Model {
     // ---- frame-online mode (model.h): every conv / deconv looks back exactly one frame (CRN.py:38 ConstantPad2d top 1 +
     // kernel 2 in time; :112-117 Chomp_T), the LSTMs carry (h, c)
     bool stream_supported() const override { return true; }
+    StateLayout stream_layout() const override {
+        StateLayout lay;
+        for (long rows : stream_rows()) lay.hist.push_back({1, rows * STREAM_HC});      // [B][rows][HC]
+        for (int l = 0; l < 2; ++l) lay.h[l] = lay.c[l] = {1024, 1};                    // [H][B]
+        return lay;
+    }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
-        ss.release();
-        ss.B = B;
-        ss.first = true;
-        for (long rows : stream_rows()) ss.hist.push_back(ss.zeros((size_t)B * rows * STREAM_HC, st));
-        for (int l = 0; l < 2; ++l) {
-            ss.h[l] = ss.zeros((size_t)1024 * B, st);
-            ss.c[l] = ss.zeros((size_t)1024 * B, st);
-        }
+        ss.begin(stream_layout(), B, st);
         (void)max_chunk;
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {
@@ -299,16 +298,15 @@ class LstmNet final : public Model {
 
     // ---- frame-online mode: the network is three unidirectional LSTMs + a per-frame Linear, so the state is (h, c) x 3
     bool stream_supported() const override { return true; }
+    StateLayout stream_layout() const override {
+        StateLayout lay;
+        lay.hist.push_back({1, 2L * NBIN * STREAM_HC});      // spec [B][2][NBIN][HC]
+        lay.hist.push_back({1, (long)NBIN * STREAM_HC});     // est magnitudes [B][NBIN][HC]
+        for (int l = 0; l < 3; ++l) lay.h[l] = lay.c[l] = {1024, 1};      // [H][B]
+        return lay;
+    }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
-        ss.release();
-        ss.B = B;
-        ss.first = true;
-        ss.hist.push_back(ss.zeros((size_t)B * 2 * NBIN * STREAM_HC, st));      // spec
-        ss.hist.push_back(ss.zeros((size_t)B * NBIN * STREAM_HC, st));          // est magnitudes
-        for (int l = 0; l < 3; ++l) {
-            ss.h[l] = ss.zeros((size_t)1024 * B, st);
-            ss.c[l] = ss.zeros((size_t)1024 * B, st);
-        }
+        ss.begin(stream_layout(), B, st);
         (void)max_chunk;
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {

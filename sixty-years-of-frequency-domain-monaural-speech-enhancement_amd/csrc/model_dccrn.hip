@@ -281,16 +281,15 @@ class Dccrn final : public Model {
     int stream_lag() const override { return causal ? 0 : NL; }
     bool stream_supported() const override { return true; }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
-        ss.release();
-        ss.B = B;
-        ss.first = true;
-        for (long rows : stream_rows()) ss.hist.push_back(ss.zeros((size_t)B * rows * stream_hc(), st));
-        for (int l = 0; l < 2; ++l) {           // [2 real LSTMs][128][2B]  (real-LSTM form: [H][B] per layer)
-            const size_t n = rlstm ? (size_t)rnn_h * B : (size_t)2 * 128 * 2 * B;
-            ss.h[l] = ss.zeros(n, st);
-            ss.c[l] = ss.zeros(n, st);
-        }
+        ss.begin(stream_layout(), B, st);
         (void)max_chunk;
+    }
+    StateLayout stream_layout() const override {
+        StateLayout lay;
+        for (long rows : stream_rows()) lay.hist.push_back({1, rows * stream_hc()});      // [B][rows][HC]
+        // [2 real LSTMs][128][part * B + b]  (real-LSTM form: [H][B] per layer)
+        for (int l = 0; l < 2; ++l) lay.h[l] = lay.c[l] = rlstm ? RowLayout{rnn_h, 1} : RowLayout{2 * 128 * 2, 1};
+        return lay;
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {
         Bufs& b = bufs(B, stream_hc() + n);

@@ -126,15 +126,14 @@ class Dpcrn final : public Model {
     // intra-frame BiLSTM runs over frequency inside one frame, LayerNorm is per frame; the inter-frame LSTM (2 layers,
     // applied in both DPRNN passes with shared weights, :28-29) carries (h, c) - four states
     bool stream_supported() const override { return true; }
+    StateLayout stream_layout() const override {
+        StateLayout lay;
+        for (long rows : stream_rows()) lay.hist.push_back({1, rows * STREAM_HC});      // [B][rows][HC]
+        for (int l = 0; l < 4; ++l) lay.h[l] = lay.c[l] = {(long)CH * NF, 1};           // [CH][S], sequence s = f * B + b
+        return lay;
+    }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
-        ss.release();
-        ss.B = B;
-        ss.first = true;
-        for (long rows : stream_rows()) ss.hist.push_back(ss.zeros((size_t)B * rows * STREAM_HC, st));
-        for (int l = 0; l < 4; ++l) {
-            ss.h[l] = ss.zeros((size_t)CH * NF * B, st);
-            ss.c[l] = ss.zeros((size_t)CH * NF * B, st);
-        }
+        ss.begin(stream_layout(), B, st);
         (void)max_chunk;
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {

@@ -268,20 +268,19 @@ class FullSubNet final : public Model {
     int stream_lag() const override { return LA; }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
         SE_CHECK(STREAM_HC + max_chunk + LA <= STREAM_TP_MAX, "FullSubNet frame-online mode: chunks of at most 58 frames");
-        ss.release();
-        ss.B = B;
-        ss.first = true;
-        const size_t S = (size_t)NBIN * B;
-        ss.hist.push_back(ss.zeros((size_t)B * 2 * NBIN * STREAM_HC, st));      // spectrum
-        ss.hist.push_back(ss.zeros((size_t)B * 2 * NBIN * STREAM_HC, st));      // estimate
-        ss.hist.push_back(ss.zeros((size_t)B, st));                             // running sum of the full-band norm
-        ss.hist.push_back(ss.zeros(S, st));                                     // ... of the sub-band norm
+        ss.begin(stream_layout(), B, st);
+    }
+    StateLayout stream_layout() const override {
+        StateLayout lay;
+        lay.hist.push_back({1, 2L * NBIN * STREAM_HC});      // spectrum [B][2][NBIN][HC]
+        lay.hist.push_back({1, 2L * NBIN * STREAM_HC});      // estimate
+        lay.hist.push_back({1, 1});                          // running sum of the full-band norm [B]
+        lay.hist.push_back({NBIN, 1});                       // ... of the sub-band norm [S], sequence s = n * B + b
         for (int l = 0; l < 2; ++l) {
-            ss.h[l] = ss.zeros((size_t)512 * B, st);
-            ss.c[l] = ss.zeros((size_t)512 * B, st);
-            ss.h[2 + l] = ss.zeros(384 * S, st);
-            ss.c[2 + l] = ss.zeros(384 * S, st);
+            lay.h[l] = lay.c[l] = {512, 1};                        // [H][B]
+            lay.h[2 + l] = lay.c[2 + l] = {384L * NBIN, 1};        // [H][S]
         }
+        return lay;
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {
         Bufs& b = bufs(B, STREAM_HC + n);

@@ -119,15 +119,17 @@ class Gcrn final : public Model {
     // ---- frame-online mode (model.h): the (1,3) convs have no extent in time (GCRN_noncprs.py:42-83), LayerNorm is per
     // frame, so the only state is (h, c) of the four grouped LSTMs (:5-39) - and the last estimate frames for the iSTFT
     bool stream_supported() const override { return true; }
-    void stream_begin(int B, int max_chunk, hipStream_t st) override {
-        ss.release();
-        ss.B = B;
-        ss.first = true;
-        ss.hist.push_back(ss.zeros((size_t)B * 2 * NBIN * STREAM_HC, st));      // est
+    StateLayout stream_layout() const override {
+        StateLayout lay;
+        lay.hist.push_back({1, 2L * NBIN * STREAM_HC});      // est [B][2][NBIN][HC]
         for (int l = 0; l < 4; ++l) {
-            ss.h[l] = ss.zeros((size_t)512 * B, st);
-            ss.c[l] = ss.zeros((size_t)1024 * B, st);          // layer 1 writes its units to every other row (stride 2 S)
+            lay.h[l] = {512, 1};           // [H][B]
+            lay.c[l] = {1024, 1};          // [2 H][B]: layer 1 writes its units to every other row (stride 2 S)
         }
+        return lay;
+    }
+    void stream_begin(int B, int max_chunk, hipStream_t st) override {
+        ss.begin(stream_layout(), B, st);
         (void)max_chunk;
     }
     void stream_bufs(int B, int n, float** spec, float** mag, float** est) override {

@@ -26,5 +26,8 @@ void stream_resampler_save(StreamResampler* r, ResamplerState* s, hipStream_t st
 void stream_resampler_restore(StreamResampler* r, ResamplerState* s, hipStream_t st);
 int64_t resampler_state_export(const ResamplerState* s, void* host_buf, int64_t cap);
 void resampler_state_import(ResamplerState* s, const void* host_buf, int64_t bytes);
+// rows of parked signals: dst <- rows[j] of src / the rows of parts[0], parts[1], ... (include/se_engine.h)
+void resampler_state_select(ResamplerState* dst, ResamplerState* src, const int32_t* rows, int32_t n_rows, hipStream_t st);
+void resampler_state_concat(ResamplerState* dst, ResamplerState* const* parts, int32_t n_parts, hipStream_t st);
 
 }  // namespace se

@@ -87,6 +87,29 @@ inline std::string rsnap_check(const ResamplerManifest& m) {
     return "";
 }
 
+// ---- rows of parked signals (se_resampler_state_select / _concat): the payload is [batch][n_total - w0] floats
+// "" or why `rows` cannot pick rows of a state of `batch` rows
+inline std::string rsnap_rows_check(const int32_t* rows, int32_t n_rows, int32_t batch) {
+    if (n_rows < 1) return "n_rows " + std::to_string(n_rows) + ": at least one row has to be selected";
+    if (!rows) return "null row list";
+    for (int32_t j = 0; j < n_rows; ++j)
+        if (rows[j] < 0 || rows[j] >= batch)
+            return "rows[" + std::to_string(j) + "] = " + std::to_string(rows[j]) + " outside 0 .. " + std::to_string(batch - 1);
+    return "";
+}
+// "" or the first field in which two parts of a concat differ: everything except the batch has to agree
+inline std::string rsnap_concat_differs(const ResamplerManifest& a, const ResamplerManifest& b) {
+    auto ne = [](const char* name, int64_t x, int64_t y) { return std::string(name) + " " + std::to_string(x) + " vs " + std::to_string(y); };
+    if (a.sr_in != b.sr_in) return ne("sr_in", a.sr_in, b.sr_in);
+    if (a.sr_out != b.sr_out) return ne("sr_out", a.sr_out, b.sr_out);
+    if (a.n_total != b.n_total) return ne("n_in", a.n_total, b.n_total);
+    if (a.t != b.t) return ne("n_out", a.t, b.t);
+    if (a.w0 != b.w0) return ne("w0", a.w0, b.w0);
+    if (a.acc_bits != b.acc_bits)
+        return "read position " + std::to_string(rsnap_double_of(a.acc_bits)) + " vs " + std::to_string(rsnap_double_of(b.acc_bits)) + " (bits differ)";
+    return "";
+}
+
 // the header into out[0, RSNAP_HEAD_BYTES); the payload follows it
 inline void rsnap_write_head(const ResamplerManifest& m, uint8_t* out) {
     using rsnap_detail::put;

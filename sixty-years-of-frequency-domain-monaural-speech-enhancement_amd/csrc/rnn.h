@@ -98,6 +98,26 @@ struct StreamState {
         }
         B = 0;
     }
+    // a new stream of B_ rows: every buffer of the model's declaration, [outer][B_][inner] floats each (stream_rows.h), zeroed.  The
+    // one way a state buffer is made - the layout se_stream_state_select / _concat cut it by is the one it was allocated from
+    void begin(const StateLayout& lay, int B_, hipStream_t st) {
+        release();
+        B = B_;
+        first = true;
+        auto make = [&](const RowLayout& l) { return zeros((size_t)(l.outer * B_ * l.inner), st); };
+        for (const RowLayout& l : lay.hist) {
+            SE_CHECK(l.outer >= 1 && l.inner >= 1, "stream state: a history buffer without a row layout");
+            hist.push_back(make(l));
+        }
+        for (int l = 0; l < 4; ++l) {
+            SE_CHECK((lay.h[l].outer >= 1) == (lay.h[l].inner >= 1) && (lay.c[l].outer >= 1) == (lay.c[l].inner >= 1),
+                     "stream state: half a row layout");
+            if (lay.h[l].outer >= 1) h[l] = make(lay.h[l]);
+            if (lay.c[l].outer >= 1) c[l] = make(lay.c[l]);
+        }
+    }
+
+  private:
     float* zeros(size_t n, hipStream_t st) {
         n = std::max<size_t>(n, 1);
         float* p = nullptr;
@@ -115,6 +135,8 @@ struct StreamState {
         SE_HIP(hipMemsetAsync(p, 0, n * sizeof(float), st));
         return p;
     }
+
+  public:
     ~StreamState() {
         release();
         for (auto& kv : parked) {

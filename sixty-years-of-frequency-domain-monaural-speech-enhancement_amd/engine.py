@@ -78,6 +78,53 @@ class StreamSnapshot:
         snap.batch = int.from_bytes(b[28:32], 'little', signed=True)      # csrc/stream_manifest.h: the sixth int32 behind magic and version
         return snap
 
+    # ---- rows of parked groups (se_stream_state_select / se_stream_state_concat): `engine` supplies the buffers' row layouts and
+    # must be of the snapshots' kind; its own stream and workspace are not touched.  The result lives on the engine's device
+    @staticmethod
+    def _check_args(what, engine, snaps):
+        if not isinstance(engine, Engine):
+            raise EngineError(f"{what}: expected an Engine, got {type(engine).__name__}")
+        for s in snaps:
+            if not isinstance(s, StreamSnapshot):
+                raise EngineError(f"{what}: expected a StreamSnapshot, got {type(s).__name__}")
+            if s.closed:
+                raise EngineError(f"{what}: the snapshot is closed")
+        if not engine._h:
+            raise EngineError(f"{what}: the engine is closed")
+
+    def select(self, engine, rows, out=None):
+        """A snapshot of `len(rows)` rows: row j is row rows[j] of this one (an index may repeat: a fork).  Every counter and mode
+        is copied.  `out`: a snapshot to fill (one that already holds the resulting layout is reused without allocating)."""
+        self._check_args('select', engine, [self] + ([out] if out is not None else []))
+        rows = [int(r) for r in rows]
+        if not rows:
+            raise EngineError("select: at least one row has to be selected")
+        arr = (C.c_int32 * len(rows))(*rows)
+        dst = out if out is not None else StreamSnapshot()
+        if engine._lib.se_stream_state_select(engine._h, dst._h, self._h, arr, len(rows), engine._stream()):
+            if out is None:
+                dst.close()
+            raise EngineError(engine._lib.se_last_error(engine._h).decode())
+        dst.batch = len(rows)
+        return dst
+
+    @classmethod
+    def concat(cls, engine, parts, out=None):
+        """A snapshot of the rows of parts[0], then parts[1], ...: groups that have advanced in lockstep (every counter equal)
+        put back into one."""
+        parts = list(parts)
+        cls._check_args('concat', engine, parts + ([out] if out is not None else []))
+        if not parts:
+            raise EngineError("concat: at least one part has to be given")
+        arr = (C.c_void_p * len(parts))(*[p._h.value for p in parts])
+        dst = out if out is not None else cls()
+        if engine._lib.se_stream_state_concat(engine._h, dst._h, arr, len(parts), engine._stream()):
+            if out is None:
+                dst.close()
+            raise EngineError(engine._lib.se_last_error(engine._h).decode())
+        dst.batch = sum(p.batch for p in parts)
+        return dst
+
 
 class Engine:
     """One engine handle = one model replica on one GPU (one per rank)."""

@@ -117,6 +117,58 @@ class ResamplerSnapshot:
             raise EngineError(snap._lib.se_last_error(None).decode())
         return snap
 
+    # ---- rows of parked signals (se_resampler_state_select / se_resampler_state_concat): the payload is [batch][history] floats, so
+    # no resampler object is needed.  The result lives where the sources do (imported images are cut on the host)
+    @staticmethod
+    def _stream_of(device):
+        if device is None:
+            return C.c_void_p(0)
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+    @staticmethod
+    def _check_args(what, snaps):
+        for s in snaps:
+            if not isinstance(s, ResamplerSnapshot):
+                raise EngineError(f"{what}: expected a ResamplerSnapshot, got {type(s).__name__}")
+            if s.closed:
+                raise EngineError(f"{what}: the snapshot is closed")
+
+    def select(self, rows, out=None):
+        """A snapshot of `len(rows)` rows: row j is row rows[j] of this one (an index may repeat)."""
+        self._check_args('select', [self] + ([out] if out is not None else []))
+        rows = [int(r) for r in rows]
+        if not rows:
+            raise EngineError("select: at least one row has to be selected")
+        arr = (C.c_int32 * len(rows))(*rows)
+        dst = out if out is not None else ResamplerSnapshot()
+        if self._lib.se_resampler_state_select(dst._h, self._h, arr, len(rows), self._stream_of(self.device)):
+            if out is None:
+                dst.close()
+            raise EngineError(self._lib.se_last_error(None).decode())
+        dst.device = self.device
+        return dst
+
+    @classmethod
+    def concat(cls, parts, out=None):
+        """A snapshot of the rows of parts[0], then parts[1], ...: rates, sample counts and read position have to agree."""
+        parts = list(parts)
+        cls._check_args('concat', parts + ([out] if out is not None else []))
+        if not parts:
+            raise EngineError("concat: at least one part has to be given")
+        devices = {p.device for p in parts if p.device is not None}
+        if len(devices) > 1:
+            raise EngineError(f"concat: the parts' payloads live on devices {sorted(devices)} (move them with to_bytes / from_bytes)")
+        device = devices.pop() if devices else None
+        arr = (C.c_void_p * len(parts))(*[p._h.value for p in parts])
+        dst = out if out is not None else cls()
+        if dst._lib.se_resampler_state_concat(dst._h, arr, len(parts), cls._stream_of(device)):
+            if out is None:
+                dst.close()
+            raise EngineError(dst._lib.se_last_error(None).decode())
+        dst.device = device
+        return dst
+
 
 class StreamResampler:
     """The stateful form of `resample()` (se_resampler_* of include/se_engine.h): `begin(batch)`, then `push(x)` with

@@ -71,6 +71,41 @@ class SourceStreamSnapshot:
             raise
         return cls(eng, res)
 
+    # ---- rows of parked groups: both halves, the resampler's - which needs no device to refuse - first
+    def select(self, engine, rows):
+        """The pair of `len(rows)` rows: row j is row rows[j] of this one, in both halves (StreamSnapshot.select,
+        ResamplerSnapshot.select).  `engine`: an engine of the snapshot's kind."""
+        if self.closed:
+            raise EngineError("select: the snapshot is closed")
+        rows = [int(r) for r in rows]
+        batch = self.resampler.counts()[2]
+        if batch != self.engine.batch:
+            raise EngineError(f"select: the engine's half holds {self.engine.batch} rows, the resampler's {batch}")
+        res = self.resampler.select(rows)
+        try:
+            eng = self.engine.select(engine, rows)
+        except EngineError:
+            res.close()
+            raise
+        return SourceStreamSnapshot(eng, res)
+
+    @classmethod
+    def concat(cls, engine, parts):
+        """The pair of the rows of parts[0], then parts[1], ... in both halves."""
+        parts = list(parts)
+        for p in parts:
+            if not isinstance(p, SourceStreamSnapshot):
+                raise EngineError(f"concat: expected a SourceStreamSnapshot, got {type(p).__name__}")
+            if p.closed:
+                raise EngineError("concat: the snapshot is closed")
+        res = ResamplerSnapshot.concat([p.resampler for p in parts])
+        try:
+            eng = StreamSnapshot.concat(engine, [p.engine for p in parts])
+        except EngineError:
+            res.close()
+            raise
+        return cls(eng, res)
+
 
 class SourceRateStream:
     """`SourceRateStream(model.engine, 48000)`: `begin(batch, ...)`, `push(x)` with x [batch, n <= max_push] at sr_in ->
