@@ -1,0 +1,236 @@
+// FullSubNet's private kernels: the two Laplace norms (utterance mean, cumulative), the sub-band unfold and the mask back end,
+// offline and frame-online.  Reference lines as in model_fullsubnet.hip: FullSubNet/fullsubnet_net_sa/model.py:68-118,
+// base_model.py:13-42 (unfold), :197-209 (offline_laplace_norm), :212-240 (cumulative_laplace_norm),
+// fullsubnet_sa_decode_vb.py:56-66 (the complex mask and the decompress, applied in the script).
+//
+// Layouts (time-major, sequences contiguous): full band [T+2][257][B]; sub bands [T+2][32][257*B], sequence s = n*B + b is
+// sub-band n of utterance b.
+#include "k_fullsubnet.h"
+
+namespace se {
+
+using namespace fsn;
+
+namespace {
+
+// sum over (f, t) of mag[b][f][t]  ->  mu[b] = sum / (F * (T + LA))   (the look-ahead pad frames are zeros)
+// ragged batch (tlen != null): frames >= tlen[b] of mag are zeros (the STFT wrote them), so only the denominator changes
+__global__ __launch_bounds__(256) void fsn_mean_kernel(const float* __restrict__ mag, int n, float denom,
+                                                       float* __restrict__ mu, const int* __restrict__ tlen) {
+    const int b = blockIdx.x;
+    if (tlen) denom = (float)NBIN * (tlen[b] + LA);
+    const float* x = mag + (long)b * n;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += x[i];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    __shared__ double part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) mu[b] = (float)((part[0] + part[1] + part[2] + part[3]) / denom);
+}
+
+// y[i] = x[i] / (mu[i % B] + 1e-5)   for time-major tensors whose innermost index is the utterance
+__global__ __launch_bounds__(256) void fsn_scale_kernel(const float* __restrict__ x, float* __restrict__ y, long n,
+                                                        int B, const float* __restrict__ mu) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = x[i] / (mu[i % B] + 1e-5f);
+}
+
+// sub-band input before normalisation: sb[t][k][n*B + b];  k < 31: noisy mag of bin reflect(n - 15 + k)
+// (base_model.py:29-42, reflect pad), k = 31: full-band output of bin n (model.py:88-96)
+__global__ __launch_bounds__(256) void fsn_build_sb_kernel(const float* __restrict__ magT, const float* __restrict__ fbo,
+                                                           float* __restrict__ sb, int B) {
+    const int S = NBIN * B;
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    const int k = blockIdx.y, t = blockIdx.z;
+    if (s >= S) return;
+    const int n = s / B, b = s - n * B;
+    float v;
+    if (k == SBW - 1) {
+        v = fbo[((long)t * NBIN + n) * B + b];
+    } else {
+        int f = n - SBN + k;
+        if (f < 0) f = -f;
+        if (f >= NBIN) f = 2 * (NBIN - 1) - f;
+        v = magT[((long)t * NBIN + f) * B + b];
+    }
+    sb[((long)t * SBW + k) * S + s] = v;
+}
+
+// column sums of a [rows][B] matrix (utterance = innermost index) -> mu[b] = sum / rows; two deterministic stages
+// (per-block partials in a fixed order, then a fixed-order fp64 sum) - no float atomics, so repeated decodes are
+// bit-identical
+// ragged batch: rows are (t, k, n) t-major; utterance b only counts its own tlen[b] + LA frames
+__global__ __launch_bounds__(256) void fsn_colsum_kernel(const float* __restrict__ x, long rows, int B,
+                                                         float* __restrict__ part, const int* __restrict__ tlen) {
+    __shared__ float sh[256];
+    // thread handles column (tid % B) of rows tid / B + k * (256 / B)
+    const int per = 256 / B;
+    const int b = threadIdx.x % B, r0 = threadIdx.x / B;
+    float s = 0.f;
+    if (per > 0 && r0 < per) {
+        const long rmax = tlen ? (long)(tlen[b] + LA) * SBW * NBIN : rows;
+        for (long r = (long)blockIdx.x * per + r0; r < rmax; r += (long)gridDim.x * per) s += x[r * B + b];
+    }
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    if (per > 0 && r0 == 0) {
+        float t = 0.f;
+        for (int k = 0; k < per; ++k) t += sh[k * B + b];
+        part[(long)blockIdx.x * B + b] = t;
+    }
+}
+__global__ void fsn_finish_mean_kernel(const float* __restrict__ part, float* __restrict__ mu, float denom, int B,
+                                       const int* __restrict__ tlen) {
+    const int b = threadIdx.x;
+    if (b >= B) return;
+    if (tlen) denom = (float)(tlen[b] + LA) * SBW * NBIN;
+    double s = 0.0;
+    for (int k = 0; k < FSN_SUM_BLOCKS; ++k) s += part[(long)k * B + b];
+    mu[b] = (float)(s / denom);
+}
+
+// out[b][c][n][t] = mask[(n*B + b)][c][t + LA]                       (forward hook), or
+// est = mask (x) spec, decompressed (fullsubnet_sa_decode_vb.py:56-66)  (decode path)
+__global__ __launch_bounds__(256) void fsn_mask_kernel(const float* __restrict__ maskBT, const float* __restrict__ spec,
+                                                       float* __restrict__ out, int B, int T, float p_out) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int n = blockIdx.y, b = blockIdx.z;
+    if (t >= T) return;
+    const int Tp = T + LA;
+    const float* m = maskBT + ((long)(n * B + b) * 2) * Tp + t + LA;
+    const float mr = m[0], mi = m[Tp];
+    const long o = (((long)b * 2) * NBIN + n) * T + t;
+    const long plane = (long)NBIN * T;
+    if (!spec) {
+        out[o] = mr;
+        out[o + plane] = mi;
+        return;
+    }
+    const float xr = spec[o], xi = spec[o + plane];
+    float er = mr * xr - mi * xi, ei = mr * xi + mi * xr;
+    if (p_out != 1.f) {
+        const float mg = sqrtf(er * er + ei * ei);
+        const float sc = mg > 0.f ? ((p_out == 2.f) ? mg : powf(mg, p_out - 1.f)) : 0.f;
+        er *= sc;
+        ei *= sc;
+    }
+    out[o] = er;
+    out[o + plane] = ei;
+}
+
+// ---- cumulative_laplace_norm (base_model.py:212-240): x / (mean over (features, frames <= t) + EPSILON), float32 sums in the
+// reference's order - the features of a frame first, then a running sum over the frames.  `csum` (optional) carries the running
+// sum across the chunks of a frame-online stream; step 0 of the call is frame t_first of the utterance.
+// full band: x / y [n][257][B] time-major, one workgroup per utterance
+__global__ __launch_bounds__(256) void fsn_cum_fb_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int B,
+                                                         float* __restrict__ csum, int t_first) {
+    __shared__ float part[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float run = (csum && t_first > 0) ? csum[b] : 0.f;
+    for (int t = 0; t < n; ++t) {
+        const float* xr = x + (long)t * NBIN * B + b;
+        const float v0 = xr[(long)tid * B], v1 = tid + 256 < NBIN ? xr[(long)(tid + 256) * B] : 0.f;
+        float s = v0 + v1;
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        __syncthreads();
+        if ((tid & 63) == 0) part[tid >> 6] = s;
+        __syncthreads();
+        run += (part[0] + part[1]) + (part[2] + part[3]);
+        const float d = run / ((float)NBIN * (float)(t_first + t + 1)) + FSN_EPS;
+        float* yr = y + (long)t * NBIN * B + b;
+        yr[(long)tid * B] = v0 / d;
+        if (tid + 256 < NBIN) yr[(long)(tid + 256) * B] = v1 / d;
+    }
+    if (csum && tid == 0) csum[b] = run;
+}
+// sub bands: sb [n][32][S] in place, one thread per sequence s (sub-band of an utterance)
+__global__ __launch_bounds__(256) void fsn_cum_sb_kernel(float* __restrict__ sb, int n, int S, float* __restrict__ csum, int t_first) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= S) return;
+    float run = (csum && t_first > 0) ? csum[s] : 0.f;
+    for (int t = 0; t < n; ++t) {
+        float* xr = sb + (long)t * SBW * S + s;
+        float v[SBW], sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < SBW; ++k) {
+            v[k] = xr[(long)k * S];
+            sum += v[k];
+        }
+        run += sum;
+        const float d = run / ((float)SBW * (float)(t_first + t + 1)) + FSN_EPS;
+#pragma unroll
+        for (int k = 0; k < SBW; ++k) xr[(long)k * S] = v[k] / d;
+    }
+    if (csum) csum[s] = run;
+}
+// frame-online: mask of network step tau (maskT [ns][2][S], s = n B + b) applied to the spectrum of frame tau - LA, which sits in
+// column col0 + tau of the chunk window ([B][2][257][Tw]); frames before the start of the stream (gt0 + tau < LA) do not exist
+__global__ __launch_bounds__(256) void fsn_stream_apply_kernel(const float* __restrict__ maskT, const float* __restrict__ spec,
+                                                               float* __restrict__ est, int B, int Tw, int ns, int col0, int gt0,
+                                                               float p_out) {
+    const int i = blockIdx.x * 256 + threadIdx.x, tau = blockIdx.y;
+    const int S = NBIN * B;
+    if (i >= S || gt0 + tau < LA) return;
+    const int n = i / B, b = i - n * B, col = col0 + tau;
+    const float mr = maskT[((long)tau * 2) * S + i], mi = maskT[((long)tau * 2 + 1) * S + i];
+    const long o = (((long)b * 2) * NBIN + n) * Tw + col, plane = (long)NBIN * Tw;
+    const float xr = spec[o], xi = spec[o + plane];
+    float er = mr * xr - mi * xi, ei = mr * xi + mi * xr;
+    if (p_out != 1.f) {
+        const float mg = sqrtf(er * er + ei * ei);
+        const float sc = mg > 0.f ? ((p_out == 2.f) ? mg : powf(mg, p_out - 1.f)) : 0.f;
+        er *= sc;
+        ei *= sc;
+    }
+    est[o] = er;
+    est[o + plane] = ei;
+    (void)ns;
+}
+
+}  // namespace
+
+void launch_fsn_mean(const float* mag, int B, int n, float denom, float* mu, const int* tlen, hipStream_t st) {
+    hipLaunchKernelGGL(fsn_mean_kernel, dim3(B), dim3(256), 0, st, mag, n, denom, mu, tlen);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_scale(const float* x, float* y, long n, int B, const float* mu, hipStream_t st) {
+    hipLaunchKernelGGL(fsn_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, n, B, mu);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_build_sb(const float* magT, const float* fbo, float* sb, int B, int steps, hipStream_t st) {
+    const int S = NBIN * B;
+    hipLaunchKernelGGL(fsn_build_sb_kernel, dim3((S + 255) / 256, SBW, steps), dim3(256), 0, st, magT, fbo, sb, B);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_colsum(const float* x, long rows, int B, float* part, const int* tlen, hipStream_t st) {
+    SE_CHECK(B >= 1 && B <= 256, "FullSubNet batch per call is limited to 256 utterances");
+    hipLaunchKernelGGL(fsn_colsum_kernel, dim3(FSN_SUM_BLOCKS), dim3(256), 0, st, x, rows, B, part, tlen);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_finish_mean(const float* part, float* mu, float denom, int B, const int* tlen, hipStream_t st) {
+    SE_CHECK(B >= 1 && B <= 256, "FullSubNet batch per call is limited to 256 utterances");
+    hipLaunchKernelGGL(fsn_finish_mean_kernel, dim3(1), dim3(256), 0, st, part, mu, denom, B, tlen);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_mask(const float* maskBT, const float* spec, float* out, int B, int T, float p_out, hipStream_t st) {
+    hipLaunchKernelGGL(fsn_mask_kernel, dim3((T + 255) / 256, NBIN, B), dim3(256), 0, st, maskBT, spec, out, B, T, p_out);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_cum_fb(const float* x, float* y, int n, int B, float* csum, int t_first, hipStream_t st) {
+    hipLaunchKernelGGL(fsn_cum_fb_kernel, dim3(B), dim3(256), 0, st, x, y, n, B, csum, t_first);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_cum_sb(float* sb, int n, int S, float* csum, int t_first, hipStream_t st) {
+    hipLaunchKernelGGL(fsn_cum_sb_kernel, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, t_first);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_stream_apply(const float* maskT, const float* spec, float* est, int B, int Tw, int ns, int col0, int gt0,
+                             float p_out, hipStream_t st) {
+    const int S = NBIN * B;
+    hipLaunchKernelGGL(fsn_stream_apply_kernel, dim3((S + 255) / 256, ns), dim3(256), 0, st, maskT, spec, est, B, Tw, ns, col0,
+                       gt0, p_out);
+    SE_HIP(hipGetLastError());
+}
+
+}  // namespace se

@@ -85,20 +85,56 @@ void launch_transpose_akt(const float* in, float* out, int A, int K, int T, long
     SE_HIP(hipGetLastError());
 }
 
-// ---- strided 4-D copy ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void copy4_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int I,
-                                                    int J, long si_b, long si_c, long si_i, long si_j, long so_b,
-                                                    long so_c, long so_i) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= J) return;
-    const int i = blockIdx.y % I, c = blockIdx.y / I, b = blockIdx.z;
-    out[(long)b * so_b + (long)c * so_c + (long)i * so_i + j] = in[(long)b * si_b + (long)c * si_c + (long)i * si_i + (long)j * si_j];
+// ---- the elementwise recurrences of TaylorSENet and G2Net; gain [B][plane], everything else [B][2][plane] ------
+namespace {
+// zero[b][c][f][t] = gain[b][f][t] * spec[b][c][f][t]     (TaylorSENet.py:73-76: gain*|X| e^{j angle X} = gain * X)
+__global__ __launch_bounds__(256) void taylor_zero_kernel(const float* __restrict__ gain, const float* __restrict__ spec,
+                                                          float* __restrict__ zero, float* __restrict__ out, long plane,
+                                                          long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long b = i / plane, r = i - b * plane;
+    const long o = b * 2 * plane + r;
+    const float g = gain[i];
+    const float zr = g * spec[o], zi = g * spec[o + plane];
+    zero[o] = zr;
+    zero[o + plane] = zi;
+    out[o] = zr;
+    out[o + plane] = zi;
 }
+// update = hob + k * pre;  pre <- update;  out += update / (k+1)!      (:85-93)
+__global__ __launch_bounds__(256) void taylor_update_kernel(const float* __restrict__ hob, float* __restrict__ pre,
+                                                            float* __restrict__ out, long n, float k, float inv_fact) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float u = hob[i] + k * pre[i];
+    pre[i] = u;
+    out[i] += u * inv_fact;
+}
+// x_next = gain * pre + resi ; gain [B][161][T], pre / resi / out [B][2][161][T]      (gaf_net_320.py:104-115)
+__global__ __launch_bounds__(256) void gaf_combine_kernel(const float* __restrict__ gain, const float* __restrict__ pre,
+                                                          const float* __restrict__ resi, float* __restrict__ out, long plane,
+                                                          long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long b = i / plane, r = i - b * plane;
+    const long o = b * 2 * plane + r;
+    const float g = gain[i];
+    out[o] = g * pre[o] + resi[o];
+    out[o + plane] = g * pre[o + plane] + resi[o + plane];
+}
+}  // namespace
 
-void launch_copy4(const float* in, float* out, int B, int C, int I, int J, long si_b, long si_c, long si_i, long si_j,
-                  long so_b, long so_c, long so_i, hipStream_t s) {
-    hipLaunchKernelGGL(copy4_kernel, dim3((J + 255) / 256, C * I, B), dim3(256), 0, s, in, out, C, I, J, si_b, si_c,
-                       si_i, si_j, so_b, so_c, so_i);
+void launch_taylor_zero(const float* gain, const float* spec, float* zero, float* out, long plane, long total, hipStream_t s) {
+    hipLaunchKernelGGL(taylor_zero_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, gain, spec, zero, out, plane, total);
+    SE_HIP(hipGetLastError());
+}
+void launch_taylor_update(const float* hob, float* pre, float* out, long n, float k, float inv_fact, hipStream_t s) {
+    hipLaunchKernelGGL(taylor_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hob, pre, out, n, k, inv_fact);
+    SE_HIP(hipGetLastError());
+}
+void launch_gaf_combine(const float* gain, const float* pre, const float* resi, float* out, long plane, long total, hipStream_t s) {
+    hipLaunchKernelGGL(gaf_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, gain, pre, resi, out, plane, total);
     SE_HIP(hipGetLastError());
 }
 

@@ -233,9 +233,13 @@ void launch_dccrn_mask(const float* mask, const float* spec, float* est, int B, 
 void launch_transpose_akt(const float* in, float* out, int A, int K, int T, long in_sa, long in_sk, long out_st,
                           long out_sk, hipStream_t s);
 
-// y = x  (strided 4-D copy / layout change):  out[b][c][i][j] at strides so_*, in at si_*; inner j contiguous in out.
-void launch_copy4(const float* in, float* out, int B, int C, int I, int J, long si_b, long si_c, long si_i, long si_j,
-                  long so_b, long so_c, long so_i, hipStream_t s);
+// TaylorSENet's zero-order term and high-order recurrence (TaylorSENet.py:73-76, :85-93); gain [B][plane], spec / zero / out
+// [B][2][plane], total = B * plane;  hob / pre / out: n elements
+//   zero = out = gain * spec;      update = hob + k * pre, pre <- update, out += update * inv_fact
+void launch_taylor_zero(const float* gain, const float* spec, float* zero, float* out, long plane, long total, hipStream_t s);
+void launch_taylor_update(const float* hob, float* pre, float* out, long n, float k, float inv_fact, hipStream_t s);
+// G2Net's stage output (gaf_net_320.py:104-115): out = gain * pre + resi; gain [B][plane], pre / resi / out [B][2][plane]
+void launch_gaf_combine(const float* gain, const float* pre, const float* resi, float* out, long plane, long total, hipStream_t s);
 
 void launch_fill(float* p, long n, float v, hipStream_t s);
 // ragged batches only (no-op otherwise): x [B][rows][T], frames t >= tlen[b] of every row set to zero

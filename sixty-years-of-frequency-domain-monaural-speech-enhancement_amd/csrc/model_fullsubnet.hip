@@ -15,190 +15,16 @@
 //                     LSTM cell fused in the epilogue.
 #include "decode_frame.h"
 #include "rnn.h"
+#include "k_fullsubnet.h"
 #include "../../include/se_engine.h"
 
 namespace se {
 
+using namespace fsn;      // NBIN, LA, SBN, SBW, FSN_SUM_BLOCKS, FSN_EPS (k_fullsubnet.h)
+
 namespace {
 
-constexpr int NFFT = 512, HOP = 256, NBIN = 257, LA = 2, SBN = 15, SBW = 2 * SBN + 2;   // 31 noisy + 1 full-band
-
-// sum over (f, t) of mag[b][f][t]  ->  mu[b] = sum / (F * (T + LA))   (the look-ahead pad frames are zeros)
-// ragged batch (tlen != null): frames >= tlen[b] of mag are zeros (the STFT wrote them), so only the denominator changes
-__global__ __launch_bounds__(256) void fsn_mean_kernel(const float* __restrict__ mag, int n, float denom,
-                                                       float* __restrict__ mu, const int* __restrict__ tlen) {
-    const int b = blockIdx.x;
-    if (tlen) denom = (float)NBIN * (tlen[b] + LA);
-    const float* x = mag + (long)b * n;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) s += x[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    __shared__ double part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) mu[b] = (float)((part[0] + part[1] + part[2] + part[3]) / denom);
-}
-
-// y[i] = x[i] / (mu[i % B] + 1e-5)   for time-major tensors whose innermost index is the utterance
-__global__ __launch_bounds__(256) void fsn_scale_kernel(const float* __restrict__ x, float* __restrict__ y, long n,
-                                                        int B, const float* __restrict__ mu) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) y[i] = x[i] / (mu[i % B] + 1e-5f);
-}
-
-// sub-band input before normalisation: sb[t][k][n*B + b];  k < 31: noisy mag of bin reflect(n - 15 + k)
-// (base_model.py:29-42, reflect pad), k = 31: full-band output of bin n (model.py:88-96)
-__global__ __launch_bounds__(256) void fsn_build_sb_kernel(const float* __restrict__ magT, const float* __restrict__ fbo,
-                                                           float* __restrict__ sb, int B) {
-    const int S = NBIN * B;
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    const int k = blockIdx.y, t = blockIdx.z;
-    if (s >= S) return;
-    const int n = s / B, b = s - n * B;
-    float v;
-    if (k == SBW - 1) {
-        v = fbo[((long)t * NBIN + n) * B + b];
-    } else {
-        int f = n - SBN + k;
-        if (f < 0) f = -f;
-        if (f >= NBIN) f = 2 * (NBIN - 1) - f;
-        v = magT[((long)t * NBIN + f) * B + b];
-    }
-    sb[((long)t * SBW + k) * S + s] = v;
-}
-
-// column sums of a [rows][B] matrix (utterance = innermost index) -> mu[b] = sum / rows; two deterministic stages
-// (per-block partials in a fixed order, then a fixed-order fp64 sum) - no float atomics, so repeated decodes are
-// bit-identical
-constexpr int FSN_SUM_BLOCKS = 1024;
-// ragged batch: rows are (t, k, n) t-major; utterance b only counts its own tlen[b] + LA frames
-__global__ __launch_bounds__(256) void fsn_colsum_kernel(const float* __restrict__ x, long rows, int B,
-                                                         float* __restrict__ part, const int* __restrict__ tlen) {
-    __shared__ float sh[256];
-    // thread handles column (tid % B) of rows tid / B + k * (256 / B)
-    const int per = 256 / B;
-    const int b = threadIdx.x % B, r0 = threadIdx.x / B;
-    float s = 0.f;
-    if (per > 0 && r0 < per) {
-        const long rmax = tlen ? (long)(tlen[b] + LA) * SBW * NBIN : rows;
-        for (long r = (long)blockIdx.x * per + r0; r < rmax; r += (long)gridDim.x * per) s += x[r * B + b];
-    }
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    if (per > 0 && r0 == 0) {
-        float t = 0.f;
-        for (int k = 0; k < per; ++k) t += sh[k * B + b];
-        part[(long)blockIdx.x * B + b] = t;
-    }
-}
-__global__ void fsn_finish_mean_kernel(const float* __restrict__ part, float* __restrict__ mu, float denom, int B,
-                                       const int* __restrict__ tlen) {
-    const int b = threadIdx.x;
-    if (b >= B) return;
-    if (tlen) denom = (float)(tlen[b] + LA) * SBW * NBIN;
-    double s = 0.0;
-    for (int k = 0; k < FSN_SUM_BLOCKS; ++k) s += part[(long)k * B + b];
-    mu[b] = (float)(s / denom);
-}
-
-// out[b][c][n][t] = mask[(n*B + b)][c][t + LA]                       (forward hook), or
-// est = mask (x) spec, decompressed (fullsubnet_sa_decode_vb.py:56-66)  (decode path)
-__global__ __launch_bounds__(256) void fsn_mask_kernel(const float* __restrict__ maskBT, const float* __restrict__ spec,
-                                                       float* __restrict__ out, int B, int T, float p_out) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const int n = blockIdx.y, b = blockIdx.z;
-    if (t >= T) return;
-    const int Tp = T + LA;
-    const float* m = maskBT + ((long)(n * B + b) * 2) * Tp + t + LA;
-    const float mr = m[0], mi = m[Tp];
-    const long o = (((long)b * 2) * NBIN + n) * T + t;
-    const long plane = (long)NBIN * T;
-    if (!spec) {
-        out[o] = mr;
-        out[o + plane] = mi;
-        return;
-    }
-    const float xr = spec[o], xi = spec[o + plane];
-    float er = mr * xr - mi * xi, ei = mr * xi + mi * xr;
-    if (p_out != 1.f) {
-        const float mg = sqrtf(er * er + ei * ei);
-        const float sc = mg > 0.f ? ((p_out == 2.f) ? mg : powf(mg, p_out - 1.f)) : 0.f;
-        er *= sc;
-        ei *= sc;
-    }
-    out[o] = er;
-    out[o + plane] = ei;
-}
-
-// ---- cumulative_laplace_norm (base_model.py:212-240): x / (mean over (features, frames <= t) + EPSILON), float32 sums in the
-// reference's order - the features of a frame first, then a running sum over the frames.  `csum` (optional) carries the running
-// sum across the chunks of a frame-online stream; step 0 of the call is frame t_first of the utterance.
-constexpr float FSN_EPS = 1.1920928955078125e-07f;        // np.finfo(np.float32).eps (constant.py:8)
-// full band: x / y [n][257][B] time-major, one workgroup per utterance
-__global__ __launch_bounds__(256) void fsn_cum_fb_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int B,
-                                                         float* __restrict__ csum, int t_first) {
-    __shared__ float part[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    float run = (csum && t_first > 0) ? csum[b] : 0.f;
-    for (int t = 0; t < n; ++t) {
-        const float* xr = x + (long)t * NBIN * B + b;
-        const float v0 = xr[(long)tid * B], v1 = tid + 256 < NBIN ? xr[(long)(tid + 256) * B] : 0.f;
-        float s = v0 + v1;
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-        __syncthreads();
-        if ((tid & 63) == 0) part[tid >> 6] = s;
-        __syncthreads();
-        run += (part[0] + part[1]) + (part[2] + part[3]);
-        const float d = run / ((float)NBIN * (float)(t_first + t + 1)) + FSN_EPS;
-        float* yr = y + (long)t * NBIN * B + b;
-        yr[(long)tid * B] = v0 / d;
-        if (tid + 256 < NBIN) yr[(long)(tid + 256) * B] = v1 / d;
-    }
-    if (csum && tid == 0) csum[b] = run;
-}
-// sub bands: sb [n][32][S] in place, one thread per sequence s (sub-band of an utterance)
-__global__ __launch_bounds__(256) void fsn_cum_sb_kernel(float* __restrict__ sb, int n, int S, float* __restrict__ csum, int t_first) {
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= S) return;
-    float run = (csum && t_first > 0) ? csum[s] : 0.f;
-    for (int t = 0; t < n; ++t) {
-        float* xr = sb + (long)t * SBW * S + s;
-        float v[SBW], sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < SBW; ++k) {
-            v[k] = xr[(long)k * S];
-            sum += v[k];
-        }
-        run += sum;
-        const float d = run / ((float)SBW * (float)(t_first + t + 1)) + FSN_EPS;
-#pragma unroll
-        for (int k = 0; k < SBW; ++k) xr[(long)k * S] = v[k] / d;
-    }
-    if (csum) csum[s] = run;
-}
-// frame-online: mask of network step tau (maskT [ns][2][S], s = n B + b) applied to the spectrum of frame tau - LA, which sits in
-// column col0 + tau of the chunk window ([B][2][257][Tw]); frames before the start of the stream (gt0 + tau < LA) do not exist
-__global__ __launch_bounds__(256) void fsn_stream_apply_kernel(const float* __restrict__ maskT, const float* __restrict__ spec,
-                                                               float* __restrict__ est, int B, int Tw, int ns, int col0, int gt0,
-                                                               float p_out) {
-    const int i = blockIdx.x * 256 + threadIdx.x, tau = blockIdx.y;
-    const int S = NBIN * B;
-    if (i >= S || gt0 + tau < LA) return;
-    const int n = i / B, b = i - n * B, col = col0 + tau;
-    const float mr = maskT[((long)tau * 2) * S + i], mi = maskT[((long)tau * 2 + 1) * S + i];
-    const long o = (((long)b * 2) * NBIN + n) * Tw + col, plane = (long)NBIN * Tw;
-    const float xr = spec[o], xi = spec[o + plane];
-    float er = mr * xr - mi * xi, ei = mr * xi + mi * xr;
-    if (p_out != 1.f) {
-        const float mg = sqrtf(er * er + ei * ei);
-        const float sc = mg > 0.f ? ((p_out == 2.f) ? mg : powf(mg, p_out - 1.f)) : 0.f;
-        er *= sc;
-        ei *= sc;
-    }
-    est[o] = er;
-    est[o + plane] = ei;
-    (void)ns;
-}
+constexpr int NFFT = 512, HOP = 256;
 
 class FullSubNet final : public Model {
   public:
@@ -242,8 +68,7 @@ class FullSubNet final : public Model {
         const int B = (int)shape[0], T = (int)shape[3];
         Bufs& b = bufs(B, T);
         network(b, in, st);
-        hipLaunchKernelGGL(fsn_mask_kernel, dim3((T + 255) / 256, NBIN, B), dim3(256), 0, st, b.maskBT, nullptr, out, B, T, 1.f);
-        SE_HIP(hipGetLastError());
+        launch_fsn_mask(b.maskBT, nullptr, out, B, T, 1.f, st);
     }
 
     void enhance(const float* wav, long pitch, int B, int L, float* out, long out_pitch, hipStream_t st) override {
@@ -252,9 +77,7 @@ class FullSubNet final : public Model {
         launch_rms_scale(wav, B, L, pitch, b.c, st);                                               // :38-39
         launch_stft(ctx.geom, wav, pitch, B, L, L, b.c, ctx.p_in, b.spec, b.mag, T, T, st);        // :46-54
         network(b, b.mag, st);                                                                     // :56
-        hipLaunchKernelGGL(fsn_mask_kernel, dim3((T + 255) / 256, NBIN, B), dim3(256), 0, st, b.maskBT, b.spec, b.est, B, T,
-                           ctx.p_out);                                                             // :57-66
-        SE_HIP(hipGetLastError());
+        launch_fsn_mask(b.maskBT, b.spec, b.est, B, T, ctx.p_out, st);                                    // :57-66
         launch_istft(ctx.geom, b.est, B, T, T, b.frames, b.c, out, out_pitch, L, st);              // :69-72
     }
 
@@ -300,18 +123,16 @@ class FullSubNet final : public Model {
         // magnitudes of the new frames, time-major [ns][257][B]; at the end of the stream two zero frames (model.py:79)
         launch_transpose_akt(b.mag + HC, b.magT, B, NBIN, n, (long)NBIN * Tw, Tw, (long)NBIN * B, B, st);
         if (last) launch_fill(b.magT + (size_t)n * S, (long)LA * S, 0.f, st);
-        hipLaunchKernelGGL(fsn_cum_fb_kernel, dim3(B), dim3(256), 0, st, b.magT, b.xfb, ns, B, ss.hist[2], t0);
+        launch_fsn_cum_fb(b.magT, b.xfb, ns, B, ss.hist[2], t0, st);
         fb[0].run_stream(b.xfb, b.G, ss.c[0], ss.h[0], b.h[0], ns, B, ss.first, st, pf);
         fb[1].run_stream(b.h[0], b.G, ss.c[1], ss.h[1], b.h[1], ns, B, ss.first, st, pf);
         run_pointwise(fb_fc, b.h[1], 512L * B, B, b.fbo, (long)NBIN * B, B, ns, B, st, pf);
-        hipLaunchKernelGGL(fsn_build_sb_kernel, dim3((S + 255) / 256, SBW, ns), dim3(256), 0, st, b.magT, b.fbo, b.sb, B);
-        hipLaunchKernelGGL(fsn_cum_sb_kernel, dim3((S + 255) / 256), dim3(256), 0, st, b.sb, ns, S, ss.hist[3], t0);
+        launch_fsn_build_sb(b.magT, b.fbo, b.sb, B, ns, st);
+        launch_fsn_cum_sb(b.sb, ns, S, ss.hist[3], t0, st);
         sbl[0].run_stream(b.sb, b.G, ss.c[2], ss.h[2], b.h[0], ns, S, ss.first, st, pf);
         sbl[1].run_stream(b.h[0], b.G, ss.c[3], ss.h[3], b.h[1], ns, S, ss.first, st, pf);
         run_pointwise(sb_fc, b.h[1], 384L * S, S, b.maskT, 2L * S, S, ns, S, st, pf);
-        hipLaunchKernelGGL(fsn_stream_apply_kernel, dim3((S + 255) / 256, ns), dim3(256), 0, st, b.maskT, b.spec, b.est, B, Tw, ns,
-                           HC - LA, t0, ctx.p_out);
-        SE_HIP(hipGetLastError());
+        launch_fsn_stream_apply(b.maskT, b.spec, b.est, B, Tw, ns, HC - LA, t0, ctx.p_out, st);
         launch_hist_save(b.spec, ss.hist[0], B, 2L * NBIN, Tw, HC, st);
         launch_hist_save(b.est, ss.hist[1], B, 2L * NBIN, Tw, HC, st);
         ss.first = false;
@@ -381,28 +202,28 @@ class FullSubNet final : public Model {
         // ---- full-band model (model.py:84-85): utterance-mean normalisation, LSTM(257->512)x2, Linear + ReLU
         const Ragged* rg = ragged_ctx();
         const int* tlen = rg ? rg->tlen : nullptr;
-        if (!cum) hipLaunchKernelGGL(fsn_mean_kernel, dim3(B), dim3(256), 0, st, mag, NBIN * T, (float)NBIN * Tp, b.mu, tlen);
+        if (!cum) launch_fsn_mean(mag, B, NBIN * T, (float)NBIN * Tp, b.mu, tlen, st);
         launch_fill(b.magT + (size_t)T * S, (long)LA * S, 0.f, st);                                // look-ahead pad :79 (a kernel, not a memset node: graph-replay safe)
         launch_transpose_akt(mag, b.magT, B, NBIN, T, (long)NBIN * T, T, (long)NBIN * B, B, st);
         const long nfb = (long)Tp * S;
         // (cumulative norm, ragged rows: frames >= tlen[b] are zeros - the STFT wrote them - and everything is causal, so a
         // row's own frames and its two look-ahead frames see exactly what the clip decoded alone sees)
-        if (cum) hipLaunchKernelGGL(fsn_cum_fb_kernel, dim3(B), dim3(256), 0, st, b.magT, b.xfb, Tp, B, (float*)nullptr, 0);
-        else hipLaunchKernelGGL(fsn_scale_kernel, dim3((unsigned)((nfb + 255) / 256)), dim3(256), 0, st, b.magT, b.xfb, nfb, B, b.mu);
+        if (cum) launch_fsn_cum_fb(b.magT, b.xfb, Tp, B, nullptr, 0, st);
+        else launch_fsn_scale(b.magT, b.xfb, nfb, B, b.mu, st);
         fb[0].run(b.xfb, b.G, b.cell, b.h[0], Tp, B, st, pf);
         fb[1].run(b.h[0], b.G, b.cell, b.h[1], Tp, B, st, pf);
         run_pointwise(fb_fc, b.h[1], 512L * B, B, b.fbo, (long)NBIN * B, B, Tp, B, st, pf);
         // ---- sub-band input (:88-97): unfold(noisy, 15) ++ unfold(fb_out, 0), normalised by its utterance mean
-        hipLaunchKernelGGL(fsn_build_sb_kernel, dim3((S + 255) / 256, SBW, Tp), dim3(256), 0, st, b.magT, b.fbo, b.sb, B);
+        launch_fsn_build_sb(b.magT, b.fbo, b.sb, B, Tp, st);
         const long rows = (long)Tp * SBW * NBIN;
         SE_CHECK(B <= 256, "FullSubNet batch per call is limited to 256 utterances");
         if (cum) {
-            hipLaunchKernelGGL(fsn_cum_sb_kernel, dim3((S + 255) / 256), dim3(256), 0, st, b.sb, Tp, S, (float*)nullptr, 0);
+            launch_fsn_cum_sb(b.sb, Tp, S, nullptr, 0, st);
         } else {
-            hipLaunchKernelGGL(fsn_colsum_kernel, dim3(FSN_SUM_BLOCKS), dim3(256), 0, st, b.sb, rows, B, b.part, tlen);
-            hipLaunchKernelGGL(fsn_finish_mean_kernel, dim3(1), dim3(256), 0, st, b.part, b.mu2, (float)rows, B, tlen);
+            launch_fsn_colsum(b.sb, rows, B, b.part, tlen, st);
+            launch_fsn_finish_mean(b.part, b.mu2, (float)rows, B, tlen, st);
             const long nsb = rows * B;
-            hipLaunchKernelGGL(fsn_scale_kernel, dim3((unsigned)((nsb + 255) / 256)), dim3(256), 0, st, b.sb, b.sb, nsb, B, b.mu2);
+            launch_fsn_scale(b.sb, b.sb, nsb, B, b.mu2, st);
         }
         SE_HIP(hipGetLastError());
         // ---- sub-band model (:106-114): LSTM(32->384)x2 over 257*B sequences, Linear(384->2)

@@ -17,18 +17,7 @@ namespace {
 constexpr int NFFT = 320, HOP = 160, NBIN = 161, NDIL = 4;
 constexpr int DIL[NDIL] = {1, 2, 5, 9};
 
-// x_next = gain * pre + resi ; gain [B][161][T], pre / resi / out [B][2][161][T]
-__global__ __launch_bounds__(256) void gaf_combine_kernel(const float* __restrict__ gain, const float* __restrict__ pre,
-                                                          const float* __restrict__ resi, float* __restrict__ out, long plane,
-                                                          long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const long b = i / plane, r = i - b * plane;
-    const long o = b * 2 * plane + r;
-    const float g = gain[i];
-    out[o] = g * pre[o] + resi[o];
-    out[o + plane] = g * pre[o + plane] + resi[o + plane];
-}
+// (x_next = gain * pre + resi: launch_gaf_combine, k_misc.hip)
 
 struct G2TcmSeq {      // nn.Sequential(Tcm_list, Tcm_list, Conv1d(256, 161, 1)[, Sigmoid])
     TcmBlock blk[2 * NDIL];
@@ -275,8 +264,7 @@ class G2Net final : public Model {
             fk.join(0);
             fk.join(1);
             float* nxt = b.pre[s & 1];
-            hipLaunchKernelGGL(gaf_combine_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, b.gain, pre, b.resi, nxt,
-                               plane, tot);
+            launch_gaf_combine(b.gain, pre, b.resi, nxt, plane, tot, st);
             pre = nxt;
         }
         SE_HIP(hipGetLastError());

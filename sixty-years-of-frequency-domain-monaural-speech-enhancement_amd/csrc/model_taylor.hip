@@ -16,30 +16,7 @@ namespace {
 constexpr int NFFT = 320, HOP = 160, NBIN = 161, NDIL = 4;
 constexpr int DIL[NDIL] = {1, 2, 5, 9};
 
-// zero[b][c][f][t] = gain[b][f][t] * spec[b][c][f][t]     (TaylorSENet.py:73-76: gain*|X| e^{j angle X} = gain * X)
-__global__ __launch_bounds__(256) void taylor_zero_kernel(const float* __restrict__ gain, const float* __restrict__ spec,
-                                                          float* __restrict__ zero, float* __restrict__ out, long plane,
-                                                          long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const long b = i / plane, r = i - b * plane;
-    const long o = b * 2 * plane + r;
-    const float g = gain[i];
-    const float zr = g * spec[o], zi = g * spec[o + plane];
-    zero[o] = zr;
-    zero[o + plane] = zi;
-    out[o] = zr;
-    out[o + plane] = zi;
-}
-// update = hob + k * pre;  pre <- update;  out += update / (k+1)!      (:85-93)
-__global__ __launch_bounds__(256) void taylor_update_kernel(const float* __restrict__ hob, float* __restrict__ pre,
-                                                            float* __restrict__ out, long n, float k, float inv_fact) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float u = hob[i] + k * pre[i];
-    pre[i] = u;
-    out[i] += u * inv_fact;
-}
+// (the zero-order product and the recurrence's update: launch_taylor_zero / launch_taylor_update, k_misc.hip)
 
 struct TcmStack {       // p x TCM_list(dilations) of SqueezedTCM (:617-685)
     TcmBlock blk[2 * NDIL];
@@ -274,8 +251,7 @@ class TaylorSENet final : public Model {
             run_conv(zgain, act4(b.dlast, 16, NBIN, T), nullptr, b.gain, 1, NBIN, B, T, T, st, pf);
         }
         const long plane = (long)NBIN * T, tot = plane * B;
-        hipLaunchKernelGGL(taylor_zero_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, b.gain, b.spec, b.zero, b.est,
-                           plane, tot);
+        launch_taylor_zero(b.gain, b.spec, b.zero, b.est, plane, tot, st);
         // ---- separate encoder (:78-82) and the high-order recurrence (:84-93); `zero` doubles as pre_term
         fk.join(0);
         if (!sen_first) sen.run(act4(b.spec, 2, NBIN, T), b.sens, b.us, B, T, st, pf);
@@ -285,8 +261,7 @@ class TaylorSENet final : public Model {
             const float* y = htcm[k].run(b.hx, b.X, b.ts, B, T, st, pf);
             run_pointwise(h_out[k], y, 256L * T, T, b.hob, 2L * NBIN * T, T, B, T, st, pf);
             fact *= (float)(k + 1);
-            hipLaunchKernelGGL(taylor_update_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, b.hob, b.zero, b.est, n2,
-                               (float)k, 1.f / fact);
+            launch_taylor_update(b.hob, b.zero, b.est, n2, (float)k, 1.f / fact, st);
         }
         SE_HIP(hipGetLastError());
     }
