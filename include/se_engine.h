@@ -374,6 +374,30 @@ int64_t se_resample_samples(int32_t n_in, int32_t sr_in, int32_t sr_out);
 int se_resample(const float* in_dev, int64_t in_pitch, int32_t batch, int32_t n_in, int32_t sr_in, int32_t sr_out,
                 float* out_dev, int64_t out_pitch, void* stream);
 
+/* The same conversion for rows of DIFFERENT lengths in one call - the clips of a directory in front of se_enhance_ragged.  Stateless
+ * like se_resample (no handle, errors through se_last_error(NULL), work enqueued on `stream`).
+ *   in_dev  [batch][in_pitch] (elements): row b holds n_in[b] valid samples - float (SE_SAMPLES_F32), or int16 as a PCM_16 file
+ *           stores them (SE_SAMPLES_S16: value / 32768, exact in fp32, as se_pcm16_decode).  n_in is a HOST array of `batch`
+ *           entries, read before the call returns.  Nothing past a row's own length is read.
+ *   out_dev [batch][out_pitch]: row b receives se_resample_samples(n_in[b], sr_in, sr_out) samples, then zeros up to
+ *           se_resample_samples(max n_in, sr_in, sr_out) - the row convention of se_enhance_ragged, which takes the buffer as it
+ *           is.  Nothing past that is written.
+ *   CONTRACT: row b's samples equal, as numbers, what se_resample returns for that clip alone (for SE_SAMPLES_S16: se_pcm16_decode
+ *   followed by se_resample) - the same float64 sum term by term at the same read positions, the fix_length zero tail included.
+ *   sr_in == sr_out copies (and converts) the rows through.
+ * The row lengths travel as kernel arguments, 64 rows a launch: a batch is ceil(batch / 64) launches and no copy.  The filter
+ * table is kept per ratio and device from the first call at that ratio on.  For sr_in % sr_out == 0 a later call allocates nothing
+ * and waits for nothing.  For other ratios the table of read positions (a function of the output index and the ratio alone) is
+ * kept per ratio too, shared by all rows and long enough for the longest row seen: a call waits for the device only when that
+ * table has to grow.  Calls may come from several threads and hipStreams.
+ * Refused, each with its own reason and before anything is enqueued: a null pointer; batch < 1; an n_in[b] < 1 (named by index); a
+ * format other than the two; rates <= 0 (or sr_out / sr_in below the filter table's resolution, 1 / 512); in_pitch below the
+ * longest row or out_pitch below its output when batch > 1; a row whose output count passes 2^31 - 1. */
+#define SE_SAMPLES_F32 0
+#define SE_SAMPLES_S16 1
+int se_resample_ragged(const void* in_dev, int32_t in_format, int64_t in_pitch, int32_t batch, const int32_t* n_in /* HOST */,
+                       int32_t sr_in, int32_t sr_out, float* out_dev, int64_t out_pitch, void* stream);
+
 /* The same conversion for a signal that arrives piecewise - in front of se_stream_*, whose 16 kHz input a live source delivers at
  * 48 / 44.1 / 32 kHz.  A stand-alone object next to the engine (no engine handle, errors through se_last_error(NULL)); one
  * object serves `batch` <= max_batch parallel rows that advance together, on the device that is current at create.  All device

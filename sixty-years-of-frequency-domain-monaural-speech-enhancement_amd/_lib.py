@@ -26,6 +26,7 @@ SYMBOLS = [
     'se_resampler_state_create', 'se_resampler_state_destroy', 'se_resampler_state_bytes', 'se_resampler_state_counts',
     'se_resampler_save', 'se_resampler_restore', 'se_resampler_state_export', 'se_resampler_state_import',
     'se_stream_state_select', 'se_stream_state_concat', 'se_resampler_state_select', 'se_resampler_state_concat',
+    'se_resample_ragged',
 ]
 
 
@@ -93,6 +94,7 @@ def load():
     lib.se_pcm16_decode.argtypes = [vp, i64, i32, i32, vp, i64, vp]
     lib.se_pcm16_encode.argtypes = [vp, i64, i32, i32, vp, i64, vp]
     lib.se_resample.argtypes = [vp, i64, i32, i32, i32, i32, vp, i64, vp]
+    lib.se_resample_ragged.argtypes = [vp, i32, i64, i32, C.POINTER(i32), i32, i32, vp, i64, vp]
     lib.se_resampler_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     lib.se_resampler_destroy.argtypes = [vp]
     lib.se_resampler_begin.argtypes = [vp, i32, vp]

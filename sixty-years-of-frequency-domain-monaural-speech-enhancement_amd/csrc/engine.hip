@@ -140,6 +140,13 @@ int se_resample(const float* in_dev, int64_t in_pitch, int32_t batch, int32_t n_
     });
 }
 
+int se_resample_ragged(const void* in_dev, int32_t in_format, int64_t in_pitch, int32_t batch, const int32_t* n_in, int32_t sr_in,
+                       int32_t sr_out, float* out_dev, int64_t out_pitch, void* stream) {
+    return guard(nullptr, [&] {         // every refusal is the launcher's (resample_ragged.h), made before anything is enqueued
+        se::launch_resample_ragged(in_dev, in_format, in_pitch, batch, n_in, sr_in, sr_out, out_dev, out_pitch, static_cast<hipStream_t>(stream));
+    });
+}
+
 // the stateful resampler: an object of its own next to the engine (k_resample.hip), errors through se_last_error(NULL)
 static se::StreamResampler* rs_of(se_resampler* r) { return reinterpret_cast<se::StreamResampler*>(r); }
 

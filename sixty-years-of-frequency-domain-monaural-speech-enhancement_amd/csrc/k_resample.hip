@@ -6,9 +6,20 @@
 // interpolation between table entries, float64 accumulation - restated in oracle/resample.py; parity is pinned to
 // that restatement only.  One thread per output sample; the table (256 KB of doubles) lives in L2.
 //
-// Two kernels share the tap arithmetic (resample_taps): resample_kernel, stateless, for a whole clip, and
-// resample_stream_kernel for the stateful StreamResampler below, which is fed piecewise and returns, push by push, the very
-// numbers resample_kernel gives for the whole signal - the same float64 sum term by term, at the same read positions.
+// Three kernels share the tap arithmetic (resample_taps): resample_kernel, stateless, for whole clips of one length;
+// resample_ragged_kernel, stateless, for whole clips of different lengths in one call (se_resample_ragged: the staged batch of the
+// file driver); and resample_stream_kernel for the stateful StreamResampler below, which is fed piecewise.  The last two are held to
+// equality with the first: a row of a ragged call, and the pushes of a stream concatenated, are the very numbers resample_kernel
+// gives for that signal alone - the same float64 sum term by term, at the same read positions.
+//   ragged   : one grid over (row, block of 256 outputs); the rows' n_in / n_calc are kernel arguments, 64 rows a launch
+//              (resample_ragged.h: sizes, refusals, the split - host code alone), so the lengths reach the device without a copy or
+//              a wait.  Input is float or raw PCM_16: the tap read forms x / 32768 as pcm16_decode_kernel does, so no float copy of
+//              the batch is made.  Threads behind a row's computed samples write zeros up to the longest row's output (fix_length
+//              tail and se_enhance_ragged's row padding alike).  Filter table and, for ratios that are no integer decimation, the
+//              table of read positions are kept per (ratio, device) for the life of the process; the positions depend on the output
+//              index and the ratio alone, so one table serves all rows and all calls, and a call waits for the device only when a
+//              longer row makes the table grow (hipDeviceSynchronize: other hipStreams may read the old one).  The tap loop is the
+//              plain per-thread one: staging the integer-decimation coefficient set in LDS was left out.
 //   window   : per row the last 2 * reach input samples ("history": reach = the taps one wing can span, resample_pos.h - an
 //              output not yet released sits at most reach samples before the end and looks less than reach further back)
 //              in one of two buffers; a push reads [history | the caller's new samples] in place and writes the next
@@ -32,6 +43,7 @@
 #include "common.h"
 #include "hip_owned.h"
 #include "resample_pos.h"
+#include "resample_ragged.h"
 #include "resampler.h"
 #include "resampler_manifest.h"
 #include <climits>
@@ -307,9 +319,153 @@ void launch_resample(const float* x, long in_pitch, int batch, int n_in, int sr_
     SE_HIP(hipGetLastError());
 }
 
+// ---- se_resample_ragged: rows of different lengths in one call (sizes, refusals and the split over launches: resample_ragged.h)
+namespace {
+
+// a row of raw PCM_16 samples read as pcm16_decode_kernel would have written it: x / 32768, exact in fp32
+struct ClipAtS16 {
+    const short* __restrict__ x;
+    __device__ float operator()(int p) const { return (float)x[p] * (1.f / 32768.f); }
+};
+
+struct RaggedArgs {
+    const void* x; long in_pitch;                 // row 0 of THIS launch
+    float* y; long out_pitch;
+    const double* win;
+    const double* treg;      // [>= the longest row's n_calc] read positions shared by all rows, or nullptr -> t * inc exactly
+    double inc, scale;
+    int index_step;
+    int n_out_max;           // every row is written up to here: its outputs, then zeros
+    int pass;                // sr_in == sr_out: y[t] = x[t]
+    int n_in[RS_RAGGED_ROWS], n_calc[RS_RAGGED_ROWS];
+};
+
+// grid (blocks of outputs, rows of the launch): each row under its own n_in and n_calc; the blocks (and threads) behind a row's
+// computed samples write its zeros - the fix_length tail and the padding up to the longest row's output alike
+template <typename X, typename S>
+__global__ __launch_bounds__(RS_RAGGED_BLOCK) void resample_ragged_kernel(const RaggedArgs a) {
+    const long tl = (long)blockIdx.x * RS_RAGGED_BLOCK + threadIdx.x;
+    if (tl >= a.n_out_max) return;
+    const int t = (int)tl;
+    const int row = blockIdx.y;
+    float* yp = a.y + (long)row * a.out_pitch;
+    if (t >= a.n_calc[row]) {
+        yp[t] = 0.f;
+        return;
+    }
+    const X x{static_cast<const S*>(a.x) + (long)row * a.in_pitch};
+    if (a.pass) {
+        yp[t] = x(t);
+        return;
+    }
+    const double tr = a.treg ? a.treg[t] : (double)t * a.inc;
+    const int n = (int)tr;
+    yp[t] = (float)resample_taps(x, a.win, n, tr - n, a.n_in[row], a.scale, a.index_step);
+}
+
+// What the ragged call keeps per ratio and device for the life of the process: the (scaled) filter table and, when the ratio is
+// no integer decimation, the position table - on the host as far as it has been summed, on the device as far as the longest row
+// seen needed it.  se_resample's own tables (Tables above) are left alone.
+struct RaggedRatio {
+    int sr_in = 0, sr_out = 0;
+    double* win = nullptr;
+    std::vector<double> tr;
+    double acc = 0.0;
+    double* dev_tr = nullptr;
+    size_t dev_cap = 0;
+};
+struct RaggedTables {
+    std::mutex mu;
+    std::vector<double> host;
+    std::vector<std::unique_ptr<RaggedRatio>> ratios;
+};
+RaggedTables& ragged_tables() {
+    static RaggedTables t[64];
+    int dev = 0;
+    SE_HIP(hipGetDevice(&dev));
+    SE_CHECK(dev >= 0 && dev < 64, "device ordinal");
+    return t[dev];
+}
+
+}  // namespace
+
+void launch_resample_ragged(const void* x, int in_format, long in_pitch, int batch, const int32_t* n_in, int sr_in, int sr_out, float* y,
+                            long out_pitch, hipStream_t s) {
+    const std::string fn = "se_resample_ragged: ";
+    RaggedPlan p{};
+    const std::string why = ragged_plan(RaggedCall{x != nullptr, y != nullptr, in_format, in_pitch, batch, n_in, sr_in, sr_out, out_pitch}, p);
+    SE_CHECK(why.empty(), fn + why);
+    RaggedArgs a{};
+    a.y = y; a.in_pitch = in_pitch; a.out_pitch = out_pitch;
+    a.n_out_max = p.n_out_max; a.pass = p.pass;
+    a.inc = p.plan.inc; a.scale = p.plan.scale; a.index_step = p.plan.index_step;
+    RaggedTables& T = ragged_tables();
+    std::lock_guard<std::mutex> lock(T.mu);
+    if (!p.pass) {
+        RaggedRatio* R = nullptr;
+        for (auto& r : T.ratios)
+            if (r->sr_in == sr_in && r->sr_out == sr_out) R = r.get();
+        if (!R) {                                                   // the first call at this ratio on this device
+            if (T.host.empty()) T.host = build_window();
+            std::vector<double> w(T.host);
+            if (p.plan.ratio < 1.0)
+                for (auto& v : w) v *= p.plan.ratio;                // interp_win *= sample_ratio
+            std::unique_ptr<RaggedRatio> fresh(new RaggedRatio());
+            fresh->sr_in = sr_in; fresh->sr_out = sr_out;
+            SE_HIP(hipMalloc(&fresh->win, RS_NWIN * sizeof(double)));
+            const hipError_t e = hipMemcpy(fresh->win, w.data(), RS_NWIN * sizeof(double), hipMemcpyHostToDevice);
+            if (e != hipSuccess) (void)hipFree(fresh->win);
+            SE_HIP(e);
+            R = fresh.get();
+            T.ratios.push_back(std::move(fresh));
+        }
+        a.win = R->win;
+        if (!p.plan.exact && p.n_calc_max > 0) {
+            // resampy advances the read position by repeated float64 addition: the sum is carried on from where it stopped
+            const size_t want = std::max<size_t>((size_t)p.n_calc_max, R->dev_cap);
+            ragged_positions_extend(p.plan, R->tr, R->acc, (int64_t)want);
+            for (int b = 0; b < batch; ++b) {                       // the last position a row reads at lies inside the row
+                const RaggedRow r = ragged_row(p, n_in[b]);
+                SE_CHECK(r.n_calc == 0 || (int64_t)R->tr[(size_t)r.n_calc - 1] < r.n_in, fn + "a read position past the end of row " + std::to_string(b));
+            }
+            if ((size_t)p.n_calc_max > R->dev_cap) {
+                // the table grows: the one place the call waits - launches on other hipStreams may still read the old table
+                const size_t cap = std::max<size_t>((size_t)p.n_calc_max, 2 * R->dev_cap);
+                ragged_positions_extend(p.plan, R->tr, R->acc, (int64_t)cap);
+                SE_HIP(hipDeviceSynchronize());
+                if (R->dev_tr) (void)hipFree(R->dev_tr);
+                R->dev_tr = nullptr;
+                R->dev_cap = 0;
+                SE_HIP(hipMalloc(&R->dev_tr, cap * sizeof(double)));
+                SE_HIP(hipMemcpy(R->dev_tr, R->tr.data(), cap * sizeof(double), hipMemcpyHostToDevice));
+                R->dev_cap = cap;
+            }
+            a.treg = R->dev_tr;
+        }
+    }
+    // ---- every refusal is above
+    const size_t esz = in_format == RS_SAMPLES_S16 ? sizeof(short) : sizeof(float);
+    const dim3 block(RS_RAGGED_BLOCK);
+    for (int k = 0; k < p.launches; ++k) {
+        int32_t row0 = 0, rows = 0;
+        ragged_launch_rows(batch, k, row0, rows);
+        a.x = static_cast<const char*>(x) + (size_t)row0 * (size_t)in_pitch * esz;
+        a.y = y + (size_t)row0 * (size_t)out_pitch;
+        for (int r = 0; r < rows; ++r) {
+            const RaggedRow rr = ragged_row(p, n_in[row0 + r]);
+            a.n_in[r] = rr.n_in;
+            a.n_calc[r] = rr.n_calc;
+        }
+        const dim3 grid((unsigned)(((long)p.n_out_max + RS_RAGGED_BLOCK - 1) / RS_RAGGED_BLOCK), (unsigned)rows);
+        if (in_format == RS_SAMPLES_S16) hipLaunchKernelGGL((resample_ragged_kernel<ClipAtS16, short>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((resample_ragged_kernel<ClipAt, float>), grid, block, 0, s, a);
+        SE_HIP(hipGetLastError());
+    }
+}
+
 // ---- the stateful resampler (se_resampler_* of include/se_engine.h; layout and rules in the header comment of this file)
 namespace {
-struct DeviceScope {          // the object's device is current while a call runs; the caller's is restored on the way out
+struct DeviceScope {        // the object's device is current while a call runs; the caller's is restored on the way out
     int prev = -1;
     explicit DeviceScope(int dev) {
         SE_HIP(hipGetDevice(&prev));

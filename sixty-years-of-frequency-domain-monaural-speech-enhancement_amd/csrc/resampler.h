@@ -6,6 +6,12 @@
 
 namespace se {
 
+// The offline resampler (launch_resample of kernels.h) for rows of different lengths in one call (se_resample_ragged): row b holds
+// n_in[b] (HOST array) float or PCM_16 samples (in_format: SE_SAMPLES_*) and gets what launch_resample gives it alone, then zeros up
+// to the longest row's output; makes every check of the call itself (resample_ragged.h) before anything is enqueued
+void launch_resample_ragged(const void* x, int in_format, long in_pitch, int batch, const int32_t* n_in, int sr_in, int sr_out, float* y,
+                            long out_pitch, hipStream_t s);
+
 class StreamResampler;
 StreamResampler* stream_resampler_create(int sr_in, int sr_out, int max_batch, int max_push);
 void stream_resampler_destroy(StreamResampler* r);

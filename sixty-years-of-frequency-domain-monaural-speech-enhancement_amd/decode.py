@@ -212,9 +212,11 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
                rank reads, decodes and writes ONLY its own clips (one process per GPU, no collective on the data path);
                clips of different lengths share calls (se_enhance_ragged: each clip gets exactly its batch-1 result)
                within a padding cap;
-      reader   threads copy the raw PCM_16 samples of the next call into pinned memory, a side stream uploads them, turns
-               them into floats (se_pcm16_decode) and resamples to 16 kHz where the corpus is not (se_resample,
-               librosa.resample(..., 16000) of e.g. DCCRN/dccrn_decode_vb.py:26) - while the current call decodes;
+      reader   threads copy the raw PCM_16 samples of the next call into pinned memory, a side stream uploads them and, where
+               the corpus is not at 16 kHz, resamples all rows of the call at once straight from the 2-byte samples
+               (se_resample_ragged, librosa.resample(..., 16000) of e.g. DCCRN/dccrn_decode_vb.py:26); a 16 kHz call is
+               turned into floats (se_pcm16_decode), a call that mixes rates goes row by row (se_resample) - while the
+               current call decodes;
       decode   the caller's stream: se_enhance_ragged / se_enhance_batch, then PCM_16 quantisation on the device
                (se_pcm16_encode) and one asynchronous D2H of 2-byte samples;
       writer   a thread writes each clip's `<out>/<same file name>` as soon as its call's samples have landed.
@@ -232,8 +234,9 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
     length (plan_long_groups: at most min(N, max_batch) rows, padding within max_pad) and each group shares one window walk
     (Engine.enhance_long_ragged - every row gets what it gets alone, up to fp32 rounding); the engine is then made for the
     largest call of either kind; a model outside LONG_RAGGED_MODELS (the `_vb` DCCRN) raises before any file is written.
-    Like the one-at-a-time path, a group bypasses the reader / writer pipeline: its clips are read, uploaded and resampled one after
-    another on the calling thread, and the group's rows plus each clip's temporaries are resident together while it is assembled -
+    Like the one-at-a-time path, a group bypasses the reader / writer pipeline: its clips are read one after another on the calling thread and
+    uploaded, a group of one rate is resampled by one call (se_resample_ragged; a group that mixes rates clip by clip), and the
+    group's rows plus the native-rate samples are resident together while it is assembled -
     sized for the occasional long recordings of a corpus, not for a corpus made of them.
     stats['long_calls'] counts the windowed calls (= long_clips when long_batch is 1)."""
     import queue
@@ -352,22 +355,30 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
                     with torch.cuda.stream(side):
                         st = C.c_void_p(side.cuda_stream)
                         sl.d_in[:nb * nmax].copy_(sl.h_in[:nb * nmax], non_blocking=True)
-                        if raw16:
-                            _check(lib.se_pcm16_decode(p(sl.d_in), nmax, nb, nmax, p(sl.d_nat), nmax, st))
-                        if all(rates[i] == 16000 for i in b):
-                            wav = sl.d_nat                     # already at 16 kHz: rows of pitch nmax = lmax
-                        else:
+                        one_rate = rates[b[0]] if all(rates[i] == rates[b[0]] for i in b) else None
+                        if one_rate not in (None, 16000):
+                            # librosa.resample(feat_wav, orig_fs, 16000, fix=True, scale=False), dccrn_decode_vb.py:26, of every row
+                            # in ONE call, straight from the uploaded samples (raw PCM_16 is read as it is: no float copy is made)
                             wav = sl.wav
-                            esz = 4
-                            for r, i in enumerate(b):
-                                src = C.c_void_p(sl.d_nat.data_ptr() + esz * r * nmax)
-                                dst = C.c_void_p(sl.wav.data_ptr() + esz * r * lmax)
-                                if rates[i] == 16000:     # librosa.resample returns its input when the rates agree
-                                    sl.wav[r * lmax:r * lmax + native[i]].copy_(sl.d_nat[r * nmax:r * nmax + native[i]],
-                                                                                non_blocking=True)
-                                else:
-                                    # librosa.resample(feat_wav, orig_fs, 16000, fix=True, scale=False), dccrn_decode_vb.py:26
-                                    _check(lib.se_resample(src, native[i], 1, native[i], rates[i], 16000, dst, lengths[i], st))
+                            n_nat = (C.c_int32 * nb)(*[native[i] for i in b])
+                            _check(lib.se_resample_ragged(p(sl.d_in), resample.SAMPLES_S16 if raw16 else resample.SAMPLES_F32, nmax,
+                                                          nb, n_nat, one_rate, 16000, p(sl.wav), lmax, st))
+                        else:
+                            if raw16:
+                                _check(lib.se_pcm16_decode(p(sl.d_in), nmax, nb, nmax, p(sl.d_nat), nmax, st))
+                            if one_rate == 16000:
+                                wav = sl.d_nat                 # already at 16 kHz: rows of pitch nmax = lmax
+                            else:                              # a call that mixes rates: row by row
+                                wav = sl.wav
+                                esz = 4
+                                for r, i in enumerate(b):
+                                    src = C.c_void_p(sl.d_nat.data_ptr() + esz * r * nmax)
+                                    dst = C.c_void_p(sl.wav.data_ptr() + esz * r * lmax)
+                                    if rates[i] == 16000:     # librosa.resample returns its input when the rates agree
+                                        sl.wav[r * lmax:r * lmax + native[i]].copy_(sl.d_nat[r * nmax:r * nmax + native[i]],
+                                                                                    non_blocking=True)
+                                    else:
+                                        _check(lib.se_resample(src, native[i], 1, native[i], rates[i], 16000, dst, lengths[i], st))
                         sl.ready.record(side)
                     busy['stage'] += time.perf_counter() - t1
                     staged.put((b, sl, wav))
@@ -462,16 +473,27 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
                                    C.c_void_p(wav.data_ptr()), lengths[i], C.c_void_p(main.cuda_stream)))
         return wav
 
+    def resident_group(grp, rate):
+        """the clips of a group that share a rate other than 16 kHz: uploaded side by side, resampled by one call into the rows"""
+        nmax = max(native[i] for i in grp)
+        host = torch.zeros((len(grp), nmax), dtype=torch.float32)
+        for r, i in enumerate(grp):
+            host[r, :native[i]] = torch.from_numpy(np.ascontiguousarray(wavio.read_wav(os.path.join(mix, files[i]))[0], dtype=np.float32))
+        return resample.resample_ragged(host.to(dev), [native[i] for i in grp], rate, 16000)
+
     for grp in long_groups:
         st = C.c_void_p(main.cuda_stream)
-        if len(grp) == 1:
-            out = eng.enhance_long(resident(grp[0]).view(1, -1))
-        else:
-            lens = [lengths[i] for i in grp]
+        lens = [lengths[i] for i in grp]
+        one_rate = rates[grp[0]] if all(rates[i] == rates[grp[0]] for i in grp) else None
+        if one_rate not in (None, 16000):
+            rows = resident_group(grp, one_rate)
+        elif len(grp) == 1:
+            rows = resident(grp[0]).view(1, -1)
+        else:                                          # 16 kHz clips, or a group that mixes rates: clip by clip
             rows = torch.empty((len(grp), max(lens)), dtype=torch.float32, device=dev)      # (nothing past a row's length is read)
             for r, i in enumerate(grp):
                 rows[r, :lengths[i]].copy_(resident(i))
-            out = eng.enhance_long_ragged(rows, lens)
+        out = eng.enhance_long(rows) if len(grp) == 1 else eng.enhance_long_ragged(rows, lens)
         nb, n = out.shape
         q = torch.empty((nb, n), dtype=torch.int16, device=dev)
         _check(lib.se_pcm16_encode(C.c_void_p(out.data_ptr()), n, nb, n, C.c_void_p(q.data_ptr()), n, st))

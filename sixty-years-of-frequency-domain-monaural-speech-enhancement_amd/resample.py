@@ -3,7 +3,8 @@
 The reference decode scripts resample every clip to 16 kHz right after reading it (DCCRN/dccrn_decode_vb.py:26,
 LSTM/lstm_decode_vb.py:34).  No CPU fallback: the call fails without the HIP library / a GPU.
 
-`resample()` needs the whole clip; `StreamResampler` takes the same signal piecewise (a microphone, a 48 kHz file reader in
+`resample()` needs the whole clip, and clips of one length; `resample_ragged()` takes whole clips of different lengths in one
+call, float32 or raw PCM_16, and gives each the samples `resample()` gives it alone (the file driver's staged batch); `StreamResampler` takes the same signal piecewise (a microphone, a 48 kHz file reader in
 front of the frame-online engine) and returns, push by push, the very samples `resample()` gives for the whole of it.
 """
 import math
@@ -35,6 +36,54 @@ def resample(wav, sr_in, sr_out=16000):
     if rc:
         raise RuntimeError(lib.se_last_error(None).decode())
     return y[0] if squeeze else y
+
+
+SAMPLES_F32, SAMPLES_S16 = 0, 1            # SE_SAMPLES_* of include/se_engine.h
+
+
+def resample_ragged(x, lengths, sr_in, sr_out=16000, out=None):
+    """Rows of different lengths in one call (se_resample_ragged).  x: cuda tensor [B, pitch], float32 or int16 (PCM_16 samples as
+    the file stores them: value / 32768); row b holds lengths[b] valid samples, nothing behind them is read.
+    -> float32 [B, resample_samples(max(lengths))]: row b is `resample()` of that clip alone, sample for sample, then zeros - the rows
+    `Engine.enhance_ragged` takes.  `out`: a float32 cuda tensor of at least that many columns to write into (the view of its first
+    columns is returned; nothing behind them is written)."""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2):
+        raise EngineError("resample_ragged: x has to be a tensor [B, pitch]")
+    if x.dtype not in (torch.float32, torch.int16):
+        raise EngineError(f"resample_ragged: x is {x.dtype}, the rows are float32 or int16")
+    if x.stride(1) != 1:
+        raise EngineError("resample_ragged: the samples of a row have to be contiguous")
+    B, pitch = x.shape
+    lengths = [int(n) for n in lengths]
+    if len(lengths) != B:
+        raise EngineError(f"resample_ragged: {len(lengths)} lengths for {B} rows")
+    if B < 1:
+        raise EngineError("resample_ragged: at least one row has to be given")
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= pitch:
+            raise EngineError(f"resample_ragged: lengths[{b}] = {n} outside 1..{pitch}, the samples a row of x holds")
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in <= 0 or sr_out <= 0:
+        raise EngineError(f"resample_ragged: sample rates {sr_in} -> {sr_out} Hz: both have to be positive")
+    if not x.is_cuda:
+        raise EngineError("resample_ragged: x has to live on the GPU")
+    n_out = resample_samples(max(lengths), sr_in, sr_out)
+    if out is None:
+        out = torch.empty((B, n_out), dtype=torch.float32, device=x.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.dim() == 2
+              and out.stride(1) == 1 and out.shape[0] == B and out.shape[1] >= n_out):
+        raise EngineError(f"resample_ragged: out has to be a float32 tensor [{B}, >= {n_out}] on {x.device}")
+    lib = _lib.load()
+    arr = (C.c_int32 * B)(*lengths)
+    with torch.cuda.device(x.device):
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        rc = lib.se_resample_ragged(C.c_void_p(x.data_ptr()), SAMPLES_S16 if x.dtype == torch.int16 else SAMPLES_F32,
+                                    x.stride(0) if B > 1 else pitch, B, arr, sr_in, sr_out, C.c_void_p(out.data_ptr()),
+                                    out.stride(0) if B > 1 else out.shape[1], st)
+    if rc:
+        raise EngineError(lib.se_last_error(None).decode())
+    return out[:, :n_out]
 
 
 def ready_samples(n_in, sr_in, sr_out):
