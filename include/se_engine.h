@@ -277,6 +277,37 @@ int se_stream_state_select(se_engine* e, se_stream_state* dst, const se_stream_s
                            void* stream);
 int se_stream_state_concat(se_engine* e, se_stream_state* dst, const se_stream_state* const* parts, int32_t n_parts, void* stream);
 
+/* Groups that began at different times (additions: the ABI number stays, and se_stream_state_concat keeps refusing differing counters
+ * exactly as above).  Once a stream is past its left edge - no frame still to be transformed reads a reflected sample, no sample still
+ * to be written lies under the deficient start of the overlap-add envelope - a decode step no longer depends on the stream's absolute
+ * position, provided the position moves by whole hops.  A parked stream may then have its counters REBASED by a multiple of the hop,
+ * and two parked groups whose counters differ by such a multiple be joined into one that advances in lockstep from then on, every
+ * row getting what it would have got alone.
+ *   join  : dst = the rows of parts[0], then parts[1], ... as concat, on the counters of parts[0]; every other part is rebased onto
+ *           them.  `e`, `stream`, the upload of imported images, the reuse of `dst`, the single kernel launch and the untouched
+ *           running stream are concat's; n_parts == 1 yields a copy.  A part is accepted when
+ *             - every manifest field other than the positions (n_total, t_done, o_done, keep) agrees with parts[0] - concat's checks and
+ *               wording ("parts[0] and parts[1] differ: max_chunk 16 vs 8");
+ *             - it is in phase: the shift parts[0].n_total - n_total is a multiple of lcm(hop, 4) (the window origin `keep` is a multiple
+ *               of 4 and stays one), and n_total - t_done * hop and n_total - o_done equal those of parts[0];
+ *             - as soon as any shift is not 0, every part - parts[0] included - is past the left edge: t_done >= max(1,
+ *               ceil(n_fft / 2 / hop), and where hop < n_fft / 2 ceil(n_fft / hop) - 1 + the model's frames of look-ahead), i.e. 1 for 320 / 160, 3 for
+ *               512 / 128, 9 for the DCCRN whose decoder looks six frames ahead (csrc/stream_join.h has the derivation);
+ *             - its state holds no absolute time: a running-scale stream is refused (its ring of 1 / c per frame is indexed by the
+ *               absolute frame), and so are the models whose state counts frames - CTSNet, TaylorSENet and G2Net with the cumulative
+ *               LayerNorm, FullSubNet with the cumulative norm.  CRN, LSTM, GCRN, DPCRN and DCCRN (complex or real LSTM core, either
+ *               decoder) are accepted.
+ *           Each failure is refused with its own reason, naming the field and both values.  Parts may have been saved with live input
+ *           windows of different lengths; the result keeps, for every row, the samples from the highest rebased `keep` of any part.
+ *           The capacity checks are left to the restore of the result: an engine without SE_CFG_STREAM_SLIDING restores it if
+ *           parts[0].n_total fits its max_samples.  A joined row continues bit for bit as it would have alone at the same batch size;
+ *           at another batch size up to the fp32 rounding of kernels selected by batch size, as after select and concat.
+ *   counts: the host record a server needs to tell when a caller is in phase with a group - rows, samples received (n_total), frames
+ *           transformed (t_done), samples emitted (o_done), the hop; any out-pointer may be NULL.  An empty object is an error
+ *           (se_last_error(NULL)).  Works on an imported image without a GPU. */
+int se_stream_state_join(se_engine* e, se_stream_state* dst, const se_stream_state* const* parts, int32_t n_parts, void* stream);
+int se_stream_state_counts(const se_stream_state* s, int32_t* batch, int64_t* n_total, int64_t* t_done, int64_t* o_done, int32_t* hop);
+
 /* se_enhance_batch for clips LONGER than max_samples (any length; shorter ones take the same path): `batch` equal-length clips
  * resident on the device, decoded in windows of max_chunk_frames frames through the frame-online machinery above - conv history,
  * TCM rings, LSTM (h, c) and the running norm sums carried from window to window - under the WHOLE clip's unit-RMS scale, so

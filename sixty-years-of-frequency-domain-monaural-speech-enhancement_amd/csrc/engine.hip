@@ -5,6 +5,8 @@
 #include "resampler.h"
 #include "rnn.h"
 #include "stream_manifest.h"
+#include "k_stream_state.h"
+#include "stream_join.h"
 #include "stream_rows.h"
 #include "stream_window.h"
 #include "window_rows.h"
@@ -1514,6 +1516,11 @@ int se_stream_restore(se_engine* e, const se_stream_state* cs, void* stream) {
 // the declaration their buffers are allocated from), a call-order slot is [B][row bytes] by construction (StreamCtx::slot).  The
 // manifest arithmetic is host code (stream_rows.h); the rows move in one launch (k_stream_state.hip, stream_state_gather_kernel).
 // Neither call touches the stream running on the engine or its workspace.
+//
+// se_stream_state_join is concat for parts whose position counters differ by whole hops (stream_join.h: when a parked stream can be
+// rebased, and the plan - shifts, the one window every row keeps): the same gather with a per-part column offset into the window
+// (stream_state_join_kernel), the result on the counters of parts[0].  Nothing in a payload holds a position - the accepted models
+// carry conv history and LSTM (h, c), the engine the scale c - so rebasing a part is a matter of the manifest alone.
 namespace {
 
 std::vector<RowLayout> snapshot_layouts(se_engine* e, const SnapManifest& m, const std::string& fn) {
@@ -1551,11 +1558,34 @@ struct RowSource {
     int32_t row;
 };
 
-// dst <- the rows `src` names, in order; parts: the distinct source objects, every one checked against e and of one layout `lay`
+// "", or what in the state a stream of this engine's model carries counts frames from the start of the stream: such a state cannot be
+// moved to another position.  The models that are left ignore stream_chunk()'s t0 ((void)t0 in CRN, LSTM, GCRN, DPCRN, DCCRN)
+std::string join_counts_frames(const se_engine* e) {
+    switch (e->cfg.model) {
+        case SE_MODEL_CTSNET:
+        case SE_MODEL_G2NET:
+        case SE_MODEL_TAYLORSENET:
+            return "the cumulative LayerNorm divides its running sums by the number of frames so far, and the TCM rings are indexed by the "
+                   "absolute frame (StreamCtx::t0, k_tcm_stream.hip)";
+        case SE_MODEL_FULLSUBNET:
+            return "the cumulative Laplace norm divides its running sums by the absolute frame index (launch_fsn_cum_fb / launch_fsn_cum_sb), "
+                   "and the look-ahead skips the steps before frame 2 by it";
+        default:
+            return "";
+    }
+}
+
+// dst <- the rows `src` names, in order; parts: the distinct source objects, every one checked against e and of one layout `lay`.
+// jp (se_stream_state_join): the parts' windows differ in length - `lay` then describes the RESULT, whose window starts at jp->keep,
+// and row bd of it is columns [jp->col[p], jp->col[p] + jp->live) of its part's window row; the counters are those of parts[0]
 void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream_state*>& parts, const std::vector<int2>& rowmap,
-                 const std::vector<RowLayout>& lay, const std::string& fn, hipStream_t st) {
+                 const std::vector<RowLayout>& lay, const std::string& fn, hipStream_t st, const JoinPlan* jp = nullptr) {
     const int Bd = (int)rowmap.size(), np = (int)parts.size();
-    const SnapManifest m = snap_rows_manifest(parts[0]->man, lay, Bd);
+    SnapManifest m = snap_rows_manifest(parts[0]->man, lay, Bd);
+    if (jp) {
+        SE_CHECK(!m.segs.empty() && m.segs.back().kind == SNAP_WINDOW && (int)jp->col.size() == np, fn + "snapshot without an input window segment");
+        m.keep = jp->keep;
+    }
     const int nseg = (int)m.segs.size();
     SE_CHECK(nseg >= 1, fn + "snapshot without segments");
     long tiles = 0;
@@ -1584,8 +1614,10 @@ void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream
     for (se_stream_state* p : parts) obj_wait(p, st);
     obj_wait(dst, st);
     // one block: GatherSeg[nseg] | long src_off[np][nseg] | const float* base[np] | int2 rowmap[Bd] | int part_B[np]
+    // (join: | int window row length[np] | int window column[np])
     const size_t o_off = (size_t)nseg * sizeof(GatherSeg), o_base = o_off + (size_t)np * nseg * sizeof(long),
-                 o_map = o_base + (size_t)np * sizeof(float*), o_pb = o_map + (size_t)Bd * sizeof(int2), total = o_pb + (size_t)np * sizeof(int);
+                 o_map = o_base + (size_t)np * sizeof(float*), o_pb = o_map + (size_t)Bd * sizeof(int2), o_win = o_pb + (size_t)np * sizeof(int),
+                 total = o_win + (jp ? 2 * (size_t)np * sizeof(int) : 0);
     auto& sd = *dst->side;
     SE_HIP(hipEventSynchronize(sd.gat_ev.get()));
     if (total > sd.gat_cap) {
@@ -1607,6 +1639,11 @@ void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream
         for (int k = 0; k < nseg; ++k) soff[(size_t)p * nseg + k] = (long)(off[(size_t)k] / 4);
         base[p] = reinterpret_cast<const float*>(parts[(size_t)p]->side->dev.get());
         pb[p] = parts[(size_t)p]->man.batch;
+        if (jp) {
+            int* wi = reinterpret_cast<int*>(pin + o_win);
+            wi[p] = parts[(size_t)p]->man.n_total - parts[(size_t)p]->man.keep;
+            wi[np + p] = jp->col[(size_t)p];
+        }
     }
     std::memcpy(pin + o_map, rowmap.data(), (size_t)Bd * sizeof(int2));
     uint8_t* dev = sd.gat_dev.get();
@@ -1620,7 +1657,15 @@ void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream
     a.part_B = reinterpret_cast<const int*>(dev + o_pb);
     a.nseg = nseg;
     a.Bd = Bd;
-    launch_stream_state_gather(a, tiles, st);
+    if (jp) {
+        JoinWindow w;
+        w.seg = nseg - 1;
+        w.part_inner = reinterpret_cast<const int*>(dev + o_win);
+        w.part_col = w.part_inner + np;
+        launch_stream_state_join(a, w, tiles, st);
+    } else {
+        launch_stream_state_gather(a, tiles, st);
+    }
     dst->man = m;
     dst->filled = true;
     dst->dev_valid = true;
@@ -1687,6 +1732,60 @@ int se_stream_state_concat(se_engine* e, se_stream_state* dst, const se_stream_s
             for (int32_t r = 0; r < parts[(size_t)p]->man.batch; ++r) map.push_back(make_int2(p, r));
         }
         gather_rows(e, dst, parts, map, lay, fn, static_cast<hipStream_t>(stream));
+    });
+}
+
+int se_stream_state_join(se_engine* e, se_stream_state* dst, const se_stream_state* const* cparts, int32_t n_parts, void* stream) {
+    if (!e) return 1;
+    return guard(e, [&] {
+        const std::string fn = "se_stream_state_join: ";
+        SE_CHECK(dst && cparts, fn + "null argument");
+        SE_CHECK(e->finalized, "engine not finalized");
+        SE_CHECK(n_parts >= 1, fn + "n_parts " + std::to_string(n_parts) + ": at least one part has to be given");
+        std::vector<se_stream_state*> parts;
+        std::vector<const SnapManifest*> mans;
+        int64_t total = 0;
+        for (int32_t p = 0; p < n_parts; ++p) {
+            se_stream_state* s = const_cast<se_stream_state*>(cparts[p]);
+            SE_CHECK(s, fn + "parts[" + std::to_string(p) + "] is null");
+            SE_CHECK(s != dst, fn + "dst == parts[" + std::to_string(p) + "]: the rows are read while they are written");
+            SE_CHECK(s->filled, fn + "parts[" + std::to_string(p) + "]: the stream state object is empty");
+            total += s->man.batch;
+            SE_CHECK(total < (1 << 24), fn + "too many rows");
+            parts.push_back(s);
+            mans.push_back(&s->man);
+        }
+        check_snapshot_identity(e, parts[0]->man, fn);
+        JoinPlan plan;
+        const std::string why = snap_join_plan(mans, e->model->stream_lag(), join_counts_frames(e), plan);
+        SE_CHECK(why.empty(), fn + why);
+        // every part against the layouts of this engine's model, its window at its own length; the result's at the joined length
+        std::vector<RowLayout> lay = snapshot_layouts(e, parts[0]->man, fn);
+        SE_CHECK(!lay.empty() && parts[0]->man.segs.back().kind == SNAP_WINDOW, fn + "snapshot without an input window segment");
+        std::vector<int2> map;
+        for (int32_t p = 0; p < n_parts; ++p) {
+            const SnapManifest& pm = parts[(size_t)p]->man;
+            if (p > 0) {
+                lay.back().inner = (int64_t)pm.n_total - pm.keep;
+                const std::string bad = snap_layout_check(pm, lay);
+                SE_CHECK(bad.empty(), fn + "parts[" + std::to_string(p) + "]: " + bad);
+            }
+            for (int32_t r = 0; r < pm.batch; ++r) map.push_back(make_int2(p, r));
+        }
+        lay.back().inner = plan.live;
+        gather_rows(e, dst, parts, map, lay, fn, static_cast<hipStream_t>(stream), &plan);
+    });
+}
+
+int se_stream_state_counts(const se_stream_state* s, int32_t* batch, int64_t* n_total, int64_t* t_done, int64_t* o_done, int32_t* hop) {
+    return guard(nullptr, [&] {
+        SE_CHECK(s, "se_stream_state_counts: null argument");
+        SE_CHECK(s->filled, "se_stream_state_counts: the stream state object is empty");
+        if (batch) *batch = s->man.batch;
+        if (n_total) *n_total = s->man.n_total;
+        if (t_done) *t_done = s->man.t_done;
+        if (o_done) *o_done = s->man.o_done;
+        if (hop) *hop = s->man.hop;
     });
 }
 

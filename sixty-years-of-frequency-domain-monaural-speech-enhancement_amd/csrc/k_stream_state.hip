@@ -16,6 +16,7 @@
 // aligned relative to each other is copied as a scalar head up to the first aligned destination, float4 body, scalar tail; a run
 // whose ends are not (a window row whose pitch or origin is no multiple of 4 floats against the compact payload rows) moves as
 // scalars.  Nothing outside [0, len) of a run is read or written.
+#include "k_stream_state.h"
 #include "kernels.h"
 
 namespace se {
@@ -101,7 +102,13 @@ void launch_stream_state_copy(const StateSeg* tab_dev, int nfix, long fix_tiles,
 // the fastest axis) the lanes of a wave read rows of ONE o - a gather inside a few cache lines.  A layout whose runs are whole
 // float4s (inner a multiple of 4: every run then starts 16 B aligned in both payloads, whose segments start 16 B aligned) moves 16 B
 // per lane; the others move floats and also write the zeros between the segment's end and the next 16 B boundary.
-__global__ __launch_bounds__(256) void stream_state_gather_kernel(const GatherArgs a) {
+//
+// se_stream_state_join runs the same walk with one more table (k_stream_state.h JoinWindow): the parts of a join may hold input windows of
+// different lengths, and the result keeps the columns [col, col + inner) of each - so for the window segment alone a source row has
+// the part's own length and starts at the part's own column.  Those rows are no whole float4s in general (a live window is
+// n_total - keep samples long): the window moves as floats, a few hundred per row.  JOIN == false is the kernel select and concat launch.
+template <bool JOIN>
+__device__ __forceinline__ void state_gather_tile(const GatherArgs& a, const JoinWindow& w) {
     const int b = blockIdx.x;
     int lo = 0, hi = a.nseg - 1;
     while (lo < hi) {
@@ -114,12 +121,15 @@ __global__ __launch_bounds__(256) void stream_state_gather_kernel(const GatherAr
     const unsigned j0 = (unsigned)(b - sg.tile0) * STATE_TILE;
     if (inner == 0 || j0 >= ((n + 3u) & ~3u)) return;
     const long* __restrict__ off = a.src_off + lo;
+    const bool window = JOIN && lo == w.seg;
     auto source = [&](unsigned j) -> const float* {
         const unsigned o = j / run, rem = j - o * run, bd = rem / inner, i = rem - bd * inner;
         const int2 pr = a.rowmap[bd];
-        return a.part_base[pr.x] + off[(long)pr.x * a.nseg] + ((long)o * a.part_B[pr.x] + pr.y) * inner + i;
+        const float* base = a.part_base[pr.x] + off[(long)pr.x * a.nseg];
+        if (window) return base + ((long)o * a.part_B[pr.x] + pr.y) * w.part_inner[pr.x] + w.part_col[pr.x] + i;
+        return base + ((long)o * a.part_B[pr.x] + pr.y) * inner + i;
     };
-    if ((inner & 3u) == 0) {
+    if ((inner & 3u) == 0 && !window) {
         for (unsigned q = threadIdx.x; q < STATE_TILE / 4; q += 256) {
             const unsigned j = j0 + 4 * q;
             if (j >= n) break;
@@ -135,12 +145,23 @@ __global__ __launch_bounds__(256) void stream_state_gather_kernel(const GatherAr
     }
 }
 
+__global__ __launch_bounds__(256) void stream_state_gather_kernel(const GatherArgs a) { state_gather_tile<false>(a, JoinWindow{}); }
+__global__ __launch_bounds__(256) void stream_state_join_kernel(const GatherArgs a, const JoinWindow w) { state_gather_tile<true>(a, w); }
+
 long state_gather_tiles(long n) { return (n + STATE_TILE - 1) / STATE_TILE; }
 
 void launch_stream_state_gather(const GatherArgs& a, long tiles, hipStream_t s) {
     SE_CHECK(a.nseg >= 1 && a.Bd >= 1 && tiles >= 0 && tiles < (1L << 31), "launch_stream_state_gather: bad table");
     if (tiles == 0) return;
     hipLaunchKernelGGL(stream_state_gather_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a);
+    SE_HIP(hipGetLastError());
+}
+
+void launch_stream_state_join(const GatherArgs& a, const JoinWindow& w, long tiles, hipStream_t s) {
+    SE_CHECK(a.nseg >= 1 && a.Bd >= 1 && tiles >= 0 && tiles < (1L << 31), "launch_stream_state_join: bad table");
+    SE_CHECK(w.seg >= 0 && w.seg < a.nseg && w.part_inner && w.part_col, "launch_stream_state_join: no window segment");
+    if (tiles == 0) return;
+    hipLaunchKernelGGL(stream_state_join_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a, w);
     SE_HIP(hipGetLastError());
 }
 

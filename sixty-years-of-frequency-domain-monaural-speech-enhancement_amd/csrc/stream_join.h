@@ -1,0 +1,104 @@
+// Joining parked stream groups that began at different times (se_stream_state_join, include/se_engine.h): when a parked stream is
+// past its left edge, and the plan of a join - the shift of every part onto the counters of parts[0] and the one input window all
+// rows keep.  Host code alone, no HIP - the engine includes it, and so does a stand-alone check program (tests/stream_join_check.cpp).
+//
+// A decode step of a stream that is past its left edge does not depend on the stream's absolute position, as long as the position
+// moves by whole hops: every index the front end forms is a frame index times the hop plus a constant, the grids of the STFT and
+// the iSTFT start at the launch's own first frame / first output sample, and the networks that are accepted here take no frame
+// index at all.  What does depend on position 0, in everything se_stream_push / se_stream_flush launch (the engine's stream_process):
+//   (a) the STFT of a frame t reads samples t hop - n_fft/2 ...; where that is negative it mirrors (`idx < 0` in the forward kernel), and its
+//       wave-uniform fast path asks `t hop >= n_fft/2` of the first frame of a pair.  Frames below t_done are never transformed
+//       again, so neither test can hold once   t_done hop >= n_fft/2.
+//   (b) stream_keep_from() clamps t_done hop - n_fft/2 and n_total - n_fft/2 - 1 to 0.  The first is (a); the second is at least
+//       (t_done - 1) hop, because frame t_done - 1 was released only when sample (t_done - 1) hop + n_fft/2 had arrived.
+//   (c) the iSTFT overlap-adds into output sample o = pos - n_fft/2 every frame t with t hop <= pos < t hop + n_fft and divides by
+//       the window energy of exactly those frames.  The engine bounds the frames from below by max(0, t0 - HC); near the start
+//       that bound, not `pos - t hop < n_fft`, ends the loop, and the envelope is short of frames that would lie before frame 0.
+//       The lowest frame that covers pos is floor((pos - n_fft) / hop) + 1, which is >= 0 from pos >= n_fft - hop on; every
+//       sample still to be written has o >= o_done = max(0, (t_done - lag) hop - n_fft/2), so the bound is idle from the start where
+//       hop >= n_fft/2 (every pos is at least n_fft/2), and else once   (t_done - lag + 1) hop >= n_fft.   (lag: Model::stream_lag(),
+//       the frames a look-ahead model finalises late.)  The frames between t0 - HC and 0 that a rebased stream then LOADS where the
+//       original loaded zeros are transformed and never added.
+//   (d) the model's first-chunk handling (StreamState::first: an LSTM's first step starts from a zero state) ends with the first
+//       chunk:   t_done >= 1.
+// stream_left_edge_frames() is the smallest t_done that satisfies all four; tests/stream_join_check.cpp walks a stream sample by
+// sample through the index expressions above and finds the same number.  (The window `win` may be shorter than n_fft; frames are
+// n_fft long for every index above, so the bound is taken for n_fft.)
+#pragma once
+#include "stream_rows.h"
+#include <algorithm>
+
+namespace se {
+
+inline int stream_left_edge_frames(int n_fft, int hop, int lag) {
+    const int stft = (n_fft / 2 + hop - 1) / hop;                  // (a), (b)
+    const int istft = hop >= n_fft / 2 ? 0 : (n_fft + hop - 1) / hop - 1 + lag;      // (c)
+    return std::max(1, std::max(stft, istft));                     // (d)
+}
+
+inline int64_t snap_gcd(int64_t a, int64_t b) { return b == 0 ? a : snap_gcd(b, a % b); }
+
+// What a join does to its parts, from their manifests alone.  shift[p] = parts[0].n_total - parts[p].n_total is added to every
+// position of part p (n_total, o_done, keep; t_done moves by shift / hop).  The result keeps, for every row, the input samples from
+// `keep` on - the highest rebased keep of any part: each part's keep is at or below what its next launch reads and the parts are in
+// phase, so the highest is enough for all - i.e. columns [col[p], col[p] + live) of part p's window rows.
+struct JoinPlan {
+    std::vector<int64_t> shift;
+    std::vector<int32_t> col;
+    int32_t keep = 0, live = 0;
+};
+
+// "" and the plan, or why the parts cannot be joined.  lag: the model's stream_lag(); counts_frames: empty, or what in the model's
+// state counts frames (such a model is refused: its state cannot be rebased)
+inline std::string snap_join_plan(const std::vector<const SnapManifest*>& parts, int lag, const std::string& counts_frames, JoinPlan& plan) {
+    if (parts.empty()) return "n_parts 0: at least one part has to be given";
+    const SnapManifest& a = *parts[0];
+    auto at = [](size_t p) { return "parts[" + std::to_string(p) + "]"; };
+    auto vs = [](int64_t x, int64_t y) { return std::to_string(x) + " vs " + std::to_string(y); };
+    if (!counts_frames.empty()) return "this model's stream state cannot be rebased: " + counts_frames;
+    if (a.hop < 1 || a.n_fft < 2) return "parts[0]: front end n_fft / hop " + std::to_string(a.n_fft) + " / " + std::to_string(a.hop) + " out of range";
+    const int64_t unit = (int64_t)a.hop / snap_gcd(a.hop, 4) * 4;      // lcm(hop, 4): keep is a multiple of 4 and stays one
+    JoinPlan out;
+    bool moved = false;
+    for (size_t p = 0; p < parts.size(); ++p) {
+        const SnapManifest& b = *parts[p];
+        if (b.running)
+            return at(p) + " is a running-scale stream: its ring of 1 / c per frame is indexed by the absolute frame (running 1)";
+        if (p > 0) {
+            const std::string why = snap_concat_differs(a, b, false);
+            if (!why.empty()) return "parts[0] and " + at(p) + " differ: " + why;
+        }
+        const int64_t s = (int64_t)a.n_total - b.n_total;
+        if (s % unit != 0)
+            return "parts[0] and " + at(p) + " are out of phase: n_total " + vs(a.n_total, b.n_total) + ", the shift " + std::to_string(s) +
+                   " is not a multiple of lcm(hop, 4) = " + std::to_string(unit);
+        const int64_t fa = (int64_t)a.n_total - (int64_t)a.t_done * a.hop, fb = (int64_t)b.n_total - (int64_t)b.t_done * b.hop;
+        if (fa != fb) return "parts[0] and " + at(p) + " are out of phase: n_total - t_done * hop " + vs(fa, fb);
+        const int64_t oa = (int64_t)a.n_total - a.o_done, ob = (int64_t)b.n_total - b.o_done;
+        if (oa != ob) return "parts[0] and " + at(p) + " are out of phase: n_total - o_done " + vs(oa, ob);
+        moved = moved || s != 0;
+        out.shift.push_back(s);
+    }
+    if (moved) {
+        const int need = stream_left_edge_frames(a.n_fft, a.hop, lag);
+        for (size_t p = 0; p < parts.size(); ++p)
+            if (parts[p]->t_done < need || parts[p]->first)
+                return at(p) + " is short of the left edge: t_done " + std::to_string(parts[p]->t_done) + ", a stream can be rebased from t_done " +
+                       std::to_string(need) + " on (n_fft " + std::to_string(a.n_fft) + ", hop " + std::to_string(a.hop) + ", look-ahead " +
+                       std::to_string(lag) + ")";
+    }
+    int64_t keep = 0;
+    for (size_t p = 0; p < parts.size(); ++p) keep = std::max(keep, (int64_t)parts[p]->keep + out.shift[p]);
+    for (size_t p = 0; p < parts.size(); ++p) {
+        const int64_t col = keep - (parts[p]->keep + out.shift[p]);
+        if (keep > a.n_total || col > (int64_t)parts[p]->n_total - parts[p]->keep)
+            return at(p) + ": keep " + vs(keep - out.shift[p], parts[p]->keep) + ": the joined window starts behind the samples the part holds";
+        out.col.push_back((int32_t)col);
+    }
+    out.keep = (int32_t)keep;
+    out.live = (int32_t)(a.n_total - keep);
+    plan = std::move(out);
+    return "";
+}
+
+}  // namespace se

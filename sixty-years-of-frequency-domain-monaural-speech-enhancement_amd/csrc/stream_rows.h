@@ -89,13 +89,17 @@ inline std::vector<int64_t> snap_offsets(const SnapManifest& m) {
 }
 
 // "" or the first field in which part b differs from part a (index ib / ia in the reason): everything except batch, state_B and
-// the segment sizes has to agree for the two to be rows of one group
-inline std::string snap_concat_differs(const SnapManifest& a, const SnapManifest& b) {
+// the segment sizes has to agree for the two to be rows of one group.  positions == false leaves out n_total, t_done, o_done and keep
+// (se_stream_state_join, stream_join.h: parts whose positions differ by whole hops)
+inline std::string snap_concat_differs(const SnapManifest& a, const SnapManifest& b, bool positions = true) {
     auto ne = [](const char* name, int64_t x, int64_t y) { return std::string(name) + " " + std::to_string(x) + " vs " + std::to_string(y); };
 #define SE_SNAP_SAME(f) \
     if (a.f != b.f) return ne(#f, a.f, b.f);
     SE_SNAP_SAME(model) SE_SNAP_SAME(flags) SE_SNAP_SAME(n_fft) SE_SNAP_SAME(hop) SE_SNAP_SAME(win)
-    SE_SNAP_SAME(max_chunk) SE_SNAP_SAME(n_total) SE_SNAP_SAME(t_done) SE_SNAP_SAME(o_done) SE_SNAP_SAME(keep)
+    SE_SNAP_SAME(max_chunk)
+    if (positions) {
+        SE_SNAP_SAME(n_total) SE_SNAP_SAME(t_done) SE_SNAP_SAME(o_done) SE_SNAP_SAME(keep)
+    }
     SE_SNAP_SAME(running) SE_SNAP_SAME(ring) SE_SNAP_SAME(first)
 #undef SE_SNAP_SAME
     if (a.p_in != b.p_in) return "p_in " + std::to_string(a.p_in) + " vs " + std::to_string(b.p_in);

@@ -1,5 +1,6 @@
 """Python handle over the C-ABI engine.  torch is used only for device memory and streams."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -124,6 +125,50 @@ class StreamSnapshot:
             raise EngineError(engine._lib.se_last_error(engine._h).decode())
         dst.batch = sum(p.batch for p in parts)
         return dst
+
+    @classmethod
+    def join(cls, engine, parts, out=None):
+        """`concat` for groups that began at different times (se_stream_state_join): the rows of parts[0], then parts[1], ..., on the
+        counters of parts[0]; every other part is rebased onto them.  The parts must be in phase (their n_total differ by multiples
+        of lcm(hop, 4) - `samples_until_joinable` tells how far a caller is from that), past their left edge, not on a running scale,
+        and of a model whose state counts no frames (CRN, LSTM, GCRN, DPCRN, DCCRN); each refusal names its reason."""
+        parts = list(parts)
+        cls._check_args('join', engine, parts + ([out] if out is not None else []))
+        if not parts:
+            raise EngineError("join: at least one part has to be given")
+        arr = (C.c_void_p * len(parts))(*[p._h.value for p in parts])
+        dst = out if out is not None else cls()
+        if engine._lib.se_stream_state_join(engine._h, dst._h, arr, len(parts), engine._stream()):
+            if out is None:
+                dst.close()
+            raise EngineError(engine._lib.se_last_error(engine._h).decode())
+        dst.batch = sum(p.batch for p in parts)
+        return dst
+
+    def counts(self):
+        """(batch, n_total, t_done, o_done, hop): rows, samples received, frames transformed, samples emitted, the hop.  Host only."""
+        if self.closed:
+            raise EngineError("StreamSnapshot.counts: the snapshot is closed")
+        b, hop = C.c_int32(), C.c_int32()
+        n, t, o = C.c_int64(), C.c_int64(), C.c_int64()
+        if self._lib.se_stream_state_counts(self._h, C.byref(b), C.byref(n), C.byref(t), C.byref(o), C.byref(hop)):
+            raise EngineError(self._lib.se_last_error(None).decode())
+        return b.value, n.value, t.value, o.value, hop.value
+
+
+def samples_until_joinable(stream, group):
+    """How many more samples the stream `stream` must receive before `StreamSnapshot.join` can put it into `group`: the smallest
+    d >= 0 that makes the two n_total differ by a multiple of lcm(hop, 4) - less than one hop of buffering, and unchanged by
+    whatever whole hops the group receives meanwhile.  Both arguments are `StreamSnapshot.counts()` records (or snapshots).  None if
+    the two never can be joined: their hops differ.  Which of the two is ahead does not matter - a join rebases either way - and
+    the left edge (the first frames of a stream) is the engine's to check: its refusal names the frame count."""
+    a, g = (x.counts() if isinstance(x, StreamSnapshot) else tuple(int(v) for v in x) for x in (stream, group))
+    if len(a) != 5 or len(g) != 5 or a[4] < 1 or g[4] < 1:
+        raise EngineError("samples_until_joinable: expected two (batch, n_total, t_done, o_done, hop) records")
+    if a[4] != g[4]:
+        return None
+    unit = a[4] * 4 // math.gcd(a[4], 4)
+    return (g[1] - a[1]) % unit
 
 
 class Engine:

@@ -14,7 +14,14 @@ streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, 
   resampler's signal); `save_ms` / `restore_ms` are then the engine's half, `resampler_save_ms` / `resampler_restore_ms` the
   resampler's (se_resampler_save / se_resampler_restore), `swapped_push_ms` a whole restore -> push -> save at the source rate, and
   `resampler_snapshot_bytes` stands beside `snapshot_bytes`.
-Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000] [--swap]"""
+--staggered N: N callers that arrive one hop apart, one frame per push each (models: crn,dccrn unless --models names others that
+  StreamSnapshot.join accepts).  Every caller streams alone past its left edge and is parked; then the same N snapshots are served twice,
+  for the same frames: by turns at batch 1 (restore -> push -> save per caller and frame: `by_turns_ms`), and joined into one group
+  (StreamSnapshot.join, `join_ms` once; then one push of N rows per frame: `joined_ms`, and `joined_swapped_ms` when the group is itself
+  restored and saved around every push, as on an engine that serves other groups too).  All three are milliseconds per frame per
+  caller, medians; `frame_ms` is the audio time of a frame.  A measurement tool: no threshold is attached.
+Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000] [--swap]
+       python tools/stream_latency.py --staggered 32 [--models crn,dccrn]"""
 import argparse
 import json
 import os
@@ -176,17 +183,71 @@ def time_swap_source(src, x, c, B, chunk, piece, L):
     return out
 
 
+def time_staggered(name, N, ticks=100):
+    """--staggered: N callers one hop apart, by turns at batch 1 and joined into one group; prints the result line"""
+    import torch
+    from se_amd.engine import StreamSnapshot
+    hop = {'dccrn': 128, 'dccrn_snr': 128}.get(name, 160)
+    n_fft, lag = (320 if hop == 160 else 512), (6 if name == 'dccrn' else 0)
+    edge = max(1, -(-(n_fft // 2) // hop), 0 if hop >= n_fft // 2 else -(-n_fft // hop) - 1 + lag)      # csrc/stream_join.h
+    n0 = (edge + 1) * hop + n_fft // 2 + 1                 # the newest caller is two frames past its left edge when the group forms
+    eng = build(name, N, 16000, sliding_stream=True).engine
+    L = n0 + (N - 1 + 2 * ticks) * hop
+    x = torch.from_numpy(np.stack([synth.synth_clip(900 + b, 'speech', L) for b in range(N)])).cuda()
+    c = eng.rms_scale(x[:, :16000].contiguous())
+    snaps, pos = [], []
+    for k in range(N):                                     # caller k arrived k hops after caller 0
+        pos.append(n0 + (N - 1 - k) * hop)
+        eng.stream_begin(1, c=c[k:k + 1].contiguous(), max_chunk_frames=1)
+        eng.stream_push(x[k:k + 1, :pos[k]].contiguous())
+        snaps.append(eng.stream_save())
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def frame(t):                                          # the callers' samples of tick t, one row each
+        return torch.stack([x[k, pos[k] + t * hop:pos[k] + (t + 1) * hop] for k in range(N)])
+    group = StreamSnapshot()
+    StreamSnapshot.join(eng, snaps, out=group)             # (warms up: payload and tables of the layout)
+    join_s = timed(lambda: StreamSnapshot.join(eng, snaps, out=group))
+    eng.stream_restore(group)
+    joined = [timed(lambda: eng.stream_push(frame(t))) for t in range(ticks)]
+    eng.stream_save(group)
+    swapped = [timed(lambda: (eng.stream_restore(group), eng.stream_push(frame(t)), eng.stream_save(group))) for t in range(ticks, 2 * ticks)]
+    turns = []
+    for t in range(ticks):
+        seg = frame(t)
+        turns.append(timed(lambda: [(eng.stream_restore(snaps[k]), eng.stream_push(seg[k:k + 1]), eng.stream_save(snaps[k])) for k in range(N)]))
+    for sn in snaps + [group]:
+        sn.close()
+    per = lambda v: round(float(np.median(v[4:])) * 1e3 / N, 4)      # noqa: E731
+    print(json.dumps({'model': name, 'callers': N, 'frame_ms': hop / 16, 'by_turns_ms': per(turns), 'joined_ms': per(joined),
+                      'joined_swapped_ms': per(swapped), 'join_ms': round(join_s * 1e3, 3),
+                      'by_turns_over_joined': round(float(np.median(turns[4:]) / np.median(joined[4:])), 1)}), flush=True)
+    eng.close()
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
-    ap.add_argument('--models', default='crn,lstm,gcrn,dpcrn,dccrn,ctsnet_new,taylorsenet_new,g2net_new,fullsubnet_cum')
+    ap.add_argument('--models', default=None, help='default: every streaming model (--staggered: crn,dccrn)')
     ap.add_argument('--batch', default='1,16')
     ap.add_argument('--chunk', default='1,8')
     ap.add_argument('--seconds', type=float, default=2.0)
     ap.add_argument('--sliding', type=int, default=0, help='max_samples of a sliding-stream engine (0: a bounded engine as long as the clip)')
     ap.add_argument('--source-rate', type=int, default=0, help='push at this sample rate through SourceRateStream (0: push 16 kHz samples)')
     ap.add_argument('--swap', action='store_true', help='also time two groups alternating on the engine: restore -> push -> save per push')
+    ap.add_argument('--staggered', type=int, default=0, help='N callers one hop apart: by turns at batch 1 against joined into one group')
     a = ap.parse_args()
+    if a.staggered:
+        for name in (a.models or 'crn,dccrn').split(','):
+            time_staggered(name, a.staggered)
+        return
+    a.models = a.models or 'crn,lstm,gcrn,dpcrn,dccrn,ctsnet_new,taylorsenet_new,g2net_new,fullsubnet_cum'
     L = int(a.seconds * 16000)
     for name in a.models.split(','):
         for B in map(int, a.batch.split(',')):
