@@ -521,6 +521,36 @@ int se_resampler_state_import(se_resampler_state* s, const void* host_buf, int64
 int se_resampler_state_select(se_resampler_state* dst, const se_resampler_state* src, const int32_t* rows, int32_t n_rows, void* stream);
 int se_resampler_state_concat(se_resampler_state* dst, const se_resampler_state* const* parts, int32_t n_parts, void* stream);
 
+/* Source-rate signals that began at different times: what se_stream_state_join is to the engine's half of a parked group, for the
+ * resampler's half (an addition: the ABI number stays, and se_resampler_state_concat keeps refusing differing counters exactly as
+ * above).  For an integer decimation (sr_in % sr_out == 0, D = sr_in / sr_out) output t reads around input position t * D exactly and
+ * every index a push forms is that position plus a constant; once the left filter wing no longer reaches position 0 a parked signal
+ * may have its counters REBASED by a multiple of D (n_in and the history origin by s, n_out by s / D), and two parked groups whose
+ * counters differ by such a multiple be joined into one that advances in lockstep (csrc/resampler_join.h has the derivation).
+ *   join  : dst = the rows of parts[0], then parts[1], ... as concat, on the counters of parts[0]; every other part is rebased onto
+ *           them.  n_parts == 1 yields a copy; n_parts < 1, a null entry, an empty object and dst among the parts are refused as
+ *           concat refuses them.  A part is accepted when
+ *             - sr_in and sr_out agree with parts[0] - concat's wording ("parts[0] and parts[1] differ: sr_in 48000 vs 44100");
+ *             - the ratio is an integer decimation whose flush arithmetic has been walked over every length: D = 1 (pass-through),
+ *               2, 3.  44.1 -> 16 kHz and any upsampling are refused ("the read position is a running float64 sum from the signal's
+ *               start (sr_in % sr_out != 0)"), every other D by name;
+ *             - it is in phase: the shift parts[0].n_in - n_in is a multiple of D, and n_in - n_out * D equals that of parts[0];
+ *             - as soon as any shift is not 0, every part - parts[0] included - is past the left edge: n_out * D >= reach - 2, i.e.
+ *               n_out >= 64 at 48 -> 16 kHz and at 32 -> 16 kHz (reach: LATENCY above); the refusal names n_out, the threshold and
+ *               the rates;
+ *             - the joined history origin lies inside the samples it holds.
+ *           Parts may have been saved with histories of different lengths; the result keeps, for every row, the samples from the
+ *           highest rebased origin of any part.  Its record is parts[0]'s counters with that origin and the read position n_out * D.
+ *           Pass-through states hold counters only: any shift is accepted and the result has a payload of 0 bytes.  The result lives
+ *           where the sources do: when every source is an imported image that has not been restored yet the join runs on the host and
+ *           touches no device; imported parts among device parts are uploaded first.  A dst that already holds the layout is reused
+ *           without allocating.  One kernel per 64 rows, enqueued on `stream` and ordered against the objects' last use as
+ *           se_resampler_save is.  A refused call changes nothing; errors through se_last_error(NULL).
+ *   CONTRACT: restore the result on any se_resampler of the same rates with max_batch >= its rows.  The outputs of every later
+ *   se_resampler_push and of se_resampler_flush then equal, bit for bit and *n_out included, what each row's signal would have
+ *   produced uninterrupted.  (The sum is per output and per row in float64, so the batch size does not enter.) */
+int se_resampler_state_join(se_resampler_state* dst, const se_resampler_state* const* parts, int32_t n_parts, void* stream);
+
 /* The two ends of `enhance(args)`: `feat_wav, orig_fs = sf.read(path)` hands out int16 / 32768 as floats, and
  * `sf.write(path, y, fs)` stores PCM_16 (soundfile's default subtype for .wav: round to nearest, clipped) - e.g.
  * DCCRN/dccrn_decode_vb.py:25,64.  Both conversions are exact in fp32, so they run on the device and the host moves raw
@@ -531,7 +561,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise; + se_resampler_state_join: likewise) */
 
 #ifdef __cplusplus
 }

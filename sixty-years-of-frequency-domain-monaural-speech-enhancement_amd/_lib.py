@@ -26,7 +26,7 @@ SYMBOLS = [
     'se_resampler_state_create', 'se_resampler_state_destroy', 'se_resampler_state_bytes', 'se_resampler_state_counts',
     'se_resampler_save', 'se_resampler_restore', 'se_resampler_state_export', 'se_resampler_state_import',
     'se_stream_state_select', 'se_stream_state_concat', 'se_resampler_state_select', 'se_resampler_state_concat',
-    'se_resample_ragged', 'se_stream_state_join', 'se_stream_state_counts',
+    'se_resample_ragged', 'se_stream_state_join', 'se_stream_state_counts', 'se_resampler_state_join',
 ]
 
 
@@ -127,5 +127,6 @@ def load():
     lib.se_stream_state_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
     lib.se_resampler_state_select.argtypes = [vp, vp, C.POINTER(i32), i32, vp]
     lib.se_resampler_state_concat.argtypes = [vp, C.POINTER(vp), i32, vp]
+    lib.se_resampler_state_join.argtypes = [vp, C.POINTER(vp), i32, vp]
     _lib = lib
     return lib

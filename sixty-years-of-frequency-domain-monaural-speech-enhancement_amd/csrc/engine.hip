@@ -232,6 +232,12 @@ int se_resampler_state_concat(se_resampler_state* dst, const se_resampler_state*
                                    static_cast<hipStream_t>(stream));
     });
 }
+int se_resampler_state_join(se_resampler_state* dst, const se_resampler_state* const* parts, int32_t n_parts, void* stream) {
+    return guard(nullptr, [&] {
+        se::resampler_state_join(rst_of(dst), reinterpret_cast<se::ResamplerState* const*>(const_cast<se_resampler_state* const*>(parts)), n_parts,
+                                 static_cast<hipStream_t>(stream));
+    });
+}
 
 int se_pcm16_decode(const int16_t* in_dev, int64_t in_pitch, int32_t batch, int32_t n, float* out_dev, int64_t out_pitch,
                     void* stream) {

@@ -36,6 +36,8 @@
 //   parking  : save / restore (se_resampler_save / _restore) copy the live history [w0, n_total) of every row to and from the packed
 //              rows of a ResamplerState, one launch of resampler_state_copy_kernel; the counters travel in the host record
 //              (resampler_manifest.h).  Which buffer is current, the ring and the table are not saved: nothing later reads them.
+//              Parked signals of an integer decimation that began at different times are joined into one group by rebasing their
+//              counters (se_resampler_state_join; resampler_join.h has the conditions and their derivation).
 //   launch   : one output per thread, 64-thread blocks.  A 10 ms push at 48 kHz makes 160 outputs per row: three waves of
 //              ~384 dependent float64 steps each.  The launch is bound by that chain's latency, not by occupancy or f64
 //              rate, so the outputs are spread over as many CUs as there are waves instead of filling one 256-thread block.
@@ -46,6 +48,7 @@
 #include "resample_ragged.h"
 #include "resampler.h"
 #include "resampler_manifest.h"
+#include "resampler_join.h"
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -208,6 +211,17 @@ struct RowPtrs {
 __global__ __launch_bounds__(256) void resampler_state_gather_kernel(const RowPtrs rp, float* __restrict__ dst, int keep) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j < keep) dst[(long)blockIdx.y * keep + j] = rp.src[blockIdx.y][j];
+}
+
+// se_resampler_state_join: the parts' packed rows differ in length - row y of the destination <- `live` floats of the packed row
+// src[y] from column col[y] on (resampler_join.h: col[y] + live is that row's own length); up to 64 rows a launch, like the gather
+struct JoinRowPtrs {
+    const float* src[64];
+    int col[64];
+};
+__global__ __launch_bounds__(256) void resampler_state_join_kernel(const JoinRowPtrs rp, float* __restrict__ dst, int live) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < live) dst[(long)blockIdx.y * live + j] = rp.src[blockIdx.y][rp.col[blockIdx.y] + j];
 }
 
 struct Tables {
@@ -675,7 +689,9 @@ int StreamResampler::push(const float* in, long in_pitch, int n_new, float* out,
         pos = pos_;
         treg = upload_positions(pos, n_after, INT64_MAX, count, s);
     }
-    const int w0_next = (int)std::max<int64_t>(0, n_after - 2L * plan_.reach);
+    // (never below the origin the history has: w0_ is 0 from begin, so this is max(0, .) for a signal fed from its start; a signal
+    // rebased by se_resampler_state_join may hold a shorter history than 2 * reach and keeps its origin until the window passes it)
+    const int w0_next = (int)std::max<int64_t>(w0_, n_after - 2L * plan_.reach);
     launch(in, in_pitch, out, out_pitch, (int)n_after, w0_next, (int)pos_.t, (int)count, (int)count, treg, s);
     SE_HIP(hipEventRecord(ev_order_.get(), s));
     has_last_ = true;
@@ -973,6 +989,102 @@ void resampler_state_concat(ResamplerState* dst, ResamplerState* const* cparts, 
         parts.push_back(s);
     }
     resampler_rows(dst, parts, map, fn, st);
+}
+
+// ---- se_resampler_state_join: concat for parts whose counters differ by a multiple of sr_in / sr_out (resampler_join.h: when a parked
+// signal can be rebased, the shifts, the joined history origin and the column of each part's rows it starts at).  The parts' packed
+// rows differ in length, so the rows move through a gather of their own; where the result lives, the upload of imported parts, the
+// reuse of dst and the ordering on `st` are concat's.  Every refusal is made before the destination changes.
+void resampler_state_join(ResamplerState* dst, ResamplerState* const* cparts, int32_t n_parts, hipStream_t st) {
+    const std::string fn = "se_resampler_state_join: ";
+    SE_CHECK(dst && cparts, fn + "null argument");
+    SE_CHECK(n_parts >= 1, fn + "n_parts " + std::to_string(n_parts) + ": at least one part has to be given");
+    std::vector<ResamplerState*> parts;
+    std::vector<const ResamplerManifest*> mans;
+    std::vector<std::pair<int, int32_t>> map;
+    for (int32_t p = 0; p < n_parts; ++p) {
+        ResamplerState* s = cparts[p];
+        SE_CHECK(s, fn + "parts[" + std::to_string(p) + "] is null");
+        SE_CHECK(s != dst, fn + "dst == parts[" + std::to_string(p) + "]: the rows are read while they are written");
+        SE_CHECK(s->filled, fn + "parts[" + std::to_string(p) + "]: the resampler state object is empty");
+        SE_CHECK(map.size() + (size_t)s->man.batch < ((size_t)1 << 24), fn + "too many rows");
+        for (int32_t r = 0; r < s->man.batch; ++r) map.emplace_back(p, r);
+        parts.push_back(s);
+        mans.push_back(&s->man);
+    }
+    ResamplerJoinPlan plan;
+    const std::string why = rsnap_join_plan(mans, plan);
+    SE_CHECK(why.empty(), fn + why);
+    const ResamplerManifest m = rsnap_joined(parts[0]->man, plan, (int32_t)map.size());
+    const std::string bad = rsnap_check(m);
+    SE_CHECK(bad.empty(), fn + bad);
+    const int64_t live = plan.live;
+    SE_CHECK(live == rsnap_keep(m) && live <= INT_MAX / 4, fn + "history out of range");
+    for (size_t p = 0; p < parts.size(); ++p)       // what the gather indexes: columns [col, col + live) of rows of the part's own length
+        SE_CHECK(plan.col[p] >= 0 && plan.col[p] + live == rsnap_keep(parts[p]->man), fn + "history out of range");
+    auto finish = [&](bool on_dev) {
+        dst->man = m;
+        dst->filled = true;
+        dst->dev_valid = on_dev;
+    };
+    if (live == 0) {      // pass-through, or nothing live: counters only
+        dst->host.clear();
+        finish(false);
+        return;
+    }
+    int dev = -1;
+    for (ResamplerState* p : parts)
+        if (p->dev_valid && p->side && p->side->dev) {
+            SE_CHECK(dev < 0 || dev == p->device, fn + "the parts' payloads live on devices " + std::to_string(dev) + " and " + std::to_string(p->device) +
+                                                      " (export and import a state to move it)");
+            dev = p->device;
+        }
+    for (ResamplerState* p : parts)
+        if (!(p->dev_valid && p->side && p->side->dev))
+            SE_CHECK((int64_t)p->host.size() == rsnap_payload_bytes(p->man), fn + "a part has no payload");
+        else
+            SE_CHECK(p->dev_cap >= (int64_t)p->man.batch * rsnap_keep(p->man), fn + "a part's payload is smaller than its rows");
+    // ---- every refusal is above
+    if (dev < 0) {
+        std::vector<uint8_t> out((size_t)(m.batch * live * 4));
+        for (size_t j = 0; j < map.size(); ++j) {
+            const size_t p = (size_t)map[j].first;
+            const size_t row = (size_t)rsnap_keep(parts[p]->man);
+            std::memcpy(out.data() + j * (size_t)live * 4, parts[p]->host.data() + ((size_t)map[j].second * row + (size_t)plan.col[p]) * 4, (size_t)live * 4);
+        }
+        dst->drop_side();
+        dst->host = std::move(out);
+        finish(false);
+        return;
+    }
+    DeviceScope ds(dev);
+    for (ResamplerState* p : parts)
+        if (!p->dev_valid) {
+            p->payload_alloc((int64_t)p->man.batch * rsnap_keep(p->man), dev);
+            if (p->has_use) SE_HIP(hipEventSynchronize(p->side->ev_use.get()));
+            SE_HIP(hipMemcpy(p->side->dev.get(), p->host.data(), p->host.size(), hipMemcpyHostToDevice));
+            p->dev_valid = true;
+        }
+    dst->payload_alloc((int64_t)m.batch * live, dev);
+    for (ResamplerState* p : parts) p->wait(st);
+    dst->wait(st);
+    for (size_t y0 = 0; y0 < map.size(); y0 += 64) {
+        const int ny = (int)std::min<size_t>(64, map.size() - y0);
+        JoinRowPtrs rp{};
+        for (int y = 0; y < ny; ++y) {
+            const size_t p = (size_t)map[y0 + y].first;
+            rp.src[y] = parts[p]->side->dev.get() + (size_t)map[y0 + y].second * (size_t)rsnap_keep(parts[p]->man);
+            rp.col[y] = (int)plan.col[p];
+        }
+        hipLaunchKernelGGL(resampler_state_join_kernel, dim3((unsigned)((live + 255) / 256), (unsigned)ny), dim3(256), 0, st, rp,
+                           dst->side->dev.get() + y0 * (size_t)live, (int)live);
+        SE_HIP(hipGetLastError());
+    }
+    dst->host.clear();
+    dst->host.shrink_to_fit();
+    finish(true);
+    dst->mark(st);
+    for (ResamplerState* p : parts) p->mark(st);
 }
 
 StreamResampler* stream_resampler_create(int sr_in, int sr_out, int max_batch, int max_push) {

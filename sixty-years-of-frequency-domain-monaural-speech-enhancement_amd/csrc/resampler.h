@@ -35,5 +35,7 @@ void resampler_state_import(ResamplerState* s, const void* host_buf, int64_t byt
 // rows of parked signals: dst <- rows[j] of src / the rows of parts[0], parts[1], ... (include/se_engine.h)
 void resampler_state_select(ResamplerState* dst, ResamplerState* src, const int32_t* rows, int32_t n_rows, hipStream_t st);
 void resampler_state_concat(ResamplerState* dst, ResamplerState* const* parts, int32_t n_parts, hipStream_t st);
+// concat for parts that began at different times: every part rebased onto the counters of parts[0] (resampler_join.h)
+void resampler_state_join(ResamplerState* dst, ResamplerState* const* parts, int32_t n_parts, hipStream_t st);
 
 }  // namespace se

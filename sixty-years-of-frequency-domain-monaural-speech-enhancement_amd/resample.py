@@ -199,24 +199,37 @@ class ResamplerSnapshot:
         return dst
 
     @classmethod
-    def concat(cls, parts, out=None):
-        """A snapshot of the rows of parts[0], then parts[1], ...: rates, sample counts and read position have to agree."""
+    def _gather(cls, what, parts, out):
+        """concat / join: the rows of the parts, in order, through se_resampler_state_<what>"""
         parts = list(parts)
-        cls._check_args('concat', parts + ([out] if out is not None else []))
+        cls._check_args(what, parts + ([out] if out is not None else []))
         if not parts:
-            raise EngineError("concat: at least one part has to be given")
+            raise EngineError(f"{what}: at least one part has to be given")
         devices = {p.device for p in parts if p.device is not None}
         if len(devices) > 1:
-            raise EngineError(f"concat: the parts' payloads live on devices {sorted(devices)} (move them with to_bytes / from_bytes)")
+            raise EngineError(f"{what}: the parts' payloads live on devices {sorted(devices)} (move them with to_bytes / from_bytes)")
         device = devices.pop() if devices else None
         arr = (C.c_void_p * len(parts))(*[p._h.value for p in parts])
         dst = out if out is not None else cls()
-        if dst._lib.se_resampler_state_concat(dst._h, arr, len(parts), cls._stream_of(device)):
+        if getattr(dst._lib, 'se_resampler_state_' + what)(dst._h, arr, len(parts), cls._stream_of(device)):
             if out is None:
                 dst.close()
             raise EngineError(dst._lib.se_last_error(None).decode())
         dst.device = device
         return dst
+
+    @classmethod
+    def concat(cls, parts, out=None):
+        """A snapshot of the rows of parts[0], then parts[1], ...: rates, sample counts and read position have to agree."""
+        return cls._gather('concat', parts, out)
+
+    @classmethod
+    def join(cls, parts, out=None):
+        """`concat` for signals that began at different times (se_resampler_state_join): the rows of parts[0], then parts[1], ..., on
+        the counters of parts[0]; every other part is rebased onto them.  Integer decimations only (48 / 32 -> 16 kHz, pass-through);
+        the parts must be in phase (their n_in differ by multiples of sr_in / sr_out) and past their left edge (64 outputs at
+        48 -> 16 kHz); each refusal names its reason.  Every row then continues bit for bit as it would have alone."""
+        return cls._gather('join', parts, out)
 
 
 class StreamResampler:

@@ -7,6 +7,7 @@ into the engine's stream; what comes back is the engine's 16 kHz output (the ref
 converted back to `sr_in`).  The engine and its stream state are used as they are; on top of the engine's own latency the
 resampler looks 192 input samples (4 ms) ahead at 48 -> 16 kHz.
 """
+import math
 import struct
 
 from .engine import EngineError, StreamSnapshot
@@ -106,6 +107,69 @@ class SourceStreamSnapshot:
             raise
         return cls(eng, res)
 
+    def counts(self):
+        """Both halves' host records: (`StreamSnapshot.counts()`, `ResamplerSnapshot.counts()`) =
+        ((batch, n_total, t_done, o_done, hop), (sr_in, sr_out, batch, n_in, n_out)).  Host only."""
+        if self.closed:
+            raise EngineError("counts: the snapshot is closed")
+        return self.engine.counts(), self.resampler.counts()
+
+    @classmethod
+    def join(cls, engine, parts):
+        """`concat` for source-rate groups that began at different times: the rows of parts[0], then parts[1], ... in both halves, on
+        the counters of parts[0] (ResamplerSnapshot.join, then StreamSnapshot.join).  A caller is in phase with a group once
+        `source_samples_until_joinable` says 0; both halves have to be past their left edge.  The two halves of every part have to
+        tell one story - the engine has received what the resampler has released - which is checked here, on the host, first."""
+        parts = list(parts)
+        for p in parts:
+            if not isinstance(p, SourceStreamSnapshot):
+                raise EngineError(f"join: expected a SourceStreamSnapshot, got {type(p).__name__}")
+            if p.closed:
+                raise EngineError("join: the snapshot is closed")
+        if not parts:
+            raise EngineError("join: at least one part has to be given")
+        recs = [p.counts() for p in parts]
+        for k, (e, r) in enumerate(recs):
+            if e[0] != r[2]:
+                raise EngineError(f"join: parts[{k}]: the engine's half holds {e[0]} rows, the resampler's {r[2]}")
+            if e[1] != r[4]:        # (equal in every part: the engine's shift is then the resampler's output shift as well)
+                raise EngineError(f"join: parts[{k}]: the engine's half has received {e[1]} samples, the resampler's has released {r[4]}")
+        res = ResamplerSnapshot.join([p.resampler for p in parts])
+        try:
+            eng = StreamSnapshot.join(engine, [p.engine for p in parts])
+        except EngineError:
+            res.close()
+            raise
+        return cls(eng, res)
+
+
+JOIN_DECIMATIONS = (1, 2, 3)         # csrc/resampler_join.h RSJOIN_DECIMATIONS: the sr_in / sr_out se_resampler_state_join accepts
+
+
+def source_samples_until_joinable(stream, group):
+    """How many more samples at sr_in the source-rate stream `stream` must push before `SourceStreamSnapshot.join` can put it into
+    `group`: the smallest d >= 0 that makes the two n_in differ by a multiple of D * lcm(hop, 4), D = sr_in / sr_out - the resampler's
+    half rebases by multiples of D, the engine's by multiples of lcm(hop, 4) at sr_out: 480 samples at 48 kHz with hop 160, 384 with
+    hop 128.  Unchanged by whatever whole hops the group receives meanwhile.  Both arguments are `SourceStreamSnapshot.counts()` records
+    (or snapshots).  None if the two never can be joined: other rates, a ratio the join refuses (44.1 kHz, upsampling, a decimation
+    other than 1, 2, 3), other hops.  The left edges are the library's to check: its refusals name the counts."""
+    recs = []
+    for x in (stream, group):
+        e, r = x.counts() if isinstance(x, SourceStreamSnapshot) else x
+        e, r = tuple(int(v) for v in e), tuple(int(v) for v in r)
+        if len(e) != 5 or len(r) != 5 or e[4] < 1 or r[0] < 1 or r[1] < 1:
+            raise EngineError("source_samples_until_joinable: expected two ((batch, n_total, t_done, o_done, hop), "
+                              "(sr_in, sr_out, batch, n_in, n_out)) records")
+        recs.append((e, r))
+    (ea, ra), (eg, rg) = recs
+    if ra[:2] != rg[:2] or ea[4] != eg[4]:
+        return None
+    sr_in, sr_out = ra[:2]
+    if sr_in % sr_out or sr_in // sr_out not in JOIN_DECIMATIONS:
+        return None
+    unit = sr_in // sr_out * (ea[4] * 4 // math.gcd(ea[4], 4))
+    return (rg[3] - ra[3]) % unit
+
 
 class SourceRateStream:
     """`SourceRateStream(model.engine, 48000)`: `begin(batch, ...)`, `push(x)` with x [batch, n <= max_push] at sr_in ->
@@ -113,7 +177,9 @@ class SourceRateStream:
     takes: a per-stream scale `c` (of the 16 kHz signal, e.g. from a calibration run) or `running_rms=True`.
     `save()` / `restore()` park and resume the stream as `Engine.stream_save` / `stream_restore` do for a 16 kHz one: a
     `SourceStreamSnapshot` holds the engine's stream and the resampler's filter history and read position, so groups fed at the
-    source's rate can share one engine and one `SourceRateStream` by turns (restore -> push -> save per group)."""
+    source's rate can share one engine and one `SourceRateStream` by turns (restore -> push -> save per group).  Parked groups of an
+    integer decimation (48 / 32 kHz) that began at different times are put into one by `SourceStreamSnapshot.join`, once
+    `source_samples_until_joinable` says the late caller is in phase."""
 
     def __init__(self, engine, sr_in, sr_out=16000, max_push=None):
         self.engine = engine

@@ -20,8 +20,11 @@ streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, 
   (StreamSnapshot.join, `join_ms` once; then one push of N rows per frame: `joined_ms`, and `joined_swapped_ms` when the group is itself
   restored and saved around every push, as on an engine that serves other groups too).  All three are milliseconds per frame per
   caller, medians; `frame_ms` is the audio time of a frame.  A measurement tool: no threshold is attached.
+  With --source-rate SR (48000, 32000) the callers are fed at SR through SourceRateStream, one hop (SR / 16000 * hop source samples)
+  apart, parked as SourceStreamSnapshot pairs and joined with SourceStreamSnapshot.join (se_resampler_state_join and
+  se_stream_state_join); the same result line, with `source_rate` in it.
 Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000] [--swap]
-       python tools/stream_latency.py --staggered 32 [--models crn,dccrn]"""
+       python tools/stream_latency.py --staggered 32 [--models crn,dccrn] [--source-rate 48000]"""
 import argparse
 import json
 import os
@@ -231,6 +234,63 @@ def time_staggered(name, N, ticks=100):
     eng.close()
 
 
+def time_staggered_source(name, N, sr, ticks=100):
+    """--staggered with --source-rate: the same measurement with every caller fed at `sr` through SourceRateStream"""
+    import torch
+    from se_amd.resample import resample
+    from se_amd.source_stream import SourceRateStream, SourceStreamSnapshot
+    assert sr % 16000 == 0 and sr // 16000 in (2, 3), 'SourceStreamSnapshot.join takes integer decimations: 48000, 32000'
+    D = sr // 16000
+    hop = {'dccrn': 128, 'dccrn_snr': 128}.get(name, 160)
+    n_fft, lag = (320 if hop == 160 else 512), (6 if name == 'dccrn' else 0)
+    edge = max(1, -(-(n_fft // 2) // hop), 0 if hop >= n_fft // 2 else -(-n_fft // hop) - 1 + lag)      # csrc/stream_join.h
+    reach = 32769 // (512 // D) + 1                        # csrc/resample_pos.h
+    # the newest caller: two frames past the engine's left edge at 16 kHz (well past the resampler's own, 64 outputs) when the group forms
+    n0 = D * ((edge + 1) * hop + n_fft // 2 + 1) + reach
+    step = D * hop                                         # one hop at the source rate: D * lcm(hop, 4)
+    eng = build(name, N, 16000, sliding_stream=True).engine
+    L = n0 + (N - 1 + 2 * ticks) * step
+    x = torch.from_numpy(np.stack([synth.synth_clip(900 + b, 'speech', L, fs=sr) for b in range(N)])).cuda()
+    c = eng.rms_scale(resample(x[:, :16000 * D].contiguous(), sr))
+    src = SourceRateStream(eng, sr, max_push=n0 + (N - 1) * step)
+    snaps, pos = [], []
+    for k in range(N):                                     # caller k arrived k hops after caller 0
+        pos.append(n0 + (N - 1 - k) * step)
+        src.begin(1, c=c[k:k + 1].contiguous(), max_chunk_frames=1)
+        src.push(x[k:k + 1, :pos[k]].contiguous())
+        snaps.append(src.save())
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def frame(t):                                          # the callers' samples of tick t, one row each
+        return torch.stack([x[k, pos[k] + t * step:pos[k] + (t + 1) * step] for k in range(N)])
+    SourceStreamSnapshot.join(eng, snaps).close()          # (warms up: payloads and tables of the layout)
+    made = []
+    join_s = timed(lambda: made.append(SourceStreamSnapshot.join(eng, snaps)))
+    group = made[0]
+    src.restore(group)
+    joined = [timed(lambda: src.push(frame(t))) for t in range(ticks)]
+    src.save(group)
+    swapped = [timed(lambda: (src.restore(group), src.push(frame(t)), src.save(group))) for t in range(ticks, 2 * ticks)]
+    turns = []
+    for t in range(ticks):
+        seg = frame(t)
+        turns.append(timed(lambda: [(src.restore(snaps[k]), src.push(seg[k:k + 1]), src.save(snaps[k])) for k in range(N)]))
+    for sn in snaps + [group]:
+        sn.close()
+    src.close()
+    per = lambda v: round(float(np.median(v[4:])) * 1e3 / N, 4)      # noqa: E731
+    print(json.dumps({'model': name, 'callers': N, 'source_rate': sr, 'frame_ms': hop / 16, 'by_turns_ms': per(turns), 'joined_ms': per(joined),
+                      'joined_swapped_ms': per(swapped), 'join_ms': round(join_s * 1e3, 3),
+                      'by_turns_over_joined': round(float(np.median(turns[4:]) / np.median(joined[4:])), 1)}), flush=True)
+    eng.close()
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -245,7 +305,10 @@ def main():
     a = ap.parse_args()
     if a.staggered:
         for name in (a.models or 'crn,dccrn').split(','):
-            time_staggered(name, a.staggered)
+            if a.source_rate:
+                time_staggered_source(name, a.staggered, a.source_rate)
+            else:
+                time_staggered(name, a.staggered)
         return
     a.models = a.models or 'crn,lstm,gcrn,dpcrn,dccrn,ctsnet_new,taylorsenet_new,g2net_new,fullsubnet_cum'
     L = int(a.seconds * 16000)
