@@ -202,6 +202,32 @@ int se_stream_begin(se_engine* e, int32_t batch, int32_t max_chunk_frames, const
  * scale of a short prefix - the price of not knowing the future - and the output tracks the offline decode as the
  * estimate settles (tests/test_gpu_streaming.py).  Scaling the input by k scales the output by k exactly as offline. */
 int se_stream_begin_running(se_engine* e, int32_t batch, int32_t max_chunk_frames, void* stream);
+/* A third way to start, for a live caller (additions: the ABI number stays): the stream runs on a TRACKING unit-RMS scale, an
+ * exponentially forgetting estimate with one value per STFT frame.  Block k is the samples [k hop, (k + 1) hop) of a row, e_k their sum
+ * of squares in float64, lambda = exp(-hop / tau_samples) (tau_samples == 0: lambda = 1, never forget), and
+ *     E_k = lambda E_(k-1) + e_k      W_k = lambda W_(k-1) + hop      (E_(-1) = W_(-1) = 0, float64)
+ * Frame t uses the blocks that end at or before its own last sample: K(t) = floor((t hop + n_fft / 2) / hop),
+ *     c_t = sqrt(W_(K(t)-1) / E_(K(t)-1)),   c_t = 1 where E <= 1e-20 (digital silence, as the running scale).
+ * Every block a frame needs has arrived when se_stream_push releases the frame (that needs sample t hop + n_fft / 2): the scale adds no
+ * latency.  At se_stream_flush the n_total mod hop samples left are one last short block (E = lambda E + e, W = lambda W + r); frames
+ * whose K(t) lies past the last block use the last state - the zeros a decode script pads behind the signal are not counted.  Frame t
+ * is transformed under c_t and taken back by 1 / c_t in the overlap-add, both rounded from the same float64 value.
+ *   - It follows the level: after a few tau the estimate is that of the recent signal, also in a SE_CFG_STREAM_SLIDING stream of hours.
+ *   - It is a function of the signal, not of the pushes: a block is summed whole, in one fixed order, out of the stream's input
+ *     window when the push that completes it arrives, so c_t is bit-identical for every split of the signal into pushes (the outputs
+ *     then differ by the fp32 rounding of differently tiled chunks only).  The window keeps the head of an incomplete block as long
+ *     as n_fft >= 2 hop - 2, also when it slides (csrc/stream_window.h); other front ends are refused.
+ *   - Its state - (E, W) per row and the two per-frame rings - holds no absolute time: tracking streams are parked, selected,
+ *     concatenated (equal tau_samples) and JOINED (se_stream_state_join below rotates the rings by the shift in frames).
+ *   - Scaling the input by k scales every c_t by 1 / k and the output by k.  A signal of period hop has c_t = the offline c.
+ * Needs what se_stream_begin_running needs.  Refused, each with its own reason: tau_samples negative, NaN or infinite; a model
+ * without a frame-online mode (se_stream_begin's wording); n_fft < 2 hop - 2.
+ *
+ * se_stream_scale copies one float per row of the running stream to c_dev (device, `batch` floats): the scale of the most recently
+ * released frame - se_stream_begin: the caller's c; the running scale: the current c; the tracking scale: c_t of the last frame
+ * released; 1 before any frame.  The level read-out of a tracking stream.  Refused without a running stream. */
+int se_stream_begin_tracking(se_engine* e, int32_t batch, int32_t max_chunk_frames, float tau_samples, void* stream);
+int se_stream_scale(se_engine* e, float* c_dev, void* stream);
 int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_new, float* out_dev, int64_t out_pitch,
                    int32_t* n_out, void* stream);
 int se_stream_flush(se_engine* e, float* out_dev, int64_t out_pitch, int32_t* n_out, void* stream);
@@ -231,7 +257,7 @@ int se_stream_flush(se_engine* e, float* out_dev, int64_t out_pitch, int32_t* n_
  *                      model id; every se_config.flags bit except SE_CFG_GRAPHS and SE_CFG_STREAM_SLIDING; n_fft / hop / win;
  *                      p_in / p_out.  Further: max_batch >= the snapshot's batch; a workspace planned for its max_chunk_frames;
  *                      without SE_CFG_STREAM_SLIDING max_samples >= the samples the stream has received, with it a window that
- *                      holds the saved live samples; for a running-scale stream a per-frame ring no longer than the snapshot's
+ *                      holds the saved live samples; for a running-scale or tracking-scale stream a per-frame ring no longer than the snapshot's
  *                      (an engine planned for a larger max_samples may need a longer one).  Each mismatch is refused with its own
  *                      reason.  WEIGHTS ARE NOT COMPARED: the same weights on both engines are the caller's duty (weights of other
  *                      SHAPES are noticed - the state buffers differ in size - but only after the handle's stream has ended).
@@ -294,7 +320,8 @@ int se_stream_state_concat(se_engine* e, se_stream_state* dst, const se_stream_s
  *               ceil(n_fft / 2 / hop), and where hop < n_fft / 2 ceil(n_fft / hop) - 1 + the model's frames of look-ahead), i.e. 1 for 320 / 160, 3 for
  *               512 / 128, 9 for the DCCRN whose decoder looks six frames ahead (csrc/stream_join.h has the derivation);
  *             - its state holds no absolute time: a running-scale stream is refused (its ring of 1 / c per frame is indexed by the
- *               absolute frame), and so are the models whose state counts frames - CTSNet, TaylorSENet and G2Net with the cumulative
+ *               absolute frame, and its sum by the absolute sample count; a TRACKING-scale stream is accepted - its (E, W) are relative,
+ *               and its rings are rotated by shift / hop frames on the way, csrc/stream_join.h - with equal tau_samples), and so are the models whose state counts frames - CTSNet, TaylorSENet and G2Net with the cumulative
  *               LayerNorm, FullSubNet with the cumulative norm.  CRN, LSTM, GCRN, DPCRN and DCCRN (complex or real LSTM core, either
  *               decoder) are accepted.
  *           Each failure is refused with its own reason, naming the field and both values.  Parts may have been saved with live input

@@ -10,6 +10,7 @@
 #include "stream_rows.h"
 #include "stream_window.h"
 #include "window_rows.h"
+#include <cmath>
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -80,16 +81,27 @@ struct se_engine {
         DevBuf<float> frame_inv;
         int ring = 0;
         DevBuf<float> c;
+        // tracking unit-RMS scale (se_stream_begin_tracking): `sumsq` holds (E, W) per row, every frame has a scale of its own - c_t
+        // in the ring frame_c for the forward transform, 1 / c_t in frame_inv for the inverse; lam = exp(-hop / tau) (1: tau == 0)
+        bool tracking = false;
+        float tau = 0.f;
+        double lam = 1.0;
+        DevBuf<float> frame_c;
+        bool per_frame() const { return running || tracking; }
+        int scale_mode() const { return tracking ? 2 : running ? 1 : 0; }      // SnapManifest::running
         // the hipStream the last push / flush / begin of this handle ran on: a new stream that starts on ANOTHER hipStream
         // re-uses (and clears) the parked state buffers, so it must be ordered behind the work still in flight there
         bool has_last = false;
         hipStream_t last_st = nullptr;
         Event ev_order;
         // a stream or a windowed decode starts: nothing received (or a whole clip of n_total_ samples), nothing done, no carve
-        void start(int batch_, int n_total_, bool running_) {
+        void start(int batch_, int n_total_, bool running_, bool tracking_ = false, float tau_ = 0.f, int hop = 1) {
             batch = batch_;
             n_total = n_total_;
             running = running_;
+            tracking = tracking_;
+            tau = tracking_ ? tau_ : 0.f;
+            lam = tracking_ && tau_ > 0.f ? std::exp(-(double)hop / (double)tau_) : 1.0;
             t_done = o_done = w0 = 0;
             carve_B = carve_n = -1;
             ext = nullptr;
@@ -719,7 +731,8 @@ static void stream_process(se_engine* e, int t_end, bool last, float* out_dev, i
         {
             if (rows) launch_window_rows(rows->len, rw, MB, B, t0 + n, st);
             RaggedScope rs(view);
-            launch_stft(g, wav, pitch, B, S.n_total, Lpad, S.c.get(), e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, w0);
+            launch_stft(g, wav, pitch, B, S.n_total, Lpad, S.c.get(), e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, w0,
+                        S.tracking ? S.frame_c.get() : nullptr, S.ring);
         }
         e->model->stream_chunk(B, t0, n, st, last && t0 + n == t_end);
         S.t_done = t0 + n;
@@ -731,8 +744,8 @@ static void stream_process(se_engine* e, int t_end, bool last, float* out_dev, i
         if (o_hi > S.o_done) {
             if (rows && t_fin != t0 + n) launch_window_rows(rows->len, rw, MB, B, t_fin, st);      // (else the STFT's view holds)
             RaggedScope rs(view);
-            launch_istft(g, est, B, t_fin, Tw, nullptr, S.running ? nullptr : S.c.get(), out_dev + *written, out_pitch, o_hi, st, t0 - HC,
-                         std::max(0, t0 - HC), S.o_done, S.running ? S.frame_inv.get() : nullptr, S.ring);
+            launch_istft(g, est, B, t_fin, Tw, nullptr, S.per_frame() ? nullptr : S.c.get(), out_dev + *written, out_pitch, o_hi, st, t0 - HC,
+                         std::max(0, t0 - HC), S.o_done, S.per_frame() ? S.frame_inv.get() : nullptr, S.ring);
             *written += o_hi - S.o_done;
             S.o_done = o_hi;
         }
@@ -751,15 +764,34 @@ static int window_frames(const se_engine* e, int requested, int dflt) {
     return std::min(requested > 0 ? requested : dflt, room);
 }
 
-static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_frames, const float* c_dev, bool running, void* stream) {
+// the rings and sums of the per-frame scales: made once per handle, for the engine's plan (the running and the tracking scale share them)
+static void scale_rings_alloc(se_engine* e, bool tracking) {
+    se_engine::Stream& S = e->strm;
+    if (!S.sumsq) {
+        S.ring = 64;
+        while (S.ring < e->plan_frames + 64) S.ring <<= 1;
+        S.sumsq.alloc((size_t)2 * e->ctx.max_batch);      // (running: one sum per row; tracking: (E, W) per row)
+        S.frame_inv.alloc((size_t)e->ctx.max_batch * S.ring);
+    }
+    if (tracking && !S.frame_c) S.frame_c.alloc((size_t)e->ctx.max_batch * S.ring);
+}
+
+static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_frames, const float* c_dev, bool running, void* stream,
+                             bool tracking = false, float tau = 0.f) {
     if (!e) return 1;
     return guard(e, [&] {
         SE_CHECK(e->finalized, "engine not finalized");
         e->strm.carve_B = -1;          // (any decode re-carves the arena: a stream running on this handle zero-fills its next windows)
+        if (tracking)
+            SE_CHECK(std::isfinite(tau) && tau >= 0.f,
+                     "se_stream_begin_tracking: tau_samples has to be a finite number >= 0 (0: never forget), got " + std::to_string(tau));
         SE_CHECK(e->model->stream_supported(), "this model has no frame-online mode (CRN, LSTM, GCRN, DPCRN, DCCRN, FullSubNet with the cumulative norm and the cLN `_new` weights of CTSNet / TaylorSENet / G2Net have)");
         SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
         check_stream_geometry(e);
         const StftGeom& g = e->ctx.geom;
+        if (tracking)
+            SE_CHECK(g.n_fft >= 2 * g.hop - 2, "se_stream_begin_tracking: n_fft " + std::to_string(g.n_fft) + " < 2 hop - 2 (hop " + std::to_string(g.hop) +
+                                                   "): the stream's input window does not keep the head of an incomplete hop block");
         hipStream_t st = static_cast<hipStream_t>(stream);
         se_engine::Stream& S = e->strm;
         // work of the previous stream on another hipStream: wait for the event that stream_mark() recorded behind ITS last
@@ -775,17 +807,13 @@ static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_fram
         if (!S.c) S.c.alloc(e->ctx.max_batch);      // (se_enhance_long may have made it already)
         if (c_dev) SE_HIP(hipMemcpyAsync(S.c.get(), c_dev, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, st));
         else launch_fill(S.c.get(), batch, 1.f, st);
-        if (running) {
-            if (!S.sumsq) {
-                S.ring = 64;
-                while (S.ring < e->plan_frames + 64) S.ring <<= 1;
-                S.sumsq.alloc(e->ctx.max_batch);
-                S.frame_inv.alloc((size_t)e->ctx.max_batch * S.ring);
-            }
-            SE_HIP(hipMemsetAsync(S.sumsq.get(), 0, (size_t)batch * sizeof(double), st));
+        if (running || tracking) {
+            scale_rings_alloc(e, tracking);
+            SE_HIP(hipMemsetAsync(S.sumsq.get(), 0, (size_t)batch * (tracking ? 2 : 1) * sizeof(double), st));
             launch_fill(S.frame_inv.get(), (long)batch * S.ring, 1.f, st);
+            if (tracking) launch_fill(S.frame_c.get(), (long)batch * S.ring, 1.f, st);
         }
-        S.start(batch, 0, running);
+        S.start(batch, 0, running, tracking, tau, g.hop);
         e->model->stream_begin(batch, S.max_chunk, st);
         S.active = true;
         stream_mark(S, st);
@@ -797,6 +825,23 @@ int se_stream_begin(se_engine* e, int32_t batch, int32_t max_chunk_frames, const
 }
 int se_stream_begin_running(se_engine* e, int32_t batch, int32_t max_chunk_frames, void* stream) {
     return stream_begin_impl(e, batch, max_chunk_frames, nullptr, true, stream);
+}
+
+int se_stream_begin_tracking(se_engine* e, int32_t batch, int32_t max_chunk_frames, float tau_samples, void* stream) {
+    return stream_begin_impl(e, batch, max_chunk_frames, nullptr, false, stream, true, tau_samples);
+}
+
+int se_stream_scale(se_engine* e, float* c_dev, void* stream) {
+    if (!e) return 1;
+    return guard(e, [&] {
+        se_engine::Stream& S = e->strm;
+        SE_CHECK(S.active, "se_stream_scale without se_stream_begin");
+        SE_CHECK(c_dev, "se_stream_scale: null argument");
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        stream_order_wait(S, st);
+        SE_HIP(hipMemcpyAsync(c_dev, S.c.get(), (size_t)S.batch * sizeof(float), hipMemcpyDeviceToDevice, st));
+        stream_mark(S, st);
+    });
 }
 
 int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_new, float* out_dev, int64_t out_pitch,
@@ -840,7 +885,10 @@ int se_stream_push(se_engine* e, const float* wav_dev, int64_t pitch, int32_t n_
         // frame t is final once sample t * hop + n_fft / 2 has arrived (its right half is real signal, and frame 0's reflected
         // left half needs sample n_fft / 2 as well)
         const int t_avail = S.n_total > g.n_fft / 2 ? (S.n_total - g.n_fft / 2 - 1) / g.hop + 1 : 0;
-        if (S.running)      // c of the frames this push releases: sqrt(samples so far / their sum of squares)
+        if (S.tracking)     // c_t of the frames this push releases, from the hop blocks it completes
+            launch_stream_track(g, S.wav.get(), S.pitch, S.batch, S.n_total, n_new, false, S.lam, S.sumsq.get(), S.c.get(), S.frame_c.get(),
+                                S.frame_inv.get(), S.ring, S.t_done, std::max(t_avail, S.t_done), st, S.w0);
+        else if (S.running)      // c of the frames this push releases: sqrt(samples so far / their sum of squares)
             launch_stream_rms(S.wav.get(), S.pitch, S.batch, S.n_total, n_new, S.sumsq.get(), S.c.get(), S.frame_inv.get(), S.ring, S.t_done,
                               std::max(t_avail, S.t_done), st, S.w0);
         int written = 0;
@@ -864,7 +912,10 @@ int se_stream_flush(se_engine* e, float* out_dev, int64_t out_pitch, int32_t* n_
         hipStream_t st = static_cast<hipStream_t>(stream);
         ArenaCall call(e, st, ArenaCall::MARK_ONLY);
         e->ctx.prof_reset();
-        if (S.running)
+        if (S.tracking)
+            launch_stream_track(e->ctx.geom, S.wav.get(), S.pitch, S.batch, S.n_total, 0, true, S.lam, S.sumsq.get(), S.c.get(), S.frame_c.get(),
+                                S.frame_inv.get(), S.ring, S.t_done, e->model->num_frames(S.n_total), st, S.w0);
+        else if (S.running)
             launch_stream_rms(S.wav.get(), S.pitch, S.batch, S.n_total, 0, S.sumsq.get(), S.c.get(), S.frame_inv.get(), S.ring, S.t_done,
                               e->model->num_frames(S.n_total), st, S.w0);
         stream_process(e, e->model->num_frames(S.n_total), true, out_dev, out_pitch, &written, st);
@@ -1131,7 +1182,8 @@ struct EngSeg {
 };
 
 // every buffer chunk k of the stream writes and chunk k + 1 reads, except the input window, in payload order
-std::vector<EngSeg> engine_segments(se_engine* e, int batch, bool running, int ring) {
+// (mode: SnapManifest::running - 0 a fixed scale, 1 the running scale, 2 the tracking scale)
+std::vector<EngSeg> engine_segments(se_engine* e, int batch, int mode, int ring) {
     se_engine::Stream& S = e->strm;
     std::vector<EngSeg> v;
     auto add = [&](int32_t kind, int32_t index, void* p, int64_t bytes) {
@@ -1143,9 +1195,10 @@ std::vector<EngSeg> engine_segments(se_engine* e, int batch, bool running, int r
         v.push_back(s);
     };
     add(SNAP_C, 0, S.c.get(), (int64_t)batch * sizeof(float));
-    if (running) {
-        add(SNAP_SUMSQ, 0, S.sumsq.get(), (int64_t)batch * sizeof(double));
+    if (mode) {
+        add(SNAP_SUMSQ, 0, S.sumsq.get(), (int64_t)batch * (mode == 2 ? 2 : 1) * sizeof(double));
         add(SNAP_FRAME_INV, 0, S.frame_inv.get(), (int64_t)batch * ring * sizeof(float));
+        if (mode == 2) add(SNAP_FRAME_INV, 1, S.frame_c.get(), (int64_t)batch * ring * sizeof(float));
     }
     if (StreamState* ss = e->model->stream_state()) {
         for (size_t i = 0; i < ss->hist.size(); ++i) add(SNAP_HIST, (int32_t)i, ss->hist[i], (int64_t)ss->size_of.at(ss->hist[i]) * sizeof(float));
@@ -1357,8 +1410,9 @@ int se_stream_save(se_engine* e, se_stream_state* s, void* stream) {
         m.o_done = S.o_done;
         // only what a later launch can still read (stream_window.h): rows stored back to back, not at this engine's pitch
         m.keep = std::max(S.w0, stream_keep_from(g.n_fft, g.hop, S.t_done, S.n_total));
-        m.running = S.running ? 1 : 0;
-        m.ring = S.running ? S.ring : 0;
+        m.running = S.scale_mode();
+        m.ring = S.per_frame() ? S.ring : 0;
+        if (S.tracking) std::memcpy(&m.reserved[0], &S.tau, sizeof(float));
         const StreamState* ss = e->model->stream_state();
         const StreamSlots* sl = e->model->stream_slots();
         m.first = ss ? (ss->first ? 1 : 0) : 1;
@@ -1366,7 +1420,7 @@ int se_stream_save(se_engine* e, se_stream_state* s, void* stream) {
         const int live = m.n_total - m.keep;
         const int wcap = snap_window_cap(g);
         SE_CHECK(live >= 0 && live <= wcap, "se_stream_save: " + std::to_string(live) + " live input samples, more than a window and a hop");
-        const std::vector<EngSeg> eng = engine_segments(e, S.batch, S.running, S.ring);
+        const std::vector<EngSeg> eng = engine_segments(e, S.batch, S.scale_mode(), S.ring);
         for (const EngSeg& sg : eng) {
             SE_CHECK(sg.ptr && sg.seg.bytes >= 0 && (sg.seg.bytes & 3) == 0, "se_stream_save: a carried buffer is missing or of an odd size");
             m.segs.push_back(sg.seg);
@@ -1424,12 +1478,19 @@ int se_stream_restore(se_engine* e, const se_stream_state* cs, void* stream) {
         SE_CHECK(live <= snap_window_cap(g), fn + "more live input samples than a window and a hop");
         se_engine::Stream& S = e->strm;
         int ring = 0;
+        SE_CHECK(m.running >= 0 && m.running <= 2, fn + "unknown scale mode " + std::to_string(m.running) + " in the snapshot");
+        float tau = 0.f;
+        if (m.running == 2) {
+            std::memcpy(&tau, &m.reserved[0], sizeof(float));
+            SE_CHECK(std::isfinite(tau) && tau >= 0.f, fn + "the snapshot of a tracking-scale stream records a tau_samples that is not a finite number >= 0");
+            SE_CHECK(g.n_fft >= 2 * g.hop - 2, fn + "n_fft < 2 hop - 2: this front end cannot run a tracking scale");
+        }
         if (m.running) {
             int need = S.sumsq ? S.ring : 64;
             if (!S.sumsq)
                 while (need < e->plan_frames + 64) need <<= 1;
             SE_CHECK(m.ring >= need && (m.ring & (m.ring - 1)) == 0,
-                     fn + "the snapshot of a running-scale stream keeps 1 / c of " + std::to_string(m.ring) + " frames per row, this engine needs " +
+                     fn + "the snapshot of a " + (m.running == 2 ? "tracking" : "running") + "-scale stream keeps 1 / c of " + std::to_string(m.ring) + " frames per row, this engine needs " +
                          std::to_string(need) + " (planned for a larger max_samples)");
             ring = m.ring;
         }
@@ -1461,15 +1522,17 @@ int se_stream_restore(se_engine* e, const se_stream_state* cs, void* stream) {
         }
         if (!S.c) S.c.alloc(e->ctx.max_batch);
         if (m.running && (!S.sumsq || S.ring != ring)) {
-            if (!S.sumsq) S.sumsq.alloc(e->ctx.max_batch);
+            if (!S.sumsq) S.sumsq.alloc((size_t)2 * e->ctx.max_batch);
             S.frame_inv.alloc((size_t)e->ctx.max_batch * ring);
+            if (S.frame_c) S.frame_c.alloc((size_t)e->ctx.max_batch * ring);
             S.ring = ring;
         }
+        if (m.running == 2 && !S.frame_c) S.frame_c.alloc((size_t)e->ctx.max_batch * S.ring);
         // the model's state buffers: left where they are when they already have the snapshot's layout (two groups that alternate
         // on one engine), else made as a new stream makes them - the slots of the cLN networks in the recorded order and sizes,
         // which a stream creates lazily on its first chunk and checks on every later one
         if (StreamState* ss = e->model->stream_state()) {
-            if (ss->B != m.batch || !same_segs(engine_segments(e, m.batch, m.running != 0, ring), m.segs, nfix))
+            if (ss->B != m.batch || !same_segs(engine_segments(e, m.batch, m.running, ring), m.segs, nfix))
                 e->model->stream_begin(m.batch, m.max_chunk, st);
             ss->first = m.first != 0;
         } else if (StreamSlots* sl = e->model->stream_slots()) {
@@ -1488,14 +1551,14 @@ int se_stream_restore(se_engine* e, const se_stream_state* cs, void* stream) {
                 sl->B = m.batch;
             }
         }
-        const std::vector<EngSeg> eng = engine_segments(e, m.batch, m.running != 0, ring);
+        const std::vector<EngSeg> eng = engine_segments(e, m.batch, m.running, ring);
         // (a snapshot from before the first chunk into an engine whose slots exist: they were zeroed above and stay out of the copy)
         std::vector<EngSeg> dst;
         for (const EngSeg& sg : eng)
             if (!(sg.seg.kind == SNAP_SLOT && want_slots.empty())) dst.push_back(sg);
         SE_CHECK(same_segs(dst, m.segs, nfix),
                  fn + "the snapshot's state buffers do not have the sizes this engine's model keeps (weights of other shapes?); the handle's stream has ended");
-        S.start(m.batch, m.n_total, m.running != 0);
+        S.start(m.batch, m.n_total, m.running == 1, m.running == 2, tau, g.hop);
         S.t_done = m.t_done;
         S.o_done = m.o_done;
         S.w0 = sliding ? m.keep : 0;
@@ -1620,10 +1683,10 @@ void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream
     for (se_stream_state* p : parts) obj_wait(p, st);
     obj_wait(dst, st);
     // one block: GatherSeg[nseg] | long src_off[np][nseg] | const float* base[np] | int2 rowmap[Bd] | int part_B[np]
-    // (join: | int window row length[np] | int window column[np])
+    // (join: | int window row length[np] | int window column[np] | int ring rotation[np])
     const size_t o_off = (size_t)nseg * sizeof(GatherSeg), o_base = o_off + (size_t)np * nseg * sizeof(long),
                  o_map = o_base + (size_t)np * sizeof(float*), o_pb = o_map + (size_t)Bd * sizeof(int2), o_win = o_pb + (size_t)np * sizeof(int),
-                 total = o_win + (jp ? 2 * (size_t)np * sizeof(int) : 0);
+                 total = o_win + (jp ? 3 * (size_t)np * sizeof(int) : 0);
     auto& sd = *dst->side;
     SE_HIP(hipEventSynchronize(sd.gat_ev.get()));
     if (total > sd.gat_cap) {
@@ -1649,6 +1712,7 @@ void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream
             int* wi = reinterpret_cast<int*>(pin + o_win);
             wi[p] = parts[(size_t)p]->man.n_total - parts[(size_t)p]->man.keep;
             wi[np + p] = jp->col[(size_t)p];
+            wi[2 * np + p] = jp->rot[(size_t)p];
         }
     }
     std::memcpy(pin + o_map, rowmap.data(), (size_t)Bd * sizeof(int2));
@@ -1668,6 +1732,15 @@ void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream
         w.seg = nseg - 1;
         w.part_inner = reinterpret_cast<const int*>(dev + o_win);
         w.part_col = w.part_inner + np;
+        w.part_rot = w.part_inner + 2 * np;
+        // the per-frame rings of a tracking-scale group move with the frames (stream_join.h): the SNAP_FRAME_INV segments, side by side
+        for (int k = 0; k < nseg; ++k)
+            if (m.segs[(size_t)k].kind == SNAP_FRAME_INV && m.running == 2) {
+                SE_CHECK(tab[(size_t)k].inner == m.ring && (m.ring & (m.ring - 1)) == 0, fn + "per-frame ring of an odd length");
+                if (w.ring_hi == w.ring_lo) w.ring_lo = k, w.ring_hi = k + 1;
+                else if (k == w.ring_hi) w.ring_hi = k + 1;
+                else SE_CHECK(false, fn + "per-frame rings are not adjacent segments");
+            }
         launch_stream_state_join(a, w, tiles, st);
     } else {
         launch_stream_state_gather(a, tiles, st);

@@ -1326,6 +1326,101 @@ void launch_stream_rms(const float* wav, long pitch, int B, int n_total, int n_n
     SE_HIP(hipGetLastError());
 }
 
+// ---- tracking unit-RMS scale of a frame-online stream (se_stream_begin_tracking) ---------------------------------------
+// An exponentially forgetting estimate over whole hop blocks (include/se_engine.h has the definition): block k is the samples
+// [k hop, (k + 1) hop) with energy e_k, E_k = lambda E_{k-1} + e_k, W_k = lambda W_{k-1} + hop, and frame t is transformed under
+// c_t = sqrt(W / E) of the state behind block t + D - 1, D = (n_fft / 2) / hop - the last block that ends at or before the frame's
+// own last sample, so it is complete when the frame is released.  One workgroup per row:
+//   - the blocks this call completes, [k0, k1) = [(n_total - n_new) / hop, n_total / hop), are summed WHOLE out of the stream's
+//     window, one wave per block, lane l taking the samples l, l + 64, ... in float64, then a butterfly over the lanes: the order
+//     is a function of the block alone, so the states are bit-identical however the signal was split into pushes;
+//   - thread 0 runs the recursion over up to 256 block energies in LDS and leaves the state behind each of them there;
+//   - frame k - D + 1 takes the state behind block k.  Frames of [t0, t1) at or below k0 - D take the state the row arrived with
+//     (a push that ends on a block boundary completes the block one sample before it releases the frame); at the flush
+//     (`fin`) the n_total mod hop samples left are one last short block of weight r, and every frame behind it takes the last state.
+// c_t and 1 / c_t are both rounded from one float64 value into the two rings; c[b] is the scale of frame t1 - 1.
+__device__ __forceinline__ double track_scale(double E, double W) { return E > 1e-20 ? sqrt(W / E) : 1.0; }
+
+__global__ __launch_bounds__(256) void stream_track_kernel(const float* __restrict__ wav, long pitch, int hop, int D, int k0, int k1, int r,
+                                                           double lam, double* __restrict__ ew, float* __restrict__ c,
+                                                           float* __restrict__ frame_c, float* __restrict__ frame_inv, int ring, int t0,
+                                                           int t1, int w0) {
+    __shared__ double sh_e[256];
+    __shared__ double sh_E[257], sh_W[257];      // [0]: the state in front of the batch, [j + 1]: behind its block j
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* x = wav + (long)b * pitch - w0;      // column 0 of a row holds sample w0
+    float* fc = frame_c + (long)b * ring;
+    float* fi = frame_inv + (long)b * ring;
+    const int mask = ring - 1;
+    const int nb = k1 - k0 + (r > 0 ? 1 : 0);
+    if (tid == 0) {
+        sh_E[0] = ew[2 * b];
+        sh_W[0] = ew[2 * b + 1];
+    }
+    __syncthreads();
+    auto put = [&](int t, double cd) {
+        fc[t & mask] = (float)cd;
+        fi[t & mask] = (float)(1.0 / cd);
+        if (t == t1 - 1) c[b] = (float)cd;
+    };
+    {   // frames that take the state the row arrived with
+        const double cd = track_scale(sh_E[0], sh_W[0]);
+        for (int t = t0 + tid; t < t1 && t + D - 1 < k0; t += 256) put(t, cd);
+    }
+    for (int base = 0; base < nb; base += 256) {
+        const int m = min(256, nb - base);
+        for (int j = wave; j < m; j += 4) {
+            const int k = k0 + base + j, len = k < k1 ? hop : r;
+            const float* xb = x + (long)k * hop;
+            double s = 0.0;
+            for (int i = lane; i < len; i += 64) s += (double)xb[i] * xb[i];
+            for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+            if (lane == 0) sh_e[j] = s;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double E = sh_E[0], W = sh_W[0];
+            for (int j = 0; j < m; ++j) {
+                E = lam * E + sh_e[j];
+                W = lam * W + (double)(k0 + base + j < k1 ? hop : r);
+                sh_E[j + 1] = E;
+                sh_W[j + 1] = W;
+            }
+        }
+        __syncthreads();
+        for (int j = tid; j < m; j += 256) {
+            const int t = k0 + base + j - D + 1;
+            if (t >= t0 && t < t1) put(t, track_scale(sh_E[j + 1], sh_W[j + 1]));
+        }
+        __syncthreads();
+        if (tid == 0) {
+            sh_E[0] = sh_E[m];
+            sh_W[0] = sh_W[m];
+        }
+        __syncthreads();
+    }
+    {   // frames behind the last block there is (the flush)
+        const double cd = track_scale(sh_E[0], sh_W[0]);
+        for (int t = max(t0, k0 + nb - D + 1) + tid; t < t1; t += 256) put(t, cd);
+    }
+    if (tid == 0 && nb > 0) {
+        ew[2 * b] = sh_E[0];
+        ew[2 * b + 1] = sh_W[0];
+    }
+}
+void launch_stream_track(const StftGeom& g, const float* wav, long pitch, int B, int n_total, int n_new, bool fin, double lam, double* ew,
+                         float* c, float* frame_c, float* frame_inv, int ring, int t0, int t1, hipStream_t s, int w0) {
+    SE_CHECK(g.hop >= 1 && g.n_fft >= 2 * g.hop - 2, "launch_stream_track: the head of the incomplete block is kept only where n_fft >= 2 hop - 2");
+    SE_CHECK(n_new >= 0 && n_total >= n_new && !(fin && n_new != 0), "launch_stream_track: bad sample counts");
+    SE_CHECK(ring > 0 && (ring & (ring - 1)) == 0 && t0 >= 0 && t1 - t0 <= ring, "launch_stream_track: the released frames do not fit the ring");
+    const int k0 = (n_total - n_new) / g.hop, k1 = n_total / g.hop, r = fin ? n_total - k1 * g.hop : 0;
+    SE_CHECK((k1 == k0 && r == 0) || ((long)k0 * g.hop >= w0 && n_total - w0 <= pitch),
+             "launch_stream_track: a block to be summed starts below the sample origin");
+    hipLaunchKernelGGL(stream_track_kernel, dim3(B), dim3(256), 0, s, wav, pitch, g.hop, (g.n_fft / 2) / g.hop, k0, k1, r, lam, ew, c, frame_c,
+                       frame_inv, ring, t0, t1, w0);
+    SE_HIP(hipGetLastError());
+}
+
 // ---- sliding input window of a frame-online stream (SE_CFG_STREAM_SLIDING, stream_window.h) --------------------------------
 // The live tail of every row moves to column 0 of the OTHER buffer of the pair: source and destination never alias, so the
 // copy needs no order.  One float4 per thread, grid (segment of 256 float4, row).

@@ -119,16 +119,17 @@ void launch_rms_scale(const float* wav, int B, int L, long pitch, float* c_out, 
 }
 
 void launch_stft(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale,
-                 float p_in, float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0, int w0) {
+                 float p_in, float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0, int w0,
+                 const float* frame_c, int ring) {
     SE_CHECK(t_first >= 0 && t_first < T, "launch_stft: empty frame range");
     SE_CHECK(w0 >= 0 && (w0 == 0 || (long)t_first * g.hop - g.n_fft / 2 >= w0), "launch_stft: frames reach below the sample origin");
     SE_CHECK(g.n_fft == 512 || g.n_fft == 320, "unsupported n_fft (320 and 512 are the reference geometries)");
     StageScope prof(STAGE_STFT, s, 4.0 * L * B + (spec_ri ? 8.0 : 0.0) * g.F() * T * B + (mag ? 4.0 : 0.0) * g.F() * T * B);
-    launch_stft2(g, wav, pitch, B, L, Lpad, c_scale, p_in, spec_ri, mag, T, Tp, s, t_first, col0, w0);
+    launch_stft2(g, wav, pitch, B, L, Lpad, c_scale, p_in, spec_ri, mag, T, Tp, s, t_first, col0, w0, frame_c, ring);
     // (the record restates launch_stft2's selection from the arguments passed on: k_stft2.hip, 32 frames and 4 waves per block)
     if (std::vector<FeLaunchRec>* log = fe_launch_log()) {
         FeLaunchRec r;
-        r.kernel = "stft2"; r.N = g.n_fft; r.MAG = mag != nullptr; r.CP = p_in == 1.f ? 0 : (p_in == 0.5f ? 1 : 2);
+        r.kernel = "stft2"; r.N = g.n_fft; r.MAG = mag != nullptr; r.FSC = frame_c != nullptr; r.CP = p_in == 1.f ? 0 : (p_in == 0.5f ? 1 : 2);
         r.gx = (T - t_first + 31) / 32; r.gy = B; r.block = 256;
         r.shmem = (long)std::max((size_t)4 * g.n_fft * 8, (size_t)g.F() * 33 * 4);
         r.ragged = ragged_ctx() != nullptr;

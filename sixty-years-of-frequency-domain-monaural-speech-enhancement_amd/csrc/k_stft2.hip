@@ -24,6 +24,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 namespace se {
@@ -197,10 +198,17 @@ struct Stft2Args {
     int w0;      // sample origin: column 0 of `wav` holds the absolute sample w0 (0 offline; the sliding window of a stream)
 };
 
+struct Stft2ArgsF : Stft2Args {
+    const float* frame_c; int ring_mask;      // [B][ring_mask + 1]: frame t is scaled by frame_c[b][t & ring_mask]
+};
+
 // ------------------------------------------------------------------------------------------------ forward
 // CP: magnitude exponent of the decode script: 0 none (1.0), 1 square root (0.5, every script's compressed variant), 2 powf
-template <int N, bool MAG, int CP>
-__global__ __launch_bounds__(Shape<false>::NT) void stft2_kernel(const Stft2Args a) {
+// FSC: per-frame scales (streams on a tracking unit-RMS scale, se_stream_begin_tracking): frame t is scaled by
+// frame_c[b][t & ring_mask] in place of c_scale[b], in the fast path and in sample() - a kernel of its own (stft2f_kernel), so
+// that the common kernel keeps its registers and its code: every FSC statement sits behind `if constexpr`
+template <int N, bool MAG, int CP, bool FSC = false>
+__global__ __launch_bounds__(Shape<false>::NT) void stft2_kernel(const std::conditional_t<FSC, Stft2ArgsF, Stft2Args> a) {
     constexpr int NW = Shape<false>::NW, NT = Shape<false>::NT, NQ = Shape<false>::NQ, KSTEP = Shape<false>::KSTEP;
     constexpr int F = N / 2 + 1, R1 = N / 64, NB = (F + 63) / 64;     // NB bins per lane (k = lane + 64 m)
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -236,13 +244,13 @@ __global__ __launch_bounds__(Shape<false>::NT) void stft2_kernel(const Stft2Args
     // sample positions below are absolute (reflection, zero pad and the fast path's test are those of origin 0); every read is
     // x[idx] = wav[idx - w0] - a sliding stream window never holds less than the frames of this launch reach (stream_window.h)
     const float* x = a.wav + (long)b * a.pitch - a.w0;
-    auto sample = [&](int t, int n, float w) {
+    auto sample = [&](int t, int n, float w, float cc) {      // (cc: the frame's scale - c, or under FSC its own)
         float v = 0.f;
         if (t < Tb) {
             int idx = t * a.hop + n - N / 2;
             if (idx < 0) idx = -idx;
             if (idx >= Lpad) idx = 2 * (Lpad - 1) - idx;
-            if (idx >= 0 && idx < L) v = x[idx] * c * w;
+            if (idx >= 0 && idx < L) v = x[idx] * cc * w;
         }
         return v;
     };
@@ -254,16 +262,26 @@ __global__ __launch_bounds__(Shape<false>::NT) void stft2_kernel(const Stft2Args
         bool nz0 = false, nz1 = false;
         // frames wholly inside the clip (all but the first two and the last few of a row): no reflection, no bounds - the
         // wave-uniform fast path loads x[t * hop - N/2 + lane + 64 j] with immediate offsets
+        float c0 = c, c1 = c;
+        if constexpr (FSC) {      // the frames' own scales (a slot of a frame that does not exist holds a finite leftover and scales zeros)
+            const float* fcr = a.frame_c + (long)b * (a.ring_mask + 1);
+            c0 = fcr[t & a.ring_mask];
+            c1 = fcr[(t + 1) & a.ring_mask];
+        }
         if (t + 1 < Tb && t * a.hop >= N / 2 && (t + 1) * a.hop + N / 2 <= L) {
             const float* p0 = x + (t * a.hop - N / 2 + lane);
 #pragma unroll
             for (int j = 0; j < R1; ++j) {
-                const float cw = c * wn[j];
-                z[j] = make_float2(p0[64 * j] * cw, p0[a.hop + 64 * j] * cw);
+                if constexpr (FSC) {
+                    z[j] = make_float2(p0[64 * j] * (c0 * wn[j]), p0[a.hop + 64 * j] * (c1 * wn[j]));
+                } else {
+                    const float cw = c * wn[j];
+                    z[j] = make_float2(p0[64 * j] * cw, p0[a.hop + 64 * j] * cw);
+                }
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < R1; ++j) z[j] = make_float2(sample(t, lane + 64 * j, wn[j]), sample(t + 1, lane + 64 * j, wn[j]));
+            for (int j = 0; j < R1; ++j) z[j] = make_float2(sample(t, lane + 64 * j, wn[j], c0), sample(t + 1, lane + 64 * j, wn[j], c1));
         }
 #pragma unroll
         for (int j = 0; j < R1; ++j) {
@@ -528,17 +546,24 @@ void set_lds(Kern kernel, size_t bytes) {
 }  // namespace
 
 void launch_stft2(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale, float p_in,
-                  float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0, int w0) {
+                  float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0, int w0, const float* frame_c, int ring) {
     const Ragged* rg = ragged_ctx();
+    SE_CHECK(!frame_c || (ring > 0 && (ring & (ring - 1)) == 0), "launch_stft2: per-frame scales live in a power-of-two ring");
     Stft2Args a{wav, pitch, B, L, Lpad, c_scale, p_in, spec_ri, mag, T, Tp, g.hop,
                 rg ? rg->len : nullptr, rg ? rg->lpad : nullptr, rg ? rg->tlen : nullptr, t_first, col0,
                 fft_table(g.n_fft, g.win), w0};
     dim3 grid((T - t_first + NFB - 1) / NFB, B);
     // (every variant stays below the 64 KB of LDS a kernel may use without raising its limit)
     const int cp = p_in == 1.f ? 0 : (p_in == 0.5f ? 1 : 2);
+    Stft2ArgsF af;
+    static_cast<Stft2Args&>(af) = a;
+    af.frame_c = frame_c;
+    af.ring_mask = frame_c ? ring - 1 : 0;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(Shape<false>::NT), g.n_fft == 512 ? stft2_lds<512>() : stft2_lds<320>(), s, a); };
-#define SE_STFT2_CASE(NN, MM) \
-    (cp == 0 ? go(stft2_kernel<NN, MM, 0>) : cp == 1 ? go(stft2_kernel<NN, MM, 1>) : go(stft2_kernel<NN, MM, 2>))
+    auto gof = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(Shape<false>::NT), g.n_fft == 512 ? stft2_lds<512>() : stft2_lds<320>(), s, af); };
+#define SE_STFT2_CASE(NN, MM)                                                                                                      \
+    (frame_c ? (cp == 0 ? gof(stft2_kernel<NN, MM, 0, true>) : cp == 1 ? gof(stft2_kernel<NN, MM, 1, true>) : gof(stft2_kernel<NN, MM, 2, true>)) \
+             : (cp == 0 ? go(stft2_kernel<NN, MM, 0>) : cp == 1 ? go(stft2_kernel<NN, MM, 1>) : go(stft2_kernel<NN, MM, 2>)))
     if (g.n_fft == 512) {
         if (mag) SE_STFT2_CASE(512, true);
         else SE_STFT2_CASE(512, false);

@@ -11,6 +11,10 @@ struct JoinWindow {
     int seg = -1;
     const int* part_inner = nullptr;
     const int* part_col = nullptr;
+    // tracking-scale streams (stream_join.h): segments [ring_lo, ring_hi) are per-frame rings [B][inner], inner a power of two, and
+    // entry i of a row of part p comes from its entry (i - part_rot[p]) & (inner - 1); ring_lo >= ring_hi: none
+    int ring_lo = 0, ring_hi = 0;
+    const int* part_rot = nullptr;
 };
 void launch_stream_state_join(const GatherArgs& a, const JoinWindow& w, long tiles, hipStream_t s);
 

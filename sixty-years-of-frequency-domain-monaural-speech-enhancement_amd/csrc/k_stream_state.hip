@@ -122,14 +122,16 @@ __device__ __forceinline__ void state_gather_tile(const GatherArgs& a, const Joi
     if (inner == 0 || j0 >= ((n + 3u) & ~3u)) return;
     const long* __restrict__ off = a.src_off + lo;
     const bool window = JOIN && lo == w.seg;
+    const bool rotate = JOIN && lo >= w.ring_lo && lo < w.ring_hi;
     auto source = [&](unsigned j) -> const float* {
         const unsigned o = j / run, rem = j - o * run, bd = rem / inner, i = rem - bd * inner;
         const int2 pr = a.rowmap[bd];
         const float* base = a.part_base[pr.x] + off[(long)pr.x * a.nseg];
         if (window) return base + ((long)o * a.part_B[pr.x] + pr.y) * w.part_inner[pr.x] + w.part_col[pr.x] + i;
+        if (rotate) return base + ((long)o * a.part_B[pr.x] + pr.y) * inner + ((i - (unsigned)w.part_rot[pr.x]) & (inner - 1u));
         return base + ((long)o * a.part_B[pr.x] + pr.y) * inner + i;
     };
-    if ((inner & 3u) == 0 && !window) {
+    if ((inner & 3u) == 0 && !window && !rotate) {
         for (unsigned q = threadIdx.x; q < STATE_TILE / 4; q += 256) {
             const unsigned j = j0 + 4 * q;
             if (j >= n) break;
@@ -160,6 +162,7 @@ void launch_stream_state_gather(const GatherArgs& a, long tiles, hipStream_t s) 
 void launch_stream_state_join(const GatherArgs& a, const JoinWindow& w, long tiles, hipStream_t s) {
     SE_CHECK(a.nseg >= 1 && a.Bd >= 1 && tiles >= 0 && tiles < (1L << 31), "launch_stream_state_join: bad table");
     SE_CHECK(w.seg >= 0 && w.seg < a.nseg && w.part_inner && w.part_col, "launch_stream_state_join: no window segment");
+    SE_CHECK(w.ring_lo >= w.ring_hi || (w.ring_lo >= 0 && w.ring_hi <= a.nseg && w.part_rot), "launch_stream_state_join: bad ring segments");
     if (tiles == 0) return;
     hipLaunchKernelGGL(stream_state_join_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a, w);
     SE_HIP(hipGetLastError());

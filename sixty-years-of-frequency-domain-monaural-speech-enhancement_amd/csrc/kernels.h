@@ -73,7 +73,10 @@ void launch_rms_scale(const float* wav, int B, int L, long pitch, float* c_out, 
 // w0 (sliding stream windows, stream_window.h): column 0 of a wav row holds the absolute sample w0 - L, Lpad and the frame
 // numbers stay absolute, and no frame of the launch may start below w0.
 void launch_stft(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale,
-                 float p_in, float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first = 0, int col0 = 0, int w0 = 0);
+                 float p_in, float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first = 0, int col0 = 0, int w0 = 0,
+                 const float* frame_c = nullptr, int ring = 0);
+// frame_c (optional, [B][ring], ring a power of two): frame t is scaled by frame_c[b][t % ring] in place of c_scale[b] - streams on
+// a TRACKING unit-RMS scale (se_stream_begin_tracking), whose every frame has a scale of its own; a kernel variant of its own
 
 // Inverse: spec_ri [B][2][F][Tp] -> windowed frames [B][T][n_fft] (scratch) -> overlap-add, divide by the
 // overlap-added squared window, drop n_fft/2 head, write Lout samples, divide by c.
@@ -90,6 +93,12 @@ void launch_istft(const StftGeom& g, const float* spec_ri, int B, int T, int Tp,
 // sqrt(n_total / sumsq[b]), frames [t0, t1) get 1 / c[b] in the ring frame_inv [B][ring]; w0: the sample origin of wav
 void launch_stream_rms(const float* wav, long pitch, int B, int n_total, int n_new, double* sumsq, float* c, float* frame_inv,
                        int ring, int t0, int t1, hipStream_t s, int w0 = 0);
+// tracking unit-RMS scale of frame-online streams (k_misc.hip, the definition is in include/se_engine.h): the hop blocks that the
+// n_new newest samples complete are summed whole, ew[b] = (E, W) follows E = lam E + e_k, W = lam W + hop over them, frames
+// [t0, t1) get c_t in the ring frame_c and 1 / c_t in the ring frame_inv (both [B][ring]), c[b] the scale of frame t1 - 1.
+// fin (the flush, n_new == 0): the n_total % hop samples left count as one last short block
+void launch_stream_track(const StftGeom& g, const float* wav, long pitch, int B, int n_total, int n_new, bool fin, double lam, double* ew,
+                         float* c, float* frame_c, float* frame_inv, int ring, int t0, int t1, hipStream_t s, int w0 = 0);
 // sliding stream window: dst[b][i] = src[b][shift + i], i < n, for B rows of `pitch` floats in two DIFFERENT buffers (the
 // engine ping-pongs between them).  shift, n and pitch are multiples of 4 and both bases 16 B aligned: 16 B accesses only.
 void launch_stream_slide(const float* src, float* dst, long pitch, int B, int shift, int n, hipStream_t s);
@@ -97,7 +106,8 @@ void launch_stream_slide(const float* src, float* dst, long pitch, int B, int sh
 // the kernels behind the two launchers above (k_stft2.hip): FFT points in registers, two LDS exchanges, 32-frame tiles
 // moved through LDS so that the [F][T]-major spectrogram is touched in 128 B runs
 void launch_stft2(const StftGeom& g, const float* wav, long pitch, int B, int L, int Lpad, const float* c_scale, float p_in,
-                  float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0, int w0 = 0);
+                  float* spec_ri, float* mag, int T, int Tp, hipStream_t s, int t_first, int col0, int w0 = 0,
+                  const float* frame_c = nullptr, int ring = 0);
 void launch_istft2(const StftGeom& g, const float* spec_ri, int B, int T, int Tp, const float* c_scale, float* wav_out,
                    long out_pitch, int Lout, hipStream_t s, int t_off, int t_lo, int o_lo, const float* frame_inv = nullptr,
                    int ring = 0);

@@ -45,8 +45,34 @@ inline int64_t snap_gcd(int64_t a, int64_t b) { return b == 0 ? a : snap_gcd(b, 
 struct JoinPlan {
     std::vector<int64_t> shift;
     std::vector<int32_t> col;
+    std::vector<int32_t> rot;      // tracking scale: ring positions part p's per-frame rings move up by, in [0, ring)
     int32_t keep = 0, live = 0;
 };
+
+// The tracking scale (se_stream_begin_tracking) in a join.  Its state per row is (E, W) and two rings, c_t and 1 / c_t of frame t at
+// position t & (ring - 1).  (E, W) are sums over the row's own past, weighted by the distance in blocks from the newest block: no
+// absolute position enters, and the shift is a whole number of hops, so the blocks of the rebased row are the blocks it had.  The
+// kernel finds the blocks a push completes from n_total alone ([(n_total - n_new) / hop, n_total / hop)), which the manifest rebases.
+// The rings ARE indexed by the absolute frame: frame t of the part is frame t + s / hop of the result (s the shift in samples), so
+// entry i of a rebased ring row is entry (i - s / hop) mod ring of the part's - a rotation, applied to whole rows by the join
+// kernel.  Only some entries are live, i.e. read again: the forward transform reads c_t of frames >= t_done, all of them written
+// by a later push before they are read; the inverse reads 1 / c_t of the frames that still cover an output sample to be written,
+// o >= o_done: t hop + n_fft > o_done + n_fft / 2, i.e. t >= floor((o_done - n_fft / 2) / hop) + 1 (clamped to 0), up to t_done - 1.
+// That is fewer than n_fft / hop + look-ahead + 1 entries of a ring of >= 64, so rotating whole rows moves them all and nothing else
+// that matters.
+// rotation of a ring of `ring` entries (a power of two) by a shift of s samples, s a multiple of hop of either sign
+inline int32_t snap_ring_rot(int64_t s, int32_t hop, int32_t ring) {
+    const int64_t f = s / hop;
+    return (int32_t)(((f % ring) + ring) % ring);
+}
+// the source position of entry i of a rotated ring row
+inline int32_t snap_ring_src(int32_t i, int32_t rot, int32_t ring) { return (i - rot) & (ring - 1); }
+// frames [lo, t_done) of a stream are the ones whose 1 / c_t the inverse transform still reads
+inline int64_t snap_ring_live_from(int64_t o_done, int32_t n_fft, int32_t hop) {
+    const int64_t x = o_done - n_fft / 2;      // floor division of a value that may be negative
+    const int64_t q = x >= 0 ? x / hop : -((-x + hop - 1) / hop);
+    return std::max<int64_t>(0, q + 1);
+}
 
 // "" and the plan, or why the parts cannot be joined.  lag: the model's stream_lag(); counts_frames: empty, or what in the model's
 // state counts frames (such a model is refused: its state cannot be rebased)
@@ -62,8 +88,10 @@ inline std::string snap_join_plan(const std::vector<const SnapManifest*>& parts,
     bool moved = false;
     for (size_t p = 0; p < parts.size(); ++p) {
         const SnapManifest& b = *parts[p];
-        if (b.running)
+        if (b.running == 1)
             return at(p) + " is a running-scale stream: its ring of 1 / c per frame is indexed by the absolute frame (running 1)";
+        if (b.running == 2 && (b.ring < 1 || (b.ring & (b.ring - 1)) != 0))
+            return at(p) + " is a tracking-scale stream whose ring length " + std::to_string(b.ring) + " is no power of two";
         if (p > 0) {
             const std::string why = snap_concat_differs(a, b, false);
             if (!why.empty()) return "parts[0] and " + at(p) + " differ: " + why;
@@ -78,6 +106,7 @@ inline std::string snap_join_plan(const std::vector<const SnapManifest*>& parts,
         if (oa != ob) return "parts[0] and " + at(p) + " are out of phase: n_total - o_done " + vs(oa, ob);
         moved = moved || s != 0;
         out.shift.push_back(s);
+        out.rot.push_back(b.running == 2 ? snap_ring_rot(s, a.hop, b.ring) : 0);
     }
     if (moved) {
         const int need = stream_left_edge_frames(a.n_fft, a.hop, lag);

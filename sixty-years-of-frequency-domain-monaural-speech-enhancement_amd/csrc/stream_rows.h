@@ -6,7 +6,8 @@
 //   conv history [B][rows][HC]              (1, rows * HC)         LSTM state [H][B]                 (H, 1)
 //   DCCRN's complex LSTM [2][128][2 B]      (2 * 128 * 2, 1)       a per-sequence state [H][F][B]    (H * F, 1)
 //   a call-order slot [B][row bytes]        (1, row bytes / 4)     sumsq [B] doubles                 (1, 2)
-//   frame_inv [B][ring]                     (1, ring)              the window [B][n_total - keep]    (1, n_total - keep)
+//   (E, W) [B][2] doubles (tracking scale)  (1, 4)
+//   frame_inv, frame_c [B][ring]            (1, ring)              the window [B][n_total - keep]    (1, n_total - keep)
 // The layouts are not part of a snapshot: the model declares them where it allocates the buffers (rnn.h StreamState::begin,
 // kernels.h StreamCtx::slot), and an engine of the snapshot's kind is asked for them when rows are selected or joined.
 #pragma once
@@ -28,7 +29,7 @@ struct StateLayout {
 inline bool snap_engine_layout(const SnapManifest& m, const SnapSeg& s, RowLayout& l) {
     switch (s.kind) {
         case SNAP_C: l = {1, 1}; return true;
-        case SNAP_SUMSQ: l = {1, 2}; return true;
+        case SNAP_SUMSQ: l = {1, m.running == 2 ? 4 : 2}; return true;      // (tracking scale: (E, W) per row)
         case SNAP_FRAME_INV: l = {1, m.ring}; return true;
         case SNAP_WINDOW: l = {1, (int64_t)m.n_total - m.keep}; return true;
         default: return false;
@@ -102,6 +103,12 @@ inline std::string snap_concat_differs(const SnapManifest& a, const SnapManifest
     }
     SE_SNAP_SAME(running) SE_SNAP_SAME(ring) SE_SNAP_SAME(first)
 #undef SE_SNAP_SAME
+    if (a.running == 2 && a.reserved[0] != b.reserved[0]) {      // the float bits of se_stream_begin_tracking's time constant
+        float ta, tb;
+        std::memcpy(&ta, &a.reserved[0], sizeof(float));
+        std::memcpy(&tb, &b.reserved[0], sizeof(float));
+        return "tau_samples " + std::to_string(ta) + " vs " + std::to_string(tb);
+    }
     if (a.p_in != b.p_in) return "p_in " + std::to_string(a.p_in) + " vs " + std::to_string(b.p_in);
     if (a.p_out != b.p_out) return "p_out " + std::to_string(a.p_out) + " vs " + std::to_string(b.p_out);
     if ((a.state_B != 0) != (b.state_B != 0)) return ne("state_B", a.state_B, b.state_B);

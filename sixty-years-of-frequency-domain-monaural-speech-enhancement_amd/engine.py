@@ -351,9 +351,12 @@ class Engine:
         return self._rows_call('enhance_long_ragged', wav, lengths, out, max_chunk_frames)
 
     # ------------------------------------------------------------------ frame-online decoding
-    def stream_begin(self, batch, c=None, max_chunk_frames=16, running_rms=False):
+    def stream_begin(self, batch, c=None, max_chunk_frames=16, running_rms=False, tracking_rms=None):
         """Start `batch` parallel streams; c: per-stream scale tensor (what rms_scale() returns offline) or None = 1.
-        running_rms=True: no scale from the caller - the engine keeps a running unit-RMS estimate (se_stream_begin_running)."""
+        running_rms=True: no scale from the caller - the engine keeps a running unit-RMS estimate (se_stream_begin_running).
+        tracking_rms=<seconds>: a unit-RMS estimate per frame that forgets with that time constant (se_stream_begin_tracking; the
+        seconds are converted at 16 kHz, 0.0 = never forget, None = off) - what a live caller starts with: it follows the level, does
+        not depend on how the signal is split into pushes, and such streams can be joined."""
         batch = int(batch)
         if not 1 <= batch <= self.max_batch:
             raise EngineError(f"stream_begin: batch {batch} outside 1..max_batch ({self.max_batch})")
@@ -361,6 +364,15 @@ class Engine:
             self._check_tensor(c, 'stream_begin c')
             if not c.is_contiguous() or c.numel() < batch:        # the engine copies `batch` floats from c
                 raise EngineError(f"stream_begin c: need a contiguous tensor of >= {batch} scales, got shape {tuple(c.shape)}")
+        if tracking_rms is not None:
+            if c is not None:
+                raise EngineError("stream_begin: tracking_rms and a caller-provided scale exclude each other")
+            if running_rms:
+                raise EngineError("stream_begin: tracking_rms and running_rms=True exclude each other")
+            self._stream_batch = 0
+            self._check(self._lib.se_stream_begin_tracking(self._h, batch, max_chunk_frames, float(tracking_rms) * 16000.0, self._stream()))
+            self._stream_batch = batch
+            return
         self._stream_batch = 0
         if running_rms:
             if c is not None:
@@ -371,6 +383,19 @@ class Engine:
         self._check(self._lib.se_stream_begin(self._h, batch, max_chunk_frames,
                                               C.c_void_p(c.data_ptr()) if c is not None else None, self._stream()))
         self._stream_batch = batch
+
+    def stream_scale(self):
+        """The scale of the most recently released frame of every stream, a float32 tensor [batch] (se_stream_scale): the caller's c,
+        the running scale's current c, the tracking scale's c_t; 1 before any frame."""
+        import torch
+        if self._closed():
+            raise EngineError("stream_scale: the engine is closed")
+        # (room for max_batch rows: the engine copies the rows of ITS stream, and refuses by itself when it has none)
+        out = torch.empty((self.max_batch,), dtype=torch.float32, device=torch.device('cuda', self.device))
+        self._check(self._lib.se_stream_scale(self._h, C.c_void_p(out.data_ptr()), self._stream()))
+        if not self._stream_batch:       # a stream this object did not begin (a begin that was refused leaves the engine's as it was)
+            raise EngineError("stream_scale without stream_begin")
+        return out[:self._stream_batch]
 
     def stream_push(self, wav):
         """wav [batch, n_new] -> the output samples that became final, [batch, n_out] (n_out may be 0)."""

@@ -174,7 +174,7 @@ def source_samples_until_joinable(stream, group):
 class SourceRateStream:
     """`SourceRateStream(model.engine, 48000)`: `begin(batch, ...)`, `push(x)` with x [batch, n <= max_push] at sr_in ->
     enhanced 16 kHz samples [batch, n_out] (n_out may be 0), `flush()` -> the rest.  `begin` takes what `Engine.stream_begin`
-    takes: a per-stream scale `c` (of the 16 kHz signal, e.g. from a calibration run) or `running_rms=True`.
+    takes: a per-stream scale `c` (of the 16 kHz signal, e.g. from a calibration run) or `running_rms=True`, or `tracking_rms=<seconds>` (of 16 kHz time).
     `save()` / `restore()` park and resume the stream as `Engine.stream_save` / `stream_restore` do for a 16 kHz one: a
     `SourceStreamSnapshot` holds the engine's stream and the resampler's filter history and read position, so groups fed at the
     source's rate can share one engine and one `SourceRateStream` by turns (restore -> push -> save per group).  Parked groups of an
@@ -186,9 +186,9 @@ class SourceRateStream:
         self.resampler = StreamResampler(sr_in, sr_out, max_batch=engine.max_batch, max_push=max_push, device=engine.device)
         self._batch = 0
 
-    def begin(self, batch, c=None, max_chunk_frames=16, running_rms=False):
+    def begin(self, batch, c=None, max_chunk_frames=16, running_rms=False, tracking_rms=None):
         self._batch = 0
-        self.engine.stream_begin(batch, c=c, max_chunk_frames=max_chunk_frames, running_rms=running_rms)
+        self.engine.stream_begin(batch, c=c, max_chunk_frames=max_chunk_frames, running_rms=running_rms, tracking_rms=tracking_rms)
         self.resampler.begin(batch)
         self._batch = int(batch)
 

@@ -302,7 +302,15 @@ def main():
     ap.add_argument('--source-rate', type=int, default=0, help='push at this sample rate through SourceRateStream (0: push 16 kHz samples)')
     ap.add_argument('--swap', action='store_true', help='also time two groups alternating on the engine: restore -> push -> save per push')
     ap.add_argument('--staggered', type=int, default=0, help='N callers one hop apart: by turns at batch 1 against joined into one group')
+    ap.add_argument('--tracking', type=float, default=None, metavar='SECONDS',
+                    help='begin on the tracking unit-RMS scale with this time constant (0: never forget) instead of a fixed scale')
+    ap.add_argument('--running', action='store_true', help='begin on the running unit-RMS scale instead of a fixed scale')
     a = ap.parse_args()
+    if (a.tracking is not None or a.running) and (a.swap or a.staggered or a.source_rate):
+        ap.error('--tracking / --running time the plain push loop only: not with --swap, --staggered or --source-rate')
+    if a.tracking is not None and a.running:
+        ap.error('--tracking and --running exclude each other')
+    scale_kw = {'tracking_rms': a.tracking} if a.tracking is not None else {'running_rms': True} if a.running else None
     if a.staggered:
         for name in (a.models or 'crn,dccrn').split(','):
             if a.source_rate:
@@ -327,7 +335,7 @@ def main():
                 piece = chunk * hop
                 times = []
                 for rep in range(2):           # first pass warms up (lazy state slots, kernel attributes)
-                    eng.stream_begin(B, c=c, max_chunk_frames=chunk)
+                    eng.stream_begin(B, max_chunk_frames=chunk, **(scale_kw or {'c': c}))
                     times, enq = [], []
                     for p in range(0, L - piece + 1, piece):
                         torch.cuda.synchronize()
@@ -346,6 +354,8 @@ def main():
                              'pushes': len(times[4:]), 'mean_ms': round(float(np.mean(times[4:])) * 1e3, 3)}
                 if a.swap:
                     extra.update(time_swap(eng, x, c, B, chunk, piece, L))
+                if scale_kw:
+                    extra['scale'] = 'tracking %g s' % a.tracking if a.tracking is not None else 'running'
                 print(json.dumps({'model': name, 'streams': B, 'frames_per_push': chunk, 'ms_per_push': round(t * 1e3, 3), **extra,
                                   'p95_ms': round(float(np.percentile(times[4:], 95)) * 1e3, 3),
                                   'p05_ms': round(float(np.percentile(times[4:], 5)) * 1e3, 3),
