@@ -4,6 +4,7 @@
 #include "model.h"
 #include "resampler.h"
 #include "rnn.h"
+#include "batch_parts.h"
 #include "stream_manifest.h"
 #include "k_stream_state.h"
 #include "stream_join.h"
@@ -57,8 +58,16 @@ struct se_engine {
     // rows' own).  Not under the profiler (per-launch durations of concurrent launches are not what a roofline prices), not
     // for graph replay, ragged or frame-online calls.  SE_BATCH_SPLIT=0 / 1: off / on for every model.
     // (Uformer and DPCRN: THREE parts - + 1.5 % over two; CTSNet and TaylorSENet: two - a third loses for TaylorSENet)
-    static constexpr int MAX_TWINS = 2;
+    // DCCRN (and its causal-decoder configuration): two equal halves, + 1.8 % at batch 256 (profiles/dccrn_split.md).  Its conv
+    // launches drain through a partly filled last round each, and the other half's launches fill it.  The forms meant to put one
+    // part's LSTM section under the other part's convs were measured and lost to equal halves: unequal parts (SE_BATCH_LEAD) do hide
+    // all of the recurrence (exposed 2.3 -> 0 ms in a kernel trace) but the smaller part ends at 3/4 of the step and the larger one
+    // runs the rest alone, without a neighbour to fill its tails; a lower-priority twin stream hid it too and ended level, and still
+    // lost 0.3 ms - the recurrence launches stretch from 1.1 to 1.6 ... 2.1 ms beside conv waves and slow those down for as long; three
+    // parts lose more.  How a batch is cut is batch_parts.h; SE_BATCH_PARTS=1..3 and SE_BATCH_LEAD=4..12 (8: equal) reach the other cuts.
+    static constexpr int MAX_TWINS = BATCH_PARTS_MAX - 1;
     int ntwins = 0;
+    int split_lead = BATCH_LEAD_EQUAL;           // batch_parts.h: the first part's share of a split call
     std::unique_ptr<EngineCtx> ctx2[MAX_TWINS];
     std::unique_ptr<Model> twin[MAX_TWINS];      // (behind ctx2: the models go before their contexts)
     Event ev_tfork, ev_tjoin[MAX_TWINS];
@@ -324,15 +333,21 @@ int se_engine_create(const se_config* cfg, se_engine** out) {
             e->ctx.geom = StftGeom{cfg->n_fft, cfg->hop > 0 ? cfg->hop : e->ctx.geom.hop, cfg->win > 0 ? cfg->win : cfg->n_fft};
         }
         static const int split_env = getenv("SE_BATCH_SPLIT") ? atoi(getenv("SE_BATCH_SPLIT")) : -1;
+        static const int parts_env = getenv("SE_BATCH_PARTS") ? atoi(getenv("SE_BATCH_PARTS")) : 0;
+        static const int lead_env = getenv("SE_BATCH_LEAD") ? atoi(getenv("SE_BATCH_LEAD")) : 0;
         const bool split = split_env >= 0 ? split_env != 0
                                           : (cfg->model == SE_MODEL_UFORMER || cfg->model == SE_MODEL_DPCRN || cfg->model == SE_MODEL_CTSNET ||
-                                             cfg->model == SE_MODEL_TAYLORSENET);
-        if (split && e->ctx.max_batch >= 64) {
-            const int parts = (cfg->model == SE_MODEL_UFORMER || cfg->model == SE_MODEL_DPCRN) ? 3 : 2;
+                                             cfg->model == SE_MODEL_TAYLORSENET || cfg->model == SE_MODEL_DCCRN);
+        if (split && e->ctx.max_batch >= BATCH_SPLIT_MIN) {
+            const int parts = parts_env >= 1 && parts_env <= BATCH_PARTS_MAX ? parts_env
+                              : (cfg->model == SE_MODEL_UFORMER || cfg->model == SE_MODEL_DPCRN) ? 3 : 2;
             e->ntwins = parts - 1;
+            e->split_lead = lead_env >= BATCH_LEAD_MIN && lead_env <= BATCH_LEAD_MAX ? lead_env : BATCH_LEAD_EQUAL;
             for (int i = 0; i < e->ntwins; ++i) {
                 e->ctx2[i].reset(new EngineCtx());
-                e->ctx2[i]->max_batch = (e->ctx.max_batch + i + 1) / (i + 2);      // the first: a half (two-part calls), the second: a third
+                // equal parts: the first twin a half (two-part calls), the second a third; unequal: the largest part any call hands it
+                e->ctx2[i]->max_batch = e->split_lead == BATCH_LEAD_EQUAL ? (e->ctx.max_batch + i + 1) / (i + 2)
+                                                                          : std::max(1, batch_parts_twin_rows(e->ctx.max_batch, e->ntwins, e->split_lead, i));
                 e->ctx2[i]->max_samples = e->ctx.max_samples;
                 e->ctx2[i]->p_in = e->ctx.p_in;
                 e->ctx2[i]->p_out = e->ctx.p_out;
@@ -526,10 +541,9 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
         const bool want_graph = (graphs_env >= 0 ? graphs_env != 0 : (e->cfg.flags & SE_CFG_GRAPHS) != 0) && !e->ctx.prof.on &&
                                 e->model->graph_capturable();
         if (!want_graph) {
-            if (e->ntwins > 0 && !e->ctx.prof.on && batch >= 64) {
-                // three parts from 192 clips on where the model has them (at 64 clips a third part loses: DPCRN - 3 %), else two
-                const int parts = (e->ntwins >= 2 && batch >= 192) ? 3 : 2;
-                const int Bp = (batch + parts - 1) / parts;           // rows per part (the last part may be shorter)
+            // (batch_parts.h: three parts from 192 clips on where the model has them, else two; equal or unequal by split_lead)
+            const BatchParts bp = e->ctx.prof.on ? BatchParts() : batch_parts_cut(batch, batch_parts_count(batch, e->ntwins), e->split_lead);
+            if (bp.n > 1) {
                 struct Active {
                     Active() { batch_split_active() = true; }
                     ~Active() { batch_split_active() = false; }
@@ -548,9 +562,9 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
                     }
                 } join{e, st};
                 SE_HIP(hipEventRecord(e->ev_tfork.get(), st));
-                for (int i = 0; i < parts - 1; ++i) {
-                    const int r0 = (i + 1) * Bp, nr = std::min(Bp, batch - r0);
-                    if (nr <= 0) break;
+                for (int i = 0; i < bp.n - 1; ++i) {
+                    const int r0 = bp.r0[i + 1], nr = bp.rows[i + 1];
+                    SE_CHECK(nr <= e->ctx2[i]->max_batch, "a part of the batch exceeds its instance's workspace");
                     hipStream_t s2 = twin_stream(e->cfg.device, i);
                     SE_HIP(hipStreamWaitEvent(s2, e->ev_tfork.get(), 0));
                     e->twin[i]->enhance(wav_in_dev + (size_t)r0 * in_pitch, in_pitch, nr, n_samples, wav_out_dev + (size_t)r0 * out_pitch,
@@ -558,7 +572,7 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
                     SE_HIP(hipEventRecord(e->ev_tjoin[i].get(), s2));
                     join.n = i + 1;
                 }
-                e->model->enhance(wav_in_dev, in_pitch, std::min(Bp, batch), n_samples, wav_out_dev, out_pitch, st);
+                e->model->enhance(wav_in_dev, in_pitch, bp.rows[0], n_samples, wav_out_dev, out_pitch, st);
                 return;
             }
             e->model->enhance(wav_in_dev, in_pitch, batch, n_samples, wav_out_dev, out_pitch, st);
