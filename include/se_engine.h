@@ -104,6 +104,18 @@ enum se_model_id {
  * size, cap on max_chunk_frames).  Any model that streams, se_stream_begin and se_stream_begin_running alike; the offline
  * calls are not affected, and a model that cannot stream still cannot. */
 #define SE_CFG_STREAM_SLIDING (1 << 17)
+/* SE_MODEL_DCCRN with the look-ahead decoder (without SE_CFG_DCCRN_CAUSAL_DEC) in se_enhance_long_ragged: the engine hands the
+ * rows' whole-clip frame counts to the network, and every chunk of the window walk clears the columns at or past each row's own
+ * last frame behind the encoder layers, the LSTM core and every decoder layer (one launch for the seven tensors that become
+ * final together, one behind each of decoder layers 1 - 5; the cut is derived on the device, nothing waits on the host) - the
+ * zeros a clip decoded alone has where its decoder looks one frame ahead.  Opt-in: without the bit se_enhance_long_ragged
+ * refuses this network as before.  With it nothing else changes: se_enhance_batch, se_enhance_ragged, se_enhance_long (equal
+ * rows) and se_stream_* enqueue exactly the launches of an engine without it.  DCCRN only, and not with
+ * SE_CFG_DCCRN_CAUSAL_DEC (that decoder looks back and is accepted without the bit): se_engine_create fails for either.
+ * Combines with SE_CFG_DCCRN_REAL_LSTM, SE_CFG_DCCRN_MASK_C / _R, the two complexnn conventions, SE_CFG_GRAPHS and
+ * SE_CFG_STREAM_SLIDING.  Like every model bit it is part of a parked stream's identity (se_stream_restore / _state_select /
+ * _state_concat / _state_join compare it). */
+#define SE_CFG_DCCRN_ROW_ENDS (1 << 18)
 
 typedef struct se_config {
     int32_t model;        /* enum se_model_id */
@@ -364,9 +376,11 @@ int se_enhance_long(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int
  * frames that launch owns, derived on the device without a host synchronisation).  The networks are causal, so what a row's state holds after its end
  * never reaches a sample of it, and no operator on these paths reduces over the batch.  FullSubNet with the cumulative norm
  * looks two frames ahead at its input only and sees there the zero frames of the STFT, as it does when the row is decoded alone.
- * NOT accepted here: SE_MODEL_DCCRN with the look-ahead decoder (without SE_CFG_DCCRN_CAUSAL_DEC) - its decoder looks one frame
- * ahead per layer into tensors that are not zero behind a row's own last frame, and the per-layer zeroing a row that ends
- * mid-walk needs is not built yet; the call refuses it with that reason (se_enhance_long and se_enhance_ragged decode it as before).
+ * NOT accepted here by default: SE_MODEL_DCCRN with the look-ahead decoder (without SE_CFG_DCCRN_CAUSAL_DEC) - its decoder looks
+ * one frame ahead per layer into tensors that are not zero behind a row's own last frame; the call refuses it with that reason
+ * (se_enhance_long and se_enhance_ragged decode it as before).  An engine created with SE_CFG_DCCRN_ROW_ENDS is accepted: every
+ * chunk then clears those tensors at or past each row's own end, layer by layer, and each row gets what se_enhance_long returns
+ * for it alone, its last six frames included.
  *   max_chunk_frames: as se_enhance_long.  in_pitch >= max lengths (batch > 1), out_pitch >= se_output_samples(e, max lengths),
  *   batch <= max_batch.  Models, refusal reasons and the effect on a running stream: as se_enhance_long (a refused call
  *   touches nothing, an accepted one ends the stream). */
@@ -588,7 +602,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise; + se_resampler_state_join: likewise) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise; + se_resampler_state_join: likewise; + the flag bit SE_CFG_DCCRN_ROW_ENDS: no new entry point, same number) */
 
 #ifdef __cplusplus
 }

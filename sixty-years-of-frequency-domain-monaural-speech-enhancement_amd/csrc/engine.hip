@@ -326,6 +326,13 @@ int se_engine_create(const se_config* cfg, se_engine** out) {
         e->ctx.p_in = cfg->p_in > 0.f ? cfg->p_in : 1.f;
         e->ctx.p_out = cfg->p_out > 0.f ? cfg->p_out : 1.f;
         e->ctx.flags = cfg->flags;
+        // (the bit names a remedy for DCCRN's look-ahead decoder alone: anywhere else it would be carried along without a meaning)
+        SE_CHECK(!(cfg->flags & SE_CFG_DCCRN_ROW_ENDS) || cfg->model == SE_MODEL_DCCRN,
+                 "SE_CFG_DCCRN_ROW_ENDS is a bit of SE_MODEL_DCCRN (the per-layer zero tails its look-ahead decoder needs in "
+                 "se_enhance_long_ragged): no other model takes it");
+        SE_CHECK(!(cfg->flags & SE_CFG_DCCRN_ROW_ENDS) || !(cfg->flags & SE_CFG_DCCRN_CAUSAL_DEC),
+                 "SE_CFG_DCCRN_ROW_ENDS does not combine with SE_CFG_DCCRN_CAUSAL_DEC: the causal decoder looks back, not ahead, and "
+                 "se_enhance_long_ragged accepts it without the bit");
         e->model = make_model(cfg->model, e->ctx);
         e->ctx.geom = e->model->default_geom();
         if (cfg->n_fft > 0) {
@@ -669,6 +676,19 @@ struct RaggedScope {
     RaggedScope& operator=(const RaggedScope&) = delete;
 };
 
+// the rows' whole-clip frame counts for a model that cuts its own tensors at each row's end (window_rows.h), while this scope enqueues
+struct WindowEndsScope {
+    const bool on;
+    explicit WindowEndsScope(const WindowEnds* w) : on(w != nullptr) {
+        if (on) set_window_ends_ctx(w);
+    }
+    ~WindowEndsScope() {
+        if (on) set_window_ends_ctx(nullptr);
+    }
+    WindowEndsScope(const WindowEndsScope&) = delete;
+    WindowEndsScope& operator=(const WindowEndsScope&) = delete;
+};
+
 int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, int32_t batch, const int32_t* lengths,
                       float* wav_out_dev, int64_t out_pitch, void* stream) {
     if (!e) return 1;
@@ -709,7 +729,9 @@ int se_enhance_ragged(se_engine* e, const float* wav_in_dev, int64_t in_pitch, i
 // frames from there on are written as zeros and never overlap-added.  The network is causal and runs as for rows of one length,
 // without per-row sizes: past its end a row is fed zero frames.  That is exact for a look-ahead at the network's INPUT (FullSubNet,
 // cumulative norm: the zero frames `last` appends are the ones the STFT wrote); a model that looks ahead behind its input layer (the
-// `_vb` DCCRN's decoder) needs zeros behind every layer, which is not built yet: the caller refuses it.
+// `_vb` DCCRN's decoder) needs zeros behind every layer: an engine made with SE_CFG_DCCRN_ROW_ENDS gets the rows' whole-clip frame
+// counts and the window origin through a context of its own (window_rows.h WindowEnds), published around stream_chunk only - never
+// together with the ragged context - and clears the columns at or past each row's end itself; without the bit the caller refuses it.
 static void stream_process(se_engine* e, int t_end, bool last, float* out_dev, int64_t out_pitch, int* written, hipStream_t st,
                            const Ragged* rows = nullptr) {
     se_engine::Stream& S = e->strm;
@@ -748,7 +770,11 @@ static void stream_process(se_engine* e, int t_end, bool last, float* out_dev, i
             launch_stft(g, wav, pitch, B, S.n_total, Lpad, S.c.get(), e->ctx.p_in, spec, mag, t0 + n, Tw, st, t0, HC, w0,
                         S.tracking ? S.frame_c.get() : nullptr, S.ring);
         }
-        e->model->stream_chunk(B, t0, n, st, last && t0 + n == t_end);
+        {
+            const WindowEnds ends{rows ? rows->tlen : nullptr, t0};
+            WindowEndsScope ws(rows && (e->cfg.flags & SE_CFG_DCCRN_ROW_ENDS) ? &ends : nullptr);
+            e->model->stream_chunk(B, t0, n, st, last && t0 + n == t_end);
+        }
         S.t_done = t0 + n;
         const bool end = last && S.t_done == t_end;
         // estimate frames below t_fin are final (a model that looks ahead finalises LAG frames late); samples whose every
@@ -965,10 +991,11 @@ static void enhance_long_impl(se_engine* e, const std::string& fn, const float* 
                               float* wav_out_dev, int64_t out_pitch, hipStream_t st) {
     SE_CHECK(e->model->stream_supported(),
              fn + " decodes in windows, which needs a network that is causal end to end: " + why_not_causal(e));
-    SE_CHECK(!(lengths && e->cfg.model == SE_MODEL_DCCRN && e->model->stream_lag() > 0),
+    SE_CHECK(!(lengths && e->cfg.model == SE_MODEL_DCCRN && e->model->stream_lag() > 0 && !(e->cfg.flags & SE_CFG_DCCRN_ROW_ENDS)),
              fn + ": DCCRN's look-ahead decoder reads one frame ahead per layer into tensors that are not zero "
                   "behind a row's own last frame; the per-layer zeroing that rows of different lengths need is not built yet: decode "
-                  "them one at a time with se_enhance_long (the causal decoder, SE_CFG_DCCRN_CAUSAL_DEC, is accepted)");
+                  "them one at a time with se_enhance_long (the causal decoder, SE_CFG_DCCRN_CAUSAL_DEC, is accepted, and so is an "
+                  "engine created with SE_CFG_DCCRN_ROW_ENDS)");
     SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
     const StftGeom& g = e->ctx.geom;
     int Lmax = 0;

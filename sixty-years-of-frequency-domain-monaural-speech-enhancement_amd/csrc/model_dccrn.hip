@@ -33,6 +33,7 @@
 // calls the same encoder() / core() / decoder() on the new columns of its windows.  core() is real_lstm_core() or complex_lstm_core().
 #include "rnn.h"
 #include "gauss.h"
+#include "window_rows.h"
 #include "../../include/se_engine.h"
 
 namespace se {
@@ -269,7 +270,9 @@ class Dccrn final : public Model {
     // whose look-ahead column DHC - k + n its input already has - and the estimate six frames behind (the engine finalises
     // it six frames late, stream_lag).  The chunk that ends the stream fills the remaining columns with zeros where their
     // future would be - what the offline decode sees past its last frame.  The history columns of all fourteen tensors come
-    // back from / go to the state in one launch each.
+    // back from / go to the state in one launch each.  In a windowed walk over rows of DIFFERENT lengths a row's "no future" comes
+    // before the walk's: stream_chunk clears the columns at or past each row's own end behind the encoder, the core and every
+    // decoder layer (SE_CFG_DCCRN_ROW_ENDS).
     // The causal decoder (SE_CFG_DCCRN_CAUSAL_DEC: `out[..., :-1]`, DCCRN_SNR/DCCRN.py:159) has a schedule of its own: every
     // tensor is a window of CHC = 4 history columns + the n new frames, and EVERY layer - decoder included - produces columns
     // [CHC, CHC + n) only; the one column a transposed conv looks back on (CHC - 1) is the layer input's history, restored from
@@ -310,6 +313,20 @@ class Dccrn final : public Model {
         // them - up to the end of the window (c1 beyond every layer's lag) in the chunk that ends the stream; causal: no lag
         encoder(b, b.spec, 0, NL, Tw, HC, false, st);
         core(b, b.E[NL - 1] + HC, 1024L * Tw, b.D[0] + HC, 1024L * Tw, Tw, n, st, true);
+        // Rows of different lengths in one windowed walk (SE_CFG_DCCRN_ROW_ENDS; the engine publishes the rows' frame counts around
+        // this call, window_rows.h): past its own last frame a row is fed zero frames, but bias, BatchNorm shift and the LSTM's
+        // response to silence make every tensor behind the input non-zero there, and each decoder layer looks one frame ahead.  A
+        // clip decoded alone has zeros there, so columns [cut_b, Tw) of E[0..5] and D[0] - final together - are cleared in one launch
+        // here, and D[k + 1] behind decoder layer k (decoder()), before layer k + 1 reads its look-ahead column; history columns
+        // included, and before the history is saved, so the state a later chunk restores holds the zeros (and nothing a re-carve
+        // left).  Both cores take the same cuts: their (h, c) past a row's end stay finite, belong to that row alone and reach
+        // frames at or past its end only, none of which the iSTFT adds into a sample of it.
+        if (const WindowEnds* we = window_ends_ctx()) {
+            SE_CHECK(!causal && we->t0 == t0, "DCCRN: row ends published for another chunk, or for the causal decoder");
+            ZeroTailBatch zb;
+            for (int k = 1; k <= NL + 1; ++k) zb.add(tens[k], rows[k]);
+            launch_window_zero_tail_batch(zb, B, Tw, we->tlen, t0, HC, st);
+        }
         decoder(b, 0, NL, Tw, HC, last ? Tw + NL : Tw, causal ? 0 : 1, false, st);
         const int cm = HC - stream_lag();      // the estimate's first new column
         launch_dccrn_mask(b.D[NL] + cm, b.spec + cm, b.est + cm, B, NBIN, last ? Tw - cm : n, Tw, ctx.p_out, st, mask_mode);
@@ -491,6 +508,9 @@ class Dccrn final : public Model {
             run_deconv(dec[k], a0, &a1, b.D[k + 1], cout, 2 * F, b.B, Tw, Tw, st, &ctx.prof, nullptr, c0 - back, std::min(c1 - back, Tw),
                        lag != 0);
             if (!causal && k + 1 < NL && !conv_zeroes_tail(dec[k])) launch_zero_tail(b.D[k + 1], b.B, (long)cout * (2 * F), Tw, st);
+            // (a chunk of a windowed walk over rows of different lengths, stream_chunk: the same cut relative to the window)
+            if (const WindowEnds* we = k + 1 < NL ? window_ends_ctx() : nullptr)
+                launch_window_zero_tail(b.D[k + 1], b.B, (long)cout * (2 * F), Tw, we->tlen, we->t0, DHC, st);
         }
     }
 

@@ -118,6 +118,9 @@ LONG_MODELS = frozenset({'lstm', 'crn', 'gcrn', 'dpcrn', 'dccrn', 'dccrn_snr', '
 # ... and of those, the models whose long clips may share a window walk (Engine.enhance_long_ragged): all but the `_vb` DCCRN, whose
 # decoder looks ahead behind the input layer (include/se_engine.h)
 LONG_RAGGED_MODELS = LONG_MODELS - {'dccrn'}
+# ... unless the engine is created with a bit that makes the network clear its tensors behind each row's own end, layer by layer
+# (SE_CFG_DCCRN_ROW_ENDS, include/se_engine.h): the driver makes such an engine when long clips are to be grouped (long_batch > 1)
+LONG_RAGGED_FLAGS = {'dccrn': 1 << 18}
 
 
 def plan_long(lengths, max_seconds, fs=16000):
@@ -233,7 +236,9 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
     long_batch: rows per windowed call.  1 (the default): one long clip at a time, as above.  N > 1: the long clips are grouped by
     length (plan_long_groups: at most min(N, max_batch) rows, padding within max_pad) and each group shares one window walk
     (Engine.enhance_long_ragged - every row gets what it gets alone, up to fp32 rounding); the engine is then made for the
-    largest call of either kind; a model outside LONG_RAGGED_MODELS (the `_vb` DCCRN) raises before any file is written.
+    largest call of either kind.  A model of LONG_RAGGED_FLAGS (the `_vb` DCCRN, whose decoder looks ahead) gets an engine created
+    with that bit when there are long clips to group, and the engine of before otherwise; a model in neither table raises before
+    any file is written.
     Like the one-at-a-time path, a group bypasses the reader / writer pipeline: its clips are read one after another on the calling thread and
     uploaded, a group of one rate is resampled by one call (se_resample_ragged; a group that mixes rates clip by clip), and the
     group's rows plus the native-rate samples are resident together while it is assembled -
@@ -279,7 +284,8 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
         raise ValueError(f'{model} needs a whole utterance in one call and cannot be decoded in windows: '
                          f'{", ".join(files[i] for i in long_own)} exceed max_seconds = {max_seconds} '
                          f'({", ".join("%.1f s" % (lengths[i] / 16000.0) for i in long_own)})')
-    if long_own and long_batch > 1 and model not in LONG_RAGGED_MODELS:
+    group_flags = LONG_RAGGED_FLAGS.get(model, 0) if long_own and long_batch > 1 else 0
+    if long_own and long_batch > 1 and model not in LONG_RAGGED_MODELS and not group_flags:
         raise ValueError(f'{model} cannot decode long clips of different lengths in one call (long_batch = {long_batch}): '
                          f'its decoder looks ahead in time; use long_batch = 1')
     long_groups = [[long_own[k] for k in grp]
@@ -304,7 +310,8 @@ def enhance(args, model='dccrn', checkpoint=None, p_in=None, p_out=None, max_bat
     eng_len = max((lengths[i] for b in mine for i in b), default=0)
     nat_len = max((native[i] for b in mine for i in b), default=0)
     net = _build(model, checkpoint, state_dict, device=device, max_batch=eng_batch,
-                 max_samples=max(eng_samples if long_own else eng_len, 512), p_in=p_in, p_out=p_out)
+                 max_samples=max(eng_samples if long_own else eng_len, 512), p_in=p_in, p_out=p_out,
+                 **({'flags': group_flags} if group_flags else {}))
     eng = net.engine
     lib = _lib.load()
     n_out_max = eng.output_samples(eng_len)

@@ -14,7 +14,12 @@ Usage: python tools/long_decode_bench.py [--models crn,dccrn,g2net_new] [--secon
 --bound and max_batch = --group: once one at a time (se_enhance_long, a call per clip) and once in groups of up to --group rows
 (se_enhance_long_ragged, the groups of se_amd.decode.plan_long_groups within --max-pad).  Same box, same binary, same engine.  One
 JSON line per model: calls, median wall ms, clips / s and audio seconds / s of both, their ratio, and the largest
-rms(grouped row - its one-at-a-time decode) / rms(the latter) over the clips."""
+rms(grouped row - its one-at-a-time decode) / rms(the latter) over the clips.  --row-ends makes the engine with `row_ends=True`
+(SE_CFG_DCCRN_ROW_ENDS: the `_vb` DCCRN, which se_enhance_long_ragged refuses without it).
+
+--flag-cost: what the bit costs where it should cost nothing - se_enhance_long of --group (3) equal rows of --seconds on a DCCRN
+engine with and without the bit, the two engines alive together and measured in turns (plain, flagged, plain, ...), --reps runs
+each.  One JSON line: median, min and max wall ms of both sides."""
 import argparse
 import gc
 import json
@@ -67,7 +72,7 @@ def ragged(torch, a):
         batches.append((g, rows, [lens[i] for i in g]))
     audio = sum(lens) / 16000.0
     for name in a.models.split(','):
-        m = build(name, a.group, a.bound)
+        m = build(name, a.group, a.bound, **({'row_ends': True} if a.row_ends else {}))
         eng = m.engine
         one = lambda: [eng.enhance_long(c.view(1, -1), None, a.chunk) for c in clips]
         grouped = lambda: [eng.enhance_long_ragged(rows, ls, a.chunk) for _, rows, ls in batches]
@@ -81,9 +86,9 @@ def ragged(torch, a):
                 y = f()
                 torch.cuda.synchronize()
                 times.append(time.perf_counter() - t0)
-            return float(np.median(times)), y
-        t1, y1 = timed(one)
-        tg, yg = timed(grouped)
+            return float(np.median(times)), y, times
+        t1, y1, all1 = timed(one)
+        tg, yg, allg = timed(grouped)
         err = 0.0
         for (g, _, _), y in zip(batches, yg):
             for r, i in enumerate(g):
@@ -91,12 +96,36 @@ def ragged(torch, a):
                 got = y[r, :ref.shape[0]].cpu().numpy()
                 err = max(err, float(np.sqrt(np.mean((got - ref) ** 2)) / max(np.sqrt(np.mean(ref ** 2)), 1e-12)))
         eng.close()
-        side = lambda t, calls: {'calls': calls, 'ms': round(t * 1e3, 2), 'clips_per_s': round(len(lens) / t, 2),
-                                 'audio_s_per_s': round(audio / t, 1)}
+        side = lambda t, calls, ts: {'calls': calls, 'ms': round(t * 1e3, 2), 'ms_min': round(min(ts) * 1e3, 2), 'ms_max': round(max(ts) * 1e3, 2),
+                                     'clips_per_s': round(len(lens) / t, 2),
+                                     'audio_s_per_s': round(audio / t, 1)}
         print(json.dumps({'model': name, 'clips': len(lens), 'seconds': [round(L / 16000.0, 2) for L in lens], 'audio_s': round(audio, 2),
                           'max_samples': a.bound, 'max_chunk_frames': a.chunk, 'group': a.group, 'max_pad': a.max_pad,
-                          'groups': [len(g) for g in groups], 'one_at_a_time': side(t1, len(lens)),
-                          'grouped': side(tg, len(groups)), 'speedup_grouped': round(t1 / tg, 3), 'max_rel_rms_diff': err}), flush=True)
+                          'row_ends': bool(a.row_ends), 'groups': [len(g) for g in groups],
+                          'one_at_a_time': side(t1, len(lens), all1), 'grouped': side(tg, len(groups), allg), 'speedup_grouped': round(t1 / tg, 3), 'max_rel_rms_diff': err}), flush=True)
+
+
+def flag_cost(torch, a):
+    L = int(a.seconds * 16000)
+    x = torch.from_numpy(np.stack([synth.synth_clip(900 + b, 'speech', L) for b in range(a.group)])).cuda()
+    engines = {'plain': build('dccrn', a.group, a.bound).engine, 'row_ends': build('dccrn', a.group, a.bound, row_ends=True).engine}
+    out = {k: e.enhance_long(x, None, a.chunk) for k, e in engines.items()}          # warm-up of both
+    torch.cuda.synchronize()
+    same = bool(torch.equal(out['plain'], out['row_ends']))
+    times = {k: [] for k in engines}
+    for _ in range(a.reps):
+        for k, e in engines.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e.enhance_long(x, out[k], a.chunk)
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    for e in engines.values():
+        e.close()
+    st = lambda ts: {'ms': round(float(np.median(ts)) * 1e3, 3), 'ms_min': round(min(ts) * 1e3, 3), 'ms_max': round(max(ts) * 1e3, 3)}
+    print(json.dumps({'model': 'dccrn', 'rows': a.group, 'seconds': a.seconds, 'max_samples': a.bound, 'max_chunk_frames': a.chunk,
+                      'reps': a.reps, 'plain': st(times['plain']), 'row_ends': st(times['row_ends']), 'outputs_bit_equal': same,
+                      'ratio_row_ends_over_plain': round(float(np.median(times['row_ends']) / np.median(times['plain'])), 4)}), flush=True)
 
 
 def main():
@@ -112,7 +141,12 @@ def main():
     ap.add_argument('--span', default='20,60', help='shortest,longest clip of --ragged in seconds')
     ap.add_argument('--group', type=int, default=8, help='rows per grouped call of --ragged (and max_batch of its engine)')
     ap.add_argument('--max-pad', dest='max_pad', type=float, default=0.15, help='padding cap of a group of --ragged')
+    ap.add_argument('--row-ends', dest='row_ends', action='store_true', help='--ragged: engines with row_ends=True (DCCRN)')
+    ap.add_argument('--flag-cost', dest='flag_cost', action='store_true',
+                    help='enhance_long of --group equal rows on a DCCRN engine with and without row_ends, in turns')
     a = ap.parse_args()
+    if a.flag_cost:
+        return flag_cost(torch, a)
     if a.ragged:
         return ragged(torch, a)
     L = int(a.seconds * 16000)
