@@ -116,6 +116,19 @@ enum se_model_id {
  * SE_CFG_STREAM_SLIDING.  Like every model bit it is part of a parked stream's identity (se_stream_restore / _state_select /
  * _state_concat / _state_join compare it). */
 #define SE_CFG_DCCRN_ROW_ENDS (1 << 18)
+/* Frame-online streams of the models whose state counts frames from the start of the stream - SE_MODEL_CTSNET, SE_MODEL_G2NET and
+ * SE_MODEL_TAYLORSENET (the cumulative LayerNorm divides by the frames so far, the TCM rings are indexed by the frame), and
+ * SE_MODEL_FULLSUBNET with SE_CFG_FSN_CUMULATIVE and without SE_CFG_FSN_GRU (the cumulative Laplace norms, the look-ahead skip):
+ * the engine keeps one int32 per row on the device, the row's frame ORIGIN, and every kernel that read the group's frame index t
+ * reads the row's own index t - origin[b] instead.  se_stream_begin / _begin_running / _begin_tracking zero the origins; a parked
+ * stream carries them (a segment of its own in the snapshot); se_stream_state_join adds shift / hop to the origins of every part
+ * it rebases, so a rebased row keeps dividing by its own frame count and indexing its own rings where it always did - and the
+ * join, which refuses these models without the bit, is exact for them with it.  Origins accumulate over repeated joins and may be
+ * negative (a part older than parts[0]).  Opt-in: without the bit nothing changes (the kernels get a null pointer, snapshots stay
+ * byte-identical, the join refuses these models as before); with it a stream that is never joined computes, bit for bit, what it
+ * computes without.  se_engine_create fails for any other model or configuration.  Like every model bit it is part of a parked
+ * stream's identity (se_stream_restore / _state_select / _state_concat / _state_join compare it). */
+#define SE_CFG_STREAM_ROW_ORIGINS (1 << 19)
 
 typedef struct se_config {
     int32_t model;        /* enum se_model_id */
@@ -334,8 +347,11 @@ int se_stream_state_concat(se_engine* e, se_stream_state* dst, const se_stream_s
  *             - its state holds no absolute time: a running-scale stream is refused (its ring of 1 / c per frame is indexed by the
  *               absolute frame, and its sum by the absolute sample count; a TRACKING-scale stream is accepted - its (E, W) are relative,
  *               and its rings are rotated by shift / hop frames on the way, csrc/stream_join.h - with equal tau_samples), and so are the models whose state counts frames - CTSNet, TaylorSENet and G2Net with the cumulative
- *               LayerNorm, FullSubNet with the cumulative norm.  CRN, LSTM, GCRN, DPCRN and DCCRN (complex or real LSTM core, either
- *               decoder) are accepted.
+ *               LayerNorm, FullSubNet with the cumulative norm - unless the engine was created with SE_CFG_STREAM_ROW_ORIGINS: every
+ *               row then carries its own frame origin, the join adds shift / hop to the origins of the rows it rebases, and these
+ *               four configurations are accepted under the same phase and left-edge conditions (their state is per row, zero-initialised
+ *               slots are the causal padding, and every model-side index is taken from the row's own origin).  CRN, LSTM, GCRN, DPCRN
+ *               and DCCRN (complex or real LSTM core, either decoder) are accepted with or without the bit.
  *           Each failure is refused with its own reason, naming the field and both values.  Parts may have been saved with live input
  *           windows of different lengths; the result keeps, for every row, the samples from the highest rebased `keep` of any part.
  *           The capacity checks are left to the restore of the result: an engine without SE_CFG_STREAM_SLIDING restores it if
@@ -602,7 +618,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise; + se_resampler_state_join: likewise; + the flag bit SE_CFG_DCCRN_ROW_ENDS: no new entry point, same number) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise; + se_resampler_state_join: likewise; + the flag bit SE_CFG_DCCRN_ROW_ENDS: no new entry point, same number; + the flag bit SE_CFG_STREAM_ROW_ORIGINS: likewise, and a snapshot segment kind only engines with the bit write) */
 
 #ifdef __cplusplus
 }

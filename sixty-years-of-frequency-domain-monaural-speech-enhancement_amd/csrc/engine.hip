@@ -90,6 +90,9 @@ struct se_engine {
         DevBuf<float> frame_inv;
         int ring = 0;
         DevBuf<float> c;
+        // SE_CFG_STREAM_ROW_ORIGINS: the rows' frame origins [max_batch] (made at create; EngineCtx::stream_origin points here), zero
+        // in a stream that was begun, whatever its snapshot recorded in one that was restored
+        DevBuf<int32_t> origin;
         // tracking unit-RMS scale (se_stream_begin_tracking): `sumsq` holds (E, W) per row, every frame has a scale of its own - c_t
         // in the ring frame_c for the forward transform, 1 / c_t in frame_inv for the inverse; lam = exp(-hop / tau) (1: tau == 0)
         bool tracking = false;
@@ -333,6 +336,18 @@ int se_engine_create(const se_config* cfg, se_engine** out) {
         SE_CHECK(!(cfg->flags & SE_CFG_DCCRN_ROW_ENDS) || !(cfg->flags & SE_CFG_DCCRN_CAUSAL_DEC),
                  "SE_CFG_DCCRN_ROW_ENDS does not combine with SE_CFG_DCCRN_CAUSAL_DEC: the causal decoder looks back, not ahead, and "
                  "se_enhance_long_ragged accepts it without the bit");
+        // (per-row frame origins are read by the kernels of the models whose state counts frames, and by nothing else)
+        if (cfg->flags & SE_CFG_STREAM_ROW_ORIGINS) {
+            const bool cln = cfg->model == SE_MODEL_CTSNET || cfg->model == SE_MODEL_G2NET || cfg->model == SE_MODEL_TAYLORSENET;
+            const bool fsn = cfg->model == SE_MODEL_FULLSUBNET && (cfg->flags & SE_CFG_FSN_CUMULATIVE) && !(cfg->flags & SE_CFG_FSN_GRU);
+            SE_CHECK(cln || fsn,
+                     "SE_CFG_STREAM_ROW_ORIGINS is a bit of the models whose stream state counts frames - SE_MODEL_CTSNET, SE_MODEL_G2NET, "
+                     "SE_MODEL_TAYLORSENET, and SE_MODEL_FULLSUBNET with SE_CFG_FSN_CUMULATIVE and without SE_CFG_FSN_GRU: no other "
+                     "configuration takes it (the others are joined without it)");
+            e->strm.origin.alloc((size_t)e->ctx.max_batch);
+            SE_HIP(hipMemset(e->strm.origin.get(), 0, (size_t)e->ctx.max_batch * sizeof(int32_t)));
+            e->ctx.stream_origin = e->strm.origin.get();
+        }
         e->model = make_model(cfg->model, e->ctx);
         e->ctx.geom = e->model->default_geom();
         if (cfg->n_fft > 0) {
@@ -853,6 +868,7 @@ static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_fram
             launch_fill(S.frame_inv.get(), (long)batch * S.ring, 1.f, st);
             if (tracking) launch_fill(S.frame_c.get(), (long)batch * S.ring, 1.f, st);
         }
+        if (S.origin) SE_HIP(hipMemsetAsync(S.origin.get(), 0, (size_t)batch * sizeof(int32_t), st));
         S.start(batch, 0, running, tracking, tau, g.hop);
         e->model->stream_begin(batch, S.max_chunk, st);
         S.active = true;
@@ -1026,6 +1042,7 @@ static void enhance_long_impl(se_engine* e, const std::string& fn, const float* 
         RaggedScope rs(rows);
         launch_rms_scale(wav_in_dev, batch, Lmax, in_pitch, S.c.get(), st);
     }
+    if (S.origin) SE_HIP(hipMemsetAsync(S.origin.get(), 0, (size_t)batch * sizeof(int32_t), st));      // (a windowed decode begins at frame 0 in every row)
     S.start(batch, Lmax, false);
     S.ext = wav_in_dev;
     S.ext_pitch = in_pitch;
@@ -1250,6 +1267,7 @@ std::vector<EngSeg> engine_segments(se_engine* e, int batch, int mode, int ring)
     }
     if (StreamSlots* sl = e->model->stream_slots())
         for (size_t i = 0; i < sl->v.size(); ++i) add(SNAP_SLOT, (int32_t)i, sl->v[i].first, (int64_t)sl->v[i].second);
+    if (S.origin) add(SNAP_ORIGIN, 0, S.origin.get(), (int64_t)batch * sizeof(int32_t));      // (right in front of the window: snap_origin_why)
     return v;
 }
 
@@ -1397,6 +1415,8 @@ void check_snapshot_identity(const se_engine* e, const SnapManifest& m, const st
              fn + "front end differs (snapshot n_fft / hop / win " + std::to_string(m.n_fft) + " / " + std::to_string(m.hop) + " / " +
                  std::to_string(m.win) + ", engine " + std::to_string(g.n_fft) + " / " + std::to_string(g.hop) + " / " + std::to_string(g.win) + ")");
     SE_CHECK(m.p_in == e->ctx.p_in && m.p_out == e->ctx.p_out, fn + "magnitude exponents p_in / p_out differ");
+    const std::string org = snap_origin_why(m);
+    SE_CHECK(org.empty(), fn + org);
     SE_CHECK(e->model->stream_supported(), fn + "this engine's model has no frame-online mode");
 }
 
@@ -1670,20 +1690,24 @@ struct RowSource {
 
 // "", or what in the state a stream of this engine's model carries counts frames from the start of the stream: such a state cannot be
 // moved to another position.  The models that are left ignore stream_chunk()'s t0 ((void)t0 in CRN, LSTM, GCRN, DPCRN, DCCRN)
+// With SE_CFG_STREAM_ROW_ORIGINS every row counts from its own origin, which the join moves along (stream_join.h): "" for every model
 std::string join_counts_frames(const se_engine* e) {
+    if (e->cfg.flags & SE_CFG_STREAM_ROW_ORIGINS) return "";
+    const char* hint = " (an engine created with SE_CFG_STREAM_ROW_ORIGINS keeps a frame origin per row and joins this model)";
     switch (e->cfg.model) {
         case SE_MODEL_CTSNET:
         case SE_MODEL_G2NET:
         case SE_MODEL_TAYLORSENET:
-            return "the cumulative LayerNorm divides its running sums by the number of frames so far, and the TCM rings are indexed by the "
-                   "absolute frame (StreamCtx::t0, k_tcm_stream.hip)";
+            return std::string("the cumulative LayerNorm divides its running sums by the number of frames so far, and the TCM rings are indexed by the "
+                               "absolute frame (StreamCtx::t0, k_tcm_stream.hip)") + hint;
         case SE_MODEL_FULLSUBNET:
-            return "the cumulative Laplace norm divides its running sums by the absolute frame index (launch_fsn_cum_fb / launch_fsn_cum_sb), "
-                   "and the look-ahead skips the steps before frame 2 by it";
+            return std::string("the cumulative Laplace norm divides its running sums by the absolute frame index (launch_fsn_cum_fb / launch_fsn_cum_sb), "
+                               "and the look-ahead skips the steps before frame 2 by it") + hint;
         default:
             return "";
     }
 }
+static_assert(SNAP_FLAG_ROW_ORIGINS == SE_CFG_STREAM_ROW_ORIGINS, "stream_manifest.h names the bit of include/se_engine.h");
 
 // dst <- the rows `src` names, in order; parts: the distinct source objects, every one checked against e and of one layout `lay`.
 // jp (se_stream_state_join): the parts' windows differ in length - `lay` then describes the RESULT, whose window starts at jp->keep,
@@ -1724,10 +1748,10 @@ void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream
     for (se_stream_state* p : parts) obj_wait(p, st);
     obj_wait(dst, st);
     // one block: GatherSeg[nseg] | long src_off[np][nseg] | const float* base[np] | int2 rowmap[Bd] | int part_B[np]
-    // (join: | int window row length[np] | int window column[np] | int ring rotation[np])
+    // (join: | int window row length[np] | int window column[np] | int ring rotation[np] | int shift in frames[np])
     const size_t o_off = (size_t)nseg * sizeof(GatherSeg), o_base = o_off + (size_t)np * nseg * sizeof(long),
                  o_map = o_base + (size_t)np * sizeof(float*), o_pb = o_map + (size_t)Bd * sizeof(int2), o_win = o_pb + (size_t)np * sizeof(int),
-                 total = o_win + (jp ? 3 * (size_t)np * sizeof(int) : 0);
+                 total = o_win + (jp ? 4 * (size_t)np * sizeof(int) : 0);
     auto& sd = *dst->side;
     SE_HIP(hipEventSynchronize(sd.gat_ev.get()));
     if (total > sd.gat_cap) {
@@ -1754,6 +1778,7 @@ void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream
             wi[p] = parts[(size_t)p]->man.n_total - parts[(size_t)p]->man.keep;
             wi[np + p] = jp->col[(size_t)p];
             wi[2 * np + p] = jp->rot[(size_t)p];
+            wi[3 * np + p] = jp->frames[(size_t)p];
         }
     }
     std::memcpy(pin + o_map, rowmap.data(), (size_t)Bd * sizeof(int2));
@@ -1774,6 +1799,14 @@ void gather_rows(se_engine* e, se_stream_state* dst, const std::vector<se_stream
         w.part_inner = reinterpret_cast<const int*>(dev + o_win);
         w.part_col = w.part_inner + np;
         w.part_rot = w.part_inner + 2 * np;
+        // the rows' frame origins move with the frames too (stream_join.h): + shift / hop on the way through the same launch
+        w.part_frames = w.part_inner + 3 * np;
+        for (int k = 0; k < nseg; ++k)
+            if (m.segs[(size_t)k].kind == SNAP_ORIGIN) {
+                SE_CHECK(w.origin_seg < 0 && tab[(size_t)k].outer == 1 && tab[(size_t)k].inner == 1 && tab[(size_t)k].n == Bd && (int)jp->frames.size() == np,
+                         fn + "frame origin segment of an odd layout");
+                w.origin_seg = k;
+            }
         // the per-frame rings of a tracking-scale group move with the frames (stream_join.h): the SNAP_FRAME_INV segments, side by side
         for (int k = 0; k < nseg; ++k)
             if (m.segs[(size_t)k].kind == SNAP_FRAME_INV && m.running == 2) {
@@ -1877,7 +1910,7 @@ int se_stream_state_join(se_engine* e, se_stream_state* dst, const se_stream_sta
         }
         check_snapshot_identity(e, parts[0]->man, fn);
         JoinPlan plan;
-        const std::string why = snap_join_plan(mans, e->model->stream_lag(), join_counts_frames(e), plan);
+        const std::string why = snap_join_plan(mans, e->model->stream_lag(), join_counts_frames(e), plan, e->model->stream_state() != nullptr);
         SE_CHECK(why.empty(), fn + why);
         // every part against the layouts of this engine's model, its window at its own length; the result's at the joined length
         std::vector<RowLayout> lay = snapshot_layouts(e, parts[0]->man, fn);

@@ -27,11 +27,12 @@ void launch_fsn_finish_mean(const float* part, float* mu, float denom, int B, co
 // the decompressed product with spec [B][2][257][T]
 void launch_fsn_mask(const float* maskBT, const float* spec, float* out, int B, int T, float p_out, hipStream_t st);
 // x -> y [n][257][B]; csum [B] (may be null), read when t_first > 0, written when not null
-void launch_fsn_cum_fb(const float* x, float* y, int n, int B, float* csum, int t_first, hipStream_t st);
+// origin (optional, [B] int32 on the device: SE_CFG_STREAM_ROW_ORIGINS): row b counts from t_first - origin[b]
+void launch_fsn_cum_fb(const float* x, float* y, int n, int B, float* csum, int t_first, hipStream_t st, const int32_t* origin = nullptr);
 // sb [n][32][S] in place; csum [S] as above
-void launch_fsn_cum_sb(float* sb, int n, int S, float* csum, int t_first, hipStream_t st);
+void launch_fsn_cum_sb(float* sb, int n, int S, float* csum, int t_first, hipStream_t st, const int32_t* origin = nullptr);
 // maskT [ns][2][257 * B] on columns [col0, col0 + ns) of spec -> est [B][2][257][Tw]; steps with gt0 + tau < LA are skipped
 void launch_fsn_stream_apply(const float* maskT, const float* spec, float* est, int B, int Tw, int ns, int col0, int gt0,
-                             float p_out, hipStream_t st);
+                             float p_out, hipStream_t st, const int32_t* origin = nullptr);
 
 }  // namespace se

@@ -124,9 +124,11 @@ __global__ __launch_bounds__(256) void fsn_mask_kernel(const float* __restrict__
 // sum across the chunks of a frame-online stream; step 0 of the call is frame t_first of the utterance.
 // full band: x / y [n][257][B] time-major, one workgroup per utterance
 __global__ __launch_bounds__(256) void fsn_cum_fb_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int B,
-                                                         float* __restrict__ csum, int t_first) {
+                                                         float* __restrict__ csum, int t_first,
+                                                         const int32_t* __restrict__ origin) {
     __shared__ float part[4];
     const int b = blockIdx.x, tid = threadIdx.x;
+    if (origin) t_first -= origin[b];      // the row's own frame index (one workgroup per row: uniform, read once)
     float run = (csum && t_first > 0) ? csum[b] : 0.f;
     for (int t = 0; t < n; ++t) {
         const float* xr = x + (long)t * NBIN * B + b;
@@ -145,9 +147,12 @@ __global__ __launch_bounds__(256) void fsn_cum_fb_kernel(const float* __restrict
     if (csum && tid == 0) csum[b] = run;
 }
 // sub bands: sb [n][32][S] in place, one thread per sequence s (sub-band of an utterance)
-__global__ __launch_bounds__(256) void fsn_cum_sb_kernel(float* __restrict__ sb, int n, int S, float* __restrict__ csum, int t_first) {
+// origin (optional, [B]): sequence s = n * B + b belongs to row s % B, whose own frame index is t_first - origin[s % B]
+__global__ __launch_bounds__(256) void fsn_cum_sb_kernel(float* __restrict__ sb, int n, int S, float* __restrict__ csum, int t_first,
+                                                         const int32_t* __restrict__ origin, int B) {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
+    if (origin) t_first -= origin[s % B];
     float run = (csum && t_first > 0) ? csum[s] : 0.f;
     for (int t = 0; t < n; ++t) {
         float* xr = sb + (long)t * SBW * S + s;
@@ -168,10 +173,12 @@ __global__ __launch_bounds__(256) void fsn_cum_sb_kernel(float* __restrict__ sb,
 // column col0 + tau of the chunk window ([B][2][257][Tw]); frames before the start of the stream (gt0 + tau < LA) do not exist
 __global__ __launch_bounds__(256) void fsn_stream_apply_kernel(const float* __restrict__ maskT, const float* __restrict__ spec,
                                                                float* __restrict__ est, int B, int Tw, int ns, int col0, int gt0,
-                                                               float p_out) {
+                                                               float p_out, const int32_t* __restrict__ origin) {
     const int i = blockIdx.x * 256 + threadIdx.x, tau = blockIdx.y;
     const int S = NBIN * B;
-    if (i >= S || gt0 + tau < LA) return;
+    if (i >= S) return;
+    if (origin) gt0 -= origin[i % B];      // the row's own frame index: a row younger than the look-ahead skips its steps alone
+    if (gt0 + tau < LA) return;
     const int n = i / B, b = i - n * B, col = col0 + tau;
     const float mr = maskT[((long)tau * 2) * S + i], mi = maskT[((long)tau * 2 + 1) * S + i];
     const long o = (((long)b * 2) * NBIN + n) * Tw + col, plane = (long)NBIN * Tw;
@@ -217,19 +224,20 @@ void launch_fsn_mask(const float* maskBT, const float* spec, float* out, int B, 
     hipLaunchKernelGGL(fsn_mask_kernel, dim3((T + 255) / 256, NBIN, B), dim3(256), 0, st, maskBT, spec, out, B, T, p_out);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_cum_fb(const float* x, float* y, int n, int B, float* csum, int t_first, hipStream_t st) {
-    hipLaunchKernelGGL(fsn_cum_fb_kernel, dim3(B), dim3(256), 0, st, x, y, n, B, csum, t_first);
+void launch_fsn_cum_fb(const float* x, float* y, int n, int B, float* csum, int t_first, hipStream_t st, const int32_t* origin) {
+    hipLaunchKernelGGL(fsn_cum_fb_kernel, dim3(B), dim3(256), 0, st, x, y, n, B, csum, t_first, origin);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_cum_sb(float* sb, int n, int S, float* csum, int t_first, hipStream_t st) {
-    hipLaunchKernelGGL(fsn_cum_sb_kernel, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, t_first);
+void launch_fsn_cum_sb(float* sb, int n, int S, float* csum, int t_first, hipStream_t st, const int32_t* origin) {
+    SE_CHECK(!origin || (S >= NBIN && S % NBIN == 0), "launch_fsn_cum_sb: per-row origins need S = 257 * B sequences");
+    hipLaunchKernelGGL(fsn_cum_sb_kernel, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, t_first, origin, S / NBIN);
     SE_HIP(hipGetLastError());
 }
 void launch_fsn_stream_apply(const float* maskT, const float* spec, float* est, int B, int Tw, int ns, int col0, int gt0,
-                             float p_out, hipStream_t st) {
+                             float p_out, hipStream_t st, const int32_t* origin) {
     const int S = NBIN * B;
     hipLaunchKernelGGL(fsn_stream_apply_kernel, dim3((S + 255) / 256, ns), dim3(256), 0, st, maskT, spec, est, B, Tw, ns, col0,
-                       gt0, p_out);
+                       gt0, p_out, origin);
     SE_HIP(hipGetLastError());
 }
 

@@ -763,9 +763,11 @@ __device__ __forceinline__ void cln_wave_scan(double* sc, int T, int c0, double 
 
 __global__ __launch_bounds__(256) void cln_scan_kernel(const double* __restrict__ sum, const double* __restrict__ sq,
                                                        float* __restrict__ mean, float* __restrict__ rstd, int R, int T,
-                                                       int c0, long tg0, int n_new, double* __restrict__ carry) {
+                                                       int c0, long tg0, int n_new, double* __restrict__ carry,
+                                                       const int32_t* __restrict__ origin) {
     extern __shared__ double sc[];       // [2][T]
     const int b = blockIdx.x;
+    if (origin) tg0 -= origin[b];        // the row's own frame index of column 0 (wave-uniform: one read)
     for (int t = c0 + threadIdx.x; t < T; t += 256) {
         const bool live = tg0 + t >= 0;
         sc[t] = live ? sum[(long)b * T + t] : 0.0;
@@ -835,8 +837,10 @@ __global__ __launch_bounds__(256) void cln_apply_kernel(const float* __restrict_
                                                         const float* __restrict__ gain, const float* __restrict__ bias,
                                                         const float* __restrict__ pre_slope,
                                                         const float* __restrict__ post_slope, const float* __restrict__ fir,
-                                                        int K, int R, int F, int T, int t_first, long tg0) {
+                                                        int K, int R, int F, int T, int t_first, long tg0,
+                                                        const int32_t* __restrict__ origin) {
     const int t = t_first + blockIdx.x * 256 + threadIdx.x, b = blockIdx.z;
+    if (origin) tg0 -= origin[b];        // (b is a grid dimension: uniform over the workgroup)
     if (t >= T) return;
     const float* mu = mean + (long)b * T;
     const float* rs = rstd + (long)b * T;
@@ -949,10 +953,11 @@ __global__ __launch_bounds__(256) void cln_window_kernel(const float* __restrict
                                                          const float* __restrict__ pre_slope,
                                                          const float* __restrict__ post_slope, const float* __restrict__ fir,
                                                          int K, int R, int F, int T, int c0, int t_first, long tg0, int n_new,
-                                                         double* __restrict__ carry) {
+                                                         double* __restrict__ carry, const int32_t* __restrict__ origin) {
     extern __shared__ double sc[];       // [2][T] totals, then [2][T] floats mean / rstd behind them
     __shared__ double sh[2][256];
     const int b = blockIdx.x;
+    if (origin) tg0 -= origin[b];        // the row's own frame index of column 0 (wave-uniform: one read)
     float* mu = reinterpret_cast<float*>(sc + 2 * T);
     float* rs = mu + T;
     // per-column sums over the rows: WP columns at a time (WP = the window width rounded up to a power of two, at most 64),
@@ -1056,7 +1061,8 @@ template <int W, int VPT>
 __global__ __launch_bounds__(256) void cln_window_reg_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                              const float* __restrict__ gain, const float* __restrict__ bias,
                                                              const float* __restrict__ post_slope, int R, int F, int T, int c0,
-                                                             long tg0, double* __restrict__ carry, const float* res) {
+                                                             long tg0, double* __restrict__ carry, const float* res,
+                                                             const int32_t* __restrict__ origin) {
     __shared__ double sh[4][2 * W];
     __shared__ float s_mu[W], s_rs[W];
     __shared__ float s_par[3][256];          // gain, bias, PReLU slope per channel (C = R / F <= 256, checked by the launcher)
@@ -1087,6 +1093,7 @@ __global__ __launch_bounds__(256) void cln_window_reg_kernel(const float* __rest
     if (tid == 0) {
         ca = carry[2 * b];
         cq = carry[2 * b + 1];
+        if (origin) tg0 -= origin[b];        // the row's own frame index (read in the same batch; only thread 0 counts frames)
     }
     {
         const int C = R / F;
@@ -1190,10 +1197,10 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
             norm_log_res(res);
             if (cx->n == 1)
                 hipLaunchKernelGGL((cln_window_reg_kernel<1, 41>), dim3(B), dim3(256), 0, s, x, y, gain, bias, post_slope, R, F, T,
-                                   c0, tg0, carry, res);
+                                   c0, tg0, carry, res, cx->origin);
             else
                 hipLaunchKernelGGL((cln_window_reg_kernel<2, 82>), dim3(B), dim3(256), 0, s, x, y, gain, bias, post_slope, R, F, T,
-                                   c0, tg0, carry, res);
+                                   c0, tg0, carry, res, cx->origin);
             SE_HIP(hipGetLastError());
             return;
         }
@@ -1202,7 +1209,7 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
             const size_t lds = (size_t)T * 24 + (K > 0 ? (size_t)R * (T - c0) * 4 : 0);
             norm_log_launch("cln_window", B, 256, lds, 0, c0);
             hipLaunchKernelGGL(cln_window_kernel, dim3(B), dim3(256), lds, s, x, y, gain, bias, pre_slope, post_slope,
-                               fir, K, R, F, T, c0, cx->H, tg0, cx->n, carry);
+                               fir, K, R, F, T, c0, cx->H, tg0, cx->n, carry, cx->origin);
             SE_HIP(hipGetLastError());
             return;
         }
@@ -1214,16 +1221,16 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
         hipLaunchKernelGGL(cln_stats_kernel, dim3((T - c0 + WP - 1) / WP, B), dim3(256), 0, s, x, pre_slope, sum, sq, R, F, T, c0,
                            WP);
         hipLaunchKernelGGL(cln_scan_kernel, dim3(B), dim3(256), (size_t)T * 16, s, sum, sq, mean, rstd, R, T, c0, tg0, cx->n,
-                           carry);
+                           carry, cx->origin);
         hipLaunchKernelGGL(cln_apply_kernel, dim3((cx->n + 255) / 256, (R + 7) / 8, B), dim3(256), 0, s, x, y, mean, rstd, gain,
-                           bias, pre_slope, post_slope, fir, K, R, F, T, cx->H, tg0);
+                           bias, pre_slope, post_slope, fir, K, R, F, T, cx->H, tg0, cx->origin);
         SE_HIP(hipGetLastError());
         return;
     }
     norm_log_launch("cln_stats", (long)((T + 63) / 64) * B, 256, 0, 0, 0, 64);
     norm_log_launch("cln_scan", B, 256, (size_t)T * 16);
     hipLaunchKernelGGL(cln_stats_kernel, dim3((T + 63) / 64, B), dim3(256), 0, s, x, pre_slope, sum, sq, R, F, T, 0, 64);
-    hipLaunchKernelGGL(cln_scan_kernel, dim3(B), dim3(256), (size_t)T * 16, s, sum, sq, mean, rstd, R, T, 0, 0L, 0, nullptr);
+    hipLaunchKernelGGL(cln_scan_kernel, dim3(B), dim3(256), (size_t)T * 16, s, sum, sq, mean, rstd, R, T, 0, 0L, 0, nullptr, nullptr);
     static const bool plane_on = !(getenv("SE_CLN_PLANE") && atoi(getenv("SE_CLN_PLANE")) == 0);
     if (K <= 0 && !pre_slope && (plane_on || res)) {
         norm_log_launch("cln_apply_plane", (long)B * C, 256, (size_t)T * 8);
@@ -1235,7 +1242,7 @@ void launch_cln(const float* x, float* y, const float* gain, const float* bias, 
     }
     norm_log_launch("cln_apply", (long)((T + 255) / 256) * ((R + 7) / 8) * B, 256, 0);
     hipLaunchKernelGGL(cln_apply_kernel, dim3((T + 255) / 256, (R + 7) / 8, B), dim3(256), 0, s, x, y, mean, rstd, gain,
-                       bias, pre_slope, post_slope, fir, K, R, F, T, 0, 0L);
+                       bias, pre_slope, post_slope, fir, K, R, F, T, 0, 0L, nullptr);
     SE_HIP(hipGetLastError());
 }
 

@@ -15,6 +15,10 @@ struct JoinWindow {
     // entry i of a row of part p comes from its entry (i - part_rot[p]) & (inner - 1); ring_lo >= ring_hi: none
     int ring_lo = 0, ring_hi = 0;
     const int* part_rot = nullptr;
+    // per-row frame origins (stream_join.h): segment `origin_seg` is [Bd] int32, and a row of part p arrives as its value +
+    // part_frames[p]; origin_seg < 0: none
+    int origin_seg = -1;
+    const int* part_frames = nullptr;
 };
 void launch_stream_state_join(const GatherArgs& a, const JoinWindow& w, long tiles, hipStream_t s);
 

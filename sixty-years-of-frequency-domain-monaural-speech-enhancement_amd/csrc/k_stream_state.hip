@@ -123,6 +123,7 @@ __device__ __forceinline__ void state_gather_tile(const GatherArgs& a, const Joi
     const long* __restrict__ off = a.src_off + lo;
     const bool window = JOIN && lo == w.seg;
     const bool rotate = JOIN && lo >= w.ring_lo && lo < w.ring_hi;
+    const bool origin = JOIN && lo == w.origin_seg;
     auto source = [&](unsigned j) -> const float* {
         const unsigned o = j / run, rem = j - o * run, bd = rem / inner, i = rem - bd * inner;
         const int2 pr = a.rowmap[bd];
@@ -142,6 +143,10 @@ __device__ __forceinline__ void state_gather_tile(const GatherArgs& a, const Joi
         for (unsigned q = threadIdx.x; q < STATE_TILE; q += 256) {
             const unsigned j = j0 + q;
             if (j >= npad) break;
+            if (origin) {      // [Bd] int32 (inner == 1, so j is the row): the part's shift in frames rides on the copy
+                reinterpret_cast<int*>(sg.dst)[j] = j < n ? *reinterpret_cast<const int*>(source(j)) + w.part_frames[a.rowmap[j].x] : 0;
+                continue;
+            }
             sg.dst[j] = j < n ? *source(j) : 0.f;
         }
     }
@@ -163,6 +168,7 @@ void launch_stream_state_join(const GatherArgs& a, const JoinWindow& w, long til
     SE_CHECK(a.nseg >= 1 && a.Bd >= 1 && tiles >= 0 && tiles < (1L << 31), "launch_stream_state_join: bad table");
     SE_CHECK(w.seg >= 0 && w.seg < a.nseg && w.part_inner && w.part_col, "launch_stream_state_join: no window segment");
     SE_CHECK(w.ring_lo >= w.ring_hi || (w.ring_lo >= 0 && w.ring_hi <= a.nseg && w.part_rot), "launch_stream_state_join: bad ring segments");
+    SE_CHECK(w.origin_seg < 0 || (w.origin_seg < a.nseg && w.origin_seg != w.seg && w.part_frames), "launch_stream_state_join: bad origin segment");
     if (tiles == 0) return;
     hipLaunchKernelGGL(stream_state_join_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a, w);
     SE_HIP(hipGetLastError());

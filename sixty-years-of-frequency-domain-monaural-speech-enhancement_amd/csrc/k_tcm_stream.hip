@@ -70,6 +70,7 @@ struct TcmChainArgs {
     const float* x; float* y;       // windows [B][256][Tw] of the chain's input / output, new frames in columns [H, H + n)
     int Tw, H, n; long t0;
     int nblk, fp_max;               // fp_max: widest FIR window of the chain (K - 1 + NS)
+    const int32_t* origin;          // per-row frame origins (StreamCtx::origin) or null: the row counts frames and indexes its rings by t0 - origin[b]
     TcmStreamBlk blk[TCM_CHAIN_MAX];
 };
 
@@ -93,6 +94,7 @@ __global__ __launch_bounds__(256) void tcm_chain_kernel(const TcmChainArgs a) {
     const float* xb = a.x + (long)b * 256 * a.Tw + a.H;
     float* yb = a.y + (long)b * 256 * a.Tw + a.H;
     const int r = tid & 63, p = tid >> 6;
+    const long t_own = a.t0 - (a.origin ? a.origin[b] : 0);      // one workgroup per row: uniform, read once
 
     float wreg[64 > 16 * KS ? 64 : 16 * KS];
     {
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(256) void tcm_chain_kernel(const TcmChainArgs a) {
     }
 
     for (int c0 = 0; c0 < a.n; ++c0) {
-        const long tbase = a.t0 + c0;                  // stream index of this frame
+        const long tbase = t_own + c0;                 // the row's own stream index of this frame
         xs[tid] = xb[(long)tid * a.Tw + c0];
         for (int bi = 0; bi < NB; ++bi) {
             const TcmStreamBlk& B = a.blk[bi];
@@ -336,7 +338,7 @@ void launch_tcm_chain(const TcmStreamW* const* f, const TcmFusedHeads* hd, const
     StreamCtx* cx = stream_ctx();
     SE_CHECK(cx && nblk >= 1 && nblk <= TCM_CHAIN_MAX, "launch_tcm_chain: 1..8 blocks inside a frame-online chunk");
     TcmChainArgs a{};
-    a.x = x; a.y = y; a.Tw = cx->H + cx->n; a.H = cx->H; a.n = cx->n; a.t0 = cx->t0; a.nblk = nblk;
+    a.x = x; a.y = y; a.Tw = cx->H + cx->n; a.H = cx->H; a.n = cx->n; a.t0 = cx->t0; a.nblk = nblk; a.origin = cx->origin;
     const int ks = f[0]->ks;
     int fp = 1;
     for (int i = 0; i < nblk; ++i) {

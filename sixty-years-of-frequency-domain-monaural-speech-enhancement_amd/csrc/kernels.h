@@ -128,6 +128,9 @@ struct StreamCtx {
     int H = 0, n = 0;        // window = H history columns + n new frames
     long t0 = 0;             // index of the first new frame in the stream
     int B = 0;
+    // per-row frame origins [B] on the device (SE_CFG_STREAM_ROW_ORIGINS; null: every row's is 0): row b's own index of group frame t
+    // is t - origin[b], and the kernels that count frames or index rings by them (launch_cln, launch_tcm_chain) take it from there
+    const int32_t* origin = nullptr;
     std::vector<std::pair<void*, size_t>>* slots = nullptr;     // device state, owned by the model
     size_t cursor = 0;
     const void* memo_src = nullptr;     // source whose history the previous launch restored (parity classes of one deconv)
@@ -162,8 +165,8 @@ struct StreamSlots {
 };
 struct StreamScope {
     StreamCtx cx;
-    StreamScope(StreamSlots& sl, int H, int n, long t0, int B) {
-        cx.H = H; cx.n = n; cx.t0 = t0; cx.B = B; cx.slots = &sl.v;
+    StreamScope(StreamSlots& sl, int H, int n, long t0, int B, const int32_t* origin = nullptr) {
+        cx.H = H; cx.n = n; cx.t0 = t0; cx.B = B; cx.origin = origin; cx.slots = &sl.v;
         set_stream_ctx(&cx);
     }
     ~StreamScope() { set_stream_ctx(nullptr); }

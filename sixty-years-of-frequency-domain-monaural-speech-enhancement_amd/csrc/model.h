@@ -14,6 +14,9 @@ struct EngineCtx {
     int max_batch = 1, max_samples = 64000;
     float p_in = 1.f, p_out = 1.f;
     int flags = 0;          // se_config.flags
+    // SE_CFG_STREAM_ROW_ORIGINS: the frame origin of every row of the running stream ([max_batch] int32 on the device, owned by the
+    // engine), null without the bit - what the frame-counting models hand to their kernels in stream_chunk
+    const int32_t* stream_origin = nullptr;
     // hipGraph replay asked for (SE_CFG_GRAPHS, or SE_GRAPH=1 / 0 in the environment): models that would fork work onto an
     // auxiliary stream stay on the caller's stream then, so that the decode can be captured (graphs were silently
     // dropped for TaylorSENet, the most launch-heavy model)

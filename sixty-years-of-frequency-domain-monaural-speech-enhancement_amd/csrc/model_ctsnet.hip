@@ -182,7 +182,7 @@ class CtsNet final : public Model {
         (void)last;
         Bufs& b = bufs(B, STREAM_HC + n);
         const int T = b.T;
-        StreamScope sc(slots, STREAM_HC, n, t0, B);
+        StreamScope sc(slots, STREAM_HC, n, t0, B, ctx.stream_origin);
         step1(b, b.mag, b.est1, st);
         launch_mag_phase(b.est1, b.spec, b.s1, B, NBIN, T, 1.f, st);
         step2(b, b.spec, b.s1, b.est, st);

@@ -123,16 +123,16 @@ class FullSubNet final : public Model {
         // magnitudes of the new frames, time-major [ns][257][B]; at the end of the stream two zero frames (model.py:79)
         launch_transpose_akt(b.mag + HC, b.magT, B, NBIN, n, (long)NBIN * Tw, Tw, (long)NBIN * B, B, st);
         if (last) launch_fill(b.magT + (size_t)n * S, (long)LA * S, 0.f, st);
-        launch_fsn_cum_fb(b.magT, b.xfb, ns, B, ss.hist[2], t0, st);
+        launch_fsn_cum_fb(b.magT, b.xfb, ns, B, ss.hist[2], t0, st, ctx.stream_origin);
         fb[0].run_stream(b.xfb, b.G, ss.c[0], ss.h[0], b.h[0], ns, B, ss.first, st, pf);
         fb[1].run_stream(b.h[0], b.G, ss.c[1], ss.h[1], b.h[1], ns, B, ss.first, st, pf);
         run_pointwise(fb_fc, b.h[1], 512L * B, B, b.fbo, (long)NBIN * B, B, ns, B, st, pf);
         launch_fsn_build_sb(b.magT, b.fbo, b.sb, B, ns, st);
-        launch_fsn_cum_sb(b.sb, ns, S, ss.hist[3], t0, st);
+        launch_fsn_cum_sb(b.sb, ns, S, ss.hist[3], t0, st, ctx.stream_origin);
         sbl[0].run_stream(b.sb, b.G, ss.c[2], ss.h[2], b.h[0], ns, S, ss.first, st, pf);
         sbl[1].run_stream(b.h[0], b.G, ss.c[3], ss.h[3], b.h[1], ns, S, ss.first, st, pf);
         run_pointwise(sb_fc, b.h[1], 384L * S, S, b.maskT, 2L * S, S, ns, S, st, pf);
-        launch_fsn_stream_apply(b.maskT, b.spec, b.est, B, Tw, ns, HC - LA, t0, ctx.p_out, st);
+        launch_fsn_stream_apply(b.maskT, b.spec, b.est, B, Tw, ns, HC - LA, t0, ctx.p_out, st, ctx.stream_origin);
         launch_hist_save(b.spec, ss.hist[0], B, 2L * NBIN, Tw, HC, st);
         launch_hist_save(b.est, ss.hist[1], B, 2L * NBIN, Tw, HC, st);
         ss.first = false;

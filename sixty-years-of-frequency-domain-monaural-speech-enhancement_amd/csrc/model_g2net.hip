@@ -135,7 +135,7 @@ class G2Net final : public Model {
     void stream_chunk(int B, int t0, int n, hipStream_t st, bool last) override {
         (void)last;
         Bufs& b = bufs(B, STREAM_HC + n);
-        StreamScope sc(slots, STREAM_HC, n, t0, B);
+        StreamScope sc(slots, STREAM_HC, n, t0, B, ctx.stream_origin);
         stream_estimate(network(b, st), b.est, B, NBIN, b.T, ctx.p_out, st);
     }
 

@@ -5,7 +5,8 @@
 // A decode step of a stream that is past its left edge does not depend on the stream's absolute position, as long as the position
 // moves by whole hops: every index the front end forms is a frame index times the hop plus a constant, the grids of the STFT and
 // the iSTFT start at the launch's own first frame / first output sample, and the networks that are accepted here take no frame
-// index at all.  What does depend on position 0, in everything se_stream_push / se_stream_flush launch (the engine's stream_process):
+// index at all (or take it per row from the row's own frame origin: "Per-row frame origins" below).  What does depend on position 0,
+// in everything se_stream_push / se_stream_flush launch (the engine's stream_process):
 //   (a) the STFT of a frame t reads samples t hop - n_fft/2 ...; where that is negative it mirrors (`idx < 0` in the forward kernel), and its
 //       wave-uniform fast path asks `t hop >= n_fft/2` of the first frame of a pair.  Frames below t_done are never transformed
 //       again, so neither test can hold once   t_done hop >= n_fft/2.
@@ -46,8 +47,48 @@ struct JoinPlan {
     std::vector<int64_t> shift;
     std::vector<int32_t> col;
     std::vector<int32_t> rot;      // tracking scale: ring positions part p's per-frame rings move up by, in [0, ring)
+    std::vector<int32_t> frames;   // shift[p] / hop: what the join adds to the frame origins of part p's rows (snap_join_origin)
     int32_t keep = 0, live = 0;
 };
+
+// Per-row frame origins (SE_CFG_STREAM_ROW_ORIGINS, the SNAP_ORIGIN segment): the models that count frames in a join.
+//
+// The state of the cLN networks (CTSNet_new, TaylorSENet_new, G2Net_new) and of FullSubNet with the cumulative norm counts frames from
+// the start of the stream: the cLN divides its running float64 sums by R (t + 1) and masks FIR / history columns by t >= 0
+// (cln_window_reg_kernel, cln_window_kernel, cln_scan_kernel, cln_apply_kernel), the TCM chain kernel divides by 64 (t + 1) and keeps
+// its FIR / dilated-conv histories in rings indexed by t & (R - 1) (tcm_chain_kernel), FullSubNet's two cumulative norms divide by
+// the frame index (fsn_cum_fb_kernel, fsn_cum_sb_kernel) and its mask stage skips the steps with t < look-ahead
+// (fsn_stream_apply_kernel).  None of that state is shared between rows.  With the bit every row b carries an origin o_b (frames,
+// int32, zero at se_stream_begin*), and each of these kernels forms t = (group frame) - o_b before it does anything else with it.
+// A join moves part p's group frame by f_p = shift[p] / hop and adds f_p to the origins of its rows: t is what it was, so the row
+// keeps dividing by its own frame count and reads and writes its rings where it always did.  No ring is rotated, and the carried
+// sums are the sums of exactly the frames the divisor counts.  Origins accumulate over joins (o_b + f_p + f'_q ...) and are negative
+// for a row of a part older than parts[0].
+//
+// Every other use of the frame index t0 on these models' paths (Model::stream_chunk and the engine's stream_process), and why none
+// of them is model state that a rebase could break:
+//   * CTSNet / G2Net / TaylorSENet stream_chunk: t0 goes into StreamScope (-> StreamCtx::t0) and nowhere else.  StreamCtx::t0 is read
+//     by launch_cln (tg0 = t0 - H) and launch_tcm_chain (a.t0) alone; both hand StreamCtx::origin to their kernels.  The host
+//     branches of those launchers and of the models (the register form for n <= 2, the 32768 switch of the window form, CTSNet's
+//     decoder fork for n <= 2) look at the chunk length n and the tensor sizes, never at t0.  The history exchange
+//     (stream_exchange, gc_stream_prepare) moves the last columns of a window through per-row slots without an index.
+//   * FullSubNet stream_chunk: t0 goes to the three launchers named above, each with the origin pointer.  `ss.first` (an LSTM's first
+//     step starts from a zero state) is the one host-side branch on model state; it is group-wide and ends with the first chunk -
+//     (d) of the derivation above - and snap_join_plan refuses a moved part that still has it.  `last` (two more steps on zero
+//     frames) is the end of the stream, a front-end position common to the group.  A row whose own index is below the look-ahead
+//     is not kept out of a join by the left-edge threshold (1 frame for 512 / 256, below the look-ahead of 2) but by the phase check:
+//     o_done = (t_done - 2) hop - n_fft / 2 is clamped to 0 below t_done 3, so n_total - o_done of such a part differs from that of any
+//     part that is further on.  Parts that are ALL that young join with shift 0 or among themselves, and the kernel skips the steps
+//     below the look-ahead per row from the row's own index, so nothing rests on that exclusion.
+//   * stream_process: t0 is S.t_done - the STFT's first frame, the iSTFT's frame bounds, the per-frame scale rings, the window
+//     origin: all front end, all indexed by the GROUP frame, which is why the tracking-scale rings are still rotated by the join
+//     and the running scale is still refused.  Nothing there is per-row model state.
+// So the front-end threshold stream_left_edge_frames() suffices for these models too: past it the front end does not depend on the
+// absolute position (a) - (d); the model state is per row; zero-initialised slots and ring entries are the causal padding a row's
+// kernels find at its own negative indices, rebased or not; and every model-side index is taken from the row's own origin.
+//
+// the origin of a row of part p after the join (int32 wrap-around would need 2^31 frames: a stream ends long before)
+inline int32_t snap_join_origin(int32_t origin, int32_t frames) { return origin + frames; }
 
 // The tracking scale (se_stream_begin_tracking) in a join.  Its state per row is (E, W) and two rings, c_t and 1 / c_t of frame t at
 // position t & (ring - 1).  (E, W) are sums over the row's own past, weighted by the distance in blocks from the newest block: no
@@ -75,8 +116,12 @@ inline int64_t snap_ring_live_from(int64_t o_done, int32_t n_fft, int32_t hop) {
 }
 
 // "" and the plan, or why the parts cannot be joined.  lag: the model's stream_lag(); counts_frames: empty, or what in the model's
-// state counts frames (such a model is refused: its state cannot be rebased)
-inline std::string snap_join_plan(const std::vector<const SnapManifest*>& parts, int lag, const std::string& counts_frames, JoinPlan& plan) {
+// state counts frames (such a model is refused: its state cannot be rebased); first_counts: the model keeps a StreamState, whose
+// `first` flag SnapManifest::first records (Model::stream_state() != null: the engine says so).  A model that keeps call-order slots
+// instead has no such flag and se_stream_save records a constant 1 for it, which says nothing - its first chunk is behind it once
+// t_done >= 1, and `need` is at least 1.
+inline std::string snap_join_plan(const std::vector<const SnapManifest*>& parts, int lag, const std::string& counts_frames, JoinPlan& plan,
+                                  bool first_counts = true) {
     if (parts.empty()) return "n_parts 0: at least one part has to be given";
     const SnapManifest& a = *parts[0];
     auto at = [](size_t p) { return "parts[" + std::to_string(p) + "]"; };
@@ -107,11 +152,12 @@ inline std::string snap_join_plan(const std::vector<const SnapManifest*>& parts,
         moved = moved || s != 0;
         out.shift.push_back(s);
         out.rot.push_back(b.running == 2 ? snap_ring_rot(s, a.hop, b.ring) : 0);
+        out.frames.push_back((int32_t)(s / a.hop));      // (s is a multiple of the hop)
     }
     if (moved) {
         const int need = stream_left_edge_frames(a.n_fft, a.hop, lag);
         for (size_t p = 0; p < parts.size(); ++p)
-            if (parts[p]->t_done < need || parts[p]->first)
+            if (parts[p]->t_done < need || (first_counts && parts[p]->first))
                 return at(p) + " is short of the left edge: t_done " + std::to_string(parts[p]->t_done) + ", a stream can be rebased from t_done " +
                        std::to_string(need) + " on (n_fft " + std::to_string(a.n_fft) + ", hop " + std::to_string(a.hop) + ", look-ahead " +
                        std::to_string(lag) + ")";

@@ -25,8 +25,12 @@ enum SnapKind : int32_t {
     SNAP_H = 5,          // StreamState::h[index]
     SNAP_CELL = 6,       // StreamState::c[index]
     SNAP_SLOT = 7,       // StreamSlots::v[index], in call order
-    SNAP_WINDOW = 8      // input samples [keep, n_total) of every row, rows back to back: [batch][n_total - keep] float
+    SNAP_WINDOW = 8,     // input samples [keep, n_total) of every row, rows back to back: [batch][n_total - keep] float
+    SNAP_ORIGIN = 9      // the rows' frame origins [batch] int32: in every snapshot of an engine with SE_CFG_STREAM_ROW_ORIGINS, the
+                         // last segment in front of the window, and in no other
 };
+constexpr int32_t SNAP_KIND_MAX = SNAP_ORIGIN;
+constexpr int32_t SNAP_FLAG_ROW_ORIGINS = 1 << 19;      // SE_CFG_STREAM_ROW_ORIGINS (include/se_engine.h; the engine asserts the two agree)
 
 struct SnapSeg {
     int32_t kind = 0, index = 0;
@@ -58,6 +62,25 @@ inline int64_t snap_payload_bytes(const SnapManifest& m) {
     for (const SnapSeg& s : m.segs) n += snap_align16(s.bytes);
     return n;
 }
+// "" or why the origin segment of m is not where the flags of m put it: one segment [batch] int32 right in front of the window
+// with SNAP_FLAG_ROW_ORIGINS, none without
+inline std::string snap_origin_why(const SnapManifest& m) {
+    const bool want = (m.flags & SNAP_FLAG_ROW_ORIGINS) != 0;
+    int n = 0;
+    for (size_t k = 0; k < m.segs.size(); ++k) {
+        if (m.segs[k].kind != SNAP_ORIGIN) continue;
+        ++n;
+        if (!want) return "a frame origin segment in a snapshot of an engine without SE_CFG_STREAM_ROW_ORIGINS";
+        if (m.segs[k].index != 0 || m.segs[k].bytes != (int64_t)m.batch * 4)
+            return "frame origin segment of " + std::to_string(m.segs[k].bytes) + " bytes, " + std::to_string(m.batch) + " rows keep " +
+                   std::to_string((int64_t)m.batch * 4);
+        if (k + 2 != m.segs.size() || m.segs.back().kind != SNAP_WINDOW) return "frame origin segment misplaced (it goes right in front of the input window)";
+    }
+    if (n > 1) return "more than one frame origin segment";
+    if (want && n == 0) return "no frame origin segment in a snapshot of an engine with SE_CFG_STREAM_ROW_ORIGINS";
+    return "";
+}
+
 inline int64_t snap_table_bytes(const SnapManifest& m) { return SNAP_HEAD_BYTES + SNAP_SEG_BYTES * (int64_t)m.segs.size(); }
 inline int64_t snap_image_bytes(const SnapManifest& m) { return snap_table_bytes(m) + snap_payload_bytes(m); }
 
@@ -129,7 +152,7 @@ inline std::string snap_parse(const void* buf, int64_t bytes, SnapManifest& m, i
         s.kind = get<int32_t>(p);
         s.index = get<int32_t>(p);
         s.bytes = get<int64_t>(p);
-        if (s.kind < SNAP_C || s.kind > SNAP_WINDOW || s.index < 0)
+        if (s.kind < SNAP_C || s.kind > SNAP_KIND_MAX || s.index < 0)
             return "stream state image: segment " + std::to_string(k) + " of unknown kind";
         if (s.bytes < 0 || s.bytes > SNAP_MAX_BYTES || (s.bytes & 3))
             return "stream state image: segment " + std::to_string(k) + " has a negative, overflowing or odd size";
@@ -149,6 +172,8 @@ inline std::string snap_parse(const void* buf, int64_t bytes, SnapManifest& m, i
     for (int32_t k = 0; k < nseg; ++k)
         if (m.segs[(size_t)k].kind == SNAP_WINDOW && (k != nseg - 1 || m.segs[(size_t)k].bytes != (int64_t)m.batch * (m.n_total - m.keep) * 4))
             return "stream state image: input window segment misplaced or of the wrong size";
+    const std::string org = snap_origin_why(m);
+    if (!org.empty()) return "stream state image: " + org;
     payload_off = table;
     return "";
 }

@@ -8,6 +8,7 @@
 //   a call-order slot [B][row bytes]        (1, row bytes / 4)     sumsq [B] doubles                 (1, 2)
 //   (E, W) [B][2] doubles (tracking scale)  (1, 4)
 //   frame_inv, frame_c [B][ring]            (1, ring)              the window [B][n_total - keep]    (1, n_total - keep)
+//   frame origins [B] int32                 (1, 1)
 // The layouts are not part of a snapshot: the model declares them where it allocates the buffers (rnn.h StreamState::begin,
 // kernels.h StreamCtx::slot), and an engine of the snapshot's kind is asked for them when rows are selected or joined.
 #pragma once
@@ -32,13 +33,14 @@ inline bool snap_engine_layout(const SnapManifest& m, const SnapSeg& s, RowLayou
         case SNAP_SUMSQ: l = {1, m.running == 2 ? 4 : 2}; return true;      // (tracking scale: (E, W) per row)
         case SNAP_FRAME_INV: l = {1, m.ring}; return true;
         case SNAP_WINDOW: l = {1, (int64_t)m.n_total - m.keep}; return true;
+        case SNAP_ORIGIN: l = {1, 1}; return true;      // (int32, moved like floats: select and concat cut it by rows, the join adds to it)
         default: return false;
     }
 }
 
 inline const char* snap_kind_name(int32_t kind) {
-    static const char* const names[] = {"?", "c", "sumsq", "frame_inv", "hist", "h", "cell", "slot", "window"};
-    return kind >= SNAP_C && kind <= SNAP_WINDOW ? names[kind] : names[0];
+    static const char* const names[] = {"?", "c", "sumsq", "frame_inv", "hist", "h", "cell", "slot", "window", "origin"};
+    return kind >= SNAP_C && kind <= SNAP_KIND_MAX ? names[kind] : names[0];
 }
 inline std::string snap_seg_name(const SnapSeg& s) { return std::string(snap_kind_name(s.kind)) + "[" + std::to_string(s.index) + "]"; }
 

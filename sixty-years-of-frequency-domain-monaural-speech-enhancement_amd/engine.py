@@ -176,23 +176,28 @@ class Engine:
 
     SE_CFG_STREAM_SLIDING = 1 << 17      # include/se_engine.h
     SE_CFG_DCCRN_ROW_ENDS = 1 << 18
+    SE_CFG_STREAM_ROW_ORIGINS = 1 << 19
 
     def __init__(self, model, device=0, max_batch=1, max_samples=64000, p_in=1.0, p_out=1.0,
-                 n_fft=0, hop=0, win=0, graphs=False, flags=0, sliding_stream=False, row_ends=False):
+                 n_fft=0, hop=0, win=0, graphs=False, flags=0, sliding_stream=False, row_ends=False,
+                 row_origins=False):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.model = model
         cfg = _lib.SeConfig(_lib.MODEL_IDS[model], device, max_batch, max_samples, p_in, p_out, n_fft, hop, win,
                             (1 if graphs else 0) | int(flags) | (self.SE_CFG_STREAM_SLIDING if sliding_stream else 0) |
-                            (self.SE_CFG_DCCRN_ROW_ENDS if row_ends else 0))
+                            (self.SE_CFG_DCCRN_ROW_ENDS if row_ends else 0) | (self.SE_CFG_STREAM_ROW_ORIGINS if row_origins else 0))
         # SE_CFG_GRAPHS | model-specific SE_CFG_* bits | SE_CFG_STREAM_SLIDING (frame-online streams may outlive max_samples) |
-        # SE_CFG_DCCRN_ROW_ENDS (DCCRN's look-ahead decoder in enhance_long_ragged: rows cleared behind their own ends, layer by layer)
+        # SE_CFG_DCCRN_ROW_ENDS (DCCRN's look-ahead decoder in enhance_long_ragged: rows cleared behind their own ends, layer by layer) |
+        # SE_CFG_STREAM_ROW_ORIGINS (the cLN networks and FullSubNet with the cumulative norm: a frame origin per stream row, which
+        # StreamSnapshot.join moves along - the join refuses these models without it)
         if self._lib.se_engine_create(C.byref(cfg), C.byref(self._h)):
             raise EngineError(self._lib.se_last_error(None).decode())
         self.device = device
         self.max_batch, self.max_samples = max_batch, max_samples
         self.sliding_stream = bool(cfg.flags & self.SE_CFG_STREAM_SLIDING)
         self.row_ends = bool(cfg.flags & self.SE_CFG_DCCRN_ROW_ENDS)
+        self.row_origins = bool(cfg.flags & self.SE_CFG_STREAM_ROW_ORIGINS)
         self.finalized = False
         self._stream_batch = 0          # rows of the open frame-online stream (0 = none)
 

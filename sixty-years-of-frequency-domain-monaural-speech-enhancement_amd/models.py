@@ -31,11 +31,14 @@ class _EngineModule:
     p_out = 1.0
 
     def __init__(self, device=0, max_batch=1, max_samples=64000, p_in=None, p_out=None, graphs=False, flags=0,
-                 sliding_stream=False, row_ends=False):
+                 sliding_stream=False, row_ends=False, row_origins=False):
         # model-specific SE_CFG_* bits (include/se_engine.h); sliding_stream: SE_CFG_STREAM_SLIDING, frame-online streams of
         # this engine keep a sliding window of their input and may outlive max_samples; row_ends: SE_CFG_DCCRN_ROW_ENDS, DCCRN
-        # (look-ahead decoder) alone - enhance_long_ragged then accepts it (the engine refuses the bit for every other model)
-        self._flags = flags | (Engine.SE_CFG_STREAM_SLIDING if sliding_stream else 0) | (Engine.SE_CFG_DCCRN_ROW_ENDS if row_ends else 0)
+        # (look-ahead decoder) alone - enhance_long_ragged then accepts it (the engine refuses the bit for every other model);
+        # row_origins: SE_CFG_STREAM_ROW_ORIGINS, the cLN networks and FullSubNet with the cumulative norm alone - a frame origin per
+        # stream row, with which StreamSnapshot.join accepts them
+        self._flags = (flags | (Engine.SE_CFG_STREAM_SLIDING if sliding_stream else 0) | (Engine.SE_CFG_DCCRN_ROW_ENDS if row_ends else 0) |
+                       (Engine.SE_CFG_STREAM_ROW_ORIGINS if row_origins else 0))
         self._graphs = graphs          # replay enhance_batch as a hipGraph per shape (small, launch-bound batches)
         self._device = device
         self._max_batch = max_batch
@@ -305,7 +308,7 @@ class CTSNet:
         self.engine = Engine('ctsnet', kw.get('device', 0), kw.get('max_batch', 1), kw.get('max_samples', 64000),
                              kw.get('p_in', 1.0), kw.get('p_out', 1.0), graphs=kw.get('graphs', False),
                              flags=kw.get('flags', 0) | self._stage2._flags, sliding_stream=kw.get('sliding_stream', False),
-                             row_ends=kw.get('row_ends', False))
+                             row_ends=kw.get('row_ends', False), row_origins=kw.get('row_origins', False))
         self.engine.load_state_dict(sd)
         return self
 

@@ -15,7 +15,8 @@ streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, 
   resampler's (se_resampler_save / se_resampler_restore), `swapped_push_ms` a whole restore -> push -> save at the source rate, and
   `resampler_snapshot_bytes` stands beside `snapshot_bytes`.
 --staggered N: N callers that arrive one hop apart, one frame per push each (models: crn,dccrn unless --models names others that
-  StreamSnapshot.join accepts).  Every caller streams alone past its left edge and is parked; then the same N snapshots are served twice,
+  StreamSnapshot.join accepts; ctsnet_new, taylorsenet_new, g2net_new and fullsubnet_cum get engines with `row_origins=True`,
+  SE_CFG_STREAM_ROW_ORIGINS, without which the join refuses them).  Every caller streams alone past its left edge and is parked; then the same N snapshots are served twice,
   for the same frames: by turns at batch 1 (restore -> push -> save per caller and frame: `by_turns_ms`), and joined into one group
   (StreamSnapshot.join, `join_ms` once; then one push of N rows per frame: `joined_ms`, and `joined_swapped_ms` when the group is itself
   restored and saved around every push, as on an engine that serves other groups too).  All three are milliseconds per frame per
@@ -37,6 +38,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import se_amd  # noqa: E402,F401
 from se_amd import synth  # noqa: E402
 
+ROW_ORIGINS = ('ctsnet_new', 'taylorsenet_new', 'g2net_new', 'fullsubnet_cum')
 SEEDS = {'crn': 12, 'lstm': 11, 'gcrn': 16, 'dpcrn': 13, 'dccrn': 14, 'taylorsenet_new': 19, 'g2net_new': 20}
 
 
@@ -190,11 +192,12 @@ def time_staggered(name, N, ticks=100):
     """--staggered: N callers one hop apart, by turns at batch 1 and joined into one group; prints the result line"""
     import torch
     from se_amd.engine import StreamSnapshot
-    hop = {'dccrn': 128, 'dccrn_snr': 128}.get(name, 160)
-    n_fft, lag = (320 if hop == 160 else 512), (6 if name == 'dccrn' else 0)
+    hop = {'dccrn': 128, 'dccrn_snr': 128, 'fullsubnet_cum': 256}.get(name, 160)
+    n_fft, lag = (320 if hop == 160 else 512), {'dccrn': 6, 'fullsubnet_cum': 2}.get(name, 0)
     edge = max(1, -(-(n_fft // 2) // hop), 0 if hop >= n_fft // 2 else -(-n_fft // hop) - 1 + lag)      # csrc/stream_join.h
     n0 = (edge + 1) * hop + n_fft // 2 + 1                 # the newest caller is two frames past its left edge when the group forms
-    eng = build(name, N, 16000, sliding_stream=True).engine
+    # the models whose state counts frames are joined on engines that keep a frame origin per row (SE_CFG_STREAM_ROW_ORIGINS)
+    eng = build(name, N, 16000, sliding_stream=True, **({'row_origins': True} if name in ROW_ORIGINS else {})).engine
     L = n0 + (N - 1 + 2 * ticks) * hop
     x = torch.from_numpy(np.stack([synth.synth_clip(900 + b, 'speech', L) for b in range(N)])).cuda()
     c = eng.rms_scale(x[:, :16000].contiguous())
