@@ -118,7 +118,8 @@ enum se_model_id {
 #define SE_CFG_DCCRN_ROW_ENDS (1 << 18)
 /* Frame-online streams of the models whose state counts frames from the start of the stream - SE_MODEL_CTSNET, SE_MODEL_G2NET and
  * SE_MODEL_TAYLORSENET (the cumulative LayerNorm divides by the frames so far, the TCM rings are indexed by the frame), and
- * SE_MODEL_FULLSUBNET with SE_CFG_FSN_CUMULATIVE and without SE_CFG_FSN_GRU (the cumulative Laplace norms, the look-ahead skip):
+ * SE_MODEL_FULLSUBNET with SE_CFG_FSN_CUMULATIVE or SE_CFG_FSN_CUM_LAYERNORM and without SE_CFG_FSN_GRU (the cumulative norms, the
+ * look-ahead skip):
  * the engine keeps one int32 per row on the device, the row's frame ORIGIN, and every kernel that read the group's frame index t
  * reads the row's own index t - origin[b] instead.  se_stream_begin / _begin_running / _begin_tracking zero the origins; a parked
  * stream carries them (a segment of its own in the snapshot); se_stream_state_join adds shift / hop to the origins of every part
@@ -129,6 +130,17 @@ enum se_model_id {
  * computes without.  se_engine_create fails for any other model or configuration.  Like every model bit it is part of a parked
  * stream's identity (se_stream_restore / _state_select / _state_concat / _state_join compare it). */
 #define SE_CFG_STREAM_ROW_ORIGINS (1 << 19)
+/* FullSubNet with norm_type = "offline_gaussian_norm" (FullSubNet/fullsubnet_net_sa/base_model.py:242-255, selected at :296-308):
+ * (x - mean) / (std + 1e-5), mean and the unbiased std (torch.std) over the whole utterance, the two look-ahead pad frames included
+ * (model.py:79 pads before :84 norms).  Like offline_laplace_norm it spans the utterance: nothing streams, se_stream_begin and
+ * se_enhance_long refuse the engine and name SE_CFG_FSN_CUM_LAYERNORM.  Combines with SE_CFG_FSN_GRU. */
+#define SE_CFG_FSN_GAUSSIAN (1 << 20)
+/* FullSubNet with norm_type = "cumulative_layer_norm" (base_model.py:258-294): every input minus its running mean, over its running
+ * standard deviation, both over the frames seen so far.  Causal up to look_ahead = 2 frames as SE_CFG_FSN_CUMULATIVE is: se_stream_*,
+ * the parked-stream calls, se_enhance_long and se_enhance_long_ragged accept the engine (without SE_CFG_FSN_GRU, which decodes offline
+ * only), and so does SE_CFG_STREAM_ROW_ORIGINS.  A stream carries two running sums (x, x^2) per utterance and per sub-band sequence.
+ * At most one of SE_CFG_FSN_CUMULATIVE, SE_CFG_FSN_GAUSSIAN, SE_CFG_FSN_CUM_LAYERNORM; se_engine_create fails for any other model. */
+#define SE_CFG_FSN_CUM_LAYERNORM (1 << 21)
 
 typedef struct se_config {
     int32_t model;        /* enum se_model_id */
@@ -618,7 +630,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise; + se_resampler_state_join: likewise; + the flag bit SE_CFG_DCCRN_ROW_ENDS: no new entry point, same number; + the flag bit SE_CFG_STREAM_ROW_ORIGINS: likewise, and a snapshot segment kind only engines with the bit write) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise; + se_resampler_state_join: likewise; + the flag bit SE_CFG_DCCRN_ROW_ENDS: no new entry point, same number; + the flag bit SE_CFG_STREAM_ROW_ORIGINS: likewise, and a snapshot segment kind only engines with the bit write; + the flag bits SE_CFG_FSN_GAUSSIAN, SE_CFG_FSN_CUM_LAYERNORM: no new entry point, same number) */
 
 #ifdef __cplusplus
 }

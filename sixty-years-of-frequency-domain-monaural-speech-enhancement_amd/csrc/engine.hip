@@ -306,6 +306,7 @@ static std::unique_ptr<Model> make_model(int id, EngineCtx& c) {
 // by default; with a fifth stream in the process (caller's + three auxiliary + this one) two of them shared a queue and G2Net's
 // three-stream fork, built later in the same process, ran slower than on one stream (0.448 -> 0.417 in bench.py's zoo).
 static hipStream_t twin_stream(int dev, int i = 0) { return EngineCtx::shared_aux(dev, i); }
+static std::string why_not_causal(const se_engine* e);
 
 int se_engine_create(const se_config* cfg, se_engine** out) {
     se_engine* e = nullptr;
@@ -336,13 +337,23 @@ int se_engine_create(const se_config* cfg, se_engine** out) {
         SE_CHECK(!(cfg->flags & SE_CFG_DCCRN_ROW_ENDS) || !(cfg->flags & SE_CFG_DCCRN_CAUSAL_DEC),
                  "SE_CFG_DCCRN_ROW_ENDS does not combine with SE_CFG_DCCRN_CAUSAL_DEC: the causal decoder looks back, not ahead, and "
                  "se_enhance_long_ragged accepts it without the bit");
+        // (FullSubNet's norm_type, base_model.py:296-308: offline_laplace_norm is no bit; the other three exclude one another)
+        {
+            const uint32_t norms = SE_CFG_FSN_GAUSSIAN | SE_CFG_FSN_CUM_LAYERNORM;
+            SE_CHECK(!(cfg->flags & norms) || cfg->model == SE_MODEL_FULLSUBNET,
+                     "SE_CFG_FSN_GAUSSIAN and SE_CFG_FSN_CUM_LAYERNORM are bits of SE_MODEL_FULLSUBNET (its norm_type, "
+                     "offline_gaussian_norm / cumulative_layer_norm): no other model takes them");
+            const int nnorm = !!(cfg->flags & SE_CFG_FSN_CUMULATIVE) + !!(cfg->flags & SE_CFG_FSN_GAUSSIAN) + !!(cfg->flags & SE_CFG_FSN_CUM_LAYERNORM);
+            SE_CHECK(cfg->model != SE_MODEL_FULLSUBNET || nnorm <= 1,
+                     "FullSubNet has one norm_type: at most one of SE_CFG_FSN_CUMULATIVE, SE_CFG_FSN_GAUSSIAN and SE_CFG_FSN_CUM_LAYERNORM");
+        }
         // (per-row frame origins are read by the kernels of the models whose state counts frames, and by nothing else)
         if (cfg->flags & SE_CFG_STREAM_ROW_ORIGINS) {
             const bool cln = cfg->model == SE_MODEL_CTSNET || cfg->model == SE_MODEL_G2NET || cfg->model == SE_MODEL_TAYLORSENET;
-            const bool fsn = cfg->model == SE_MODEL_FULLSUBNET && (cfg->flags & SE_CFG_FSN_CUMULATIVE) && !(cfg->flags & SE_CFG_FSN_GRU);
+            const bool fsn = cfg->model == SE_MODEL_FULLSUBNET && (cfg->flags & (SE_CFG_FSN_CUMULATIVE | SE_CFG_FSN_CUM_LAYERNORM)) && !(cfg->flags & SE_CFG_FSN_GRU);
             SE_CHECK(cln || fsn,
                      "SE_CFG_STREAM_ROW_ORIGINS is a bit of the models whose stream state counts frames - SE_MODEL_CTSNET, SE_MODEL_G2NET, "
-                     "SE_MODEL_TAYLORSENET, and SE_MODEL_FULLSUBNET with SE_CFG_FSN_CUMULATIVE and without SE_CFG_FSN_GRU: no other "
+                     "SE_MODEL_TAYLORSENET, and SE_MODEL_FULLSUBNET with SE_CFG_FSN_CUMULATIVE or SE_CFG_FSN_CUM_LAYERNORM and without SE_CFG_FSN_GRU: no other "
                      "configuration takes it (the others are joined without it)");
             e->strm.origin.alloc((size_t)e->ctx.max_batch);
             SE_HIP(hipMemset(e->strm.origin.get(), 0, (size_t)e->ctx.max_batch * sizeof(int32_t)));
@@ -840,7 +851,12 @@ static int stream_begin_impl(se_engine* e, int32_t batch, int32_t max_chunk_fram
         if (tracking)
             SE_CHECK(std::isfinite(tau) && tau >= 0.f,
                      "se_stream_begin_tracking: tau_samples has to be a finite number >= 0 (0: never forget), got " + std::to_string(tau));
-        SE_CHECK(e->model->stream_supported(), "this model has no frame-online mode (CRN, LSTM, GCRN, DPCRN, DCCRN, FullSubNet with the cumulative norm and the cLN `_new` weights of CTSNet / TaylorSENet / G2Net have)");
+        // (FullSubNet is in the list of those that have one - with a cumulative norm and the LSTM: a refused FullSubNet is told which of
+        // the two it lacks)
+        SE_CHECK(e->model->stream_supported(),
+                 std::string("this model has no frame-online mode (CRN, LSTM, GCRN, DPCRN, DCCRN, FullSubNet with a cumulative norm and "
+                             "without the GRU, and the cLN `_new` weights of CTSNet / TaylorSENet / G2Net have)") +
+                     (e->cfg.model == SE_MODEL_FULLSUBNET ? ": " + why_not_causal(e) : std::string()));
         SE_CHECK(batch >= 1 && batch <= e->ctx.max_batch, "batch exceeds max_batch given at create");
         check_stream_geometry(e);
         const StftGeom& g = e->ctx.geom;
@@ -987,6 +1003,9 @@ static std::string why_not_causal(const se_engine* e) {
             return "Uformer attends over every frame of the utterance and its dilated convolutions look ahead in time";
         case SE_MODEL_FULLSUBNET:
             if (e->cfg.flags & SE_CFG_FSN_GRU) return "the GRU FullSubNet (SE_CFG_FSN_GRU) has no frame-online mode";
+            if (e->cfg.flags & SE_CFG_FSN_GAUSSIAN)
+                return "FullSubNet with offline_gaussian_norm (SE_CFG_FSN_GAUSSIAN) subtracts a mean and divides by a standard deviation over "
+                       "the whole utterance (cumulative_layer_norm, SE_CFG_FSN_CUM_LAYERNORM, standardises by the frames so far and streams)";
             return "FullSubNet with offline_laplace_norm divides every frame by a mean over the whole utterance "
                    "(cumulative_laplace_norm, SE_CFG_FSN_CUMULATIVE, does not)";
         case SE_MODEL_CTSNET:
@@ -1701,6 +1720,9 @@ std::string join_counts_frames(const se_engine* e) {
             return std::string("the cumulative LayerNorm divides its running sums by the number of frames so far, and the TCM rings are indexed by the "
                                "absolute frame (StreamCtx::t0, k_tcm_stream.hip)") + hint;
         case SE_MODEL_FULLSUBNET:
+            if (e->cfg.flags & SE_CFG_FSN_CUM_LAYERNORM)
+                return std::string("the cumulative LayerNorm of FullSubNet divides its running sums by the absolute frame index (launch_fsn_cln_fb / "
+                                   "launch_fsn_cln_sb), and the look-ahead skips the steps before frame 2 by it") + hint;
             return std::string("the cumulative Laplace norm divides its running sums by the absolute frame index (launch_fsn_cum_fb / launch_fsn_cum_sb), "
                                "and the look-ahead skips the steps before frame 2 by it") + hint;
         default:

@@ -1,6 +1,7 @@
-// FullSubNet's private kernels: the two Laplace norms (utterance mean, cumulative), the sub-band unfold and the mask back end,
-// offline and frame-online.  Reference lines as in model_fullsubnet.hip: FullSubNet/fullsubnet_net_sa/model.py:68-118,
-// base_model.py:13-42 (unfold), :197-209 (offline_laplace_norm), :212-240 (cumulative_laplace_norm),
+// FullSubNet's private kernels: the four norms of norm_wrapper (utterance mean, cumulative mean, utterance mean / std, cumulative
+// mean / std), the sub-band unfold and the mask back end, offline and frame-online.  Reference lines as in model_fullsubnet.hip:
+// FullSubNet/fullsubnet_net_sa/model.py:68-118, base_model.py:13-42 (unfold), :197-209 (offline_laplace_norm), :212-240
+// (cumulative_laplace_norm), :242-255 (offline_gaussian_norm), :258-294 (cumulative_layer_norm),
 // fullsubnet_sa_decode_vb.py:56-66 (the complex mask and the decompress, applied in the script).
 //
 // Layouts (time-major, sequences contiguous): full band [T+2][257][B]; sub bands [T+2][32][257*B], sequence s = n*B + b is
@@ -169,6 +170,159 @@ __global__ __launch_bounds__(256) void fsn_cum_sb_kernel(float* __restrict__ sb,
     }
     if (csum) csum[s] = run;
 }
+// ---- offline_gaussian_norm (base_model.py:242-255): (x - mean) / (std + 1e-5), mean and the unbiased std (torch.std: N - 1) over the
+// whole utterance.  Both moments in ONE pass over a [rows][B] matrix (utterance = innermost index: the full band is [Tp * 257][B], the
+// sub bands [Tp * 32 * 257][B]), accumulated in float64 (the square of a float is exact there, so S2 - N mean^2 cancels nothing
+// that float32 holds), in the two deterministic stages of fsn_colsum / fsn_finish_mean: per-block partials in a fixed order, then
+// a fixed-order sum - no atomics, repeated decodes are bit-identical.  part [gridDim.x][2][B] float64.
+// ragged batch: rows are t-major, frame_rows of them per frame; utterance b only counts its own tlen[b] + LA frames
+__global__ __launch_bounds__(256) void fsn_moments_kernel(const float* __restrict__ x, long rows, int B, double* __restrict__ part,
+                                                          const int* __restrict__ tlen, long frame_rows) {
+    __shared__ double sh[2][256];
+    // thread handles column (tid % B) of rows tid / B + k * (256 / B), as fsn_colsum_kernel
+    const int per = 256 / B;
+    const int b = threadIdx.x % B, r0 = threadIdx.x / B;
+    double s1 = 0.0, s2 = 0.0;
+    if (per > 0 && r0 < per) {
+        long rmax = rows;
+        if (tlen && (long)(tlen[b] + LA) * frame_rows < rows) rmax = (long)(tlen[b] + LA) * frame_rows;
+#pragma unroll 4
+        for (long r = (long)blockIdx.x * per + r0; r < rmax; r += (long)gridDim.x * per) {
+            const double v = x[r * B + b];
+            s1 += v;
+            s2 += v * v;
+        }
+    }
+    sh[0][threadIdx.x] = s1;
+    sh[1][threadIdx.x] = s2;
+    __syncthreads();
+    if (per > 0 && r0 == 0) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int k = 0; k < per; ++k) {
+            t1 += sh[0][k * B + b];
+            t2 += sh[1][k * B + b];
+        }
+        part[((long)blockIdx.x * 2) * B + b] = t1;
+        part[((long)blockIdx.x * 2 + 1) * B + b] = t2;
+    }
+}
+// part [FSN_SUM_BLOCKS][2][B] -> stat[b] = mean, stat[B + b] = std + 1e-5 (float32, the divisor of :253);  N = rows, or the row's own
+// (tlen[b] + LA) * frame_rows;  var = (S2 - N mean^2) / (N - 1) in float64
+__global__ void fsn_finish_gauss_kernel(const double* __restrict__ part, float* __restrict__ stat, long rows, int B,
+                                        const int* __restrict__ tlen, long frame_rows) {
+    const int b = threadIdx.x;
+    if (b >= B) return;
+    long cnt = rows;
+    if (tlen && (long)(tlen[b] + LA) * frame_rows < rows) cnt = (long)(tlen[b] + LA) * frame_rows;
+    const double N = (double)cnt;
+    double s1 = 0.0, s2 = 0.0;
+    for (int k = 0; k < FSN_SUM_BLOCKS; ++k) {
+        s1 += part[((long)k * 2) * B + b];
+        s2 += part[((long)k * 2 + 1) * B + b];
+    }
+    const double mean = s1 / N;
+    const double var = fmax(s2 - N * mean * mean, 0.0) / fmax(N - 1.0, 1.0);
+    stat[b] = (float)mean;
+    stat[B + b] = (float)sqrt(var) + 1e-5f;
+}
+// y[i] = (x[i] - mean[i % B]) / (std[i % B] + 1e-5)   for time-major tensors whose innermost index is the utterance
+__global__ __launch_bounds__(256) void fsn_gauss_apply_kernel(const float* __restrict__ x, float* __restrict__ y, long n, int B,
+                                                              const float* __restrict__ stat) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int b = (int)(i % B);
+    y[i] = (x[i] - stat[b]) / stat[B + b];
+}
+
+// ---- cumulative_layer_norm (base_model.py:258-294): the two-sum forms of the cumulative kernels above.  Running float32 sums of x and
+// x^2 in the reference's order (the features of a frame first, then over the frames), and the reference's expression as written
+// (:285-287, :292) - no fused multiply-add, which would round differently than the tensor expression does:
+//   mean = S1 / n;  var = (S2 - 2 mean S1) / n + mean^2;  std = sqrt(var + EPSILON);  y = (x - mean) / std
+// A stream that starts with frames of zeros has S1 = S2 = 0: mean = 0, std = sqrt(EPSILON), y = exact zeros.
+__device__ __forceinline__ void fsn_cln_stats(float s1, float s2, float cnt, float& mean, float& sd) {
+#pragma clang fp contract(off)
+    mean = s1 / cnt;
+    const float twice = 2.f * mean;
+    const float cross = twice * s1;
+    const float mm = mean * mean;
+    const float var = (s2 - cross) / cnt + mm;
+    sd = sqrtf(var + FSN_EPS);
+}
+// full band: x / y [n][257][B] time-major, one workgroup per utterance; csum / csum2 [B]: the running sums of x and x^2
+__global__ __launch_bounds__(256) void fsn_cln_fb_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int B,
+                                                         float* __restrict__ csum, float* __restrict__ csum2, int t_first,
+                                                         const int32_t* __restrict__ origin) {
+    __shared__ float part[2][4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (origin) t_first -= origin[b];      // the row's own frame index (one workgroup per row: uniform, read once)
+    const bool carry = csum && t_first > 0;
+    float run = carry ? csum[b] : 0.f, run2 = carry ? csum2[b] : 0.f;
+    for (int t = 0; t < n; ++t) {
+        const float* xr = x + (long)t * NBIN * B + b;
+        const float v0 = xr[(long)tid * B], v1 = tid + 256 < NBIN ? xr[(long)(tid + 256) * B] : 0.f;
+        float s, q;
+        {
+#pragma clang fp contract(off)
+            const float q0 = v0 * v0, q1 = v1 * v1;
+            s = v0 + v1;
+            q = q0 + q1;
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            s += __shfl_down(s, o, 64);
+            q += __shfl_down(q, o, 64);
+        }
+        __syncthreads();
+        if ((tid & 63) == 0) {
+            part[0][tid >> 6] = s;
+            part[1][tid >> 6] = q;
+        }
+        __syncthreads();
+        run += (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
+        run2 += (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
+        float mean, sd;
+        fsn_cln_stats(run, run2, (float)NBIN * (float)(t_first + t + 1), mean, sd);
+        float* yr = y + (long)t * NBIN * B + b;
+        yr[(long)tid * B] = (v0 - mean) / sd;
+        if (tid + 256 < NBIN) yr[(long)(tid + 256) * B] = (v1 - mean) / sd;
+    }
+    if (csum && tid == 0) {
+        csum[b] = run;
+        csum2[b] = run2;
+    }
+}
+// sub bands: sb [n][32][S] in place, one thread per sequence s (consecutive threads read consecutive s: coalesced); csum / csum2 [S]
+// origin (optional, [B]): sequence s = n * B + b belongs to row s % B, whose own frame index is t_first - origin[s % B]
+__global__ __launch_bounds__(256) void fsn_cln_sb_kernel(float* __restrict__ sb, int n, int S, float* __restrict__ csum,
+                                                         float* __restrict__ csum2, int t_first, const int32_t* __restrict__ origin,
+                                                         int B) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= S) return;
+    if (origin) t_first -= origin[s % B];
+    const bool carry = csum && t_first > 0;
+    float run = carry ? csum[s] : 0.f, run2 = carry ? csum2[s] : 0.f;
+    for (int t = 0; t < n; ++t) {
+        float* xr = sb + (long)t * SBW * S + s;
+        float v[SBW], sum = 0.f, sq = 0.f;
+#pragma unroll
+        for (int k = 0; k < SBW; ++k) {
+#pragma clang fp contract(off)
+            v[k] = xr[(long)k * S];
+            const float q = v[k] * v[k];
+            sum += v[k];
+            sq += q;
+        }
+        run += sum;
+        run2 += sq;
+        float mean, sd;
+        fsn_cln_stats(run, run2, (float)SBW * (float)(t_first + t + 1), mean, sd);
+#pragma unroll
+        for (int k = 0; k < SBW; ++k) xr[(long)k * S] = (v[k] - mean) / sd;
+    }
+    if (csum) {
+        csum[s] = run;
+        csum2[s] = run2;
+    }
+}
 // frame-online: mask of network step tau (maskT [ns][2][S], s = n B + b) applied to the spectrum of frame tau - LA, which sits in
 // column col0 + tau of the chunk window ([B][2][257][Tw]); frames before the start of the stream (gt0 + tau < LA) do not exist
 __global__ __launch_bounds__(256) void fsn_stream_apply_kernel(const float* __restrict__ maskT, const float* __restrict__ spec,
@@ -231,6 +385,33 @@ void launch_fsn_cum_fb(const float* x, float* y, int n, int B, float* csum, int 
 void launch_fsn_cum_sb(float* sb, int n, int S, float* csum, int t_first, hipStream_t st, const int32_t* origin) {
     SE_CHECK(!origin || (S >= NBIN && S % NBIN == 0), "launch_fsn_cum_sb: per-row origins need S = 257 * B sequences");
     hipLaunchKernelGGL(fsn_cum_sb_kernel, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, t_first, origin, S / NBIN);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_moments(const float* x, long rows, int B, double* part, const int* tlen, long frame_rows, hipStream_t st) {
+    SE_CHECK(B >= 1 && B <= 256, "FullSubNet batch per call is limited to 256 utterances");
+    SE_CHECK(rows >= 1 && frame_rows >= 1 && rows % frame_rows == 0, "launch_fsn_moments: rows is a whole number of frames");
+    hipLaunchKernelGGL(fsn_moments_kernel, dim3(FSN_SUM_BLOCKS), dim3(256), 0, st, x, rows, B, part, tlen, frame_rows);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_finish_gauss(const double* part, float* stat, long rows, int B, const int* tlen, long frame_rows, hipStream_t st) {
+    SE_CHECK(B >= 1 && B <= 256, "FullSubNet batch per call is limited to 256 utterances");
+    hipLaunchKernelGGL(fsn_finish_gauss_kernel, dim3(1), dim3(256), 0, st, part, stat, rows, B, tlen, frame_rows);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_gauss_apply(const float* x, float* y, long n, int B, const float* stat, hipStream_t st) {
+    hipLaunchKernelGGL(fsn_gauss_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, n, B, stat);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_cln_fb(const float* x, float* y, int n, int B, float* csum, float* csum2, int t_first, hipStream_t st,
+                       const int32_t* origin) {
+    SE_CHECK(!csum == !csum2, "launch_fsn_cln_fb: the two running sums come together");
+    hipLaunchKernelGGL(fsn_cln_fb_kernel, dim3(B), dim3(256), 0, st, x, y, n, B, csum, csum2, t_first, origin);
+    SE_HIP(hipGetLastError());
+}
+void launch_fsn_cln_sb(float* sb, int n, int S, float* csum, float* csum2, int t_first, hipStream_t st, const int32_t* origin) {
+    SE_CHECK(!csum == !csum2, "launch_fsn_cln_sb: the two running sums come together");
+    SE_CHECK(!origin || (S >= NBIN && S % NBIN == 0), "launch_fsn_cln_sb: per-row origins need S = 257 * B sequences");
+    hipLaunchKernelGGL(fsn_cln_sb_kernel, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, csum2, t_first, origin, S / NBIN);
     SE_HIP(hipGetLastError());
 }
 void launch_fsn_stream_apply(const float* maskT, const float* spec, float* est, int B, int Tw, int ns, int col0, int gt0,

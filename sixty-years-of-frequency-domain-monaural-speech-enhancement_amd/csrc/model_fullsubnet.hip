@@ -1,7 +1,8 @@
 // FullSubNet on the MI355X engine.
 //
 // Reference: FullSubNet/fullsubnet_net_sa/model.py:68-118 (Model.forward), base_model.py:13-42 (unfold),
-// :197-209 (offline_laplace_norm), sequence_model.py:66-84; constructor and decode loop
+// :197-209 (offline_laplace_norm), :212-240 (cumulative_laplace_norm), :242-255 (offline_gaussian_norm), :258-294
+// (cumulative_layer_norm), selected at :296-308; sequence_model.py:66-84; constructor and decode loop
 // FullSubNet/fullsubnet_sa_decode_vb.py:11-24, :37-72 (complex mask applied in the script, :56-61).
 //
 // Batch semantics: the reference only ever decodes B = 1 and its forward runs the training-time `drop_band`
@@ -41,7 +42,10 @@ class FullSubNet final : public Model {
         const int S = NBIN * ctx.max_batch;
         // sequence_model = "LSTM" (the decode script's choice, fullsubnet_sa_decode_vb.py:16) or "GRU" (sequence_model.py:36-43)
         const bool gru = (ctx.flags & SE_CFG_FSN_GRU) != 0;
-        cum = (ctx.flags & SE_CFG_FSN_CUMULATIVE) != 0;      // norm_type = "cumulative_laplace_norm" (base_model.py:212-240)
+        // norm_type (base_model.py:296-308; se_engine_create lets at most one of the three bits through)
+        norm = (ctx.flags & SE_CFG_FSN_CUMULATIVE) ? NORM_CUM_LAPLACE
+               : (ctx.flags & SE_CFG_FSN_GAUSSIAN) ? NORM_GAUSSIAN
+               : (ctx.flags & SE_CFG_FSN_CUM_LAYERNORM) ? NORM_CUM_LAYERNORM : NORM_LAPLACE;
         is_gru = gru;
         auto load = [&](const std::string& p, int layer, int I, int H) {
             return gru ? load_gru(sd, p, layer, "", I, H) : load_lstm(sd, p, layer, "", I, H);
@@ -81,13 +85,14 @@ class FullSubNet final : public Model {
         launch_istft(ctx.geom, b.est, B, T, T, b.frames, b.c, out, out_pitch, L, st);              // :69-72
     }
 
-    // ---- frame-online mode (model.h), with the cumulative norm only: every operator is then causal and the network looks
-    // look_ahead = 2 frames ahead (model.py:79, :117 - the mask of frame t is the output of step t + 2).  A chunk of n new
-    // frames runs n network steps and finalises the estimate of frames [t0 - 2, t0 + n - 2) (stream_lag); the chunk that ends
-    // the stream runs two more steps on the zero frames the offline forward pads.  State: the two running sums of the norms
-    // (per utterance / per sub-band sequence), (h, c) of the four LSTM layers, the last columns of spectrum and estimate.
+    // ---- frame-online mode (model.h), with one of the two cumulative norms only: every operator is then causal and the
+    // network looks look_ahead = 2 frames ahead (model.py:79, :117 - the mask of frame t is the output of step t + 2).  A chunk
+    // of n new frames runs n network steps and finalises the estimate of frames [t0 - 2, t0 + n - 2) (stream_lag); the chunk
+    // that ends the stream runs two more steps on the zero frames the offline forward pads.  State: the running sums of the
+    // norms (per utterance / per sub-band sequence; the cumulative LayerNorm carries two of each, of x and of x^2), (h, c) of
+    // the four LSTM layers, the last columns of spectrum and estimate.
     static constexpr int STREAM_TP_MAX = 64;      // longest window (frames incl. look-ahead) whose sub-band gate tensor is always kept
-    bool stream_supported() const override { return cum && !is_gru; }
+    bool stream_supported() const override { return causal() && !is_gru; }
     int stream_lag() const override { return LA; }
     void stream_begin(int B, int max_chunk, hipStream_t st) override {
         SE_CHECK(STREAM_HC + max_chunk + LA <= STREAM_TP_MAX, "FullSubNet frame-online mode: chunks of at most 58 frames");
@@ -97,8 +102,10 @@ class FullSubNet final : public Model {
         StateLayout lay;
         lay.hist.push_back({1, 2L * NBIN * STREAM_HC});      // spectrum [B][2][NBIN][HC]
         lay.hist.push_back({1, 2L * NBIN * STREAM_HC});      // estimate
-        lay.hist.push_back({1, 1});                          // running sum of the full-band norm [B]
-        lay.hist.push_back({NBIN, 1});                       // ... of the sub-band norm [S], sequence s = n * B + b
+        // running sums of the full-band norm [B], then of the sub-band norm [S], sequence s = n * B + b; the cumulative LayerNorm
+        // carries the sum of x and the sum of x^2 (slots of the same two shapes: the row operations know both)
+        for (int k = 0; k < nsums(); ++k) lay.hist.push_back({1, 1});
+        for (int k = 0; k < nsums(); ++k) lay.hist.push_back({NBIN, 1});
         for (int l = 0; l < 2; ++l) {
             lay.h[l] = lay.c[l] = {512, 1};                        // [H][B]
             lay.h[2 + l] = lay.c[2 + l] = {384L * NBIN, 1};        // [H][S]
@@ -112,7 +119,7 @@ class FullSubNet final : public Model {
         *est = b.est;
     }
     void stream_chunk(int B, int t0, int n, hipStream_t st, bool last) override {
-        SE_CHECK(ss.B == B && ss.hist.size() == 4, "stream_chunk without stream_begin");
+        SE_CHECK(ss.B == B && ss.hist.size() == (size_t)(2 + 2 * nsums()), "stream_chunk without stream_begin");
         const int HC = STREAM_HC, Tw = HC + n, S = NBIN * B;
         const int ns = n + (last ? LA : 0);                 // network steps of this chunk
         SE_CHECK(Tw + LA <= STREAM_TP_MAX, "FullSubNet frame-online mode: chunk too long");
@@ -123,12 +130,14 @@ class FullSubNet final : public Model {
         // magnitudes of the new frames, time-major [ns][257][B]; at the end of the stream two zero frames (model.py:79)
         launch_transpose_akt(b.mag + HC, b.magT, B, NBIN, n, (long)NBIN * Tw, Tw, (long)NBIN * B, B, st);
         if (last) launch_fill(b.magT + (size_t)n * S, (long)LA * S, 0.f, st);
-        launch_fsn_cum_fb(b.magT, b.xfb, ns, B, ss.hist[2], t0, st, ctx.stream_origin);
+        if (norm == NORM_CUM_LAYERNORM) launch_fsn_cln_fb(b.magT, b.xfb, ns, B, ss.hist[2], ss.hist[3], t0, st, ctx.stream_origin);
+        else launch_fsn_cum_fb(b.magT, b.xfb, ns, B, ss.hist[2], t0, st, ctx.stream_origin);
         fb[0].run_stream(b.xfb, b.G, ss.c[0], ss.h[0], b.h[0], ns, B, ss.first, st, pf);
         fb[1].run_stream(b.h[0], b.G, ss.c[1], ss.h[1], b.h[1], ns, B, ss.first, st, pf);
         run_pointwise(fb_fc, b.h[1], 512L * B, B, b.fbo, (long)NBIN * B, B, ns, B, st, pf);
         launch_fsn_build_sb(b.magT, b.fbo, b.sb, B, ns, st);
-        launch_fsn_cum_sb(b.sb, ns, S, ss.hist[3], t0, st, ctx.stream_origin);
+        if (norm == NORM_CUM_LAYERNORM) launch_fsn_cln_sb(b.sb, ns, S, ss.hist[4], ss.hist[5], t0, st, ctx.stream_origin);
+        else launch_fsn_cum_sb(b.sb, ns, S, ss.hist[3], t0, st, ctx.stream_origin);
         sbl[0].run_stream(b.sb, b.G, ss.c[2], ss.h[2], b.h[0], ns, S, ss.first, st, pf);
         sbl[1].run_stream(b.h[0], b.G, ss.c[3], ss.h[3], b.h[1], ns, S, ss.first, st, pf);
         run_pointwise(sb_fc, b.h[1], 384L * S, S, b.maskT, 2L * S, S, ns, S, st, pf);
@@ -145,10 +154,16 @@ class FullSubNet final : public Model {
     StreamState* stream_state() override { return &ss; }
 
   private:
-    bool cum = false, is_gru = false;
+    enum NormKind { NORM_LAPLACE, NORM_CUM_LAPLACE, NORM_GAUSSIAN, NORM_CUM_LAYERNORM };
+    NormKind norm = NORM_LAPLACE;
+    bool is_gru = false;
+    bool causal() const { return norm == NORM_CUM_LAPLACE || norm == NORM_CUM_LAYERNORM; }
+    int nsums() const { return norm == NORM_CUM_LAYERNORM ? 2 : 1; }      // running sums a stream carries per norm
     struct Bufs {
         int B = 0, T = 0;
         float *c, *spec, *mag, *est, *frames, *mu, *mu2, *part;
+        float *stat = nullptr, *stat2 = nullptr;      // offline_gaussian_norm: (mean, std + 1e-5) [2][B] of the full band, of the sub bands
+        double* dpart = nullptr;                      // ... and the float64 partials of its two moments [FSN_SUM_BLOCKS][2][B]
         float *magT, *xfb, *G, *h[2], *cell, *fbo, *sb, *maskT, *maskBT, *hz;
     } cur;
     LstmBig fb[2], sbl[2];
@@ -177,7 +192,7 @@ class FullSubNet final : public Model {
         // gate pre-activations: the full-band layers' [Tp][2048][B]; the sub-band layers' [Tp][1536][S] only when they do not
         // project their inputs inside the step GEMM (51 GB at 128 clips)
         // (a frame-online window - a few frames - always keeps them: the streamed steps go through LstmBig::run_stream)
-        const bool sb_gates = !(fuse_x_on(B) && sbl[0].has_x && sbl[1].has_x) || (cum && Tp <= STREAM_TP_MAX);
+        const bool sb_gates = !(fuse_x_on(B) && sbl[0].has_x && sbl[1].has_x) || (causal() && Tp <= STREAM_TP_MAX);
         b.G = a.alloc_f(sb_gates ? Tp * 1536 * S : Tp * 2048 * (size_t)B);
         b.h[0] = a.alloc_f(Tp * 384 * S);               // also the full-band hidden [Tp][512][B]
         b.h[1] = a.alloc_f(Tp * 384 * S);
@@ -185,6 +200,11 @@ class FullSubNet final : public Model {
         b.hz = a.alloc_f(384 * S);                      // zeros: h_{-1} of the sub-band layer that projects its own input
         b.maskT = a.alloc_f(Tp * 2 * S);
         b.maskBT = a.alloc_f(Tp * 2 * S);
+        if (norm == NORM_GAUSSIAN) {
+            b.stat = a.alloc_f(2 * (size_t)B);
+            b.stat2 = a.alloc_f(2 * (size_t)B);
+            b.dpart = static_cast<double*>(a.alloc((size_t)FSN_SUM_BLOCKS * 2 * B * sizeof(double)));
+        }
         cur = b;
         return cur;
     }
@@ -202,14 +222,23 @@ class FullSubNet final : public Model {
         // ---- full-band model (model.py:84-85): utterance-mean normalisation, LSTM(257->512)x2, Linear + ReLU
         const Ragged* rg = ragged_ctx();
         const int* tlen = rg ? rg->tlen : nullptr;
-        if (!cum) launch_fsn_mean(mag, B, NBIN * T, (float)NBIN * Tp, b.mu, tlen, st);
+        if (norm == NORM_LAPLACE) launch_fsn_mean(mag, B, NBIN * T, (float)NBIN * Tp, b.mu, tlen, st);
         launch_fill(b.magT + (size_t)T * S, (long)LA * S, 0.f, st);                                // look-ahead pad :79 (a kernel, not a memset node: graph-replay safe)
         launch_transpose_akt(mag, b.magT, B, NBIN, T, (long)NBIN * T, T, (long)NBIN * B, B, st);
         const long nfb = (long)Tp * S;
         // (cumulative norm, ragged rows: frames >= tlen[b] are zeros - the STFT wrote them - and everything is causal, so a
         // row's own frames and its two look-ahead frames see exactly what the clip decoded alone sees)
-        if (cum) launch_fsn_cum_fb(b.magT, b.xfb, Tp, B, nullptr, 0, st);
-        else launch_fsn_scale(b.magT, b.xfb, nfb, B, b.mu, st);
+        switch (norm) {
+            case NORM_CUM_LAPLACE: launch_fsn_cum_fb(b.magT, b.xfb, Tp, B, nullptr, 0, st); break;
+            case NORM_CUM_LAYERNORM: launch_fsn_cln_fb(b.magT, b.xfb, Tp, B, nullptr, nullptr, 0, st); break;
+            case NORM_GAUSSIAN:
+                // both moments of the padded magnitudes in one float64 pass (a ragged row: its own tlen[b] + LA frames), then the apply
+                launch_fsn_moments(b.magT, (long)Tp * NBIN, B, b.dpart, tlen, NBIN, st);
+                launch_fsn_finish_gauss(b.dpart, b.stat, (long)Tp * NBIN, B, tlen, NBIN, st);
+                launch_fsn_gauss_apply(b.magT, b.xfb, nfb, B, b.stat, st);
+                break;
+            case NORM_LAPLACE: launch_fsn_scale(b.magT, b.xfb, nfb, B, b.mu, st); break;
+        }
         fb[0].run(b.xfb, b.G, b.cell, b.h[0], Tp, B, st, pf);
         fb[1].run(b.h[0], b.G, b.cell, b.h[1], Tp, B, st, pf);
         run_pointwise(fb_fc, b.h[1], 512L * B, B, b.fbo, (long)NBIN * B, B, Tp, B, st, pf);
@@ -217,8 +246,15 @@ class FullSubNet final : public Model {
         launch_fsn_build_sb(b.magT, b.fbo, b.sb, B, Tp, st);
         const long rows = (long)Tp * SBW * NBIN;
         SE_CHECK(B <= 256, "FullSubNet batch per call is limited to 256 utterances");
-        if (cum) {
+        if (norm == NORM_CUM_LAPLACE) {
             launch_fsn_cum_sb(b.sb, Tp, S, nullptr, 0, st);
+        } else if (norm == NORM_CUM_LAYERNORM) {
+            launch_fsn_cln_sb(b.sb, Tp, S, nullptr, nullptr, 0, st);
+        } else if (norm == NORM_GAUSSIAN) {
+            // the sub-band tensor is read once for its statistics, as the Laplace path reads it, and normalised in place
+            launch_fsn_moments(b.sb, rows, B, b.dpart, tlen, (long)SBW * NBIN, st);
+            launch_fsn_finish_gauss(b.dpart, b.stat2, rows, B, tlen, (long)SBW * NBIN, st);
+            launch_fsn_gauss_apply(b.sb, b.sb, rows * B, B, b.stat2, st);
         } else {
             launch_fsn_colsum(b.sb, rows, B, b.part, tlen, st);
             launch_fsn_finish_mean(b.part, b.mu2, (float)rows, B, tlen, st);

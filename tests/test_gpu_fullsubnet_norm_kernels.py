@@ -1,0 +1,464 @@
+"""GPU: every launch of FullSubNet's Gaussian norm and cumulative LayerNorm (csrc/k_fullsubnet.hip) against float64, one launch at a time
+through csrc/tests/fsn_norm_probe.hip (libse_fsnnormprobe.so), in the manner of tests/test_gpu_model_kernels.py: NaN-filled guard regions
+around every buffer (`untouched()`), NaN in every element a ragged row must not read, and bounds DERIVED from the order of the
+operations - U = 2^-24 (float32) or V = 2^-53 (float64) times the length of the longest chain of roundings - never chosen.
+
+offline_gaussian_norm (FullSubNet/fullsubnet_net_sa/base_model.py:242-255)
+  fsn_moments       part[k][m][b] = sum of x[r][b]^(m+1) over the rows r < rmax(b) with (r // per) % 1024 == k, per = 256 // B, in float64:
+                    a thread adds ceil(rows / (1024 per)) terms, then one thread adds `per` of those -> chain = that + per (+ 1 for the
+                    square, exact in float64 for a float32 x: 48 bits).  |err| <= chain V sum|x^(m+1)|.
+  fsn_finish_gauss  S_m = sum over 1024 partials (chain 1024), mean = S1 / N, var = (S2 - N mean^2) / (N - 1), d = float(sqrt(var)) + 1e-5f.
+                    mean: one float32 rounding.  d: the float64 cancellation error (1030 V S2 + 4 V N mean^2) / (N - 1) through
+                    1 / (2 sd), the rounding of sd to float32 and the float32 addition: 2 roundings.
+  fsn_gauss_apply   (x - mean) / d in float32: 2 roundings of y (the kernel is handed the float32 statistics, the reference uses the same).
+  the three chained against the plain definition (x - mean(x)) / (std(x, ddof=1) + 1e-5) in float64 of the SAME rows: the statistics'
+                    bounds above propagated through y: |dy| <= 3 U |y| + e_mean / d + |y| e_d / d.
+
+cumulative_layer_norm (base_model.py:258-294), float32 running sums, the expression as written
+  S1, S2 after frame t: a frame's sum has `tree` additions on its longest chain (full band: v0 + v1, six shuffles, two partial adds = 9;
+                    sub bands: 32 sequential), the running sum one more per frame, S2 one more for the square:
+                    a1 = (tree + frames + 1) U sum|x|,  a2 = (tree + frames + 2) U sum x^2.
+  mean = S1 / n:    e_mean = a1 / n + U |mean|
+  cross = (2 mean) S1:  e_cross = 2 (e_mean S1 + |mean| a1) + U |cross|           (2 mean is exact)
+  diff = S2 - cross:    e_diff = a2 + e_cross + U |diff|
+  q = diff / n:         e_q = e_diff / n + U |q|
+  mm = mean mean:       e_mm = 2 |mean| e_mean + U mm
+  var = q + mm:         e_var = e_q + e_mm + U |var|  -  THE CANCELLING STEP: |q| and mm are each about mean^2, var may be far smaller
+  v = var + EPS:        e_v = e_var + U v
+  sd = sqrt(v):         e_sd = sqrt(v) - sqrt(v - e_v) + U sd         (the exact image of [v - e_v, v + e_v], larger side; needs e_v < v)
+  y = (x - mean) / sd:  e_y = (e_mean + U |x - mean|) / (sd - e_sd) + |x - mean| e_sd / (sd (sd - e_sd)) + U |y|
+  The test prints the worst error / bound of every case.  A frame of zeros at the start has S1 = S2 = 0: every term above is 0 and the
+  bound collapses to TINY - y must be an exact zero, and is asserted to be.
+  Chunked runs ([1, 3, 5]) and rows with a frame origin ({0, 2, -3}) are held to BIT identity with the one-shot run / the row run alone
+  at its shifted t_first: same operations in the same order.
+
+`test_bounds_hold_for_a_float32_restatement` (CPU) evaluates the cumulative kernels' arithmetic in numpy float32, in their order, and holds
+it to the same bounds: a bound that the intended arithmetic itself misses would be caught without a GPU."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'sixty-years-of-frequency-domain-monaural-speech-enhancement_amd')
+PROBE_LIB = os.environ.get('SE_FSNNORMPROBE_LIB') or os.path.join(PKG, 'libse_fsnnormprobe.so')
+
+U, V, TINY = 2.0 ** -24, 2.0 ** -53, 2.0 ** -126
+f32 = np.float32
+NBIN, LA, SBW, SUM_BLOCKS = 257, 2, 32, 1024
+EPS32 = float(np.finfo(np.float32).eps)          # FSN_EPS
+MU_EPS = float(f32(1e-5))
+KERNELS = ['fsn_moments', 'fsn_finish_gauss', 'fsn_gauss_apply', 'fsn_cln_fb', 'fsn_cln_sb']
+WORST = {}
+gpu = pytest.mark.gpu
+
+
+def d64(a):
+    return np.asarray(a, np.float64)
+
+
+# ------------------------------------------------------------------------------------------------ references: Gaussian
+def rmax_of(rows, frame_rows, tlen, B):
+    return [rows if tlen is None else min(rows, (tlen[b] + LA) * frame_rows) for b in range(B)]
+
+
+def gauss_data(B, Tp, frame_rows, tlen, seed):
+    """[rows][B] >= 0, NaN where a ragged row must not be read"""
+    g = np.random.default_rng(seed)
+    rows = Tp * frame_rows
+    x = (np.abs(g.standard_normal((rows, B))) * np.exp(g.uniform(-2, 1, (1, B)))).astype(f32)
+    if tlen is not None:
+        for b, r in enumerate(rmax_of(rows, frame_rows, tlen, B)):
+            x[r:, b] = np.nan
+    return x
+
+
+def ref_moments(x, B, rmax):
+    """part [1024][2][B] float64 in the kernel's cut, and its bound"""
+    per = 256 // B
+    part, bound = np.zeros((SUM_BLOCKS, 2, B)), np.zeros((SUM_BLOCKS, 2, B))
+    for b in range(B):
+        v = d64(x[:rmax[b], b])
+        blk = (np.arange(rmax[b]) // per) % SUM_BLOCKS
+        chain = -(-rmax[b] // (SUM_BLOCKS * per)) + per + 1
+        for m, w in enumerate((v, v * v)):
+            part[:, m, b] = np.bincount(blk, weights=w, minlength=SUM_BLOCKS)
+            bound[:, m, b] = chain * V * np.bincount(blk, weights=np.abs(w), minlength=SUM_BLOCKS) + TINY
+    return part, bound
+
+
+def ref_finish(part, N, chain=1030):
+    """stat [2][B] (mean, std + 1e-5) and its bound; N [B]; chain: float64 roundings behind S1 / S2 (1024 partials + the finish's own
+    few; + those of fsn_moments when the partials come from it and not from the reference).
+    The data of this file is >= 0 (magnitudes, ReLU outputs: what the model hands these kernels), and e_mean relies on it: the float64
+    sum's error is chain V sum|x|, written here as chain V |mean| N / N - for signed input, where S1 cancels, sum|x| would have to stand
+    in its place.  The kernels are not run on signed input here."""
+    S1, S2 = part[:, 0].sum(0), part[:, 1].sum(0)
+    N = d64(N)
+    mean = S1 / N
+    var = (S2 - N * mean * mean) / (N - 1)
+    sd = np.sqrt(var)
+    e_var = (chain * V * S2 + 4 * V * N * mean * mean) / (N - 1)
+    e_mean = (U + chain * V) * np.abs(mean) + TINY
+    e_d = e_var / (2 * sd) + U * sd + U * (sd + MU_EPS) + TINY
+    return np.stack([mean, sd + MU_EPS]), np.stack([e_mean, e_d])
+
+
+def ref_apply(x, stat):
+    y = (d64(x) - d64(stat[0])[None]) / d64(stat[1])[None]
+    return y, 3 * U * np.abs(y) + TINY
+
+
+# ------------------------------------------------------------------------------------------------ references: cumulative LayerNorm
+CLN_B, CLN_N, CLN_CHUNKS, ORIGINS = (1, 3), (1, 2, 9), (1, 3, 5), (0, 2, -3)
+
+
+def cln_data(n, F, S, seed, zero_first=False):
+    """[n][F][S] >= 0"""
+    g = np.random.default_rng(seed)
+    x = (np.abs(g.standard_normal((n, F, S))) * np.exp(g.uniform(-3, 1, (n, 1, S)))).astype(f32)
+    if zero_first:
+        x[0] = 0
+    return x
+
+
+def ref_cln(x, tree, t_first=0, run0=None):
+    """cumulative_layer_norm of x [n][F][S] in float64 -> y, its bound, (S1, S2) after the last frame, their bounds (module docstring);
+    run0: the carried (S1, S2) [2][S].  t_first [S] or scalar"""
+    x = d64(x)
+    n, F, S = x.shape
+    c1, c2 = (0.0, 0.0) if run0 is None else (d64(run0[0])[None], d64(run0[1])[None])
+    S1 = np.cumsum(x.sum(1), 0) + c1
+    S2 = np.cumsum((x * x).sum(1), 0) + c2
+    frames = (np.zeros(S) + t_first)[None] + np.arange(n)[:, None] + 1.0
+    cnt = F * frames
+    a1 = (tree + frames + 1) * U * np.abs(S1)                # (x >= 0: sum|x| = S1)
+    a2 = (tree + frames + 2) * U * S2
+    mean = S1 / cnt
+    e_mean = a1 / cnt + U * np.abs(mean)
+    cross = 2 * mean * S1
+    e_cross = 2 * (e_mean * np.abs(S1) + np.abs(mean) * a1) + U * np.abs(cross)
+    diff = S2 - cross
+    e_diff = a2 + e_cross + U * np.abs(diff)
+    q = diff / cnt
+    e_q = e_diff / cnt + U * np.abs(q)
+    mm = mean * mean
+    e_mm = 2 * np.abs(mean) * e_mean + U * mm
+    var = q + mm
+    e_var = e_q + e_mm + U * np.abs(var)
+    v = var + EPS32
+    e_v = e_var + U * v
+    assert (e_v < v).all(), 'the case is ill-conditioned: the rounding of var + EPS reaches its size'
+    sd = np.sqrt(v)
+    e_sd = sd - np.sqrt(v - e_v) + U * sd
+    num = x - mean[:, None]
+    y = num / sd[:, None]
+    lo = (sd - e_sd)[:, None]
+    e_y = (e_mean[:, None] + U * np.abs(num)) / lo + np.abs(num) * e_sd[:, None] / (sd[:, None] * lo) + U * np.abs(y)
+    zero = (S2 == 0)[:, None] & np.ones_like(y, bool)        # nothing seen yet but zeros: every operation is exact
+    e_y = np.where(zero, 0.0, e_y) + TINY
+    return y, e_y, np.stack([S1[-1], S2[-1]]), np.stack([a1[-1], a2[-1]]) + TINY
+
+
+def _frame_sums32(x, kind):
+    """one frame's (sum x, sum x^2) [S] of x [F][S] in float32, in the kernel's order"""
+    x = np.asarray(x, f32)
+    q = x * x
+    if kind == 'sb':
+        s, s2 = np.zeros(x.shape[1], f32), np.zeros(x.shape[1], f32)
+        for k in range(x.shape[0]):
+            s, s2 = s + x[k], s2 + q[k]
+        return s, s2
+    out = []
+    for a in (x, q):
+        z = np.zeros((512, a.shape[1]), f32)
+        z[:NBIN] = a
+        w = (z[:256] + z[256:]).reshape(4, 64, -1)
+        for o in (32, 16, 8, 4, 2, 1):
+            w = w[:, :o] + w[:, o:2 * o]
+        p = w[:, 0]
+        out.append((p[0] + p[1]) + (p[2] + p[3]))
+    return out[0], out[1]
+
+
+def eval_cln32(x, kind, t_first=0, run0=None):
+    """the kernels' arithmetic restated in numpy float32 -> (y, (S1, S2))"""
+    x = np.asarray(x, f32)
+    n, F, S = x.shape
+    if run0 is None or t_first == 0:
+        r1, r2 = np.zeros(S, f32), np.zeros(S, f32)
+    else:
+        r1, r2 = np.asarray(run0[0], f32).copy(), np.asarray(run0[1], f32).copy()
+    y = np.empty_like(x)
+    for t in range(n):
+        s, s2 = _frame_sums32(x[t], kind)
+        r1, r2 = r1 + s, r2 + s2
+        cnt = f32(F) * f32(t_first + t + 1)
+        mean = r1 / cnt
+        var = (r2 - (f32(2) * mean) * r1) / cnt + mean * mean
+        sd = np.sqrt(var + f32(EPS32))
+        y[t] = (x[t] - mean[None]) / sd[None]
+    return y, np.stack([r1, r2])
+
+
+def worst(got, ref, bound):
+    got = d64(got)
+    if not np.isfinite(got).all():
+        return float('inf')
+    return float((np.abs(got - ref) / bound).max()) if got.size else 0.0
+
+
+@pytest.mark.parametrize('kind', ['fb', 'sb'])
+def test_bounds_hold_for_a_float32_restatement(kind):
+    F, tree, S = (NBIN, 9, 3) if kind == 'fb' else (SBW, 32, 40)
+    for n in CLN_N:
+        x = cln_data(n, F, S, 100 * n + 7, zero_first=(n == 2))
+        y, ybd, run, rbd = ref_cln(x, tree)
+        g, r = eval_cln32(x, kind)
+        w = worst(g, y, ybd), worst(r, run, rbd)
+        print(kind, 'n', n, 'float32 restatement: worst error / bound (y, sums)', w)
+        assert max(w) <= 1.0
+        if n == 2:
+            assert (g[0] == 0).all() and np.isfinite(g).all()
+    # carried sums, a later first frame
+    x = cln_data(9, F, S, 907)
+    _, run = eval_cln32(x[:4], kind)
+    y, ybd, run9, rbd = ref_cln(x[4:], tree, 4, run)
+    g, r = eval_cln32(x[4:], kind, 4, run)
+    assert worst(g, y, ybd) <= 1.0 and worst(r, run9, rbd) <= 1.0
+    # a wrong count is outside the bound
+    bad, _ = eval_cln32(x[4:], kind, 3, run)
+    assert worst(bad, y, ybd) > 1.0
+
+
+# ------------------------------------------------------------------------------------------------ probe plumbing
+CT = {'p': C.c_void_p, 'i': C.c_int, 'l': C.c_long}
+SIGS = {'fnp_moments': 'plippil', 'fnp_finish_gauss': 'pplipil', 'fnp_gauss_apply': 'pplip', 'fnp_cln_fb': 'ppiippip', 'fnp_cln_sb': 'piippip'}
+_lib = None
+SLACK = 64
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        assert os.path.exists(PROBE_LIB), 'libse_fsnnormprobe.so is missing: run build() (make -C csrc)'
+        L = C.CDLL(PROBE_LIB)
+        for name, sig in SIGS.items():
+            getattr(L, name).argtypes = [CT[c] for c in sig]
+            getattr(L, name).restype = C.c_int
+        L.fnp_last_error.restype = C.c_char_p
+        _lib = L
+    return _lib
+
+
+class Buf:
+    """device buffer of n elements with NaN (floats) or -1 (int32) in it and in the slack around it, unless src fills it"""
+
+    def __init__(self, n, src=None, dtype=torch.float32):
+        self.n, self.dtype = n, dtype
+        self.fill = -1 if dtype == torch.int32 else float('nan')
+        self.t = torch.full((n + 2 * SLACK,), self.fill, dtype=dtype, device='cuda')
+        self.v = self.t[SLACK:SLACK + n]
+        if src is not None:
+            self.v.copy_(torch.as_tensor(np.ascontiguousarray(src)).reshape(-1).to(dtype))
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr() + self.t.element_size() * SLACK
+
+    def np(self, *shape):
+        return self.v.cpu().numpy().reshape(shape)
+
+    def untouched(self):
+        s = torch.cat([self.t[:SLACK], self.t[SLACK + self.n:]])
+        return bool((s == self.fill).all()) if self.dtype == torch.int32 else bool(torch.isnan(s).all())
+
+
+def call(name, *args):
+    L = lib()
+    rc = getattr(L, name)(*[a.ptr if isinstance(a, Buf) else a for a in args])
+    assert rc == 0, '%s: %s' % (name, L.fnp_last_error().decode())
+
+
+def verify(case, kernel, got, ref, bound):
+    got = d64(got)
+    assert np.isfinite(got).all(), '%s: non-finite value in what the launch owns' % case
+    r = np.abs(got - ref) / bound
+    k = int(r.argmax())
+    w = float(r.reshape(-1)[k])
+    print('%s: worst error / bound %.3f at %s (got %.9g, want %.9g, bound %.3g)' %
+          (case, w, tuple(int(i) for i in np.unravel_index(k, r.shape)), got.reshape(-1)[k], d64(ref).reshape(-1)[k],
+           np.broadcast_to(bound, r.shape).reshape(-1)[k]))
+    if w > WORST.get(kernel, (-1.0, ''))[0]:
+        WORST[kernel] = (w, case)
+    assert w <= 1.0, '%s: error %.3f of the bound' % (case, w)
+
+
+def rows_buf(tlen):
+    """a Ragged as the engine uploads it, [4][MB] (len | lpad | tlen | olen); only tlen is meaningful here"""
+    MB = len(tlen) + 2
+    a = np.full((4, MB), -12345, np.int32)
+    a[2, :len(tlen)] = tlen
+    return Buf(4 * MB, a, torch.int32), MB
+
+
+# ------------------------------------------------------------------------------------------------ Gaussian: moments, finish, apply
+def run_gauss(x, B, frame_rows, tlen, ref_part=None, ref_stat=None):
+    """the three launches on x [rows][B]; returns (part, stat, y) as numpy; y out of place for the full band, in place for the sub bands"""
+    rows = x.shape[0]
+    bx, bpart, bstat = Buf(x.size, x), Buf(SUM_BLOCKS * 2 * B, dtype=torch.float64), Buf(2 * B)
+    rb, MB = rows_buf(tlen) if tlen is not None else (None, 0)
+    call('fnp_moments', bx, rows, B, bpart, rb, MB, frame_rows)
+    assert bpart.untouched() and bx.untouched() and np.array_equal(bx.np(*x.shape), x, equal_nan=True)
+    part = bpart.np(SUM_BLOCKS, 2, B)
+    if ref_part is not None:                          # the finish on its own: partials from the float64 reference
+        bref, bs = Buf(SUM_BLOCKS * 2 * B, ref_part, torch.float64), Buf(2 * B)
+        call('fnp_finish_gauss', bref, bs, rows, B, rb, MB, frame_rows)
+        assert bs.untouched() and bref.untouched() and np.array_equal(bref.np(SUM_BLOCKS, 2, B), ref_part)
+        ref_stat.append(bs.np(2, B))
+    call('fnp_finish_gauss', bpart, bstat, rows, B, rb, MB, frame_rows)
+    assert bstat.untouched() and np.array_equal(bpart.np(SUM_BLOCKS, 2, B), part)
+    stat = bstat.np(2, B)
+    if frame_rows == NBIN:
+        by = Buf(x.size)
+        call('fnp_gauss_apply', bx, by, x.size, B, bstat)
+        assert np.array_equal(bx.np(*x.shape), x, equal_nan=True)
+    else:
+        by = bx
+        call('fnp_gauss_apply', bx, bx, x.size, B, bstat)
+    assert by.untouched() and (rb is None or rb.untouched())
+    return part, stat, by.np(*x.shape)
+
+
+@gpu
+@pytest.mark.parametrize('ragged', [False, True])
+@pytest.mark.parametrize('band', ['fb', 'sb'])
+@pytest.mark.parametrize('Tp', [3, 4, 67])
+@pytest.mark.parametrize('B', [1, 3])
+def test_gaussian_launches(B, Tp, band, ragged):
+    frame_rows = NBIN if band == 'fb' else SBW * NBIN
+    rows, T = Tp * frame_rows, Tp - LA
+    tlen = ([T, 1, max(1, T // 2)][:B] if ragged else None)      # a row of one frame among them
+    rmax = rmax_of(rows, frame_rows, tlen, B)
+    x = gauss_data(B, Tp, frame_rows, tlen, 1000 * Tp + 10 * B + ragged)
+    case = 'B%d Tp%d %s%s' % (B, Tp, band, ' ragged' if ragged else '')
+    rp, pbd = ref_moments(x, B, rmax)
+    own = []
+    part, stat, y = run_gauss(x, B, frame_rows, tlen, rp, own)
+    verify('fsn_moments ' + case, 'fsn_moments', part, rp, pbd)
+    rs, sbd = ref_finish(rp, rmax)
+    verify('fsn_finish_gauss ' + case, 'fsn_finish_gauss', own[0], rs, sbd)
+    # (the chained statistics carry the roundings of fsn_moments as well: per + ceil(rows / (1024 per)) + 1 more on the chain)
+    rs, sbd = ref_finish(rp, rmax, 1030 + 256 // B + -(-rows // (SUM_BLOCKS * (256 // B))) + 1)
+    verify('fsn_finish_gauss chained ' + case, 'fsn_finish_gauss', stat, rs, sbd)
+    live = np.stack([np.arange(rows) < r for r in rmax], 1)
+    ry, ybd = ref_apply(np.where(live, x, 0), stat)
+    verify('fsn_gauss_apply ' + case, 'fsn_gauss_apply', np.where(live, y, 0), np.where(live, ry, 0), ybd)
+    # the chain against the plain definition of :250-253 on each row's own frames
+    for b in range(B):
+        v = d64(x[:rmax[b], b])
+        mean, sd = v.mean(), v.std(ddof=1)
+        want = (v - mean) / (sd + MU_EPS)
+        bound = 3 * U * np.abs(want) + sbd[0, b] / (sd + MU_EPS) + np.abs(want) * sbd[1, b] / (sd + MU_EPS) + TINY
+        verify('gaussian chain vs torch.std definition %s row %d' % (case, b), 'fsn_gauss_apply', y[:rmax[b], b], want, bound)
+    # repeated launches are bit-identical (two deterministic stages, no atomics)
+    part2, stat2, y2 = run_gauss(x, B, frame_rows, tlen)
+    assert np.array_equal(part, part2) and np.array_equal(stat, stat2) and np.array_equal(y, y2, equal_nan=True)
+    if B == 1 and not ragged:
+        # a ragged batch of one is the clip alone: same grid, same order
+        p1, s1, y1 = run_gauss(x, 1, frame_rows, [T])
+        assert np.array_equal(p1, part) and np.array_equal(s1, stat) and np.array_equal(y1, y)
+
+
+# ------------------------------------------------------------------------------------------------ cumulative LayerNorm
+def run_cln(kind, x, B, cs=None, t_first=0, origin=None):
+    """one launch on x [n][F][S] -> y (fb: out of place; sb: in place); cs: (Buf, Buf) or None; origin: a Buf or None"""
+    n, F, S = x.shape
+    bx = Buf(x.size, x)
+    c1, c2 = cs if cs is not None else (None, None)
+    if kind == 'fb':
+        by = Buf(x.size)
+        call('fnp_cln_fb', bx, by, n, B, c1, c2, t_first, origin)
+        assert np.array_equal(bx.np(*x.shape), x)
+    else:
+        by = bx
+        call('fnp_cln_sb', bx, n, S, c1, c2, t_first, origin)
+    assert by.untouched() and (cs is None or (c1.untouched() and c2.untouched())) and (origin is None or origin.untouched())
+    return by.np(n, F, S)
+
+
+@gpu
+@pytest.mark.parametrize('B', CLN_B)
+@pytest.mark.parametrize('kind', ['fb', 'sb'])
+def test_cln(kind, B):
+    F, tree = (NBIN, 9) if kind == 'fb' else (SBW, 32)
+    S = B if kind == 'fb' else NBIN * B
+    name = 'fsn_cln_' + kind
+    for n in CLN_N:                                   # one call from t_first = 0, no carry; n = 2: an all-zero first frame
+        x = cln_data(n, F, S, 100 * n + B, zero_first=(n == 2))
+        got = run_cln(kind, x, B)
+        y, ybd, _, _ = ref_cln(x, tree)
+        verify('%s B%d n%d' % (name, B, n), name, got, y, ybd)
+        if n == 2:
+            assert (got[0] == 0).all() and np.isfinite(got).all(), 'a frame of zeros at the start must give exact, finite zeros'
+    x = cln_data(9, F, S, 900 + B)
+    y, ybd, run, rbd = ref_cln(x, tree)
+    cs1 = (Buf(S), Buf(S))                            # NaN in them: a first chunk (t_first = 0) must not read the carry
+    one = run_cln(kind, x, B, cs1, 0)
+    verify('%s B%d one shot with carry' % (name, B), name, one, y, ybd)
+    verify('%s B%d carried sums' % (name, B), name, np.stack([cs1[0].np(S), cs1[1].np(S)]), run, rbd)
+    assert np.array_equal(one, run_cln(kind, x, B))
+    cs, t0, outs = (Buf(S), Buf(S)), 0, []
+    for c in CLN_CHUNKS:
+        outs.append(run_cln(kind, np.ascontiguousarray(x[t0:t0 + c]), B, cs, t0))
+        t0 += c
+    assert np.array_equal(np.concatenate(outs), one), 'chunked outputs differ from the one-shot run'
+    assert np.array_equal(cs[0].np(S), cs1[0].np(S)) and np.array_equal(cs[1].np(S), cs1[1].np(S)), 'the carried sums differ from the one-shot run'
+    # a later chunk against float64 with its carry
+    mid = (cs1[0].np(S), cs1[1].np(S))
+    x2 = cln_data(4, F, S, 950 + B)
+    cs2 = (Buf(S, mid[0]), Buf(S, mid[1]))
+    got = run_cln(kind, x2, B, cs2, 9)
+    y2, ybd2, run2, rbd2 = ref_cln(x2, tree, 9, mid)
+    verify('%s B%d chunk at t_first 9' % (name, B), name, got, y2, ybd2)          # (the carry is an input: exact in both)
+    verify('%s B%d sums after t_first 9' % (name, B), name, np.stack([cs2[0].np(S), cs2[1].np(S)]), run2, rbd2)
+
+
+@gpu
+@pytest.mark.parametrize('kind', ['fb', 'sb'])
+def test_cln_row_origins(kind):
+    """three rows with origins {0, 2, -3} at group frame 2 (own frames 2, 0, 5: the middle row starts here and must not read its carry)
+    against each row run alone at its own t_first: bit-identical outputs and sums"""
+    B, F = 3, NBIN if kind == 'fb' else SBW
+    S = B if kind == 'fb' else NBIN * B
+    t_first, n = 2, 4
+    x = cln_data(n, F, S, 77)
+    # each row's carry: the float32 sums of a prefix of its own age (an arbitrary pair (S1, S2) may have S2 < S1^2 / n: a negative
+    # variance); the row that starts here carries NaN, which it must not read
+    carry = np.full((2, S), np.nan, f32)
+    for r, o in enumerate(ORIGINS):
+        if t_first - o > 0:
+            carry[:, r::B] = eval_cln32(cln_data(t_first - o, F, S // B, 60 + r), kind)[1]
+    cs = (Buf(S, carry[0]), Buf(S, carry[1]))
+    got = run_cln(kind, x, B, cs, t_first, Buf(B, np.asarray(ORIGINS, np.int32), torch.int32))
+    sums = (cs[0].np(S), cs[1].np(S))
+    for b, o in enumerate(ORIGINS):
+        sel = slice(b, None, B)
+        Sb = 1 if kind == 'fb' else NBIN
+        ca = (Buf(Sb, carry[0][sel]), Buf(Sb, carry[1][sel]))
+        alone = run_cln(kind, np.ascontiguousarray(x[:, :, sel]), 1, ca, t_first - o)
+        assert np.array_equal(got[:, :, sel], alone), (kind, 'row', b, 'origin', o)
+        assert np.array_equal(sums[0][sel], ca[0].np(Sb)) and np.array_equal(sums[1][sel], ca[1].np(Sb)), (kind, 'row', b, 'sums')
+    assert np.isfinite(got).all()
+    WORST.setdefault('fsn_cln_' + kind, (0.0, 'origins'))
+
+
+@gpu
+def test_every_kernel_launched():
+    """every new kernel was launched by the cases above on this device (runs last: pytest keeps file order)"""
+    for k in KERNELS:
+        print(k, 'worst error / bound %.3f in %s' % WORST.get(k, (float('nan'), 'not launched')))
+    missing = [k for k in KERNELS if k not in WORST]
+    assert not missing, 'kernels not launched: %s' % missing

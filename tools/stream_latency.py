@@ -15,7 +15,7 @@ streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, 
   resampler's (se_resampler_save / se_resampler_restore), `swapped_push_ms` a whole restore -> push -> save at the source rate, and
   `resampler_snapshot_bytes` stands beside `snapshot_bytes`.
 --staggered N: N callers that arrive one hop apart, one frame per push each (models: crn,dccrn unless --models names others that
-  StreamSnapshot.join accepts; ctsnet_new, taylorsenet_new, g2net_new and fullsubnet_cum get engines with `row_origins=True`,
+  StreamSnapshot.join accepts; ctsnet_new, taylorsenet_new, g2net_new, fullsubnet_cum and fullsubnet_cln get engines with `row_origins=True`,
   SE_CFG_STREAM_ROW_ORIGINS, without which the join refuses them).  Every caller streams alone past its left edge and is parked; then the same N snapshots are served twice,
   for the same frames: by turns at batch 1 (restore -> push -> save per caller and frame: `by_turns_ms`), and joined into one group
   (StreamSnapshot.join, `join_ms` once; then one push of N rows per frame: `joined_ms`, and `joined_swapped_ms` when the group is itself
@@ -24,7 +24,7 @@ streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, 
   With --source-rate SR (48000, 32000) the callers are fed at SR through SourceRateStream, one hop (SR / 16000 * hop source samples)
   apart, parked as SourceStreamSnapshot pairs and joined with SourceStreamSnapshot.join (se_resampler_state_join and
   se_stream_state_join); the same result line, with `source_rate` in it.
-Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000] [--swap]
+Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new,fullsubnet_cln] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000] [--swap]
        python tools/stream_latency.py --staggered 32 [--models crn,dccrn] [--source-rate 48000]"""
 import argparse
 import json
@@ -38,7 +38,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import se_amd  # noqa: E402,F401
 from se_amd import synth  # noqa: E402
 
-ROW_ORIGINS = ('ctsnet_new', 'taylorsenet_new', 'g2net_new', 'fullsubnet_cum')
+ROW_ORIGINS = ('ctsnet_new', 'taylorsenet_new', 'g2net_new', 'fullsubnet_cum', 'fullsubnet_cln')
 SEEDS = {'crn': 12, 'lstm': 11, 'gcrn': 16, 'dpcrn': 13, 'dccrn': 14, 'taylorsenet_new': 19, 'g2net_new': 20}
 
 
@@ -50,6 +50,9 @@ def build(name, B, L, **kw):
     if name == 'fullsubnet_cum':        # the causal norm (base_model.py:143-166) is what makes FullSubNet streamable
         from se_amd.models import Model
         return Model(max_batch=B, max_samples=L, norm_type='cumulative_laplace_norm', **kw).load_synthetic(15)
+    if name == 'fullsubnet_cln':        # the standardising causal norm (cumulative_layer_norm, base_model.py:258-294)
+        from se_amd.models import Model
+        return Model(max_batch=B, max_samples=L, norm_type='cumulative_layer_norm', **kw).load_synthetic(15)
     if name == 'dccrn_e':               # DCCRN(rnn_units=256, masking_mode='E'): the real-LSTM core (opt-in: --models dccrn_e)
         from se_amd.models import DCCRN
         return DCCRN(rnn_units=256, masking_mode='E', max_batch=B, max_samples=L, **kw).load_synthetic(24)
@@ -192,8 +195,8 @@ def time_staggered(name, N, ticks=100):
     """--staggered: N callers one hop apart, by turns at batch 1 and joined into one group; prints the result line"""
     import torch
     from se_amd.engine import StreamSnapshot
-    hop = {'dccrn': 128, 'dccrn_snr': 128, 'fullsubnet_cum': 256}.get(name, 160)
-    n_fft, lag = (320 if hop == 160 else 512), {'dccrn': 6, 'fullsubnet_cum': 2}.get(name, 0)
+    hop = {'dccrn': 128, 'dccrn_snr': 128, 'fullsubnet_cum': 256, 'fullsubnet_cln': 256}.get(name, 160)
+    n_fft, lag = (320 if hop == 160 else 512), {'dccrn': 6, 'fullsubnet_cum': 2, 'fullsubnet_cln': 2}.get(name, 0)
     edge = max(1, -(-(n_fft // 2) // hop), 0 if hop >= n_fft // 2 else -(-n_fft // hop) - 1 + lag)      # csrc/stream_join.h
     n0 = (edge + 1) * hop + n_fft // 2 + 1                 # the newest caller is two frames past its left edge when the group forms
     # the models whose state counts frames are joined on engines that keep a frame origin per row (SE_CFG_STREAM_ROW_ORIGINS)
@@ -321,13 +324,13 @@ def main():
             else:
                 time_staggered(name, a.staggered)
         return
-    a.models = a.models or 'crn,lstm,gcrn,dpcrn,dccrn,ctsnet_new,taylorsenet_new,g2net_new,fullsubnet_cum'
+    a.models = a.models or 'crn,lstm,gcrn,dpcrn,dccrn,ctsnet_new,taylorsenet_new,g2net_new,fullsubnet_cum,fullsubnet_cln'
     L = int(a.seconds * 16000)
     for name in a.models.split(','):
         for B in map(int, a.batch.split(',')):
             m = build(name, B, a.sliding, sliding_stream=True) if a.sliding else build(name, B, L)
             eng = m.engine
-            hop = {'dccrn': 128, 'dccrn_snr': 128, 'fullsubnet_cum': 256}.get(name, 160)
+            hop = {'dccrn': 128, 'dccrn_snr': 128, 'fullsubnet_cum': 256, 'fullsubnet_cln': 256}.get(name, 160)
             x = torch.from_numpy(np.stack([synth.synth_clip(900 + b, 'speech', L) for b in range(B)])).cuda()
             c = eng.rms_scale(x)
             if a.source_rate:
