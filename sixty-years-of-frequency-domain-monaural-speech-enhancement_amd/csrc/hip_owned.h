@@ -1,5 +1,6 @@
-// Move-only owners of the HIP resources the entry layer holds (se_engine in engine.hip, StreamResampler in k_resample.hip): a member
-// is released by its destructor, so the objects' teardown lists nothing.  Releases ignore their status - they run in destructors.
+// Move-only owners of the HIP resources the entry layer holds (se_engine in engine_impl.h, StreamResampler in k_resample.hip, the
+// parked objects of parked.h): a member is released by its destructor, so the objects' teardown lists nothing.  Releases ignore their
+// status - they run in destructors.
 #pragma once
 #include "common.h"
 #include <utility>

@@ -44,6 +44,7 @@
 #include "kernels.h"
 #include "common.h"
 #include "hip_owned.h"
+#include "parked.h"
 #include "resample_pos.h"
 #include "resample_ragged.h"
 #include "resampler.h"
@@ -203,25 +204,15 @@ __global__ __launch_bounds__(256) void resampler_state_copy_kernel(const float* 
     if (j < keep) dst[(long)blockIdx.y * dst_pitch + j] = src[(long)blockIdx.y * src_pitch + j];
 }
 
-// se_resampler_state_select / _concat: row y of the destination <- the packed row src[y], `keep` floats each; up to 64 rows a launch,
-// their sources as a kernel argument (a group is a few dozen rows, and the rows a few hundred floats)
+// se_resampler_state_select / _concat / _join: row y of the destination <- `keep` floats from src[y] on; up to 64 rows a launch, their
+// sources as a kernel argument (a group is a few dozen rows, and the rows a few hundred floats).  src[y] is a packed row of its part,
+// or (join: the parts' rows differ in length, resampler_join.h) a column inside one - so it is a float's alignment and no more
 struct RowPtrs {
     const float* src[64];
 };
 __global__ __launch_bounds__(256) void resampler_state_gather_kernel(const RowPtrs rp, float* __restrict__ dst, int keep) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j < keep) dst[(long)blockIdx.y * keep + j] = rp.src[blockIdx.y][j];
-}
-
-// se_resampler_state_join: the parts' packed rows differ in length - row y of the destination <- `live` floats of the packed row
-// src[y] from column col[y] on (resampler_join.h: col[y] + live is that row's own length); up to 64 rows a launch, like the gather
-struct JoinRowPtrs {
-    const float* src[64];
-    int col[64];
-};
-__global__ __launch_bounds__(256) void resampler_state_join_kernel(const JoinRowPtrs rp, float* __restrict__ dst, int live) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j < live) dst[(long)blockIdx.y * live + j] = rp.src[blockIdx.y][rp.col[blockIdx.y] + j];
 }
 
 struct Tables {
@@ -478,67 +469,22 @@ void launch_resample_ragged(const void* x, int in_format, long in_pitch, int bat
 }
 
 // ---- the stateful resampler (se_resampler_* of include/se_engine.h; layout and rules in the header comment of this file)
-namespace {
-struct DeviceScope {        // the object's device is current while a call runs; the caller's is restored on the way out
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        SE_HIP(hipGetDevice(&prev));
-        if (prev != dev) SE_HIP(hipSetDevice(dev));
-        else prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-}  // namespace
 
-// A parked signal: the host record (resampler_manifest.h) + one device payload, the rows' live history back to back.  The payload
-// is sized by the first save for the most a signal of that batch keeps (batch x pitch_ floats), so saving again allocates nothing.
-struct ResamplerState {
+// A parked signal (parked.h): the host record (resampler_manifest.h) + one device payload, the rows' live history back to back.  The
+// payload is sized by the first save for the most a signal of that batch keeps (batch x pitch_ floats), so saving again allocates nothing.
+struct ResamplerState : Parked {
     ResamplerManifest man;
-    bool filled = false;
-    int device = -1;                      // the device the payload and the event live on
-    bool dev_valid = false;               // dev holds the payload of `man` (false after an import, until the first restore)
-    int64_t dev_cap = 0;                  // floats
-    std::vector<uint8_t> host;            // payload of an imported image (kept: another device may restore it too)
-    struct Side {                         // what belongs to one device
-        DevBuf<float> dev;
-        Event ev_use;
-    };
-    std::unique_ptr<Side> side;
-    // the hipStream the object was last used on: a call on another one is ordered behind it
-    bool has_use = false;
-    hipStream_t use_st = nullptr;
-
-    void wait(hipStream_t st) {
-        if (has_use && use_st != st) SE_HIP(hipStreamWaitEvent(st, side->ev_use.get(), 0));
-    }
-    void mark(hipStream_t st) {
-        SE_HIP(hipEventRecord(side->ev_use.get(), st));
-        has_use = true;
-        use_st = st;
-    }
-    // what lives on the payload's device is released with that device current, behind the last work that used it
-    void drop_side() {
-        if (side && device >= 0) {
-            DeviceScope ds(device);
-            if (has_use) (void)hipEventSynchronize(side->ev_use.get());
-            side.reset();
-        }
-        side.reset();
-        has_use = false;
-        dev_valid = false;
-        dev_cap = 0;
-    }
+    float* rows() const { return reinterpret_cast<float*>(side->dev.get()); }
+    int64_t dev_cap() const { return has_payload() ? (int64_t)(side->bytes / sizeof(float)) : 0; }      // floats
     // a payload of at least `floats` on `dev` (current); the old contents are dropped when a new buffer is made
     void payload_alloc(int64_t floats, int dev) {
-        if (side && side->dev && device == dev && dev_cap >= floats) return;
-        drop_side();
-        std::unique_ptr<Side> fresh(new Side());
-        fresh->dev.alloc((size_t)floats);
-        side = std::move(fresh);
-        device = dev;
-        dev_cap = floats;
+        if (!(has_payload() && device == dev && dev_cap() >= floats)) fresh_payload((size_t)floats * sizeof(float), dev);
+    }
+    // ... that holds the imported image: once, until the object is saved into again
+    void to_device(int64_t floats, int dev) {
+        if (on_device(dev)) return;
+        payload_alloc(floats, dev);
+        upload_host();
     }
 };
 
@@ -777,17 +723,14 @@ void StreamResampler::save(ResamplerState& s, hipStream_t st) {
         order_behind_last(st);
         s.wait(st);
         const long keep = (long)rsnap_keep(m);
-        copy_state(hist_[cur_].get(), pitch_, s.side->dev.get(), keep, n_total_, w0_, batch_, st);
+        copy_state(hist_[cur_].get(), pitch_, s.rows(), keep, n_total_, w0_, batch_, st);
         SE_HIP(hipEventRecord(ev_order_.get(), st));
         has_last_ = true;
         last_st_ = st;
         s.mark(st);
     }
     s.man = m;
-    s.filled = true;
-    s.dev_valid = !pass_;
-    s.host.clear();
-    s.host.shrink_to_fit();
+    s.set_saved(!pass_);
 }
 
 void StreamResampler::restore(ResamplerState& s, hipStream_t st) {
@@ -800,7 +743,7 @@ void StreamResampler::restore(ResamplerState& s, hipStream_t st) {
                                                         std::to_string(max_batch_) + " given at create");
     const int64_t keep = rsnap_keep(m);
     SE_CHECK(keep >= 0 && keep <= pitch_ && m.n_total <= INT_MAX && m.t <= INT_MAX, fn + "history or counters out of range");
-    const bool upload = keep > 0 && (!s.dev_valid || s.device != dev_);
+    const bool upload = keep > 0 && !s.on_device(dev_);
     if (upload)
         SE_CHECK((int64_t)s.host.size() == rsnap_payload_bytes(m),
                  fn + "the payload lives on device " + std::to_string(s.device) + ", this object on device " + std::to_string(dev_) +
@@ -808,10 +751,7 @@ void StreamResampler::restore(ResamplerState& s, hipStream_t st) {
     // ---- every refusal is above: from here the call replaces whatever signal is open, as se_resampler_begin does
     if (upload) {             // an imported image, or one that moves to this device: once, until the object is saved into again
         DeviceScope ds(dev_);
-        s.payload_alloc((int64_t)m.batch * pitch_, dev_);
-        if (s.has_use) SE_HIP(hipEventSynchronize(s.side->ev_use.get()));
-        SE_HIP(hipMemcpy(s.side->dev.get(), s.host.data(), s.host.size(), hipMemcpyHostToDevice));
-        s.dev_valid = true;
+        s.to_device((int64_t)m.batch * pitch_, dev_);
     }
     active_ = true;
     ended_ = false;
@@ -824,7 +764,7 @@ void StreamResampler::restore(ResamplerState& s, hipStream_t st) {
         DeviceScope ds(dev_);
         order_behind_last(st);
         s.wait(st);
-        copy_state(s.side->dev.get(), (long)keep, hist_[cur_].get(), pitch_, n_total_, w0_, batch_, st);
+        copy_state(s.rows(), (long)keep, hist_[cur_].get(), pitch_, n_total_, w0_, batch_, st);
         SE_HIP(hipEventRecord(ev_order_.get(), st));
         has_last_ = true;
         last_st_ = st;
@@ -840,7 +780,7 @@ void resampler_state_destroy(ResamplerState* s) {
 }
 int64_t resampler_state_bytes(const ResamplerState* s) {
     if (!s || !s->filled || s->man.sr_in == s->man.sr_out) return 0;
-    return s->side && s->side->dev ? s->dev_cap * (int64_t)sizeof(float) : rsnap_payload_bytes(s->man);
+    return s->has_payload() ? (int64_t)s->side->bytes : rsnap_payload_bytes(s->man);
 }
 void resampler_state_counts(const ResamplerState* s, int32_t* sr_in, int32_t* sr_out, int32_t* batch, int64_t* n_in, int64_t* n_out) {
     SE_CHECK(s, "se_resampler_state_counts: null argument");
@@ -863,15 +803,9 @@ int64_t resampler_state_export(const ResamplerState* s, void* host_buf, int64_t 
     uint8_t* out = static_cast<uint8_t*>(host_buf);
     rsnap_write_head(s->man, out);
     if (pay == 0) return size;
-    if (!s->host.empty()) {
-        SE_CHECK((int64_t)s->host.size() == pay, "se_resampler_state_export: host image of the wrong size");
-        std::memcpy(out + RSNAP_HEAD_BYTES, s->host.data(), (size_t)pay);
-    } else {
-        SE_CHECK(s->side && s->side->dev && s->dev_valid && pay <= s->dev_cap * (int64_t)sizeof(float), "se_resampler_state_export: no payload");
-        DeviceScope ds(s->device);
-        if (s->has_use) SE_HIP(hipEventSynchronize(s->side->ev_use.get()));
-        SE_HIP(hipMemcpy(out + RSNAP_HEAD_BYTES, s->side->dev.get(), (size_t)pay, hipMemcpyDeviceToHost));
-    }
+    if (!s->host.empty()) SE_CHECK((int64_t)s->host.size() == pay, "se_resampler_state_export: host image of the wrong size");
+    else SE_CHECK(s->resident() && pay <= (int64_t)s->side->bytes, "se_resampler_state_export: no payload");
+    const_cast<ResamplerState*>(s)->export_payload(out + RSNAP_HEAD_BYTES, (size_t)pay);      // (the event is a cache of the object)
     return size;
 }
 
@@ -884,74 +818,64 @@ void resampler_state_import(ResamplerState* s, const void* host_buf, int64_t byt
     std::vector<uint8_t> pay(static_cast<const uint8_t*>(host_buf) + off, static_cast<const uint8_t*>(host_buf) + bytes);
     // nothing of the object has changed up to here
     s->man = m;
-    s->host = std::move(pay);
-    s->filled = true;
-    s->dev_valid = false;
+    s->adopt_image(std::move(pay));
 }
 
-// ---- se_resampler_state_select / se_resampler_state_concat.  The rows of the result, in order, as (part, row); every refusal is
-// made by the callers and here before the destination changes.  Sources that are all imported images (host payloads, nothing
-// uploaded yet) are cut on the host and the result is such an image; otherwise the rows move on the device the sources live on - a
-// host-only part is uploaded there first, as its first restore would do it.
+// ---- se_resampler_state_select / _concat / _join.  The rows of the result, in order, as (part, row); every refusal is made by the
+// callers and here before the destination changes.  Sources that are all imported images (host payloads, nothing uploaded yet) are
+// cut on the host and the result is such an image; otherwise the rows move on the device the sources live on - a host-only part is
+// uploaded there first, as its first restore would do it.
 namespace {
-void resampler_rows(ResamplerState* dst, const std::vector<ResamplerState*>& parts, const std::vector<std::pair<int, int32_t>>& map,
-                    const std::string& fn, hipStream_t st) {
-    ResamplerManifest m = parts[0]->man;
-    m.batch = (int32_t)map.size();
+// m: the record of the result, its rows rsnap_keep(m) floats long.  Row j <- that many floats of row map[j].y of part map[j].x, from
+// column col[part] on: a part's packed rows have the length of its own record (select and concat: the result's, and column 0)
+void resampler_rows(ResamplerState* dst, const std::vector<ResamplerState*>& parts, const std::vector<int2>& map, const ResamplerManifest& m,
+                    const std::vector<int64_t>& col, const std::string& fn, hipStream_t st) {
     const int64_t keep = rsnap_keep(m);
-    auto finish = [&](bool on_dev) {
-        dst->man = m;
-        dst->filled = true;
-        dst->dev_valid = on_dev;
-    };
     if (keep == 0) {      // pass-through, or nothing live: counters only
-        dst->host.clear();
-        finish(false);
+        dst->man = m;
+        dst->set_saved(false);
         return;
     }
     SE_CHECK(keep <= INT_MAX / 4, fn + "history out of range");
     int dev = -1;
     for (ResamplerState* p : parts)
-        if (p->dev_valid && p->side && p->side->dev) {
+        if (p->resident()) {
             SE_CHECK(dev < 0 || dev == p->device, fn + "the parts' payloads live on devices " + std::to_string(dev) + " and " + std::to_string(p->device) +
                                                       " (export and import a state to move it)");
             dev = p->device;
         }
     for (ResamplerState* p : parts)
-        if (!(p->dev_valid && p->side && p->side->dev))
-            SE_CHECK((int64_t)p->host.size() == rsnap_payload_bytes(p->man), fn + "a part has no payload");
+        if (!p->resident()) SE_CHECK((int64_t)p->host.size() == rsnap_payload_bytes(p->man), fn + "a part has no payload");
+        else SE_CHECK(p->dev_cap() >= (int64_t)p->man.batch * rsnap_keep(p->man), fn + "a part's payload is smaller than its rows");
     // ---- every refusal is above
+    auto row_at = [&](size_t j) {      // where row j of the result starts in its part's payload, in floats
+        const size_t p = (size_t)map[j].x;
+        return (size_t)map[j].y * (size_t)rsnap_keep(parts[p]->man) + (size_t)col[p];
+    };
     if (dev < 0) {
         std::vector<uint8_t> out((size_t)(m.batch * keep * 4));
         for (size_t j = 0; j < map.size(); ++j)
-            std::memcpy(out.data() + j * (size_t)keep * 4, parts[(size_t)map[j].first]->host.data() + (size_t)map[j].second * (size_t)keep * 4, (size_t)keep * 4);
+            std::memcpy(out.data() + j * (size_t)keep * 4, parts[(size_t)map[j].x]->host.data() + row_at(j) * 4, (size_t)keep * 4);
         dst->drop_side();
-        dst->host = std::move(out);
-        finish(false);
+        dst->man = m;
+        dst->adopt_image(std::move(out));
         return;
     }
     DeviceScope ds(dev);
-    for (ResamplerState* p : parts)
-        if (!p->dev_valid) {
-            p->payload_alloc((int64_t)p->man.batch * keep, dev);
-            SE_HIP(hipMemcpy(p->side->dev.get(), p->host.data(), p->host.size(), hipMemcpyHostToDevice));
-            p->dev_valid = true;
-        }
+    for (ResamplerState* p : parts) p->to_device((int64_t)p->man.batch * rsnap_keep(p->man), dev);
     dst->payload_alloc((int64_t)m.batch * keep, dev);
     for (ResamplerState* p : parts) p->wait(st);
     dst->wait(st);
     for (size_t y0 = 0; y0 < map.size(); y0 += 64) {
         const int ny = (int)std::min<size_t>(64, map.size() - y0);
         RowPtrs rp{};
-        for (int y = 0; y < ny; ++y)
-            rp.src[y] = parts[(size_t)map[y0 + y].first]->side->dev.get() + (size_t)map[y0 + y].second * (size_t)keep;
+        for (int y = 0; y < ny; ++y) rp.src[y] = parts[(size_t)map[y0 + y].x]->rows() + row_at(y0 + y);
         hipLaunchKernelGGL(resampler_state_gather_kernel, dim3((unsigned)((keep + 255) / 256), (unsigned)ny), dim3(256), 0, st, rp,
-                           dst->side->dev.get() + y0 * (size_t)keep, (int)keep);
+                           dst->rows() + y0 * (size_t)keep, (int)keep);
         SE_HIP(hipGetLastError());
     }
-    dst->host.clear();
-    dst->host.shrink_to_fit();
-    finish(true);
+    dst->man = m;
+    dst->set_saved();
     dst->mark(st);
     for (ResamplerState* p : parts) p->mark(st);
 }
@@ -964,54 +888,37 @@ void resampler_state_select(ResamplerState* dst, ResamplerState* src, const int3
     SE_CHECK(src->filled, fn + "the resampler state object is empty");
     const std::string bad = rsnap_rows_check(rows, n_rows, src->man.batch);
     SE_CHECK(bad.empty(), fn + bad);
-    std::vector<std::pair<int, int32_t>> map;
-    for (int32_t j = 0; j < n_rows; ++j) map.emplace_back(0, rows[j]);
-    resampler_rows(dst, {src}, map, fn, st);
+    std::vector<int2> map;
+    for (int32_t j = 0; j < n_rows; ++j) map.push_back(make_int2(0, rows[j]));
+    ResamplerManifest m = src->man;
+    m.batch = n_rows;
+    resampler_rows(dst, {src}, map, m, {0}, fn, st);
 }
 
 void resampler_state_concat(ResamplerState* dst, ResamplerState* const* cparts, int32_t n_parts, hipStream_t st) {
     const std::string fn = "se_resampler_state_concat: ";
     SE_CHECK(dst && cparts, fn + "null argument");
-    SE_CHECK(n_parts >= 1, fn + "n_parts " + std::to_string(n_parts) + ": at least one part has to be given");
-    std::vector<ResamplerState*> parts;
-    std::vector<std::pair<int, int32_t>> map;
-    for (int32_t p = 0; p < n_parts; ++p) {
-        ResamplerState* s = cparts[p];
-        SE_CHECK(s, fn + "parts[" + std::to_string(p) + "] is null");
-        SE_CHECK(s != dst, fn + "dst == parts[" + std::to_string(p) + "]: the rows are read while they are written");
-        SE_CHECK(s->filled, fn + "parts[" + std::to_string(p) + "]: the resampler state object is empty");
-        if (p > 0) {
-            const std::string why = rsnap_concat_differs(cparts[0]->man, s->man);
-            SE_CHECK(why.empty(), fn + "parts[0] and parts[" + std::to_string(p) + "] differ: " + why);
-        }
-        SE_CHECK(map.size() + (size_t)s->man.batch < ((size_t)1 << 24), fn + "too many rows");
-        for (int32_t r = 0; r < s->man.batch; ++r) map.emplace_back(p, r);
-        parts.push_back(s);
-    }
-    resampler_rows(dst, parts, map, fn, st);
+    const std::vector<ResamplerState*> parts = collect_parts(dst, cparts, n_parts, fn, "resampler state", [&](int32_t p, const ResamplerState* s) {
+        const std::string why = p > 0 ? rsnap_concat_differs(cparts[0]->man, s->man) : "";
+        SE_CHECK(why.empty(), fn + "parts[0] and parts[" + std::to_string(p) + "] differ: " + why);
+    });
+    const std::vector<int2> map = part_rows(parts);
+    ResamplerManifest m = parts[0]->man;
+    m.batch = (int32_t)map.size();
+    resampler_rows(dst, parts, map, m, std::vector<int64_t>(parts.size(), 0), fn, st);
 }
 
 // ---- se_resampler_state_join: concat for parts whose counters differ by a multiple of sr_in / sr_out (resampler_join.h: when a parked
 // signal can be rebased, the shifts, the joined history origin and the column of each part's rows it starts at).  The parts' packed
-// rows differ in length, so the rows move through a gather of their own; where the result lives, the upload of imported parts, the
-// reuse of dst and the ordering on `st` are concat's.  Every refusal is made before the destination changes.
+// rows differ in length; everything else - where the result lives, the upload of imported parts, the reuse of dst and the ordering on
+// `st` - is concat's, in the same mover.  Every refusal is made before the destination changes.
 void resampler_state_join(ResamplerState* dst, ResamplerState* const* cparts, int32_t n_parts, hipStream_t st) {
     const std::string fn = "se_resampler_state_join: ";
     SE_CHECK(dst && cparts, fn + "null argument");
-    SE_CHECK(n_parts >= 1, fn + "n_parts " + std::to_string(n_parts) + ": at least one part has to be given");
-    std::vector<ResamplerState*> parts;
     std::vector<const ResamplerManifest*> mans;
-    std::vector<std::pair<int, int32_t>> map;
-    for (int32_t p = 0; p < n_parts; ++p) {
-        ResamplerState* s = cparts[p];
-        SE_CHECK(s, fn + "parts[" + std::to_string(p) + "] is null");
-        SE_CHECK(s != dst, fn + "dst == parts[" + std::to_string(p) + "]: the rows are read while they are written");
-        SE_CHECK(s->filled, fn + "parts[" + std::to_string(p) + "]: the resampler state object is empty");
-        SE_CHECK(map.size() + (size_t)s->man.batch < ((size_t)1 << 24), fn + "too many rows");
-        for (int32_t r = 0; r < s->man.batch; ++r) map.emplace_back(p, r);
-        parts.push_back(s);
-        mans.push_back(&s->man);
-    }
+    const std::vector<ResamplerState*> parts =
+        collect_parts(dst, cparts, n_parts, fn, "resampler state", [&](int32_t, const ResamplerState* s) { mans.push_back(&s->man); });
+    const std::vector<int2> map = part_rows(parts);
     ResamplerJoinPlan plan;
     const std::string why = rsnap_join_plan(mans, plan);
     SE_CHECK(why.empty(), fn + why);
@@ -1022,69 +929,7 @@ void resampler_state_join(ResamplerState* dst, ResamplerState* const* cparts, in
     SE_CHECK(live == rsnap_keep(m) && live <= INT_MAX / 4, fn + "history out of range");
     for (size_t p = 0; p < parts.size(); ++p)       // what the gather indexes: columns [col, col + live) of rows of the part's own length
         SE_CHECK(plan.col[p] >= 0 && plan.col[p] + live == rsnap_keep(parts[p]->man), fn + "history out of range");
-    auto finish = [&](bool on_dev) {
-        dst->man = m;
-        dst->filled = true;
-        dst->dev_valid = on_dev;
-    };
-    if (live == 0) {      // pass-through, or nothing live: counters only
-        dst->host.clear();
-        finish(false);
-        return;
-    }
-    int dev = -1;
-    for (ResamplerState* p : parts)
-        if (p->dev_valid && p->side && p->side->dev) {
-            SE_CHECK(dev < 0 || dev == p->device, fn + "the parts' payloads live on devices " + std::to_string(dev) + " and " + std::to_string(p->device) +
-                                                      " (export and import a state to move it)");
-            dev = p->device;
-        }
-    for (ResamplerState* p : parts)
-        if (!(p->dev_valid && p->side && p->side->dev))
-            SE_CHECK((int64_t)p->host.size() == rsnap_payload_bytes(p->man), fn + "a part has no payload");
-        else
-            SE_CHECK(p->dev_cap >= (int64_t)p->man.batch * rsnap_keep(p->man), fn + "a part's payload is smaller than its rows");
-    // ---- every refusal is above
-    if (dev < 0) {
-        std::vector<uint8_t> out((size_t)(m.batch * live * 4));
-        for (size_t j = 0; j < map.size(); ++j) {
-            const size_t p = (size_t)map[j].first;
-            const size_t row = (size_t)rsnap_keep(parts[p]->man);
-            std::memcpy(out.data() + j * (size_t)live * 4, parts[p]->host.data() + ((size_t)map[j].second * row + (size_t)plan.col[p]) * 4, (size_t)live * 4);
-        }
-        dst->drop_side();
-        dst->host = std::move(out);
-        finish(false);
-        return;
-    }
-    DeviceScope ds(dev);
-    for (ResamplerState* p : parts)
-        if (!p->dev_valid) {
-            p->payload_alloc((int64_t)p->man.batch * rsnap_keep(p->man), dev);
-            if (p->has_use) SE_HIP(hipEventSynchronize(p->side->ev_use.get()));
-            SE_HIP(hipMemcpy(p->side->dev.get(), p->host.data(), p->host.size(), hipMemcpyHostToDevice));
-            p->dev_valid = true;
-        }
-    dst->payload_alloc((int64_t)m.batch * live, dev);
-    for (ResamplerState* p : parts) p->wait(st);
-    dst->wait(st);
-    for (size_t y0 = 0; y0 < map.size(); y0 += 64) {
-        const int ny = (int)std::min<size_t>(64, map.size() - y0);
-        JoinRowPtrs rp{};
-        for (int y = 0; y < ny; ++y) {
-            const size_t p = (size_t)map[y0 + y].first;
-            rp.src[y] = parts[p]->side->dev.get() + (size_t)map[y0 + y].second * (size_t)rsnap_keep(parts[p]->man);
-            rp.col[y] = (int)plan.col[p];
-        }
-        hipLaunchKernelGGL(resampler_state_join_kernel, dim3((unsigned)((live + 255) / 256), (unsigned)ny), dim3(256), 0, st, rp,
-                           dst->side->dev.get() + y0 * (size_t)live, (int)live);
-        SE_HIP(hipGetLastError());
-    }
-    dst->host.clear();
-    dst->host.shrink_to_fit();
-    finish(true);
-    dst->mark(st);
-    for (ResamplerState* p : parts) p->mark(st);
+    resampler_rows(dst, parts, map, m, plan.col, fn, st);
 }
 
 StreamResampler* stream_resampler_create(int sr_in, int sr_out, int max_batch, int max_push) {

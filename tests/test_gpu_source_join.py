@@ -111,6 +111,42 @@ def test_resampler_rows_joined_continue_bit_for_bit(sr_in, via_bytes):
     assert np.array_equal(np.concatenate([heads['A'], tail[2:]], axis=1), ref['A'])
 
 
+@pytest.mark.parametrize('imported, ahead', [('A', 1), ('G', 2)], ids=['late-imported', 'group-imported'])
+def test_resampler_join_of_an_imported_and_a_resident_part(imported, ahead):
+    """One part is an imported image, the other lives on the device: the join uploads the image there and gathers both in one launch.
+    One row each, `ahead` hops apart, parked as in the test above - the group's packed history starts before the joined origin, so its
+    row is read from a nonzero column (2 * reach - nA = 3 floats at 48 kHz).  Each row continues, call by call, bit for bit as it
+    does alone after its save."""
+    torch = _torch()
+    D = SR // 16000
+    reach = 32769 // (512 // D) + 1
+    nA = 63 * D + reach + 1
+    n = {'A': nA, 'G': nA + ahead * D * 160}
+    assert 2 * reach - nA > 0
+    rest, tail_pieces = 1201, (1, 37, 481)
+    x = {k: torch.from_numpy(_clip(seed, n[k] + rest, SR)).cuda() for k, seed in (('A', SEED_A), ('G', SEED_G))}
+    with StreamResampler(SR, max_batch=2, max_push=4000) as rs:
+        snaps, alone = {}, {}
+        for key in ('G', 'A'):
+            rs.begin(1)
+            _push_all(rs, x[key], _cuts(n[key]))
+            snaps[key] = rs.save()
+            alone[key] = _push_all(rs, x[key], _cuts(rest, tail_pieces, n[key])) + [rs.flush().cpu().numpy()]
+        image = snaps[imported].to_bytes()
+        snaps[imported].close()
+        snaps[imported] = ResamplerSnapshot.from_bytes(image)
+        with snaps['G'] as g, snaps['A'] as a:
+            assert (g.device is None, a.device is None) == (imported == 'G', imported == 'A')
+            with ResamplerSnapshot.join([g, a]) as j:
+                assert j.device is not None and j.counts() == (SR, 16000, 2, n['G'], 64 + ahead * 160)
+                rs.restore(j)
+                x2 = torch.cat([x['G'][:, n['G']:], x['A'][:, n['A']:]])
+                outs = _push_all(rs, x2, _cuts(rest, tail_pieces)) + [rs.flush().cpu().numpy()]
+    for i, key in enumerate(('G', 'A')):
+        assert [o.shape[1] for o in outs] == [o.shape[1] for o in alone[key]], 'n_out per call'
+        assert all(np.array_equal(o[i:i + 1], r) for o, r in zip(outs, alone[key])), key
+
+
 # ------------------------------------------------------------------------------------------------ 3, 4. the pair
 _ENGINES, _OFFLINE = {}, {}
 
