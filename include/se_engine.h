@@ -141,6 +141,29 @@ enum se_model_id {
  * only), and so does SE_CFG_STREAM_ROW_ORIGINS.  A stream carries two running sums (x, x^2) per utterance and per sub-band sequence.
  * At most one of SE_CFG_FSN_CUMULATIVE, SE_CFG_FSN_GAUSSIAN, SE_CFG_FSN_CUM_LAYERNORM; se_engine_create fails for any other model. */
 #define SE_CFG_FSN_CUM_LAYERNORM (1 << 21)
+/* FullSubNet's shape, Model(look_ahead, fb_num_neighbors, sb_num_neighbors) (FullSubNet/fullsubnet_net_sa/model.py:9-63).  Two fields
+ * with the zero-means-script-value convention of SE_CFG_REPEATS - a caller that passes nothing gets the decode script's model:
+ *   SE_CFG_FSN_LOOK_AHEAD(n)     bits 22-24, stores n + 1, 0 <= n <= 6; 0 in the field = the script's look_ahead = 2, and
+ *                                se_engine_create stores SE_CFG_FSN_LOOK_AHEAD(2) as the empty field: both spellings give ONE engine
+ *                                identity, a stream parked on either is restored, selected and joined on the other.  The network
+ *                                sees n zero frames behind the clip (model.py:79) and the mask of frame t is the output of step t + n
+ *                                (:117); a stream is final n frames (n * 16 ms) late, with n = 0 every frame at once.
+ *   SE_CFG_FSN_FB_NEIGHBORS(n)   bits 25-28, stores n, 0 <= n <= 15; the script's value is 0.  The sub-band model is fed 2 n + 1 bins
+ *                                of the full-band output around its own, the frequency axis reflect-padded (base_model.py:13-42).
+ * sb_num_neighbors (0..15) is no flag: se_engine_finalize reads it from the shape of sb_model.sequence_model.weight_ih_l0,
+ * [4H or 3H, (2 sb_num_neighbors + 1) + (2 fb_num_neighbors + 1)], the way DCCRN's rnn_units is read from enhance.weight_hh_l0, and fails -
+ * naming the width and fb_num_neighbors - when (width - 2 fb_num_neighbors - 2) is odd, negative or above 30.  Every value combines with
+ * SE_CFG_FSN_GRU and the four norms, and everything the engine does with the script's shape it does with these: se_enhance_batch,
+ * se_enhance_ragged, se_forward and - with a cumulative norm and the LSTM - se_stream_*, the parked-stream calls (both fields are flag
+ * bits, so they are part of a parked stream's identity: a snapshot of look_ahead = 0 is refused by an engine of look_ahead = 2),
+ * se_stream_state_join under SE_CFG_STREAM_ROW_ORIGINS, se_enhance_long and se_enhance_long_ragged.  Two engines that differ in
+ * sb_num_neighbors alone differ in their WEIGHTS, which no parked-stream call compares (se_stream_restore): keeping them apart is the
+ * caller's duty, as it is for any two sets of weights.  Still refused, because every kernel size follows from them: num_freqs other than
+ * 257, hidden sizes other than 512 / 384, output activations other than ReLU / none.  se_engine_create fails for either field on
+ * another model.  The look-ahead field is three bits wide and every value of it is a look_ahead the engine builds; a look_ahead of 7
+ * or more does not fit it (the macro masks its argument), so callers check the range themselves, as se_amd.models.Model does. */
+#define SE_CFG_FSN_LOOK_AHEAD(n) ((((n) + 1) & 7) << 22)
+#define SE_CFG_FSN_FB_NEIGHBORS(n) (((n) & 15) << 25)
 
 typedef struct se_config {
     int32_t model;        /* enum se_model_id */
@@ -630,7 +653,7 @@ int se_pcm16_encode(const float* in_dev, int64_t in_pitch, int32_t batch, int32_
                     void* stream);
 
 /* ABI version of this header. */
-int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise; + se_resampler_state_join: likewise; + the flag bit SE_CFG_DCCRN_ROW_ENDS: no new entry point, same number; + the flag bit SE_CFG_STREAM_ROW_ORIGINS: likewise, and a snapshot segment kind only engines with the bit write; + the flag bits SE_CFG_FSN_GAUSSIAN, SE_CFG_FSN_CUM_LAYERNORM: no new entry point, same number) */
+int32_t se_abi_version(void);   /* 2: se_enhance_ragged, se_get_stage_profile, se_stream_*; 3: se_uformer_forward, se_pcm16_*; 4: se_stream_begin_running; 5: se_frontend, se_backend (+ the flag bits SE_CFG_DCCRN_CAUSAL_DEC, SE_CFG_STREAM_SLIDING: no new entry point, same number; + se_enhance_long, se_enhance_long_ragged: added entry points, nothing existing changes, same number; + se_resampler_*: likewise; + se_stream_state_*, se_stream_save, se_stream_restore: likewise; + se_resampler_state_*, se_resampler_save, se_resampler_restore: likewise; + se_resampler_state_join: likewise; + the flag bit SE_CFG_DCCRN_ROW_ENDS: no new entry point, same number; + the flag bit SE_CFG_STREAM_ROW_ORIGINS: likewise, and a snapshot segment kind only engines with the bit write; + the flag bits SE_CFG_FSN_GAUSSIAN, SE_CFG_FSN_CUM_LAYERNORM: no new entry point, same number; + the flag fields SE_CFG_FSN_LOOK_AHEAD, SE_CFG_FSN_FB_NEIGHBORS: likewise) */
 
 #ifdef __cplusplus
 }

@@ -195,7 +195,10 @@ int se_engine_create(const se_config* cfg, se_engine** out) {
         e->ctx.max_samples = cfg->max_samples > 0 ? cfg->max_samples : 64000;
         e->ctx.p_in = cfg->p_in > 0.f ? cfg->p_in : 1.f;
         e->ctx.p_out = cfg->p_out > 0.f ? cfg->p_out : 1.f;
-        e->ctx.flags = cfg->flags;
+        // (SE_CFG_FSN_LOOK_AHEAD(2) spells the script's look_ahead, which an empty field means too: one engine, one set of flags - the
+        // parked-stream calls compare them - so the field is stored empty)
+        if (cfg->model == SE_MODEL_FULLSUBNET && ((cfg->flags >> 22) & 7u) == 3u) e->cfg.flags &= ~(7u << 22);
+        e->ctx.flags = e->cfg.flags;
         // (the bit names a remedy for DCCRN's look-ahead decoder alone: anywhere else it would be carried along without a meaning)
         SE_CHECK(!(cfg->flags & SE_CFG_DCCRN_ROW_ENDS) || cfg->model == SE_MODEL_DCCRN,
                  "SE_CFG_DCCRN_ROW_ENDS is a bit of SE_MODEL_DCCRN (the per-layer zero tails its look-ahead decoder needs in "
@@ -212,6 +215,14 @@ int se_engine_create(const se_config* cfg, se_engine** out) {
             const int nnorm = !!(cfg->flags & SE_CFG_FSN_CUMULATIVE) + !!(cfg->flags & SE_CFG_FSN_GAUSSIAN) + !!(cfg->flags & SE_CFG_FSN_CUM_LAYERNORM);
             SE_CHECK(cfg->model != SE_MODEL_FULLSUBNET || nnorm <= 1,
                      "FullSubNet has one norm_type: at most one of SE_CFG_FSN_CUMULATIVE, SE_CFG_FSN_GAUSSIAN and SE_CFG_FSN_CUM_LAYERNORM");
+        }
+        // (FullSubNet's look_ahead and fb_num_neighbors: bits 22-24 hold look_ahead + 1 with 0 = the script's 2, bits 25-28 the count)
+        {
+            const uint32_t shape = (7u << 22) | (15u << 25);
+            SE_CHECK(!(cfg->flags & shape) || cfg->model == SE_MODEL_FULLSUBNET,
+                     "SE_CFG_FSN_LOOK_AHEAD and SE_CFG_FSN_FB_NEIGHBORS are fields of SE_MODEL_FULLSUBNET (its look_ahead and "
+                     "fb_num_neighbors): no other model takes them");
+            // (every value of the three-bit field is a look_ahead the engine builds: 1..7 = 0..6 frames)
         }
         // (per-row frame origins are read by the kernels of the models whose state counts frames, and by nothing else)
         if (cfg->flags & SE_CFG_STREAM_ROW_ORIGINS) {

@@ -4,8 +4,11 @@
 // (cumulative_laplace_norm), :242-255 (offline_gaussian_norm), :258-294 (cumulative_layer_norm),
 // fullsubnet_sa_decode_vb.py:56-66 (the complex mask and the decompress, applied in the script).
 //
-// Layouts (time-major, sequences contiguous): full band [T+2][257][B]; sub bands [T+2][32][257*B], sequence s = n*B + b is
-// sub-band n of utterance b.
+// Layouts (time-major, sequences contiguous): full band [T+la][257][B]; sub bands [T+la][W][257*B], sequence s = n*B + b is
+// sub-band n of utterance b.  The look-ahead `la` (Model(look_ahead=), 0..6) and the sub-band width W = (2 sbn + 1) + (2 fbn + 1)
+// (sb_num_neighbors, fb_num_neighbors, 0..15 each) are kernel arguments; the two kernels that keep a sub band's W values in
+// registers have an instance for the decode script's W = 32 (fsn::SBW) and a run-time form that reads the rows twice - the same
+// float32 operations in the same order either way.
 #include "k_fullsubnet.h"
 
 namespace se {
@@ -14,12 +17,12 @@ using namespace fsn;
 
 namespace {
 
-// sum over (f, t) of mag[b][f][t]  ->  mu[b] = sum / (F * (T + LA))   (the look-ahead pad frames are zeros)
+// sum over (f, t) of mag[b][f][t]  ->  mu[b] = sum / (F * (T + la))   (the look-ahead pad frames are zeros)
 // ragged batch (tlen != null): frames >= tlen[b] of mag are zeros (the STFT wrote them), so only the denominator changes
 __global__ __launch_bounds__(256) void fsn_mean_kernel(const float* __restrict__ mag, int n, float denom,
-                                                       float* __restrict__ mu, const int* __restrict__ tlen) {
+                                                       float* __restrict__ mu, const int* __restrict__ tlen, int la) {
     const int b = blockIdx.x;
-    if (tlen) denom = (float)NBIN * (tlen[b] + LA);
+    if (tlen) denom = (float)NBIN * (tlen[b] + la);
     const float* x = mag + (long)b * n;
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) s += x[i];
@@ -37,40 +40,43 @@ __global__ __launch_bounds__(256) void fsn_scale_kernel(const float* __restrict_
     if (i < n) y[i] = x[i] / (mu[i % B] + 1e-5f);
 }
 
-// sub-band input before normalisation: sb[t][k][n*B + b];  k < 31: noisy mag of bin reflect(n - 15 + k)
-// (base_model.py:29-42, reflect pad), k = 31: full-band output of bin n (model.py:88-96)
+// sub-band input before normalisation: sb[t][k][n*B + b], W = (2 sbn + 1) + (2 fbn + 1) rows per sub band n (model.py:88-96):
+//   k <  2 sbn + 1: noisy magnitude of bin reflect(n - sbn + k)                   unfold(noisy_mag, sbn)
+//   k >= 2 sbn + 1: full-band output of bin reflect(n - fbn + k - (2 sbn + 1))    unfold(fb_output, fbn)
+// base_model.py:29-42 pads the frequency axis by num_neighbor bins with mode="reflect" (the edge bin is not repeated: bin -j is bin j,
+// bin 256 + j is bin 256 - j) and cuts windows of 2 num_neighbor + 1 bins; num_neighbor = 0 returns the input as it is (:25-27),
+// which is the same rule with nothing to reflect.  One reflection is enough: the launcher keeps sbn, fbn <= 15 < NBIN.
+// A pure gather; consecutive threads write consecutive sequences s.
 __global__ __launch_bounds__(256) void fsn_build_sb_kernel(const float* __restrict__ magT, const float* __restrict__ fbo,
-                                                           float* __restrict__ sb, int B) {
+                                                           float* __restrict__ sb, int B, int sbn, int fbn) {
     const int S = NBIN * B;
     const int s = blockIdx.x * 256 + threadIdx.x;
     const int k = blockIdx.y, t = blockIdx.z;
     if (s >= S) return;
     const int n = s / B, b = s - n * B;
-    float v;
-    if (k == SBW - 1) {
-        v = fbo[((long)t * NBIN + n) * B + b];
-    } else {
-        int f = n - SBN + k;
-        if (f < 0) f = -f;
-        if (f >= NBIN) f = 2 * (NBIN - 1) - f;
-        v = magT[((long)t * NBIN + f) * B + b];
-    }
-    sb[((long)t * SBW + k) * S + s] = v;
+    const int nw = 2 * sbn + 1, W = nw + 2 * fbn + 1;
+    const bool noisy = k < nw;
+    int f = noisy ? n - sbn + k : n - fbn + (k - nw);
+    if (f < 0) f = -f;
+    if (f >= NBIN) f = 2 * (NBIN - 1) - f;
+    const float* src = noisy ? magT : fbo;
+    sb[((long)t * W + k) * S + s] = src[((long)t * NBIN + f) * B + b];
 }
 
 // column sums of a [rows][B] matrix (utterance = innermost index) -> mu[b] = sum / rows; two deterministic stages
 // (per-block partials in a fixed order, then a fixed-order fp64 sum) - no float atomics, so repeated decodes are
 // bit-identical
-// ragged batch: rows are (t, k, n) t-major; utterance b only counts its own tlen[b] + LA frames
+// ragged batch: rows are (t, k, n) t-major, frame_rows = W * 257 of them per frame; utterance b only counts its own tlen[b] + la frames
 __global__ __launch_bounds__(256) void fsn_colsum_kernel(const float* __restrict__ x, long rows, int B,
-                                                         float* __restrict__ part, const int* __restrict__ tlen) {
+                                                         float* __restrict__ part, const int* __restrict__ tlen, long frame_rows,
+                                                         int la) {
     __shared__ float sh[256];
     // thread handles column (tid % B) of rows tid / B + k * (256 / B)
     const int per = 256 / B;
     const int b = threadIdx.x % B, r0 = threadIdx.x / B;
     float s = 0.f;
     if (per > 0 && r0 < per) {
-        const long rmax = tlen ? (long)(tlen[b] + LA) * SBW * NBIN : rows;
+        const long rmax = tlen ? (long)(tlen[b] + la) * frame_rows : rows;
         for (long r = (long)blockIdx.x * per + r0; r < rmax; r += (long)gridDim.x * per) s += x[r * B + b];
     }
     sh[threadIdx.x] = s;
@@ -82,24 +88,24 @@ __global__ __launch_bounds__(256) void fsn_colsum_kernel(const float* __restrict
     }
 }
 __global__ void fsn_finish_mean_kernel(const float* __restrict__ part, float* __restrict__ mu, float denom, int B,
-                                       const int* __restrict__ tlen) {
+                                       const int* __restrict__ tlen, long frame_rows, int la) {
     const int b = threadIdx.x;
     if (b >= B) return;
-    if (tlen) denom = (float)(tlen[b] + LA) * SBW * NBIN;
+    if (tlen) denom = (float)((long)(tlen[b] + la) * frame_rows);
     double s = 0.0;
     for (int k = 0; k < FSN_SUM_BLOCKS; ++k) s += part[(long)k * B + b];
     mu[b] = (float)(s / denom);
 }
 
-// out[b][c][n][t] = mask[(n*B + b)][c][t + LA]                       (forward hook), or
+// out[b][c][n][t] = mask[(n*B + b)][c][t + la]                       (forward hook), or
 // est = mask (x) spec, decompressed (fullsubnet_sa_decode_vb.py:56-66)  (decode path)
 __global__ __launch_bounds__(256) void fsn_mask_kernel(const float* __restrict__ maskBT, const float* __restrict__ spec,
-                                                       float* __restrict__ out, int B, int T, float p_out) {
+                                                       float* __restrict__ out, int B, int T, float p_out, int la) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int n = blockIdx.y, b = blockIdx.z;
     if (t >= T) return;
-    const int Tp = T + LA;
-    const float* m = maskBT + ((long)(n * B + b) * 2) * Tp + t + LA;
+    const int Tp = T + la;
+    const float* m = maskBT + ((long)(n * B + b) * 2) * Tp + t + la;
     const float mr = m[0], mi = m[Tp];
     const long o = (((long)b * 2) * NBIN + n) * T + t;
     const long plane = (long)NBIN * T;
@@ -147,37 +153,51 @@ __global__ __launch_bounds__(256) void fsn_cum_fb_kernel(const float* __restrict
     }
     if (csum && tid == 0) csum[b] = run;
 }
-// sub bands: sb [n][32][S] in place, one thread per sequence s (sub-band of an utterance)
+// sub bands: sb [n][W][S] in place, one thread per sequence s (sub-band of an utterance)
 // origin (optional, [B]): sequence s = n * B + b belongs to row s % B, whose own frame index is t_first - origin[s % B]
+// WC = SBW: the decode script's width, the W values of a frame held in registers;  WC = 0: any width W, the rows read a second time
+// for the divide (the same values: nothing else writes them) - the sum runs over k = 0..W-1 in order in both forms
+template <int WC>
 __global__ __launch_bounds__(256) void fsn_cum_sb_kernel(float* __restrict__ sb, int n, int S, float* __restrict__ csum, int t_first,
-                                                         const int32_t* __restrict__ origin, int B) {
+                                                         const int32_t* __restrict__ origin, int B, int W) {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
     if (origin) t_first -= origin[s % B];
     float run = (csum && t_first > 0) ? csum[s] : 0.f;
-    for (int t = 0; t < n; ++t) {
-        float* xr = sb + (long)t * SBW * S + s;
-        float v[SBW], sum = 0.f;
+    if constexpr (WC > 0) {
+        for (int t = 0; t < n; ++t) {
+            float* xr = sb + (long)t * WC * S + s;
+            float v[WC], sum = 0.f;
 #pragma unroll
-        for (int k = 0; k < SBW; ++k) {
-            v[k] = xr[(long)k * S];
-            sum += v[k];
+            for (int k = 0; k < WC; ++k) {
+                v[k] = xr[(long)k * S];
+                sum += v[k];
+            }
+            run += sum;
+            const float d = run / ((float)WC * (float)(t_first + t + 1)) + FSN_EPS;
+#pragma unroll
+            for (int k = 0; k < WC; ++k) xr[(long)k * S] = v[k] / d;
         }
-        run += sum;
-        const float d = run / ((float)SBW * (float)(t_first + t + 1)) + FSN_EPS;
-#pragma unroll
-        for (int k = 0; k < SBW; ++k) xr[(long)k * S] = v[k] / d;
+    } else {
+        for (int t = 0; t < n; ++t) {
+            float* xr = sb + (long)t * W * S + s;
+            float sum = 0.f;
+            for (int k = 0; k < W; ++k) sum += xr[(long)k * S];
+            run += sum;
+            const float d = run / ((float)W * (float)(t_first + t + 1)) + FSN_EPS;
+            for (int k = 0; k < W; ++k) xr[(long)k * S] = xr[(long)k * S] / d;
+        }
     }
     if (csum) csum[s] = run;
 }
 // ---- offline_gaussian_norm (base_model.py:242-255): (x - mean) / (std + 1e-5), mean and the unbiased std (torch.std: N - 1) over the
 // whole utterance.  Both moments in ONE pass over a [rows][B] matrix (utterance = innermost index: the full band is [Tp * 257][B], the
-// sub bands [Tp * 32 * 257][B]), accumulated in float64 (the square of a float is exact there, so S2 - N mean^2 cancels nothing
+// sub bands [Tp * W * 257][B]), accumulated in float64 (the square of a float is exact there, so S2 - N mean^2 cancels nothing
 // that float32 holds), in the two deterministic stages of fsn_colsum / fsn_finish_mean: per-block partials in a fixed order, then
 // a fixed-order sum - no atomics, repeated decodes are bit-identical.  part [gridDim.x][2][B] float64.
-// ragged batch: rows are t-major, frame_rows of them per frame; utterance b only counts its own tlen[b] + LA frames
+// ragged batch: rows are t-major, frame_rows of them per frame; utterance b only counts its own tlen[b] + la frames
 __global__ __launch_bounds__(256) void fsn_moments_kernel(const float* __restrict__ x, long rows, int B, double* __restrict__ part,
-                                                          const int* __restrict__ tlen, long frame_rows) {
+                                                          const int* __restrict__ tlen, long frame_rows, int la) {
     __shared__ double sh[2][256];
     // thread handles column (tid % B) of rows tid / B + k * (256 / B), as fsn_colsum_kernel
     const int per = 256 / B;
@@ -185,7 +205,7 @@ __global__ __launch_bounds__(256) void fsn_moments_kernel(const float* __restric
     double s1 = 0.0, s2 = 0.0;
     if (per > 0 && r0 < per) {
         long rmax = rows;
-        if (tlen && (long)(tlen[b] + LA) * frame_rows < rows) rmax = (long)(tlen[b] + LA) * frame_rows;
+        if (tlen && (long)(tlen[b] + la) * frame_rows < rows) rmax = (long)(tlen[b] + la) * frame_rows;
 #pragma unroll 4
         for (long r = (long)blockIdx.x * per + r0; r < rmax; r += (long)gridDim.x * per) {
             const double v = x[r * B + b];
@@ -207,13 +227,13 @@ __global__ __launch_bounds__(256) void fsn_moments_kernel(const float* __restric
     }
 }
 // part [FSN_SUM_BLOCKS][2][B] -> stat[b] = mean, stat[B + b] = std + 1e-5 (float32, the divisor of :253);  N = rows, or the row's own
-// (tlen[b] + LA) * frame_rows;  var = (S2 - N mean^2) / (N - 1) in float64
+// (tlen[b] + la) * frame_rows;  var = (S2 - N mean^2) / (N - 1) in float64
 __global__ void fsn_finish_gauss_kernel(const double* __restrict__ part, float* __restrict__ stat, long rows, int B,
-                                        const int* __restrict__ tlen, long frame_rows) {
+                                        const int* __restrict__ tlen, long frame_rows, int la) {
     const int b = threadIdx.x;
     if (b >= B) return;
     long cnt = rows;
-    if (tlen && (long)(tlen[b] + LA) * frame_rows < rows) cnt = (long)(tlen[b] + LA) * frame_rows;
+    if (tlen && (long)(tlen[b] + la) * frame_rows < rows) cnt = (long)(tlen[b] + la) * frame_rows;
     const double N = (double)cnt;
     double s1 = 0.0, s2 = 0.0;
     for (int k = 0; k < FSN_SUM_BLOCKS; ++k) {
@@ -290,49 +310,70 @@ __global__ __launch_bounds__(256) void fsn_cln_fb_kernel(const float* __restrict
         csum2[b] = run2;
     }
 }
-// sub bands: sb [n][32][S] in place, one thread per sequence s (consecutive threads read consecutive s: coalesced); csum / csum2 [S]
+// sub bands: sb [n][W][S] in place, one thread per sequence s (consecutive threads read consecutive s: coalesced); csum / csum2 [S]
 // origin (optional, [B]): sequence s = n * B + b belongs to row s % B, whose own frame index is t_first - origin[s % B]
+// WC as fsn_cum_sb_kernel: SBW keeps a frame's values in registers, 0 takes any W and reads the rows twice
+template <int WC>
 __global__ __launch_bounds__(256) void fsn_cln_sb_kernel(float* __restrict__ sb, int n, int S, float* __restrict__ csum,
                                                          float* __restrict__ csum2, int t_first, const int32_t* __restrict__ origin,
-                                                         int B) {
+                                                         int B, int W) {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
     if (origin) t_first -= origin[s % B];
     const bool carry = csum && t_first > 0;
     float run = carry ? csum[s] : 0.f, run2 = carry ? csum2[s] : 0.f;
-    for (int t = 0; t < n; ++t) {
-        float* xr = sb + (long)t * SBW * S + s;
-        float v[SBW], sum = 0.f, sq = 0.f;
+    if constexpr (WC > 0) {
+        for (int t = 0; t < n; ++t) {
+            float* xr = sb + (long)t * WC * S + s;
+            float v[WC], sum = 0.f, sq = 0.f;
 #pragma unroll
-        for (int k = 0; k < SBW; ++k) {
+            for (int k = 0; k < WC; ++k) {
 #pragma clang fp contract(off)
-            v[k] = xr[(long)k * S];
-            const float q = v[k] * v[k];
-            sum += v[k];
-            sq += q;
-        }
-        run += sum;
-        run2 += sq;
-        float mean, sd;
-        fsn_cln_stats(run, run2, (float)SBW * (float)(t_first + t + 1), mean, sd);
+                v[k] = xr[(long)k * S];
+                const float q = v[k] * v[k];
+                sum += v[k];
+                sq += q;
+            }
+            run += sum;
+            run2 += sq;
+            float mean, sd;
+            fsn_cln_stats(run, run2, (float)WC * (float)(t_first + t + 1), mean, sd);
 #pragma unroll
-        for (int k = 0; k < SBW; ++k) xr[(long)k * S] = (v[k] - mean) / sd;
+            for (int k = 0; k < WC; ++k) xr[(long)k * S] = (v[k] - mean) / sd;
+        }
+    } else {
+        for (int t = 0; t < n; ++t) {
+            float* xr = sb + (long)t * W * S + s;
+            float sum = 0.f, sq = 0.f;
+            for (int k = 0; k < W; ++k) {
+#pragma clang fp contract(off)
+                const float v = xr[(long)k * S];
+                const float q = v * v;
+                sum += v;
+                sq += q;
+            }
+            run += sum;
+            run2 += sq;
+            float mean, sd;
+            fsn_cln_stats(run, run2, (float)W * (float)(t_first + t + 1), mean, sd);
+            for (int k = 0; k < W; ++k) xr[(long)k * S] = (xr[(long)k * S] - mean) / sd;
+        }
     }
     if (csum) {
         csum[s] = run;
         csum2[s] = run2;
     }
 }
-// frame-online: mask of network step tau (maskT [ns][2][S], s = n B + b) applied to the spectrum of frame tau - LA, which sits in
-// column col0 + tau of the chunk window ([B][2][257][Tw]); frames before the start of the stream (gt0 + tau < LA) do not exist
+// frame-online: mask of network step tau (maskT [ns][2][S], s = n B + b) applied to the spectrum of frame tau - la, which sits in
+// column col0 + tau of the chunk window ([B][2][257][Tw]); frames before the start of the stream (gt0 + tau < la) do not exist
 __global__ __launch_bounds__(256) void fsn_stream_apply_kernel(const float* __restrict__ maskT, const float* __restrict__ spec,
                                                                float* __restrict__ est, int B, int Tw, int ns, int col0, int gt0,
-                                                               float p_out, const int32_t* __restrict__ origin) {
+                                                               float p_out, const int32_t* __restrict__ origin, int la) {
     const int i = blockIdx.x * 256 + threadIdx.x, tau = blockIdx.y;
     const int S = NBIN * B;
     if (i >= S) return;
     if (origin) gt0 -= origin[i % B];      // the row's own frame index: a row younger than the look-ahead skips its steps alone
-    if (gt0 + tau < LA) return;
+    if (gt0 + tau < la) return;
     const int n = i / B, b = i - n * B, col = col0 + tau;
     const float mr = maskT[((long)tau * 2) * S + i], mi = maskT[((long)tau * 2 + 1) * S + i];
     const long o = (((long)b * 2) * NBIN + n) * Tw + col, plane = (long)NBIN * Tw;
@@ -351,51 +392,56 @@ __global__ __launch_bounds__(256) void fsn_stream_apply_kernel(const float* __re
 
 }  // namespace
 
-void launch_fsn_mean(const float* mag, int B, int n, float denom, float* mu, const int* tlen, hipStream_t st) {
-    hipLaunchKernelGGL(fsn_mean_kernel, dim3(B), dim3(256), 0, st, mag, n, denom, mu, tlen);
+void launch_fsn_mean(const float* mag, int B, int n, float denom, float* mu, const int* tlen, hipStream_t st, int la) {
+    hipLaunchKernelGGL(fsn_mean_kernel, dim3(B), dim3(256), 0, st, mag, n, denom, mu, tlen, la);
     SE_HIP(hipGetLastError());
 }
 void launch_fsn_scale(const float* x, float* y, long n, int B, const float* mu, hipStream_t st) {
     hipLaunchKernelGGL(fsn_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, n, B, mu);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_build_sb(const float* magT, const float* fbo, float* sb, int B, int steps, hipStream_t st) {
+void launch_fsn_build_sb(const float* magT, const float* fbo, float* sb, int B, int steps, hipStream_t st, int sbn, int fbn) {
+    SE_CHECK(sbn >= 0 && sbn <= NEIGHBORS_MAX && fbn >= 0 && fbn <= NEIGHBORS_MAX, "launch_fsn_build_sb: neighbour counts are 0..15");
     const int S = NBIN * B;
-    hipLaunchKernelGGL(fsn_build_sb_kernel, dim3((S + 255) / 256, SBW, steps), dim3(256), 0, st, magT, fbo, sb, B);
+    hipLaunchKernelGGL(fsn_build_sb_kernel, dim3((S + 255) / 256, sb_width(sbn, fbn), steps), dim3(256), 0, st, magT, fbo, sb, B, sbn, fbn);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_colsum(const float* x, long rows, int B, float* part, const int* tlen, hipStream_t st) {
+void launch_fsn_colsum(const float* x, long rows, int B, float* part, const int* tlen, hipStream_t st, long frame_rows, int la) {
     SE_CHECK(B >= 1 && B <= 256, "FullSubNet batch per call is limited to 256 utterances");
-    hipLaunchKernelGGL(fsn_colsum_kernel, dim3(FSN_SUM_BLOCKS), dim3(256), 0, st, x, rows, B, part, tlen);
+    hipLaunchKernelGGL(fsn_colsum_kernel, dim3(FSN_SUM_BLOCKS), dim3(256), 0, st, x, rows, B, part, tlen, frame_rows, la);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_finish_mean(const float* part, float* mu, float denom, int B, const int* tlen, hipStream_t st) {
+void launch_fsn_finish_mean(const float* part, float* mu, float denom, int B, const int* tlen, hipStream_t st, long frame_rows, int la) {
     SE_CHECK(B >= 1 && B <= 256, "FullSubNet batch per call is limited to 256 utterances");
-    hipLaunchKernelGGL(fsn_finish_mean_kernel, dim3(1), dim3(256), 0, st, part, mu, denom, B, tlen);
+    hipLaunchKernelGGL(fsn_finish_mean_kernel, dim3(1), dim3(256), 0, st, part, mu, denom, B, tlen, frame_rows, la);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_mask(const float* maskBT, const float* spec, float* out, int B, int T, float p_out, hipStream_t st) {
-    hipLaunchKernelGGL(fsn_mask_kernel, dim3((T + 255) / 256, NBIN, B), dim3(256), 0, st, maskBT, spec, out, B, T, p_out);
+void launch_fsn_mask(const float* maskBT, const float* spec, float* out, int B, int T, float p_out, hipStream_t st, int la) {
+    hipLaunchKernelGGL(fsn_mask_kernel, dim3((T + 255) / 256, NBIN, B), dim3(256), 0, st, maskBT, spec, out, B, T, p_out, la);
     SE_HIP(hipGetLastError());
 }
 void launch_fsn_cum_fb(const float* x, float* y, int n, int B, float* csum, int t_first, hipStream_t st, const int32_t* origin) {
     hipLaunchKernelGGL(fsn_cum_fb_kernel, dim3(B), dim3(256), 0, st, x, y, n, B, csum, t_first, origin);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_cum_sb(float* sb, int n, int S, float* csum, int t_first, hipStream_t st, const int32_t* origin) {
+void launch_fsn_cum_sb(float* sb, int n, int S, float* csum, int t_first, hipStream_t st, const int32_t* origin, int W) {
     SE_CHECK(!origin || (S >= NBIN && S % NBIN == 0), "launch_fsn_cum_sb: per-row origins need S = 257 * B sequences");
-    hipLaunchKernelGGL(fsn_cum_sb_kernel, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, t_first, origin, S / NBIN);
+    SE_CHECK(W >= 1 && W <= SBW_MAX, "launch_fsn_cum_sb: the sub-band width is 1..62");
+    if (W == SBW)
+        hipLaunchKernelGGL(fsn_cum_sb_kernel<SBW>, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, t_first, origin, S / NBIN, W);
+    else
+        hipLaunchKernelGGL(fsn_cum_sb_kernel<0>, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, t_first, origin, S / NBIN, W);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_moments(const float* x, long rows, int B, double* part, const int* tlen, long frame_rows, hipStream_t st) {
+void launch_fsn_moments(const float* x, long rows, int B, double* part, const int* tlen, long frame_rows, hipStream_t st, int la) {
     SE_CHECK(B >= 1 && B <= 256, "FullSubNet batch per call is limited to 256 utterances");
     SE_CHECK(rows >= 1 && frame_rows >= 1 && rows % frame_rows == 0, "launch_fsn_moments: rows is a whole number of frames");
-    hipLaunchKernelGGL(fsn_moments_kernel, dim3(FSN_SUM_BLOCKS), dim3(256), 0, st, x, rows, B, part, tlen, frame_rows);
+    hipLaunchKernelGGL(fsn_moments_kernel, dim3(FSN_SUM_BLOCKS), dim3(256), 0, st, x, rows, B, part, tlen, frame_rows, la);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_finish_gauss(const double* part, float* stat, long rows, int B, const int* tlen, long frame_rows, hipStream_t st) {
+void launch_fsn_finish_gauss(const double* part, float* stat, long rows, int B, const int* tlen, long frame_rows, hipStream_t st, int la) {
     SE_CHECK(B >= 1 && B <= 256, "FullSubNet batch per call is limited to 256 utterances");
-    hipLaunchKernelGGL(fsn_finish_gauss_kernel, dim3(1), dim3(256), 0, st, part, stat, rows, B, tlen, frame_rows);
+    hipLaunchKernelGGL(fsn_finish_gauss_kernel, dim3(1), dim3(256), 0, st, part, stat, rows, B, tlen, frame_rows, la);
     SE_HIP(hipGetLastError());
 }
 void launch_fsn_gauss_apply(const float* x, float* y, long n, int B, const float* stat, hipStream_t st) {
@@ -408,17 +454,21 @@ void launch_fsn_cln_fb(const float* x, float* y, int n, int B, float* csum, floa
     hipLaunchKernelGGL(fsn_cln_fb_kernel, dim3(B), dim3(256), 0, st, x, y, n, B, csum, csum2, t_first, origin);
     SE_HIP(hipGetLastError());
 }
-void launch_fsn_cln_sb(float* sb, int n, int S, float* csum, float* csum2, int t_first, hipStream_t st, const int32_t* origin) {
+void launch_fsn_cln_sb(float* sb, int n, int S, float* csum, float* csum2, int t_first, hipStream_t st, const int32_t* origin, int W) {
     SE_CHECK(!csum == !csum2, "launch_fsn_cln_sb: the two running sums come together");
     SE_CHECK(!origin || (S >= NBIN && S % NBIN == 0), "launch_fsn_cln_sb: per-row origins need S = 257 * B sequences");
-    hipLaunchKernelGGL(fsn_cln_sb_kernel, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, csum2, t_first, origin, S / NBIN);
+    SE_CHECK(W >= 1 && W <= SBW_MAX, "launch_fsn_cln_sb: the sub-band width is 1..62");
+    if (W == SBW)
+        hipLaunchKernelGGL(fsn_cln_sb_kernel<SBW>, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, csum2, t_first, origin, S / NBIN, W);
+    else
+        hipLaunchKernelGGL(fsn_cln_sb_kernel<0>, dim3((S + 255) / 256), dim3(256), 0, st, sb, n, S, csum, csum2, t_first, origin, S / NBIN, W);
     SE_HIP(hipGetLastError());
 }
 void launch_fsn_stream_apply(const float* maskT, const float* spec, float* est, int B, int Tw, int ns, int col0, int gt0,
-                             float p_out, hipStream_t st, const int32_t* origin) {
+                             float p_out, hipStream_t st, const int32_t* origin, int la) {
     const int S = NBIN * B;
     hipLaunchKernelGGL(fsn_stream_apply_kernel, dim3((S + 255) / 256, ns), dim3(256), 0, st, maskT, spec, est, B, Tw, ns, col0,
-                       gt0, p_out, origin);
+                       gt0, p_out, origin, la);
     SE_HIP(hipGetLastError());
 }
 

@@ -5,6 +5,7 @@ Same class names, constructor arguments, `load_state_dict` key schema, `eval()/c
 (libse_engine.so) - these classes hold no parameters and do no arithmetic themselves.
 """
 import functools
+import operator
 
 import numpy as np
 
@@ -203,7 +204,11 @@ class Model(_EngineModule):
     sequence_model: "LSTM" (the decode script's) or "GRU" (sequence_model.py:36-43; SE_CFG_FSN_GRU); norm_type, one of the four
     of norm_wrapper (base_model.py:296-308): "offline_laplace_norm" (:197-209, the decode script's), "cumulative_laplace_norm"
     (:212-240; SE_CFG_FSN_CUMULATIVE), "offline_gaussian_norm" (:242-255; SE_CFG_FSN_GAUSSIAN) or "cumulative_layer_norm"
-    (:258-294; SE_CFG_FSN_CUM_LAYERNORM).  The two cumulative norms are causal: with the LSTM the engine then also streams."""
+    (:258-294; SE_CFG_FSN_CUM_LAYERNORM).  The two cumulative norms are causal: with the LSTM the engine then also streams.
+    look_ahead 0..6 (SE_CFG_FSN_LOOK_AHEAD: a stream is final look_ahead frames late), fb_num_neighbors 0..15
+    (SE_CFG_FSN_FB_NEIGHBORS) and sb_num_neighbors 0..15 (read by the engine from the shape of
+    sb_model.sequence_model.weight_ih_l0, [4H or 3H, (2 sbn + 1) + (2 fbn + 1)]) combine with both sequence models and all four norms.
+    num_freqs, the hidden sizes and the two output activations keep the decode script's values."""
     _model = 'fullsubnet'
     SE_CFG_FSN_GRU = 8
     SE_CFG_FSN_CUMULATIVE = 16
@@ -212,6 +217,18 @@ class Model(_EngineModule):
     # norm_type -> its SE_CFG_* bit (include/se_engine.h); the norms have no parameters, so the key schema is the same for all four
     NORM_FLAGS = {"offline_laplace_norm": 0, "cumulative_laplace_norm": SE_CFG_FSN_CUMULATIVE,
                   "offline_gaussian_norm": SE_CFG_FSN_GAUSSIAN, "cumulative_layer_norm": SE_CFG_FSN_CUM_LAYERNORM}
+    LOOK_AHEAD_MAX = 6
+    NEIGHBORS_MAX = 15
+
+    @staticmethod
+    def SE_CFG_FSN_LOOK_AHEAD(n):
+        """bits 22-24, look_ahead + 1; nothing set = the decode script's 2 (include/se_engine.h)"""
+        return ((n + 1) & 7) << 22
+
+    @staticmethod
+    def SE_CFG_FSN_FB_NEIGHBORS(n):
+        """bits 25-28, fb_num_neighbors; the decode script's value is 0"""
+        return (n & 15) << 25
 
     def __init__(self, num_freqs=257, look_ahead=2, sequence_model="LSTM", fb_num_neighbors=0, sb_num_neighbors=15,
                  fb_output_activate_function="ReLU", sb_output_activate_function=None, fb_model_hidden_size=512,
@@ -219,17 +236,41 @@ class Model(_EngineModule):
                  weight_init=True, **kw):
         cfg = (num_freqs, look_ahead, fb_num_neighbors, sb_num_neighbors, fb_output_activate_function,
                sb_output_activate_function, fb_model_hidden_size, sb_model_hidden_size, norm_type)
-        if (cfg[:-1] != (257, 2, 0, 15, "ReLU", None, 512, 384) or sequence_model not in ("LSTM", "GRU")
-                or norm_type not in self.NORM_FLAGS):
+
+        def whole(v, hi):      # any integer type (a numpy.int64 read from a config or an npz included), no bool, no float
+            try:
+                return not isinstance(v, (bool, np.bool_)) and 0 <= operator.index(v) <= hi
+            except TypeError:
+                return False
+
+        fixed = (num_freqs, fb_output_activate_function, sb_output_activate_function, fb_model_hidden_size, sb_model_hidden_size)
+        if (fixed != (257, "ReLU", None, 512, 384) or not whole(look_ahead, self.LOOK_AHEAD_MAX)
+                or not whole(fb_num_neighbors, self.NEIGHBORS_MAX) or not whole(sb_num_neighbors, self.NEIGHBORS_MAX)
+                or sequence_model not in ("LSTM", "GRU") or norm_type not in self.NORM_FLAGS):
             raise NotImplementedError("the engine builds the decode script's FullSubNet configuration (sequence model LSTM "
-                                      "or GRU, norm " + ", ".join(self.NORM_FLAGS) + "); got "
-                                      + repr(cfg + (sequence_model,)))
+                                      "or GRU, norm " + ", ".join(self.NORM_FLAGS) + ") with look_ahead in 0..6 and fb_num_neighbors "
+                                      "and sb_num_neighbors in 0..15 each; num_freqs=257, fb_model_hidden_size=512, "
+                                      "sb_model_hidden_size=384, fb_output_activate_function='ReLU' and "
+                                      "sb_output_activate_function=None are fixed; got " + repr(cfg + (sequence_model,)))
+        look_ahead, fb_num_neighbors, sb_num_neighbors = (operator.index(v) for v in (look_ahead, fb_num_neighbors, sb_num_neighbors))
         # the cumulative norms are causal - the engine then also streams (se_stream_*)
         kw['flags'] = kw.get('flags', 0) | self.NORM_FLAGS[norm_type]
+        # the script's values set nothing (zero in a field = the script's value): its flags stay what they were
+        if look_ahead != 2:
+            kw['flags'] |= self.SE_CFG_FSN_LOOK_AHEAD(look_ahead)
+        kw['flags'] |= self.SE_CFG_FSN_FB_NEIGHBORS(fb_num_neighbors)
+        self._neighbors = (sb_num_neighbors, fb_num_neighbors)
+        self.look_ahead = look_ahead
         if sequence_model == "GRU":
             kw['flags'] = kw.get('flags', 0) | self.SE_CFG_FSN_GRU
             self.__class__ = _ModelGRU            # same engine model, the GRU's [3H, .] key schema
         super().__init__(**kw)
+
+    @_class_or_instance_method
+    def state_dict_schema(cls, self):
+        """Class.state_dict_schema(): the decode script's shape; instance.state_dict_schema(): this instance's neighbour counts."""
+        sbn, fbn = getattr(self, '_neighbors', (15, 0))
+        return schemas.fullsubnet_schema(3 if cls._schema == 'fullsubnet_gru' else 4, sbn, fbn)
 
     def forward(self, x):
         B, _, F, T = x.shape

@@ -140,14 +140,15 @@ def dccrn_rlstm_schema(kernel_num=(16, 32, 64, 128, 256, 256), rnn_units=256, ff
     d['tranform.bias'] = ((inp,), 'f32')
     return d
 
-def fullsubnet_schema(gates=4):
+def fullsubnet_schema(gates=4, sb_num_neighbors=15, fb_num_neighbors=0):
     """FullSubNet/fullsubnet_net_sa/model.py:38-56 with the decode script's sizes (fullsubnet_sa_decode_vb.py:11-24);
-    gates=3: `sequence_model="GRU"` (sequence_model.py:36-43)."""
+    gates=3: `sequence_model="GRU"` (sequence_model.py:36-43).  The neighbour counts change one shape: the sub-band model's input
+    width (2 sb_num_neighbors + 1) + (2 fb_num_neighbors + 1) (model.py:50), the second dim of its weight_ih_l0."""
     d = OrderedDict()
     _lstm(d, 'fb_model.sequence_model.', 257, 512, 2, gates=gates)
     d['fb_model.fc_output_layer.weight'] = ((257, 512), 'f32')
     d['fb_model.fc_output_layer.bias'] = ((257,), 'f32')
-    _lstm(d, 'sb_model.sequence_model.', 32, 384, 2, gates=gates)
+    _lstm(d, 'sb_model.sequence_model.', (2 * sb_num_neighbors + 1) + (2 * fb_num_neighbors + 1), 384, 2, gates=gates)
     d['sb_model.fc_output_layer.weight'] = ((2, 384), 'f32')
     d['sb_model.fc_output_layer.bias'] = ((2,), 'f32')
     return d

@@ -24,7 +24,7 @@ streams (synthetic weights, seeded clips).  Prints one JSON line per (model, B, 
   With --source-rate SR (48000, 32000) the callers are fed at SR through SourceRateStream, one hop (SR / 16000 * hop source samples)
   apart, parked as SourceStreamSnapshot pairs and joined with SourceStreamSnapshot.join (se_resampler_state_join and
   se_stream_state_join); the same result line, with `source_rate` in it.
-Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new,fullsubnet_cln] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000] [--swap]
+Usage: python tools/stream_latency.py [--models crn,dccrn,ctsnet_new,fullsubnet_cln] [--batch 1,16] [--chunk 1,8] [--sliding 4000] [--source-rate 48000] [--swap] [--look-ahead 0]
        python tools/stream_latency.py --staggered 32 [--models crn,dccrn] [--source-rate 48000]"""
 import argparse
 import json
@@ -38,6 +38,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import se_amd  # noqa: E402,F401
 from se_amd import synth  # noqa: E402
 
+FSN_LOOK_AHEAD = None      # --look-ahead: Model(look_ahead=) of the FullSubNet configurations (None: the decode script's 2)
 ROW_ORIGINS = ('ctsnet_new', 'taylorsenet_new', 'g2net_new', 'fullsubnet_cum', 'fullsubnet_cln')
 SEEDS = {'crn': 12, 'lstm': 11, 'gcrn': 16, 'dpcrn': 13, 'dccrn': 14, 'taylorsenet_new': 19, 'g2net_new': 20}
 
@@ -47,6 +48,8 @@ def build(name, B, L, **kw):
     from se_amd.models import MODEL_CLASSES
     if name == 'ctsnet_new':
         return models_new.CTSNet(max_batch=B, max_samples=L, **kw).load_synthetic(17, 18)
+    if name.startswith('fullsubnet_') and FSN_LOOK_AHEAD is not None:
+        kw['look_ahead'] = FSN_LOOK_AHEAD
     if name == 'fullsubnet_cum':        # the causal norm (base_model.py:143-166) is what makes FullSubNet streamable
         from se_amd.models import Model
         return Model(max_batch=B, max_samples=L, norm_type='cumulative_laplace_norm', **kw).load_synthetic(15)
@@ -310,8 +313,13 @@ def main():
     ap.add_argument('--staggered', type=int, default=0, help='N callers one hop apart: by turns at batch 1 against joined into one group')
     ap.add_argument('--tracking', type=float, default=None, metavar='SECONDS',
                     help='begin on the tracking unit-RMS scale with this time constant (0: never forget) instead of a fixed scale')
+    ap.add_argument('--look-ahead', type=int, default=None, metavar='FRAMES',
+                    help='fullsubnet_cum / fullsubnet_cln: build Model(look_ahead=FRAMES), 0..6 (default: the decode script\'s 2); a stream '
+                         'is final FRAMES frames late')
     ap.add_argument('--running', action='store_true', help='begin on the running unit-RMS scale instead of a fixed scale')
     a = ap.parse_args()
+    global FSN_LOOK_AHEAD
+    FSN_LOOK_AHEAD = a.look_ahead
     if (a.tracking is not None or a.running) and (a.swap or a.staggered or a.source_rate):
         ap.error('--tracking / --running time the plain push loop only: not with --swap, --staggered or --source-rate')
     if a.tracking is not None and a.running:
