@@ -249,7 +249,7 @@ __global__ __launch_bounds__(Shape<false>::NT) void stft2_kernel(const std::cond
         if (t < Tb) {
             int idx = t * a.hop + n - N / 2;
             if (idx < 0) idx = -idx;
-            if (idx >= Lpad) idx = 2 * (Lpad - 1) - idx;
+            if (idx >= Lpad) idx = (Lpad - 1) - (idx - (Lpad - 1));      // (2 (Lpad - 1) - idx; the doubling leaves int from Lpad 2^30 on)
             if (idx >= 0 && idx < L) v = x[idx] * cc * w;
         }
         return v;

@@ -25,6 +25,8 @@
 // stream_left_edge_frames() is the smallest t_done that satisfies all four; tests/stream_join_check.cpp walks a stream sample by
 // sample through the index expressions above and finds the same number.  (The window `win` may be shorter than n_fft; frames are
 // n_fft long for every index above, so the bound is taken for n_fft.)
+// The position independence derived here is exercised at the far end of the counter range too: tests/test_gpu_late_stream.py moves parked
+// streams of every streamable network by up to 2^31 - 1 - max(max_samples, n_fft + 32 hop) samples and holds the continuation to bit identity.
 #pragma once
 #include "stream_rows.h"
 #include <algorithm>

@@ -158,6 +158,22 @@ void np_stream_destroy(void* h) {
     (void)hipDeviceSynchronize();
     delete static_cast<Stream*>(h);
 }
+// state slot i of the stream (call order; it exists once a chunk has taken it) from / to host memory, `bytes` = its whole size: a test
+// reads the carried sums a chunk left, or puts the sums of a stream that is far on in their place
+int np_slot_read(void* h, int i, void* host, long long bytes) {
+    return guarded(nullptr, [&] {
+        const Stream* sm = static_cast<Stream*>(h);
+        SE_CHECK(sm && host && i >= 0 && i < (int)sm->slots.v.size() && bytes == (long long)sm->slots.v[i].second, "np_slot_read: no such slot / size");
+        SE_HIP(hipMemcpy(host, sm->slots.v[i].first, (size_t)bytes, hipMemcpyDeviceToHost));
+    });
+}
+int np_slot_write(void* h, int i, const void* host, long long bytes) {
+    return guarded(nullptr, [&] {
+        Stream* sm = static_cast<Stream*>(h);
+        SE_CHECK(sm && host && i >= 0 && i < (int)sm->slots.v.size() && bytes == (long long)sm->slots.v[i].second, "np_slot_write: no such slot / size");
+        SE_HIP(hipMemcpy(sm->slots.v[i].first, host, (size_t)bytes, hipMemcpyHostToDevice));
+    });
+}
 
 // ---- TCM block: a state dict in torch layout -> TcmBlock::load (the fused weights through tcm_fused_build) -> run_tcm
 void* np_sd_create() { return new StateDict(); }

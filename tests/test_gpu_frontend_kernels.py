@@ -740,9 +740,10 @@ def istft_lds(N):
     return max(NFB * N * 4, (N // 2 + 1) * 33 * 4) + 4 * N
 
 
-def run_stft(geom, xs, L, Lpad, T, p_in, planes, c=None, Tp=None, pitch=None, t_first=0, col0=0, w0=0, rows=None):
+def run_stft(geom, xs, L, Lpad, T, p_in, planes, c=None, Tp=None, pitch=None, t_first=0, col0=0, w0=0, rows=None, shift=0):
     """one launch; xs: the clips from sample 0 (row b holds xs[b][w0:len_b] from column 0, NaN beyond).  Returns spec [B][2][F][Tp], mag
-    [B][F][Tp] (None where the plane is not asked for)"""
+    [B][F][Tp] (None where the plane is not asked for).  shift: the launch is told that the stream is `shift` frames further on - every
+    position it is given moves by shift * hop samples or shift frames, the buffers are the same"""
     N, hop, win = geom
     B, F = len(xs), N // 2 + 1
     lens = rows[0] if rows is not None else [L] * B
@@ -756,7 +757,8 @@ def run_stft(geom, xs, L, Lpad, T, p_in, planes, c=None, Tp=None, pitch=None, t_
     bm = Buf(B * F * Tp) if 'mag' in planes else None
     bc = Buf(B, c) if c is not None else None
     rb, MB = rows_buf(*rows) if rows is not None else (None, 0)
-    rec = call('fp_stft', N, hop, win, bw, pitch, B, L, Lpad, bc, p_in, bs, bm, T, Tp, t_first, col0, w0, rb, MB, nrec=1)
+    D = shift * hop
+    rec = call('fp_stft', N, hop, win, bw, pitch, B, L + D, Lpad + D, bc, p_in, bs, bm, T + shift, Tp, t_first + shift, col0, w0 + D, rb, MB, nrec=1)
     cp = 0 if p_in == 1.0 else (1 if p_in == 0.5 else 2)
     want = dict(kernel='stft2', N=N, MAG=int(bm is not None), CP=cp, FSC=0, gx=(T - t_first + NFB - 1) // NFB, gy=B, block=256,
                 shmem=stft_lds(N), ragged=int(rows is not None))
@@ -877,10 +879,48 @@ def test_stft_windowed(geom, T, t_first):
             check_forward(case, form, geom, xs, [L] * 3, [Lpad] * 3, [T] * 3, T, c, p_in, spec, mag, t_first, col0)
 
 
+def late_shift(geom, top):
+    """the largest number of frames a launch whose highest sample position is `top` can be moved by and stay at or below the sample limit of
+    the smallest sliding engine (csrc/stream_window.h), in whole multiples of 4 samples"""
+    N, hop, _ = geom
+    limit = 2 ** 31 - 1 - (N + 32 * hop)
+    f = (limit - top) // hop
+    while (f * hop) % 4:
+        f -= 1
+    return f
+
+
+@gpu
+@pytest.mark.parametrize('T,t_first', [(60, 37), (41, 40)])
+@pytest.mark.parametrize('geom', GEOMS, ids=GID)
+def test_stft_windowed_near_the_stream_limit(geom, T, t_first):
+    """the stream-window launches of test_stft_windowed (checked there against float64) once more with every position moved to the far end
+    of the counter range - the stream ends exactly at the sample limit, the window origin and the first frame lie just below it: the
+    same input, and the same spectrum BIT FOR BIT, mid-stream and with the end reflection / tail pad"""
+    N, hop, _ = geom
+    for end in (False, True):
+        padded = end and geom == (512, 128, 512)
+        L = (T - 1) * hop + (-5 if padded else 5 if end else N // 2 + 11)
+        Lpad = pad_to_hop(L, hop) if padded else L
+        w_low = min(t_first * hop - N // 2, Lpad - N // 2 - 1 if end else L) // 4 * 4
+        xs = [make_clip(L, KINDS[b % 3], 70 + b + T + N + hop) for b in range(3)]
+        c = np.asarray([1.25, 0.0371, 23.0], f32)
+        f = late_shift(geom, L)
+        assert 0 <= 2 ** 31 - 1 - (N + 32 * hop) - (L + f * hop) < 4 * hop and (t_first + f) * hop > 2 ** 31 - 40 * hop - 64 * hop
+        for w0, col0, p_in, planes in ((w_low, 4, 0.5, ('spec', 'mag')), (w_low - 4 * 25, 0, 1.0, ('spec',))):
+            Tp = col0 + T - t_first + 2
+            early = run_stft(geom, xs, L, Lpad, T, p_in, planes, c, Tp=Tp, t_first=t_first, col0=col0, w0=w0)
+            late = run_stft(geom, xs, L, Lpad, T, p_in, planes, c, Tp=Tp, t_first=t_first, col0=col0, w0=w0, shift=f)
+            for a, b in zip(early[:2], late[:2]):
+                assert (a is None and b is None) or np.array_equal(a, b, equal_nan=True), \
+                    ('stft window %s T%d t_first%d w0=%d %s: the launch %d frames later differs' % (GID[GEOMS.index(geom)], T, t_first, w0,
+                                                                                                  'end' if end else 'mid', f))
+
+
 # ---- inverse -----------------------------------------------------------------------------------------------------------------------------
-def run_istft(geom, specs, T, Lout, c=None, t_off=0, t_lo=0, o_lo=0, frame_inv=None, rows=None, Tp=None, out_pitch=None):
+def run_istft(geom, specs, T, Lout, c=None, t_off=0, t_lo=0, o_lo=0, frame_inv=None, rows=None, Tp=None, out_pitch=None, shift=0):
     """one launch; specs[b]: complex [F][n_b] holding the frames t_lo .. t_lo + n_b - 1 of row b; every other column of the buffer is NaN.
-    Returns wav [B][out_pitch]"""
+    Returns wav [B][out_pitch].  shift: the launch is told that the stream is `shift` frames further on (as run_stft)"""
     N, hop, win = geom
     B, F = len(specs), N // 2 + 1
     Tp = Tp or T - t_off + 3
@@ -893,7 +933,9 @@ def run_istft(geom, specs, T, Lout, c=None, t_off=0, t_lo=0, o_lo=0, frame_inv=N
     bc = Buf(B, c) if c is not None else None
     bf = Buf(frame_inv.size, frame_inv) if frame_inv is not None else None
     rb, MB = rows_buf(*rows) if rows is not None else (None, 0)
-    rec = call('fp_istft', N, hop, win, bs, B, T, Tp, bc, bo, out_pitch, Lout, t_off, t_lo, o_lo, bf, 64 if bf else 0, rb, MB, nrec=1)
+    D = shift * hop
+    rec = call('fp_istft', N, hop, win, bs, B, T + shift, Tp, bc, bo, out_pitch, Lout + D, t_off + shift, t_lo + shift, o_lo + D, bf, 64 if bf else 0,
+               rb, MB, nrec=1)
     own, halo = inv_geometry(geom)
     pos_base = (o_lo + N // 2) // hop * hop
     gx = (N // 2 + Lout - pos_base + own * hop - 1) // (own * hop)
@@ -972,6 +1014,25 @@ def test_istft_windowed(geom):
     wav, form, _ = run_istft(geom, specs, T, Lout, c, t_off=t_off, t_lo=t_lo, o_lo=o_lo)
     check_inverse('istft window %s later chunk' % gid, form, geom, specs, wav, t_lo, [T] * 3, o_lo, [Lout] * 3, Lout,
                   [np.full(T - t_lo, 1.0 / float(c[b])) for b in range(3)])
+
+
+@gpu
+@pytest.mark.parametrize('geom', GEOMS, ids=GID)
+def test_istft_windowed_near_the_stream_limit(geom):
+    """the later-chunk launch of test_istft_windowed (checked there against float64) with its frames and samples moved to the far end of the
+    counter range, the last sample written being the last a stream can emit: the same spectra, the same samples bit for bit.  (The first
+    chunk of a stream, t_off < 0, cannot be late.)"""
+    N, hop, _ = geom
+    c = np.asarray([1.25, 0.0371, 23.0], f32)
+    T, t_off, t_lo = 70, 34, 36
+    o_lo, Lout = 40 * hop - N // 2, T * hop - N // 2 - 3
+    specs = inv_case(geom, T - t_lo, 600 + N + hop)
+    f = late_shift(geom, Lout)
+    assert 0 <= 2 ** 31 - 1 - (N + 32 * hop) - (Lout + f * hop) < 4 * hop
+    early, _, _ = run_istft(geom, specs, T, Lout, c, t_off=t_off, t_lo=t_lo, o_lo=o_lo)
+    late, _, _ = run_istft(geom, specs, T, Lout, c, t_off=t_off, t_lo=t_lo, o_lo=o_lo, shift=f)
+    assert np.isfinite(early[:, :Lout - o_lo]).all()
+    assert np.array_equal(early, late, equal_nan=True), 'istft window %s later chunk: the launch %d frames later differs' % (GID[GEOMS.index(geom)], f)
 
 
 @gpu

@@ -32,6 +32,15 @@ cumulative_layer_norm (base_model.py:258-294), float32 running sums, the express
   Chunked runs ([1, 3, 5]) and rows with a frame origin ({0, 2, -3}) are held to BIT identity with the one-shot run / the row run alone
   at its shifted t_first: same operations in the same order.
 
+Late frames (`test_late_frames`): the four frame-counting kernels - fsn_cum_fb / fsn_cum_sb (cumulative_laplace_norm, launched through the
+  origin probe libse_originprobe.so, which takes the origin pointer) and fsn_cln_fb / fsn_cln_sb - at t_first = 2^24 + 3 and at the last
+  frame a 512 / 256 stream reaches before its sample limit, in chunks of 1 and 5 frames, against float64 with the divisor n (t_first + t + 1).
+  The carried sums are those of a stationary signal - t_first frames of the chunk's own mean frame sum, computed in float64 and rounded
+  to float32: an input, exact on both sides, so the running sum has the roundings of THIS chunk only: chain = tree + (t + 1) (+ 1, + 2 as
+  above) in place of tree + frames.  The divisor is no longer exact: (float)(t_first + t + 1) rounds an integer above 2^24 and the
+  product with (float)n rounds again - two roundings, relative 2 U, on every quotient by n (e_mean, e_q; the Laplace norm's d).  The
+  same cases run once more with row origins that put the late index into t_first - origin[b] at a small group frame.
+
 `test_bounds_hold_for_a_float32_restatement` (CPU) evaluates the cumulative kernels' arithmetic in numpy float32, in their order, and holds
 it to the same bounds: a bound that the intended arithmetic itself misses would be caught without a GPU."""
 import ctypes as C
@@ -124,9 +133,10 @@ def cln_data(n, F, S, seed, zero_first=False):
     return x
 
 
-def ref_cln(x, tree, t_first=0, run0=None):
+def ref_cln(x, tree, t_first=0, run0=None, late=False):
     """cumulative_layer_norm of x [n][F][S] in float64 -> y, its bound, (S1, S2) after the last frame, their bounds (module docstring);
-    run0: the carried (S1, S2) [2][S].  t_first [S] or scalar"""
+    run0: the carried (S1, S2) [2][S].  t_first [S] or scalar.  late: a chunk far into a stream ("Late frames" in the module docstring) -
+    the carry is an input, so the running sums have the roundings of this chunk's frames alone, and the divisor has two of its own"""
     x = d64(x)
     n, F, S = x.shape
     c1, c2 = (0.0, 0.0) if run0 is None else (d64(run0[0])[None], d64(run0[1])[None])
@@ -134,16 +144,18 @@ def ref_cln(x, tree, t_first=0, run0=None):
     S2 = np.cumsum((x * x).sum(1), 0) + c2
     frames = (np.zeros(S) + t_first)[None] + np.arange(n)[:, None] + 1.0
     cnt = F * frames
-    a1 = (tree + frames + 1) * U * np.abs(S1)                # (x >= 0: sum|x| = S1)
-    a2 = (tree + frames + 2) * U * S2
+    adds = np.arange(n)[:, None] + 1.0 if late else frames    # additions behind the running sum that are this launch's to answer for
+    ce = 2 * U if late else 0.0                               # relative error of the float32 divisor
+    a1 = (tree + adds + 1) * U * np.abs(S1)                   # (x >= 0: sum|x| = S1)
+    a2 = (tree + adds + 2) * U * S2
     mean = S1 / cnt
-    e_mean = a1 / cnt + U * np.abs(mean)
+    e_mean = a1 / cnt + (U + ce) * np.abs(mean)
     cross = 2 * mean * S1
     e_cross = 2 * (e_mean * np.abs(S1) + np.abs(mean) * a1) + U * np.abs(cross)
     diff = S2 - cross
     e_diff = a2 + e_cross + U * np.abs(diff)
     q = diff / cnt
-    e_q = e_diff / cnt + U * np.abs(q)
+    e_q = e_diff / cnt + (U + ce) * np.abs(q)
     mm = mean * mean
     e_mm = 2 * np.abs(mean) * e_mean + U * mm
     var = q + mm
@@ -453,6 +465,89 @@ def test_cln_row_origins(kind):
         assert np.array_equal(sums[0][sel], ca[0].np(Sb)) and np.array_equal(sums[1][sel], ca[1].np(Sb)), (kind, 'row', b, 'sums')
     assert np.isfinite(got).all()
     WORST.setdefault('fsn_cln_' + kind, (0.0, 'origins'))
+
+
+# ------------------------------------------------------------------------------------------------ late frames
+T_LAST = (2 ** 31 - 1 - (512 + 32 * 256)) // 256       # the last frame index of a 512 / 256 stream at its sample limit (csrc/stream_window.h)
+LATE_T, LATE_N = (2 ** 24 + 3, T_LAST), (1, 5)
+_orp = None
+
+
+def orp():
+    """the origin probe (tests/test_gpu_origin_kernels.py): the cumulative Laplace norm's launchers with the origin pointer"""
+    global _orp
+    if _orp is None:
+        path = os.path.join(PKG, 'libse_originprobe.so')
+        assert os.path.exists(path), 'libse_originprobe.so is missing: run build() (make -C csrc)'
+        L = C.CDLL(path)
+        L.orp_fsn_cum_fb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.orp_fsn_cum_sb.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.orp_last_error.restype = C.c_char_p
+        _orp = L
+    return _orp
+
+
+def run_cum(kind, x, B, cs, t_first, origin=None):
+    """one launch of the cumulative Laplace norm on x [n][F][S] -> y (fb: out of place; sb: in place)"""
+    n, F, S = x.shape
+    bx = Buf(x.size, x)
+    org = origin.ptr if origin is not None else None
+    if kind == 'fb':
+        by = Buf(x.size)
+        rc = orp().orp_fsn_cum_fb(bx.ptr, by.ptr, n, B, cs.ptr, t_first, org)
+    else:
+        by = bx
+        rc = orp().orp_fsn_cum_sb(bx.ptr, n, S, cs.ptr, t_first, org)
+    assert rc == 0, orp().orp_last_error().decode()
+    assert by.untouched() and bx.untouched() and cs.untouched() and (origin is None or origin.untouched())
+    return by.np(n, F, S)
+
+
+def ref_cum_late(x, tree, t_first, run0):
+    """cumulative_laplace_norm (base_model.py:212-240) of a late chunk x [n][F][S] in float64 -> y, its bound, the sum after the last frame,
+    its bound.  run = carry + this chunk's frame sums: tree + (t + 1) roundings; d = run / (F frames) + EPS: the divisor's two, the
+    quotient, the addition; y = x / d: one more, and the slack of tests/test_gpu_model_kernels.py ref_cum (3 U in all)"""
+    x = d64(x)
+    n, F, S = x.shape
+    run = np.cumsum(x.sum(1), 0) + d64(run0)[None]
+    adds = np.arange(n)[:, None] + 1.0
+    frames = (np.zeros(S) + t_first)[None] + adds
+    d = run / (F * frames) + EPS32
+    y = x / d[:, None, :]
+    e_s = (tree + adds + 2 + 2) * U
+    return y, (e_s[:, None, :] + 3 * U) * np.abs(y) + TINY, run[-1], (tree + adds[-1] + 1) * U * np.abs(run[-1]) + TINY
+
+
+@gpu
+@pytest.mark.parametrize('kind', ['fb', 'sb'])
+@pytest.mark.parametrize('norm', ['cum', 'cln'])
+def test_late_frames(norm, kind):
+    B, (F, tree) = 3, (NBIN, 9) if kind == 'fb' else (SBW, 32)
+    S = B if kind == 'fb' else NBIN * B
+    name = 'fsn_%s_%s' % (norm, kind)
+    for T in LATE_T:
+        for n in LATE_N:
+            t0 = T - (n - 1)                                    # the chunk's last frame is frame T
+            for own in (None, (t0, t0 - 2, t0 - 3)):            # rows of one age; or origins: a small group frame, late own frames
+                x = cln_data(n, F, S, 31 * n + (T & 1023) + (own is not None))
+                tf = np.full(S, t0) if own is None else np.asarray([own[s % B] for s in range(S)])
+                # the carry of a stationary signal: tf frames of the chunk's own mean frame sum, in float64, rounded to float32 - an input
+                m1, m2 = d64(x).sum(1).mean(0), (d64(x) ** 2).sum(1).mean(0)
+                carry = np.stack([tf * m1, tf * m2]).astype(f32)
+                group, origin = (t0, None) if own is None else (7, Buf(B, np.asarray([7 - o for o in own], np.int32), torch.int32))
+                case = '%s t_first %d n %d%s' % (name, t0, n, '' if own is None else ' as group frame 7 - origin')
+                if norm == 'cum':
+                    cs = Buf(S, carry[0])
+                    got = run_cum(kind, x, B, cs, group, origin)
+                    y, ybd, run, rbd = ref_cum_late(x, tree, tf, carry[0])
+                    sums = cs.np(S)
+                else:
+                    cs = (Buf(S, carry[0]), Buf(S, carry[1]))
+                    got = run_cln(kind, x, B, cs, group, origin)
+                    y, ybd, run, rbd = ref_cln(x, tree, tf, carry, late=True)
+                    sums = np.stack([cs[0].np(S), cs[1].np(S)])
+                verify(case, name, got, y, ybd)
+                verify(case + ' sums', name, sums, run, rbd)
 
 
 @gpu

@@ -1268,6 +1268,92 @@ def test_cln_frame_online(widths, Cc, Fq, kind, K, regime):
     run_stream_case(widths, Cc, Fq, kind, K, regime=regime)
 
 
+# ---- frame-online cumulative LayerNorm, late in a stream ---------------------------------------------------------------------------------
+# the chunk's last frame: 2^24 + 3, and the last frame a 320 / 160 stream (the cLN networks) reaches at its sample limit, csrc/stream_window.h
+LATE_FRAMES = (2 ** 24 + 3, (2 ** 31 - 1 - (320 + 32 * 160)) // 160)
+# (n, C, F, kind, regime): the register form for n = 1 and n = 2 (the second with the residual in the kernel, R just below 256 * 41), the
+# window form with and without launch_add, the three-launch form (R * W > 32768); 'offset': mean 100 x the spread, the cancelling regime
+LATE_CASES = [(1, 4, 7, 'post', 'normal'), (2, 64, 161, 'res', 'offset'), (5, 4, 7, 'res', 'offset'), (16, 8, 20, 'post', 'normal'),
+              (64, 64, 33, 'post', 'offset')]
+
+
+def ref_cln_late(x, g, b, sl, res, t0, carry):
+    """cLN of a chunk x [B][C][F][n] whose first frame is the row's frame t0, carried sums carry [B][2] (float64, an input: exact on both
+    sides) -> y, its bound (ref_cln's: the statistics are float64 in the kernels, divisor R (t + 1) included, so no rounding is added
+    for the late index; its float64 term counts the R n additions of this chunk and the four operations of the variance, not every term
+    since frame 0, which the exact carry stands for), and the sums after the chunk with their bound: every one of the R n + 1 additions rounds once in float64"""
+    B, C_, F_, n = x.shape
+    sh = (1, C_, 1, 1)
+    R = C_ * F_
+    s = carry[:, 0:1] + x.sum((1, 2)).cumsum(-1)
+    q = carry[:, 1:2] + (x * x).sum((1, 2)).cumsum(-1)
+    cnt = R * (t0 + torch.arange(1, n + 1, dtype=F64, device=x.device))
+    mu, msq = s / cnt, q / cnt
+    var = torch.clamp((q - 2 * mu * s) / cnt + mu * mu, min=0.0)
+    mu, var, msq = mu[:, None, None, :], var[:, None, None, :], msq[:, None, None, :]
+    rs = 1.0 / torch.sqrt(var + EPS)
+    z, dz = affine_bound(x, mu, rs, g.view(sh), b.view(sh), sl.view(sh), None, U * mu.abs(), U + C_DOT * 2.0 ** -53 * math.sqrt(R * n + 4) * msq / (var + EPS))
+    if res is not None:
+        z = z + res
+        dz = dz + U * z.abs()
+    sums = torch.stack([s[:, -1], q[:, -1]], 1)
+    sbd = (R * n + 2) * 2.0 ** -53 * torch.stack([carry[:, 0].abs() + x.abs().sum((1, 2, 3)), carry[:, 1] + (x * x).sum((1, 2, 3))], 1)
+    return z, dz, sums, sbd
+
+
+@gpu
+@pytest.mark.parametrize('n,Cc,Fq,kind,regime', LATE_CASES)
+@pytest.mark.parametrize('t_last', LATE_FRAMES)
+def test_cln_frame_online_late(t_last, n, Cc, Fq, kind, regime):
+    """launch_cln's frame-online forms at a late frame index of their own (the engine-level late streams keep a row's own index small through
+    its origin): one chunk of n frames ending at frame 2^24 + 3 / at the last reachable frame.  The carried sums are those of a stationary
+    signal - t0 frames with the chunk's own mean and mean square, formed in float64 - and are put into the stream's state slot in place of
+    the sums a first chunk left there.  Outputs against float64 under the bound of the frame-online cases above; the sums the chunk leaves
+    against float64 too."""
+    B, H = 2, 8
+    t0 = t_last - (n - 1)
+    R = Cc * Fq
+    x = make((B, Cc, Fq, n), regime, 900 + Cc + Fq + n).cuda()
+    g, b, sl = (v.cuda() for v in params(Cc, Fq + 1))
+    res = make(x.shape, 'normal', 902).cuda() if kind == 'res' else None
+    carry = torch.stack([t0 * R * x.mean((1, 2, 3)), t0 * R * (x * x).mean((1, 2, 3))], 1)          # [B][2] float64
+    y, bd, sums, sbd = ref_cln_late(x, g, b, sl, res, t0, carry)
+    L = lib()
+    L.np_slot_read.argtypes = L.np_slot_write.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
+    st = L.np_stream_create(B)
+    assert st
+    gd, bdv, sld = dev32(g), dev32(b), dev32(sl)
+    T = H + n
+    want = stream_form(n, R, Cc, 0, False, n, T)
+    in_kernel = res is not None and want == ['cln_window_reg']
+    full = want + (['add'] if res is not None and not in_kernel else [])
+    try:
+        for first, at in ((True, 0), (False, t0)):      # a first chunk makes the slot; then the late chunk on the seeded sums
+            win = torch.full((B, Cc, Fq, T), float('nan'), dtype=torch.float32, device='cuda')
+            win[..., H:] = x.to(torch.float32)
+            xb, yb = Buf(win.numel(), 0, win), Buf(win.numel(), 0)
+            rb = None
+            if res is not None:
+                rw = torch.full_like(win, float('nan'))
+                rw[..., H:] = res.to(torch.float32)
+                rb = Buf(win.numel(), 0, rw)
+            recs = call('np_norm2d_prelu', 1, xb, yb, gd, bdv, sld, B, Cc, Fq, T, rb, None, st, H, n, at)
+            assert kernels(recs) == full, (kernels(recs), full)
+            if first:
+                host = np.ascontiguousarray(carry.cpu().numpy(), np.float64)
+                assert L.np_slot_write(st, 0, host.ctypes.data, host.nbytes) == 0, L.np_last_error().decode()
+        left = np.zeros((B, 2), np.float64)
+        assert L.np_slot_read(st, 0, left.ctypes.data, left.nbytes) == 0, L.np_last_error().decode()
+    finally:
+        L.np_stream_destroy(st)
+    yw = yb.v.reshape(win.shape)
+    assert yb.untouched() and torch.isnan(yw[..., :H]).all(), 'the chunk wrote outside its new frames'
+    case = 'late cln t0 %d n%d C%d F%d %s %s' % (t0, n, Cc, Fq, kind, regime)
+    tags = ['stream:' + want[0] + ('<%d>' % n if want[0] == 'cln_window_reg' else '')] + (['stream:launch_add'] if 'add' in full else [])
+    verify(case, tags, yw[..., H:], y, bd)
+    verify(case + ' carried sums', [], torch.from_numpy(left).cuda(), sums, sbd)
+
+
 # ---- layernorm_cf ----------------------------------------------------------------------------------------------------------------------
 LN_CASES = [(T, C_, F_, post, pr, rs_, REGIMES[i % 5]) for i, (T, C_, F_, post, pr, rs_) in enumerate(
     [(1, 3, 1, 0, False, False), (63, 2, 2, 0, False, True), (64, 31, 1, 1, False, False), (65, 4, 8, 0, True, True), (401, 3, 11, 1, True, True),
