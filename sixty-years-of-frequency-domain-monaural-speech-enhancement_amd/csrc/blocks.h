@@ -1,5 +1,6 @@
 // Building blocks shared by the TCM / gated-U-Net models (CTSNet, TaylorSENet, G2Net).
 #pragma once
+#include "cln_select.h"
 #include "decode_frame.h"
 #include "rnn.h"
 #include <cmath>
@@ -31,7 +32,7 @@ struct NormAct {
 inline void norm2d_prelu(const NormAct& n, const float* x, float* y, int B, int C, int F, int T, hipStream_t st,
                          const float* res = nullptr) {
     if (n.cum) {
-        // the residual rides on the apply pass (offline, k_misc.hip: cln_apply_plane_kernel) or on the one- / two-frame register
+        // the residual rides on the apply pass (offline, k_cln.hip: cln_apply_plane_kernel) or on the one- / two-frame register
         // kernel of a frame-online push
         if (res && (!stream_ctx() || cln_stream_takes_res(C, F))) {
             launch_cln(x, y, n.g, n.b, nullptr, n.s, nullptr, 0, B, C, F, T, st, res);
@@ -52,8 +53,7 @@ inline float* in_stats_scratch(int B, int C, int F, int T, hipStream_t st) {
     return reinterpret_cast<float*>(device_scratch(2, (size_t)B * C * F * ((T + 31) / 32) * 2 * sizeof(float), st));
 }
 inline bool cln_stats_enabled() {
-    static const bool on = !(getenv("SE_CLN_STATS") && atoi(getenv("SE_CLN_STATS")) == 0);
-    return on && !ragged_ctx() && !stream_ctx();
+    return cln_tuning_env().stats && !ragged_ctx() && !stream_ctx();
 }
 inline float* cln_parts_scratch(int B, int Fout, int T, hipStream_t st) {
     return reinterpret_cast<float*>(device_scratch(7, (size_t)B * Fout * T * 2 * sizeof(float), st));

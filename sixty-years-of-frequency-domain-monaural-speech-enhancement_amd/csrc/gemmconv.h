@@ -90,7 +90,7 @@ struct GCParams {
     long st_b, st_c, st_f;   // float strides of the statistics tensor
     // optional (same tile configurations, one m-tile): per (b, output frequency row, frame) the (sum, sum of squares) over ALL
     // output channels of the values this launch stores - [B][Fout][Tout][2] floats - for the CumulativeLayerNorm behind the layer
-    // (k_misc.hip: cln_scan_parts_kernel sums the rows and scans the frames; the norm's own statistics pass over the tensor -
+    // (k_cln.hip: cln_scan_parts_kernel sums the rows and scans the frames; the norm's own statistics pass over the tensor -
     // 6 % of a G2Net_new / TaylorSENet_new step - is not launched)
     float* cstats;
     long cs_b, cs_f;

@@ -314,7 +314,8 @@ void launch_tcm_chain(const TcmStreamW* const* f, const TcmFusedHeads* hd, const
 // statistics of all C*F values of frames 0..t;  x [B][C][F][T] (F = 1 for 1-D), gain / bias [C].
 //   y = FIR_K( cLN( PReLU_pre(x) ) )   (TCM branch head, K > 0, not in place)   or   y = PReLU_post( cLN(x) )
 // res (optional, offline, plain 2-D form only; may alias y): y = PReLU_post( cLN(x) ) + res
-// frame-online chunk: true when launch_cln(..., res) adds the residual in its own launch (one- / two-frame register form)
+// Which kernels a call reaches, and what it refuses: cln_select.h; the kernels and the launcher: k_cln.hip.
+// frame-online chunk: true when launch_cln(..., res) adds the residual in its own launch (cln_select's takes_res for the open chunk)
 bool cln_stream_takes_res(int C, int F);
 void launch_cln(const float* x, float* y, const float* gain, const float* bias, const float* pre_slope,
                 const float* post_slope, const float* fir, int K, int B, int C, int F, int T, hipStream_t s,
@@ -442,7 +443,9 @@ struct LstmLaunchRec {
 void lstm_set_launch_log(std::vector<LstmLaunchRec>* log);
 void lstm_log_launch(const LstmLaunchRec& r);
 
-// Form of one dispatch of the normalisation passes (k_misc.hip) and of the one-workgroup-per-utterance TCM block (k_tcm.hip), for
+constexpr int NU = 8;      // independent loads per thread in the streaming passes of the norm kernels (k_misc.hip, k_cln.hip)
+
+// Form of one dispatch of the normalisation passes (k_misc.hip, k_cln.hip) and of the one-workgroup-per-utterance TCM block (k_tcm.hip), for
 // tests that must know which kernel a launch reached (csrc/tests/norm_probe.hip).  Host-side only: nothing the kernels compute
 // depends on it.  Fields a kernel does not have are 0.
 struct NormLaunchRec {

@@ -1,4 +1,4 @@
-// Test-only probe of the normalisation passes (k_misc.hip: InstanceNorm, cumulative LayerNorm, layernorm_cf, the TCM branch head)
+// Test-only probe of the normalisation passes (k_misc.hip: InstanceNorm, layernorm_cf, the TCM branch head; k_cln.hip: cumulative LayerNorm)
 // and of the TCM block (blocks.h run_tcm: k_tcm.hip's one-workgroup-per-utterance kernel or the multi-launch path), called as the
 // models call them - through blocks.h norm2d_prelu / tcm_head / run_tcm / TcmBlock::load where the models go through those, through
 // the launchers otherwise - on device buffers the caller owns, with a record of every dispatch (norm_set_launch_log).  Ragged

@@ -1,4 +1,4 @@
-"""One normalisation pass or one TCM block at a time against float64.  The norm passes of csrc/k_misc.hip (InstanceNorm in four
+"""One normalisation pass or one TCM block at a time against float64.  The norm passes of csrc/k_misc.hip and csrc/k_cln.hip (InstanceNorm in four
 forms, cumulative LayerNorm offline and frame-online, layernorm_cf, the TCM branch head) and the one-workgroup-per-utterance TCM
 block of csrc/k_tcm.hip each choose a code path from something the whole-model fixtures do not vary: the mutual 16 B alignment of
 input, output and residual, P = F * T against the unroll widths, T against 1024 and against 4, the chunk width of a stream, the
@@ -58,7 +58,7 @@ Q_PROP = 3.0
 EPS = 1e-5
 F64 = torch.float64
 REGIMES = ('normal', 'offset', 'const', 'tiny', 'outlier')
-NU = 8                      # k_misc.hip: loads in flight per thread
+NU = 8                      # kernels.h: loads in flight per thread
 
 REACHED = set()             # forms seen by the GPU cases of this process (test_every_form_reached)
 WORST = {}                  # form -> worst error / bound
