@@ -10,7 +10,13 @@
  *     the engine never frees them.  Scratch and weights are engine-owned, sized at create / finalize.
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  Work is enqueued, not synchronised;
  *     only se_engine_finalize() and se_engine_destroy() synchronise.
- *   - one handle per GPU / rank; a handle is not thread-safe.
+ *   - a handle is not thread-safe, and its calls are ordered: a call on a handle must come after that handle's previous call
+ *     in stream order (the same stream, or one made to wait for it) - the workspace is one per handle.
+ *   - several handles of one device may be driven from ONE host thread on DIFFERENT streams and be in flight at once: each
+ *     returns bit for bit what it returns when called alone, with or without SE_CFG_GRAPHS (tests/test_gpu_two_engines.py).
+ *     Handles share nothing that a running kernel writes: scratch is per (purpose, device, stream), and what a captured graph
+ *     keeps the address of is the capturing handle's own.  Two host threads driving two handles at the same time are outside
+ *     this contract (they would enqueue onto the same process-wide auxiliary streams unordered).
  *   - all floating-point data is fp32 (the reference feeds `torch.FloatTensor`).
  */
 #ifndef SE_ENGINE_H
@@ -492,7 +498,11 @@ int se_get_stage_profile(se_engine* e, int32_t stage, double* ms, int64_t* launc
 /* Sample-rate conversion in front of the path: librosa.resample(y, sr_in, sr_out, fix=True, scale=False) as called at
  * DCCRN/dccrn_decode_vb.py:26 and LSTM/lstm_decode_vb.py:34 (VoiceBank+DEMAND ships at 48 kHz; the models run at 16 kHz).
  * Stateless (no engine handle; errors through se_last_error(NULL)).  Device pointers; `n_in` samples per row in,
- * se_resample_samples(n_in, sr_in, sr_out) = ceil(n_in * sr_out / sr_in) samples per row out. */
+ * se_resample_samples(n_in, sr_in, sr_out) = ceil(n_in * sr_out / sr_in) samples per row out.
+ * Calls may be in flight on several hipStreams at once, at equal or different ratios, and may come from several threads: the
+ * filter table and (for sr_in % sr_out != 0) the table of read positions are kept per ratio and device from the first call at
+ * that ratio on, shared with se_resample_ragged, written once and then only read.  A later call at a known ratio waits for
+ * nothing; a call waits for the device only when its row is longer than any seen at its ratio and the position table grows. */
 int64_t se_resample_samples(int32_t n_in, int32_t sr_in, int32_t sr_out);
 int se_resample(const float* in_dev, int64_t in_pitch, int32_t batch, int32_t n_in, int32_t sr_in, int32_t sr_out,
                 float* out_dev, int64_t out_pitch, void* stream);

@@ -33,8 +33,19 @@ def time_registers(n_out, sample_ratio):
     return t
 
 
-def resample(x, sr_orig, sr_new):
-    """resampy.resample(x, sr_orig, sr_new, filter='kaiser_best') for a 1-D float64 signal."""
+def time_registers_fast(n_out, sample_ratio):
+    """time_registers without the Python loop: numpy's add.accumulate is the same left-to-right float64 sum
+    (tests/test_resample.py holds the two equal)."""
+    if n_out <= 0:
+        return np.empty(0, dtype=np.float64)
+    inc = np.full(n_out, 1.0 / sample_ratio, dtype=np.float64)
+    inc[0] = 0.0
+    return np.add.accumulate(inc)
+
+
+def resample_at(x, sr_orig, sr_new, ts, fast_registers=True):
+    """Output samples `ts` (indices below int(len(x) * ratio)) of resample(x, sr_orig, sr_new), each by the same arithmetic:
+    a long signal can be checked at a few places without the whole loop."""
     x = np.asarray(x, dtype=np.float64)
     ratio = float(sr_new) / sr_orig
     n_out = int(x.shape[0] * ratio)
@@ -46,9 +57,10 @@ def resample(x, sr_orig, sr_new):
     scale = min(1.0, ratio)
     index_step = int(scale * num_table)
     nwin, n_orig = win.shape[0], x.shape[0]
-    treg = time_registers(n_out, ratio)
-    y = np.zeros(n_out, dtype=np.float64)
-    for t in range(n_out):
+    treg = (time_registers_fast if fast_registers else time_registers)(n_out, ratio)
+    ts = np.asarray(ts, dtype=np.int64)
+    y = np.zeros(ts.shape[0], dtype=np.float64)
+    for j, t in enumerate(ts):
         n = int(treg[t])
         frac = scale * (treg[t] - n)
         index_frac = frac * num_table
@@ -56,15 +68,22 @@ def resample(x, sr_orig, sr_new):
         eta = index_frac - offset
         i_max = min(n + 1, (nwin - offset) // index_step)
         idx = offset + index_step * np.arange(i_max)
-        y[t] += np.dot(win[idx] + eta * delta[idx], x[n - np.arange(i_max)])
+        y[j] += np.dot(win[idx] + eta * delta[idx], x[n - np.arange(i_max)])
         frac = scale - frac
         index_frac = frac * num_table
         offset = int(index_frac)
         eta = index_frac - offset
         k_max = min(n_orig - n - 1, (nwin - offset) // index_step)
         idx = offset + index_step * np.arange(k_max)
-        y[t] += np.dot(win[idx] + eta * delta[idx], x[n + 1 + np.arange(k_max)])
+        y[j] += np.dot(win[idx] + eta * delta[idx], x[n + 1 + np.arange(k_max)])
     return y
+
+
+def resample(x, sr_orig, sr_new):
+    """resampy.resample(x, sr_orig, sr_new, filter='kaiser_best') for a 1-D float64 signal."""
+    x = np.asarray(x, dtype=np.float64)
+    n_out = int(x.shape[0] * (float(sr_new) / sr_orig))
+    return resample_at(x, sr_orig, sr_new, np.arange(n_out), fast_registers=False)
 
 
 def librosa_resample(y, orig_sr, target_sr):

@@ -100,6 +100,30 @@ inline bool first_on_device(bool (&seen)[64]) {
 // into its kernel nodes (cooperative-LSTM exchange / flags, cLN statistics, InstanceNorm partial sums) and the old
 // buffer is large enough for that shape, so replaying it after a larger shape has grown the slot stays valid.  Capacity
 // at least doubles on growth, so the retired buffers of a slot sum to less than its final size.
+// The nodes of a replayed graph do not run on the streams they were captured on, and the auxiliary streams a model forks onto
+// are process-wide (model.h: shared_aux): a pointer baked in under their key would be shared by every engine's replays and by
+// every engine's eager work on those streams, with nothing ordering the two.  So while an engine warms or captures a shape, its
+// ScratchOwner replaces the key of every auxiliary stream by a key of the engine's own (scratch_owner_set; engine.hip): what a
+// captured node points at is handed out to that engine alone, whose calls are ordered on the caller's stream.
+struct ScratchOwner {
+    static constexpr int N = 3;           // EngineCtx::MAX_AUX
+    const hipStream_t* from = nullptr;    // the engine's EngineCtx::aux: the process-wide streams it has forked onto so far, null else
+    char tag[N] = {};
+    hipStream_t key(int i) { return reinterpret_cast<hipStream_t>(&tag[i]); }      // (a map key, never used as a stream)
+};
+inline ScratchOwner*& scratch_owner() {
+    static thread_local ScratchOwner* v = nullptr;
+    return v;
+}
+inline void scratch_owner_set(ScratchOwner* o) { scratch_owner() = o; }
+// scratch_set_log: per-thread record of every hand-out (tests only; off unless a log is set): the slot's purpose and key, the
+// stream the work goes to, the buffer, and whether that stream was capturing
+struct ScratchRec { int purpose; hipStream_t key, stream; char* p; int capturing; };
+inline std::vector<ScratchRec>*& scratch_log() {
+    static thread_local std::vector<ScratchRec>* v = nullptr;
+    return v;
+}
+inline void scratch_set_log(std::vector<ScratchRec>* log) { scratch_log() = log; }
 struct ScratchPool {
     struct Slot { char* p = nullptr; size_t cap = 0; std::vector<char*> retired; };
     std::map<std::tuple<int, int, hipStream_t>, Slot> slots;
@@ -114,15 +138,40 @@ inline char* device_scratch(int purpose, size_t need, hipStream_t s) {
     ScratchPool& P = scratch_pool();
     int dev = 0;
     SE_HIP(hipGetDevice(&dev));
+    hipStream_t key = s;
+    if (ScratchOwner* o = scratch_owner())
+        for (int i = 0; i < ScratchOwner::N; ++i)
+            if (o->from && o->from[i] && o->from[i] == s) key = o->key(i);
     std::lock_guard<std::mutex> lk(P.mu);
-    ScratchPool::Slot& sl = P.slots[std::make_tuple(purpose, dev, s)];
+    ScratchPool::Slot& sl = P.slots[std::make_tuple(purpose, dev, key)];
     if (need > sl.cap) {
         if (sl.p) sl.retired.push_back(sl.p);
         const size_t cap = need > 2 * sl.cap ? need : 2 * sl.cap;
         SE_HIP(hipMalloc(&sl.p, cap));
         sl.cap = cap;
     }
+    if (std::vector<ScratchRec>* log = scratch_log()) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(s, &cap);
+        log->push_back(ScratchRec{purpose, key, s, sl.p, cap == hipStreamCaptureStatusActive ? 1 : 0});
+    }
     return sl.p;
+}
+// the slots under an engine's own keys go with the engine (its graphs are destroyed, nothing else was ever given them)
+inline void scratch_owner_release(int dev, ScratchOwner& o) {
+    ScratchPool& P = scratch_pool();
+    std::lock_guard<std::mutex> lk(P.mu);
+    for (auto it = P.slots.begin(); it != P.slots.end();) {
+        bool mine = false;
+        for (int i = 0; i < ScratchOwner::N; ++i) mine = mine || std::get<2>(it->first) == o.key(i);
+        if (mine && std::get<1>(it->first) == dev) {
+            if (it->second.p) (void)hipFree(it->second.p);
+            for (char* r : it->second.retired) (void)hipFree(r);
+            it = P.slots.erase(it);
+        } else {
+            ++it;
+        }
+    }
 }
 // Engine lifetime bookkeeping (se_engine_create / se_engine_destroy): when the LAST engine of a device goes away, the
 // device's scratch slots (and the buffers they retired) are freed - a long-lived process that creates and destroys engines

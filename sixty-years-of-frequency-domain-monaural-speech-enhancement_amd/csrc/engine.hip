@@ -289,6 +289,7 @@ int se_engine_destroy(se_engine* e) {
     for (auto& c2 : e->ctx2)
         if (c2 && c2->arena.base()) gc_unregister_overread_range(c2->arena.base());
     const int dev = e->cfg.device;
+    scratch_owner_release(dev, e->scratch_own);      // (the device is idle and the graphs that named these buffers are gone)
     delete e;
     scratch_engine_destroyed(dev);      // the device's last engine takes the engine-lifetime scratch slots with it
     if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
@@ -488,6 +489,14 @@ int se_enhance_batch(se_engine* e, const float* wav_in_dev, int64_t in_pitch, in
             const std::pair<int, int> key(batch, n_samples);
             // capture on the engine-owned stream: the caller's stream may be the legacy default stream, which cannot capture
             hipStream_t cs = e->cap_stream.get();
+            // warm-up and capture take the scratch of forked work under this engine's own keys (common.h: ScratchOwner): the
+            // warm-up grows the very slots whose addresses the capture bakes in
+            static_assert(ScratchOwner::N == EngineCtx::MAX_AUX, "one scratch key per auxiliary stream");
+            e->scratch_own.from = e->ctx.aux;
+            struct OwnScratch {
+                explicit OwnScratch(ScratchOwner* o) { scratch_owner_set(o); }
+                ~OwnScratch() { scratch_owner_set(nullptr); }
+            } own(&e->scratch_own);
             if (std::find(e->warmed.begin(), e->warmed.end(), key) == e->warmed.end()) {
                 // first call of a shape: eager, but on the capture stream (fork / join around the caller's stream) so that
                 // the lazily grown scratch buffers - keyed by stream - already exist when the shape is captured

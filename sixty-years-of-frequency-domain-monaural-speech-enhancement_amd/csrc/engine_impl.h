@@ -42,6 +42,9 @@ struct se_engine {
     int rag_next = 0;
     DevBuf<int> rag_win;           // device [4 * max_batch]: the rows' sizes as the current window launch of se_enhance_long_ragged sees them
     OwnedStream cap_stream;
+    // the keys under which work forked onto the process-wide auxiliary streams takes its scratch while a shape is warmed or captured
+    // (common.h: ScratchOwner)
+    ScratchOwner scratch_own;
     Event ev_fork, ev_join;
     // Two half-batches side by side (round 6: Uformer, DPCRN, CTSNet, TaylorSENet): a second instance of the model with its own context and
     // workspace decodes rows [B / 2, B) of a se_enhance_batch call on a process-wide auxiliary stream while the first decodes

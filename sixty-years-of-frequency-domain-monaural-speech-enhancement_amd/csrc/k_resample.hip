@@ -215,21 +215,65 @@ __global__ __launch_bounds__(256) void resampler_state_gather_kernel(const RowPt
     if (j < keep) dst[(long)blockIdx.y * keep + j] = rp.src[blockIdx.y][j];
 }
 
-struct Tables {
+// What se_resample and se_resample_ragged keep per ratio and device for the life of the process: the (scaled) filter table and, when
+// the ratio is no integer decimation, the position table - on the host as far as it has been summed, on the device as far as the
+// longest row seen needed it.  A table is written once and then only read, and a position table that must grow is replaced after
+// the device has gone idle: a launch on one hipStream never has its tables rewritten by a call on another (one table per device,
+// rewritten for every new ratio behind a wait for the CALLER's stream alone, was the rule of se_resample until two calls on two
+// streams were tested: DESIGN.md 4.5).
+struct RatioTables {
+    int sr_in = 0, sr_out = 0;
+    double* win = nullptr;
+    std::vector<double> tr;
+    double acc = 0.0;
+    double* dev_tr = nullptr;
+    size_t dev_cap = 0;
+};
+struct ResampleTables {
     std::mutex mu;
     std::vector<double> host;
-    double* dev_unit = nullptr;      // table as built (upsampling)
-    double* dev_scaled = nullptr;    // table * ratio of the last downsampling ratio seen
-    double scaled_ratio = 0.0;
-    double* dev_treg = nullptr;
-    size_t treg_cap = 0;
+    std::vector<std::unique_ptr<RatioTables>> ratios;
 };
-Tables& tables() {
-    static Tables t[64];              // one set of tables per device
+ResampleTables& resample_tables() {
+    static ResampleTables t[64];      // one set of tables per device
     int dev = 0;
     SE_HIP(hipGetDevice(&dev));
     SE_CHECK(dev >= 0 && dev < 64, "device ordinal");
     return t[dev];
+}
+// the entry of a ratio, made by the first call at this ratio on this device (T.mu held)
+RatioTables* ratio_tables(ResampleTables& T, const ResamplePlan& plan, int sr_in, int sr_out) {
+    for (auto& r : T.ratios)
+        if (r->sr_in == sr_in && r->sr_out == sr_out) return r.get();
+    if (T.host.empty()) T.host = build_window();
+    std::vector<double> w(T.host);
+    if (plan.ratio < 1.0)
+        for (auto& v : w) v *= plan.ratio;                          // interp_win *= sample_ratio
+    std::unique_ptr<RatioTables> fresh(new RatioTables());
+    fresh->sr_in = sr_in; fresh->sr_out = sr_out;
+    SE_HIP(hipMalloc(&fresh->win, RS_NWIN * sizeof(double)));
+    const hipError_t e = hipMemcpy(fresh->win, w.data(), RS_NWIN * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) (void)hipFree(fresh->win);
+    SE_HIP(e);
+    T.ratios.push_back(std::move(fresh));
+    return T.ratios.back().get();
+}
+// read positions [0, n_calc) of a ratio that is no integer decimation, on the device (T.mu held): resampy advances the read
+// position by repeated float64 addition, and the sum is carried on from where it stopped
+const double* ratio_positions(RatioTables* R, const ResamplePlan& plan, size_t n_calc) {
+    if (n_calc > R->dev_cap) {
+        // the table grows: the one place a call waits - launches on other hipStreams may still read the old table
+        const size_t cap = std::max<size_t>(n_calc, 2 * R->dev_cap);
+        ragged_positions_extend(plan, R->tr, R->acc, (int64_t)cap);
+        SE_HIP(hipDeviceSynchronize());
+        if (R->dev_tr) (void)hipFree(R->dev_tr);
+        R->dev_tr = nullptr;
+        R->dev_cap = 0;
+        SE_HIP(hipMalloc(&R->dev_tr, cap * sizeof(double)));
+        SE_HIP(hipMemcpy(R->dev_tr, R->tr.data(), cap * sizeof(double), hipMemcpyHostToDevice));
+        R->dev_cap = cap;
+    }
+    return R->dev_tr;
 }
 
 }  // namespace
@@ -274,51 +318,19 @@ long resample_out_samples(int n_in, int sr_in, int sr_out) {
 void launch_resample(const float* x, long in_pitch, int batch, int n_in, int sr_in, int sr_out, float* y, long out_pitch,
                      hipStream_t s) {
     SE_CHECK(sr_in > 0 && sr_out > 0 && n_in > 0 && batch > 0, "resample: bad arguments");
-    const double ratio = (double)sr_out / sr_in;
-    Tables& T = tables();
-    if (T.host.empty()) {
-        T.host = build_window();
-        SE_HIP(hipMalloc(&T.dev_unit, RS_NWIN * sizeof(double)));
-        SE_HIP(hipMalloc(&T.dev_scaled, RS_NWIN * sizeof(double)));
-        SE_HIP(hipMemcpy(T.dev_unit, T.host.data(), RS_NWIN * sizeof(double), hipMemcpyHostToDevice));
-    }
+    const ResamplePlan plan = resample_plan(sr_in, sr_out);
     ResampleArgs a{};
     a.x = x; a.in_pitch = in_pitch; a.n_in = n_in; a.y = y; a.out_pitch = out_pitch;
-    a.n_calc = (int)((double)n_in * ratio);                         // resampy: int(shape * sample_ratio)
+    a.n_calc = (int)((double)n_in * plan.ratio);                    // resampy: int(shape * sample_ratio)
     a.n_out = (int)resample_out_samples(n_in, sr_in, sr_out);
-    a.scale = std::min(1.0, ratio);
-    a.index_step = (int)(a.scale * RS_BITS);
-    a.inc = 1.0 / ratio;
-    if (ratio < 1.0) {
-        if (T.scaled_ratio != ratio) {                              // interp_win *= sample_ratio
-            std::vector<double> w(T.host);
-            for (auto& v : w) v *= ratio;
-            SE_HIP(hipStreamSynchronize(s));
-            SE_HIP(hipMemcpy(T.dev_scaled, w.data(), RS_NWIN * sizeof(double), hipMemcpyHostToDevice));
-            T.scaled_ratio = ratio;
-        }
-        a.win = T.dev_scaled;
-    } else {
-        a.win = T.dev_unit;
-    }
-    if (sr_in % sr_out == 0) {
-        a.treg = nullptr;                                           // t * inc is exact: same values as the running sum
-    } else {
-        // resampy advances the read position by repeated float64 addition: reproduce that rounding on the host
-        std::vector<double> tr((size_t)a.n_calc);
-        double acc = 0.0;
-        for (int i = 0; i < a.n_calc; ++i) {
-            tr[i] = acc;
-            acc += a.inc;
-        }
-        if (tr.size() > T.treg_cap) {
-            if (T.dev_treg) (void)hipFree(T.dev_treg);
-            SE_HIP(hipMalloc(&T.dev_treg, tr.size() * sizeof(double)));
-            T.treg_cap = tr.size();
-        }
-        SE_HIP(hipStreamSynchronize(s));
-        SE_HIP(hipMemcpy(T.dev_treg, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice));
-        a.treg = T.dev_treg;
+    a.scale = plan.scale; a.index_step = plan.index_step; a.inc = plan.inc;
+    {
+        ResampleTables& T = resample_tables();
+        std::lock_guard<std::mutex> lock(T.mu);
+        RatioTables* R = ratio_tables(T, plan, sr_in, sr_out);
+        a.win = R->win;
+        // (integer decimation: t * inc is exact, the same values as the running sum)
+        a.treg = (plan.exact || a.n_calc <= 0) ? nullptr : ratio_positions(R, plan, (size_t)a.n_calc);
     }
     hipLaunchKernelGGL(resample_kernel, dim3((a.n_out + 255) / 256, batch), dim3(256), 0, s, a);
     SE_HIP(hipGetLastError());
@@ -368,30 +380,6 @@ __global__ __launch_bounds__(RS_RAGGED_BLOCK) void resample_ragged_kernel(const 
     yp[t] = (float)resample_taps(x, a.win, n, tr - n, a.n_in[row], a.scale, a.index_step);
 }
 
-// What the ragged call keeps per ratio and device for the life of the process: the (scaled) filter table and, when the ratio is
-// no integer decimation, the position table - on the host as far as it has been summed, on the device as far as the longest row
-// seen needed it.  se_resample's own tables (Tables above) are left alone.
-struct RaggedRatio {
-    int sr_in = 0, sr_out = 0;
-    double* win = nullptr;
-    std::vector<double> tr;
-    double acc = 0.0;
-    double* dev_tr = nullptr;
-    size_t dev_cap = 0;
-};
-struct RaggedTables {
-    std::mutex mu;
-    std::vector<double> host;
-    std::vector<std::unique_ptr<RaggedRatio>> ratios;
-};
-RaggedTables& ragged_tables() {
-    static RaggedTables t[64];
-    int dev = 0;
-    SE_HIP(hipGetDevice(&dev));
-    SE_CHECK(dev >= 0 && dev < 64, "device ordinal");
-    return t[dev];
-}
-
 }  // namespace
 
 void launch_resample_ragged(const void* x, int in_format, long in_pitch, int batch, const int32_t* n_in, int sr_in, int sr_out, float* y,
@@ -404,26 +392,10 @@ void launch_resample_ragged(const void* x, int in_format, long in_pitch, int bat
     a.y = y; a.in_pitch = in_pitch; a.out_pitch = out_pitch;
     a.n_out_max = p.n_out_max; a.pass = p.pass;
     a.inc = p.plan.inc; a.scale = p.plan.scale; a.index_step = p.plan.index_step;
-    RaggedTables& T = ragged_tables();
+    ResampleTables& T = resample_tables();
     std::lock_guard<std::mutex> lock(T.mu);
     if (!p.pass) {
-        RaggedRatio* R = nullptr;
-        for (auto& r : T.ratios)
-            if (r->sr_in == sr_in && r->sr_out == sr_out) R = r.get();
-        if (!R) {                                                   // the first call at this ratio on this device
-            if (T.host.empty()) T.host = build_window();
-            std::vector<double> w(T.host);
-            if (p.plan.ratio < 1.0)
-                for (auto& v : w) v *= p.plan.ratio;                // interp_win *= sample_ratio
-            std::unique_ptr<RaggedRatio> fresh(new RaggedRatio());
-            fresh->sr_in = sr_in; fresh->sr_out = sr_out;
-            SE_HIP(hipMalloc(&fresh->win, RS_NWIN * sizeof(double)));
-            const hipError_t e = hipMemcpy(fresh->win, w.data(), RS_NWIN * sizeof(double), hipMemcpyHostToDevice);
-            if (e != hipSuccess) (void)hipFree(fresh->win);
-            SE_HIP(e);
-            R = fresh.get();
-            T.ratios.push_back(std::move(fresh));
-        }
+        RatioTables* R = ratio_tables(T, p.plan, sr_in, sr_out);
         a.win = R->win;
         if (!p.plan.exact && p.n_calc_max > 0) {
             // resampy advances the read position by repeated float64 addition: the sum is carried on from where it stopped
@@ -433,19 +405,7 @@ void launch_resample_ragged(const void* x, int in_format, long in_pitch, int bat
                 const RaggedRow r = ragged_row(p, n_in[b]);
                 SE_CHECK(r.n_calc == 0 || (int64_t)R->tr[(size_t)r.n_calc - 1] < r.n_in, fn + "a read position past the end of row " + std::to_string(b));
             }
-            if ((size_t)p.n_calc_max > R->dev_cap) {
-                // the table grows: the one place the call waits - launches on other hipStreams may still read the old table
-                const size_t cap = std::max<size_t>((size_t)p.n_calc_max, 2 * R->dev_cap);
-                ragged_positions_extend(p.plan, R->tr, R->acc, (int64_t)cap);
-                SE_HIP(hipDeviceSynchronize());
-                if (R->dev_tr) (void)hipFree(R->dev_tr);
-                R->dev_tr = nullptr;
-                R->dev_cap = 0;
-                SE_HIP(hipMalloc(&R->dev_tr, cap * sizeof(double)));
-                SE_HIP(hipMemcpy(R->dev_tr, R->tr.data(), cap * sizeof(double), hipMemcpyHostToDevice));
-                R->dev_cap = cap;
-            }
-            a.treg = R->dev_tr;
+            a.treg = ratio_positions(R, p.plan, (size_t)p.n_calc_max);
         }
     }
     // ---- every refusal is above

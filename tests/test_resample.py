@@ -30,6 +30,20 @@ def test_oracle_resampler_properties():
     assert np.array_equal(R.librosa_resample(x, 16000, 16000), x)
 
 
+def test_oracle_resample_at_is_the_loop_at_chosen_samples():
+    """resample_at (what tests of long rows read the oracle through) gives resample's samples exactly, and its vectorised
+    read positions are the loop's doubles."""
+    from oracle import resample as R
+    x = np.random.default_rng(7).standard_normal(3001)
+    for sr_in, sr_out in ((44100, 16000), (22050, 16000), (48000, 16000), (16000, 48000)):
+        ratio = float(sr_out) / sr_in
+        n_out = int(len(x) * ratio)
+        assert np.array_equal(R.time_registers_fast(n_out, ratio), R.time_registers(n_out, ratio))
+        ts = np.array([0, 1, 2, 57, n_out // 2, n_out - 2, n_out - 1])
+        assert np.array_equal(R.resample_at(x, sr_in, sr_out, ts), R.resample(x, sr_in, sr_out)[ts])
+    assert R.time_registers_fast(0, 0.5).shape == (0,)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('sr_in,n', [(48000, 14403), (44100, 9001), (8000, 3000), (22050, 5000)])
 def test_hip_resampler_matches_oracle(sr_in, n):
